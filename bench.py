@@ -3,6 +3,7 @@
 (BASELINE.json configs[1]: 1e5 synthetic lines, transit geometry).
 
     python bench.py --gpus N --steps K --warmup W [--workload c2|c2-1e6|c3|c4|c5|small]
+                    [--full] [--dump-outputs DIR]
 
 One step = one pass of the hot path over the synthetic workload with every input
 resident in HBM: LBL extinction (all layers) -> transit optical depth -> transmission
@@ -12,6 +13,14 @@ GPU (see pyratbay_amd/dist.py), and the spectrum is re-assembled with an RCCL
 all-gather (strong scaling: the total work per step is fixed).  Rank 0 prints ONE
 JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the headline figure.  Everything
+else it can measure or check -- the CPU baselines, the north_star leg, the rank projection,
+the other workloads (`legs`), the cold / un-pipelined / sustained figures, clocks, the
+roofline block, and with N > 1 the other decompositions and their parity with one GPU --
+runs only with --full.  --dump-outputs DIR writes what the last timed step computed
+(DIR/spectrum.npy; c5: DIR/bandflux.npy); the inputs are seeded, so two builds can be
+compared output for output.
+
 The oracle / compiled reference is used only for the `cpu_baseline` legs, never inside a
 timed GPU region.  The CPU legs run in worker processes that are started BEFORE this
 process touches the GPU (a process that has initialised HIP is never forked or exec'd);
@@ -19,6 +28,7 @@ they mirror the reference's own parallel form: one process per layer over min(co
 nlayers) workers (pyrat/line_by_line.py:232-246, clamp at pyrat/argum.py:60-66).
 """
 import argparse
+import contextlib
 import hashlib
 import json
 import os
@@ -75,9 +85,9 @@ WORKLOADS = {
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 LDS_PEAK_TBS = 150.0      # MI355X_MICROARCH.md: ds_read_b64/b128 aggregate, every CU streaming
 NORTH_STAR = 'c2-1e6'     # north_star's >= 50x target configuration
-# GPU-only legs of the default run: (workload, timed steps, warm-up steps) -- every other BASELINE
-# configuration in its single-GPU form + the two other grid / list structures, so that the
-# driver's one `python bench.py` times them all
+# GPU-only legs of a --full run: (workload, timed steps, warm-up steps) -- every other BASELINE
+# configuration in its single-GPU form + the two other grid / list structures, so that one
+# `python bench.py --full` times them all
 LEGS = (('c3', 10, 2), ('c4', 5, 1), ('c5', 157, 4), ('c5-emission', 157, 4), ('c2-res', 50, 4),
         ('c2-bands', 50, 4))
 LEG_TIMEOUT_S = 150.0
@@ -451,7 +461,7 @@ def start_legs(names):
             raise SystemExit(f'--legs: unknown leg {name!r} (known: {sorted(known)})')
         steps, warm = known[name]
         cmd = [sys.executable, os.path.abspath(__file__), '--leg-wait', '--workload', name,
-               '--steps', str(steps), '--warmup', str(warm), '--no-cpu-baseline',
+               '--steps', str(steps), '--warmup', str(warm), '--full', '--no-cpu-baseline',
                '--sustain-seconds', '0']
         procs.append((name, subprocess.Popen(cmd, stdin=subprocess.PIPE, stdout=subprocess.PIPE,
                                              stderr=subprocess.DEVNULL, text=True, cwd=ROOT)))
@@ -538,16 +548,24 @@ def main():
                     help='timed steps (default 50; c5: 157 batches of 64 walkers = 1e4 evals)')
     ap.add_argument('--warmup', type=int, default=4)
     ap.add_argument('--workload', default='c2', choices=sorted(WORKLOADS) + ['c5', 'c5-emission'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline figure (CPU '
+                         'baselines, north_star leg, rank projection, legs, cold / un-pipelined / '
+                         'sustained figures, clocks, roofline; N > 1: the other decompositions '
+                         'and their parity with one GPU)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the arrays the last timed step returned to DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='skip the CPU baselines of a --full run')
     ap.add_argument('--no-north-star', action='store_true',
-                    help='skip the 1e6-line leg of the default c2 run')
+                    help='skip the 1e6-line leg of a --full c2 run')
     ap.add_argument('--no-rank-projection', action='store_true',
                     help='skip the per-rank times of the wavenumber decomposition (one-rank RCCL '
-                         'group) of the default c2 run')
+                         'group) of a --full c2 run')
     ap.add_argument('--shard', default='wavenumber', choices=['layers', 'wavenumber'],
                     help='multi-GPU decomposition `value` is taken from (pyratbay_amd/dist.py): '
-                         "wavenumber = north_star's (shards + RCCL all-gather); the other one is "
-                         'timed in the same run and reported in config.decompositions')
+                         "wavenumber = north_star's (shards + RCCL all-gather); with --full the "
+                         'other one is timed in the same run and reported in config.decompositions')
     ap.add_argument('--cpu-layers', type=int, default=None,
                     help='layers of the one-core CPU leg (default: all at c2, 16 otherwise)')
     ap.add_argument('--cpu-worker', action='store_true', help=argparse.SUPPRESS)
@@ -555,13 +573,14 @@ def main():
     ap.add_argument('--selftest-launch', default=None, choices=['ok', 'fail'],
                     help=argparse.SUPPRESS)
     ap.add_argument('--no-legs', action='store_true',
-                    help='skip the GPU-only legs of the default c2 run (the other BASELINE '
+                    help='skip the GPU-only legs of a --full c2 run (the other BASELINE '
                          'configurations, each a child process of its own: `legs` in the JSON line)')
     ap.add_argument('--legs', default=','.join(n for n, _, _ in LEGS),
-                    help='comma-separated legs of the default run (default: %(default)s)')
+                    help='comma-separated legs of a --full run (default: %(default)s)')
     ap.add_argument('--leg-wait', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--sustain-seconds', type=float, default=3.0,
-                    help='length of the sustained legs at N=1 (config.sustained; 0: skip)')
+                    help='length of the sustained legs of a --full run at N=1 (config.sustained; '
+                         '0: skip)')
     args = ap.parse_args()
     if args.cpu_worker:
         return cpu_worker()
@@ -592,20 +611,21 @@ def main():
         raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}: launch with '
                          'python -m torch.distributed.run --nproc-per-node N bench.py --gpus N')
     w = WORKLOADS[args.workload]
+    full = args.full
     # CPU workers first: this process has not touched the GPU yet
     pool = None
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    want_cpu = full and world == 1 and not args.no_cpu_baseline
     if want_cpu:
         pool = CpuPool(max(1, min(host_cores() - 1, w['nlayers'])))
     rank_proc = None
-    if world == 1 and args.workload == 'c2' and not args.no_rank_projection:
+    if full and world == 1 and args.workload == 'c2' and not args.no_rank_projection:
         # (idle until this process has finished its GPU work; see rank_worker)
         rank_proc = subprocess.Popen([sys.executable, os.path.abspath(__file__), '--rank-worker'],
                                      stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True,
                                      cwd=ROOT)
 
     leg_procs = []
-    if world == 1 and args.workload == 'c2' and not args.no_legs and not args.leg_wait:
+    if full and world == 1 and args.workload == 'c2' and not args.no_legs and not args.leg_wait:
         leg_procs = start_legs([n for n in args.legs.split(',') if n])
 
     import torch
@@ -650,7 +670,8 @@ def main():
         software-pipelined unless PB_PIPELINE=0)."""
         t0 = time.perf_counter()
         res = {'kind': kind}
-        state = Sampler()            # (made here, entered around the timed regions: see gpu_state.py)
+        # (made here, entered around the timed regions: see gpu_state.py)
+        state = Sampler() if full else contextlib.nullcontext()
         per = 1                      # spectra per submission (> 1: dist.StackedShard)
         if kind == 'layers':
             sharded = LayerShardedTransit(case, world, rank, voigt=shared.get('voigt'),
@@ -749,7 +770,7 @@ def main():
                 out = step()
             return [out]
 
-        if world > 1 and kind != 'replicas':
+        if full and world > 1 and kind != 'replicas':
             # parity BEFORE anything is timed: the re-assembled spectrum of this decomposition
             # (collectives included) against the same spectrum computed whole on this rank's
             # own GPU.  A rank-size launch splits the phases of a tile differently from the
@@ -768,7 +789,7 @@ def main():
             if not res['parity_vs_single_gpu'] <= 1e-10:
                 raise RuntimeError(f'{kind}: sharded spectrum differs from the single-GPU one '
                                    f"by {res['parity_vs_single_gpu']:.3e} (bar 1e-10)")
-        if world == 1 and nwave <= 200000:
+        if full and world == 1 and nwave <= 200000:
             # the same W + K steps BEFORE the priming spectra below (config.cold_value): what a
             # caller sees who runs a few dozen spectra on a chip that was idle
             el0, _, _ = timed_steps(run_steps, args.steps, args.warmup, model.lbl, world, dist,
@@ -797,20 +818,30 @@ def main():
         torch.cuda.synchronize()
         res['init_seconds'] = round(time.perf_counter() - t0, 3)
 
+        last = []                    # what run_steps returned last: the timed steps' spectra
+
+        def run_steps_kept(k):
+            last[:] = run_steps(k)
+
+        # (clocks and per-launch kernel times of the timed steps: --full only)
         with state:
             elapsed, gather_ms, launches = timed_steps(
-                run_steps, args.steps, args.warmup, model.lbl, world, dist,
-                torch.cuda.synchronize, dev_reduce)
-        res['gpu_state'] = state.summary()
+                run_steps_kept, args.steps, args.warmup, model.lbl, world, dist,
+                torch.cuda.synchronize, dev_reduce, kernel_events=full)
+        if full:
+            res['gpu_state'] = state.summary()
+        if args.dump_outputs:
+            # (copied now: the passes below overwrite the pipelines' buffers)
+            res['spectrum'] = last[-1].cpu().numpy()
         # (replicas: every rank completed `steps` spectra of its own in that time)
         nspec = spectra_of(args.steps)
         res.update(model=model, elapsed=elapsed, gather_ms=gather_ms, launches=launches,
                    value=nspec / elapsed * (world if kind == 'replicas' else 1),
                    ms_per_step=1e3 * elapsed / nspec, spectra_timed=nspec,
-                   pipelined=pipelined, run_steps=run_steps)
+                   pipelined=pipelined)
         # the un-pipelined per-spectrum latency (one spectrum complete before the next starts)
         # beside the pipelined throughput, so that the one is not mistaken for the other
-        if pipelined:
+        if full and pipelined:
             def one_at_a_time(k):
                 out = None
                 for _ in range(-(-k // per)):
@@ -823,7 +854,7 @@ def main():
                 # the gather kernel's own duration (roofline) is the one measured with nothing
                 # else on the chip, not the one stretched by the neighbouring stream
                 res.update(gather_ms=g2, launches=l2)
-        if world == 1 and args.sustain_seconds > 0:
+        if full and world == 1 and args.sustain_seconds > 0:
             # sustained legs: >= sustain_seconds of back-to-back spectra in ONE timed region
             # (steady clocks and power state), for the pipelined form and one at a time
             def one_by_one(k):
@@ -854,7 +885,7 @@ def main():
         order = ['wavenumber']
     else:
         other = 'layers' if args.shard == 'wavenumber' else 'wavenumber'
-        order = [args.shard, other, 'replicas']
+        order = [args.shard, other, 'replicas'] if full else [args.shard]
     runs, failed = [], []
     for k in order:
         # a decomposition that fails (a collective the backend rejects, ...) must not take the
@@ -895,16 +926,11 @@ def main():
     layer_mode, pipelined = primary['kind'] == 'layers', primary['pipelined']
     t_init = primary['init_seconds']
     latency_ms = primary.get('unpipelined_ms_per_spectrum')
-    if os.environ.get('PB_DUMP_SPECTRUM'):
-        np.save(f"{os.environ['PB_DUMP_SPECTRUM']}.rank{rank}.npy",
-                primary['run_steps'](3)[-1].cpu().numpy())
 
     if rank == 0:
         ms_per_step = primary['ms_per_step']
         value = primary['value']
         n_lines = model.lines.nlines
-        roof = roofline_block(model, gather_ms, launches, nlayers_rank, wcount, nlayers, nwave,
-                              value, args.workload if world == 1 else None)
         if world == 1:
             par = 'single GPU' + (f", {primary['streams']} independent spectra in flight on "
                                   f"{primary['streams']} HIP streams" if pipelined else '')
@@ -928,8 +954,11 @@ def main():
                        'parallelism': par, 'backend': backend,
                        'ranks': dist.get_world_size() if world > 1 else 1,
                        'init_seconds': round(t_init, 3)},
-            'roofline': roof,
         }
+        if full:
+            out['roofline'] = roofline_block(model, gather_ms, launches, nlayers_rank, wcount,
+                                             nlayers, nwave, value,
+                                             args.workload if world == 1 else None)
         if w.get('resolution'):
             # (the `resolution` path reads the layers' factors back once per call: DESIGN.md 6b)
             out['config']['run_plans'] = 'one stream synchronisation per call'
@@ -998,6 +1027,9 @@ def main():
             # the other BASELINE configurations, GPU only, one child process at a time (this
             # process's GPU work is over; the CPU legs and the rank projection have finished)
             out['legs'] = run_legs(leg_procs)
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, 'spectrum.npy'), primary['spectrum'])
         print(json.dumps(out), flush=True)
     if pool is not None:
         pool.close()

@@ -9,11 +9,12 @@ and the band fluxes are all-gathered.  Synthetic inputs: S=4 species
 temperatures 300-3000 K, cross sections 10**U(-30,-20) smooth in T, parameter vectors within
 +-10 % of a base T / abundance vector, seed 7, per-walker hydrostatic radius.
 
-CPU legs (reference interp_ec + optdepth + trapezoid2D from oracle/_ref, else the oracle's port):
+CPU legs (with --full; reference interp_ec + optdepth + trapezoid2D from oracle/_ref, else the port):
 one core on a few evals, and all cores with one eval per worker at a time (walkers are
 independent, the way the reference's sampler parallelises them).  Workers start before the GPU
 is touched.
 """
+import contextlib
 import json
 import os
 import shutil
@@ -148,7 +149,9 @@ def main(args):
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     if world != args.gpus:
         raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}')
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    # (bench.py --full: CPU legs, clocks, the one-pass form, per-kernel roofline, box reference)
+    full = getattr(args, 'full', False)
+    want_cpu = full and world == 1 and not args.no_cpu_baseline
     procs = []
     if want_cpu:
         try:
@@ -181,7 +184,7 @@ def main(args):
     model = engine.TableSpectrum(inp['etable'], inp['ttable'], g['wn'], atm['radius'],
                                  atm['rstar'], rt_path=rt)
     pb = engine.PassBands(g['wn'], inp['bands'])
-    steps = args.steps if args.steps not in (None, 20) else 157   # default: 1e4 evals in batches of 64
+    steps = args.steps if args.steps is not None else 157   # default: 1e4 evals in batches of 64
     nbatch_distinct = 4
     batches = []
     for b in range(nbatch_distinct):
@@ -197,7 +200,7 @@ def main(args):
         return gather_walkers(flux, BATCH, world, rank) if world > 1 else flux
 
     from tools.gpu_state import Sampler
-    state = Sampler()                    # (before the warm-up: see gpu_state.py)
+    state = Sampler() if full else contextlib.nullcontext()   # (before the warm-up: gpu_state.py)
     for i in range(args.warmup):
         out = step(i)
     torch.cuda.synchronize()
@@ -211,6 +214,8 @@ def main(args):
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+    dump_dir = getattr(args, 'dump_outputs', None)
+    bandflux = out.cpu().numpy() if dump_dir else None      # (the last timed batch's band fluxes)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device='cpu' if rehearse else 'cuda')
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -221,7 +226,7 @@ def main(args):
     # -- reported beside `value`, which stays the default path's
     one_pass = None
     from pyratbay_amd import _capi
-    if world == 1 and rt == 'transit' and _capi.experiments():
+    if full and world == 1 and rt == 'transit' and _capi.experiments():
         # (experiments build of the library only: PB_LIBPBHIP=pyratbay_amd/libpbhip_exp.so)
         default_flux = out.clone()
         model.one_pass = True
@@ -243,6 +248,29 @@ def main(args):
     if rank == 0:
         evals = steps * BATCH
         value = evals / elapsed
+        # (as eval_bands runs them: the columns in the depth order of the first walker it saw)
+        ordered = model.column_order is not None
+        out_json = {
+            'metric': 'pyrat.eval() calls/sec (1e5 wavenumbers x 80 layers, sampled cross sections'
+                      + (', emission geometry)' if rt == 'emission' else ')'),
+            'value': value, 'unit': 'evals/s', 'n_gpus': world, 'steps': steps,
+            'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / steps,
+            'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f64',
+            'data': 'synthetic',
+            'config': {'workload': f'MCMC retrieval inner loop: {evals} eval() calls at 1e5 '
+                                   'wavenumbers x 80 layers, batched walkers'
+                                   + (', emission geometry (plane-parallel RT, 5-angle quadrature)'
+                                      if rt == 'emission' else ''),
+                       'batch': BATCH, 'nspec': NSPEC, 'ntemp': NTEMP, 'nbands': len(inp['bands']),
+                       'table_bytes': int(model.etable.numel() * 8),
+                       'parallelism': 'single GPU' if world == 1 else
+                       f'walker replicas x{world} + all-gather of band fluxes',
+                       'init_seconds': round(t_init, 3),
+                       'column_order': ('depth order of the first walker (TableSpectrum.'
+                                        'order_columns): spectra do not depend on it'
+                                        if ordered else 'grid order')},
+        }
+    if rank == 0 and full:
         # the two big kernels of a batch, each timed alone with events on the launch stream; the
         # dominant one (by time) is the roofline block, the other is listed beside it
         temps, dens, radius = batches[0]
@@ -259,8 +287,6 @@ def main(args):
             torch.cuda.synchronize()
             return ev0.elapsed_time(ev1) / reps
 
-        # (as eval_bands runs them: the columns in the depth order of the first walker it saw)
-        ordered = model.column_order is not None
         table = model.etable_ordered if ordered else model.etable
         # (transit geometry with ordered columns: the interpolation writes only the layers a block
         # of columns can need, TableSpectrum.tile_limit; the kernels are timed as eval_bands runs them)
@@ -359,43 +385,27 @@ def main(args):
         except Exception:                                       # noqa: BLE001
             traffic = None
         path_bytes = (16.0 * NSPEC + 32.0) * nlayers * nwave + 8.0 * nwave
-        out_json = {
-            'metric': 'pyrat.eval() calls/sec (1e5 wavenumbers x 80 layers, sampled cross sections'
-                      + (', emission geometry)' if rt == 'emission' else ')'),
-            'value': value, 'unit': 'evals/s', 'n_gpus': world, 'steps': steps,
-            'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / steps,
-            'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f64',
-            'data': 'synthetic',
-            'config': {'workload': f'MCMC retrieval inner loop: {evals} eval() calls at 1e5 '
-                                   'wavenumbers x 80 layers, batched walkers'
-                                   + (', emission geometry (plane-parallel RT, 5-angle quadrature)'
-                                      if rt == 'emission' else ''),
-                       'batch': BATCH, 'nspec': NSPEC, 'ntemp': NTEMP, 'nbands': len(inp['bands']),
-                       'table_bytes': int(model.etable.numel() * 8),
-                       'parallelism': 'single GPU' if world == 1 else
-                       f'walker replicas x{world} + all-gather of band fluxes',
-                       'init_seconds': round(t_init, 3), 'one_pass': one_pass,
-                       'column_order': ('depth order of the first walker (TableSpectrum.'
-                                        'order_columns): spectra do not depend on it'
-                                        if ordered else 'grid order'),
-                       'rt_kernel_ms_grid_order': grid_order_ms,
-                       'layers_written': (None if tile_limit is None else
-                                          {'fraction_of_ec': written_frac,
-                                           'margin_layers': model.tile_margin,
-                                           'walkers_flagged_for_repair': flagged}),
-                       'box_reference': box_reference(),
-                       'gpu_state': state.summary()},
-            'roofline': {'bound': 'hbm', 'kernel': dom['kernel'], 'achieved': dom['achieved'],
-                         'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': dom['frac'],
-                         'traffic': traffic, 'kernel_ms': dom['kernel_ms'],
-                         'kernel_bytes': dom['kernel_bytes'], 'binding': dom['bound_by'],
-                         'other_kernels': kernels[1:],
-                         'note': 'bytes = what one launch of 64 walkers must move: table slices '
-                                 'shared by the walkers that bracket them counted once',
-                         'path_bytes_per_eval_unshared': path_bytes},
-        }
+        out_json['config'].update({
+            'one_pass': one_pass, 'rt_kernel_ms_grid_order': grid_order_ms,
+            'layers_written': (None if tile_limit is None else
+                               {'fraction_of_ec': written_frac,
+                                'margin_layers': model.tile_margin,
+                                'walkers_flagged_for_repair': flagged}),
+            'box_reference': box_reference(), 'gpu_state': state.summary()})
+        out_json['roofline'] = {
+            'bound': 'hbm', 'kernel': dom['kernel'], 'achieved': dom['achieved'],
+            'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': dom['frac'], 'traffic': traffic,
+            'kernel_ms': dom['kernel_ms'], 'kernel_bytes': dom['kernel_bytes'],
+            'binding': dom['bound_by'], 'other_kernels': kernels[1:],
+            'note': 'bytes = what one launch of 64 walkers must move: table slices shared by '
+                    'the walkers that bracket them counted once',
+            'path_bytes_per_eval_unshared': path_bytes}
+    if rank == 0:
         if want_cpu:
             out_json.update(cpu_legs(inp, procs, step(0).cpu().numpy(), rt))
+        if dump_dir:
+            os.makedirs(dump_dir, exist_ok=True)
+            np.save(os.path.join(dump_dir, 'bandflux.npy'), bandflux.astype(np.float64))
         print(json.dumps(out_json), flush=True)
     for p in procs:
         try:
@@ -481,7 +491,9 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--cpu-worker', action='store_true')
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=None)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None)
     main(ap.parse_args())

@@ -17,6 +17,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# where the passes and the result go (tools/profile_round.sh sets it; relative paths: to ROOT)
+EVIDENCE = os.environ.get('PB_EVIDENCE_DIR', 'evidence')
 
 
 def counter_pass(counter, workload, out):
@@ -50,8 +52,9 @@ def main():
     workloads = sys.argv[1:] or ['c2']
     so = os.path.join(ROOT, 'pyratbay_amd', 'libpbhip.so')
     res = {'libpbhip_sha256': hashlib.sha256(open(so, 'rb').read()).hexdigest()}
+    os.makedirs(os.path.join(ROOT, EVIDENCE), exist_ok=True)
     for wl in workloads:
-        base = os.path.join(ROOT, 'gpurun_out', f'pmc_traffic_{wl}')
+        base = os.path.join(ROOT, EVIDENCE, f'pmc_traffic_{wl}')
         fetch = counter_pass('FETCH_SIZE', wl, base + '_f')
         write = counter_pass('WRITE_SIZE', wl, base + '_w')
         if wl.startswith('c5'):
@@ -72,7 +75,7 @@ def main():
                    'dispatches of the dominant gather kernel; hbm_bytes_per_launch = 2*FETCH_SIZE + '
                    'WRITE_SIZE (gfx950 correction for 16-byte-per-lane loads, '
                    'MI355X_MICROARCH.md); L2 memory-side requests incl. Infinity-Cache hits')
-    out = os.path.join(ROOT, 'gpurun_out', 'pmc_traffic.json')
+    out = os.path.join(ROOT, EVIDENCE, 'pmc_traffic.json')
     json.dump(res, open(out, 'w'), indent=1)
     print('wrote', out, '(copy to profiles/pmc_traffic.json)')
 
