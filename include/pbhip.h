@@ -553,6 +553,71 @@ int pb_band_scale(double *bandflux_d, const double *band_scale_d, const double *
 int pb_reject_walkers(double *bandflux_d, const double *temps_d, double tmin, double tmax,
                       int nlayers, int nbands, int nwalkers, void *stream);
 
+/* The retrieval batch with continuum terms (pyrat/opacity.py:206-257: every model adds to the
+ * one ec), added in registers before pb_interp_ec_batch[_limited] store a sample -- no second
+ * pass over ec.  Per walker and layer the terms of Continuum.add / pb_continuum, in its order, on
+ * top of the interpolated value:
+ *   rank-1 models in list order: kind 0 Rayleigh (Kurucz): rank1_cs_d[m][nwave] x the density of
+ *     species rank1_species[m]; kind 1 Lecavelier: 10^p[par] s0 (wn l0)^-p[par+1] x p BAR/T/K
+ *     (lecavelier.py:73-100); kind 2 CCSgray: 10^p[par] s0 where 10^p[par+1] <= p <= 10^p[par+2],
+ *     else 0, x p BAR/T/K (gray.py:63-75) -- p = rank1_pressure_d[m][nlayers] (bar), p[] = the
+ *     walker's row of pars_d;
+ *   CIA tables in order (pb_continuum's bracket rule; a temperature off a table is clamped to its
+ *     ends: finite, and the caller rejects the walker) x the product of the densities of its
+ *     cia_nspec[c] species, only where bit c of cia_mask_d[w] is set;
+ *   H- bound-free + free-free when hminus != 0 (n_H x n_e: species hm_species[0], [1]).
+ * density_d[nwalkers][nlayers][ncs]; pars_d[.][npars] with pars_stride = npars (per walker) or 0
+ * (one row for all).  Every per-sample operand (rank1_cs_d, cia_tab_d rows, cia_mask_d, wn_d,
+ * hm_sigma_bf_d, hm_ff_d rows) is in the column order of etable_d / ec_d.  At most
+ * PB_CONT_MAX_RANK1 rank-1 models, PB_CONT_MAX_CIA tables of at most PB_CONT_MAX_CIA species,
+ * one H- model. */
+#define PB_CONT_MAX_RANK1 8
+#define PB_CONT_MAX_CIA 4
+typedef struct pb_cont_batch {
+    int nrank1;
+    int rank1_kind[PB_CONT_MAX_RANK1];
+    int rank1_species[PB_CONT_MAX_RANK1];
+    int rank1_par[PB_CONT_MAX_RANK1];
+    double rank1_s0[PB_CONT_MAX_RANK1];
+    double rank1_l0[PB_CONT_MAX_RANK1];
+    const double *rank1_cs_d[PB_CONT_MAX_RANK1];
+    const double *rank1_pressure_d[PB_CONT_MAX_RANK1];
+    int ncia;
+    int cia_ntemp[PB_CONT_MAX_CIA];
+    int cia_nspec[PB_CONT_MAX_CIA];
+    int cia_species[PB_CONT_MAX_CIA][PB_CONT_MAX_CIA];
+    const double *cia_tab_d[PB_CONT_MAX_CIA];
+    const double *cia_temps_d[PB_CONT_MAX_CIA];
+    const uint8_t *cia_mask_d;
+    int hminus;
+    int hm_species[2];
+    const double *hm_sigma_bf_d;
+    const double *hm_ff_d;
+    const double *wn_d;
+    const double *density_d;
+    int ncs;
+    const double *pars_d;
+    int npars;
+    int pars_stride;
+} pb_cont_batch;
+/* Device scratch (doubles) of the two calls below: the interpolation weights, the per-(walker,
+ * layer) continuum scalars and the per-walker Lecavelier rows [nlec][nwalkers][nwave]; -1 when
+ * cont is invalid. */
+int64_t pb_interp_ec_batch_cont_work_doubles(const pb_cont_batch *cont, int nlayers, int nwave,
+                                             int nwalkers);
+/* pb_interp_ec_batch / pb_interp_ec_batch_limited + the continuum terms of `cont` (a host
+ * struct).  A gated repair call (gate_d != NULL) reuses the scalars and rows its first call left
+ * in work_d.  Arguments are checked before any HIP call. */
+int pb_interp_ec_batch_cont(double *ec_d, const double *etable_d, const double *ttable_d,
+                            const double *temps_d, const double *density_d, void *work_d,
+                            int nmol, int ntemp, int nlayers, int nwave, int nwalkers,
+                            const pb_cont_batch *cont, void *stream);
+int pb_interp_ec_batch_cont_limited(double *ec_d, const double *etable_d, const double *ttable_d,
+                                    const double *temps_d, const double *density_d, void *work_d,
+                                    int nmol, int ntemp, int nlayers, int nwave, int nwalkers,
+                                    const pb_cont_batch *cont, const int32_t *tile_limit_d,
+                                    int row0, const int32_t *gate_d, void *stream);
+
 /* =========================================================================
  * Experiments -- NOT in libpbhip.so.  `make -C pyratbay_amd/csrc EXPERIMENTS=1` builds
  * libpbhip_exp.so (compiled with -DPB_EXPERIMENTS) = the product library + the variants that were

@@ -91,6 +91,10 @@ _PROTOS = {
     'pb_emission_observables': [vp, vp, vp, vp, vp, i64, i32, i32, f64, f64, vp],
     'pb_band_scale': [vp, vp, vp, i32, i32, vp],
     'pb_reject_walkers': [vp, vp, f64, f64, i32, i32, i32, vp],
+    'pb_interp_ec_batch_cont_work_doubles': [vp, i32, i32, i32],
+    'pb_interp_ec_batch_cont': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
+    'pb_interp_ec_batch_cont_limited': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp,
+                                        i32, vp, vp],
     'pb_optdepth': [vp, vp, i64, vp, i32, f64, vp, i32, i32, vp],
     'pb_optical_depth_transit': [vp, vp, vp, vp, i32, i32, f64, i32, i32, vp],
     'pb_transit_spectrum': [vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, vp],
@@ -123,7 +127,8 @@ _EXP_PROTOS = {
     'pb_table_transit_batch': [vp, vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, i32, i32,
                                i32, vp, vp],
 }
-_RESTYPES = {'pb_transit_work_doubles': C.c_int64, 'pb_table_transit_work_doubles': C.c_int64,
+_RESTYPES = {'pb_transit_work_doubles': C.c_int64,
+             'pb_interp_ec_batch_cont_work_doubles': C.c_int64, 'pb_table_transit_work_doubles': C.c_int64,
              'pb_table_transit_supported': C.c_int, 'pb_voigt_destroy': None, 'pb_lines_destroy': None, 'pb_lbl_destroy': None,
              'pb_voigt_device_bytes': i64, 'pb_timer_destroy': None}
 _NO_CHECK = set(_RESTYPES) | {'pb_version', 'pb_roctx_available'}

@@ -339,6 +339,7 @@ class Continuum:
         self.cia = [m for m in models if isinstance(m, Collision_Induced)]
         self.hminus = [m for m in models if isinstance(m, Hydrogen_Ion)]
         self.alkali = [m for m in models if isinstance(m, VanderWaals)]
+        self.deck = [m for m in models if isinstance(m, Deck)]
         if len(self.cia) > 4 or len(self.hminus) > 1:
             raise ValueError('at most 4 CIA tables and one H- model per Continuum')
         self.cia_tab = [dev(m.tab_cross_section) for m in self.cia]
@@ -348,6 +349,7 @@ class Continuum:
             self.hm_ff = dev(self.hminus[0].ff_factors)
         self.pressure_barye = dev(self.pressure * BAR)
         self._cs_key = None
+        self._batch = []         # [(column order, BatchOperands)]
 
     def _rank1_cross_sections(self):
         """[nrank1, nwave] on the device; uploaded again only when a model's parameters
@@ -362,6 +364,47 @@ class Continuum:
             self._cs_d = dev(np.array(rows).reshape(len(rows), self.nwave))
             self._cs_key = key
         return self._cs_d
+
+    @property
+    def species(self):
+        """The species of the [nw, L, ncs] continuum density tensor of eval_bands, in model order."""
+        return _species_of(self.rank1 + self.cia + self.hminus)
+
+    @property
+    def free_pars(self):
+        """(model name, index) of every free parameter, models in order: Lecavelier has 2
+        (log10 scale, exponent), CCSgray 3 (log10 cross section, log10 bottom / top pressure)."""
+        return [(m.name, i) for m in self.rank1 if isinstance(m, (Lecavelier, CCSgray))
+                for i in range(len(m.pars))]
+
+    def _par_offsets(self):
+        out, k = [], 0
+        for m in self.rank1:
+            out.append(k)
+            if isinstance(m, (Lecavelier, CCSgray)):
+                k += len(m.pars)
+        return out
+
+    def current_pars(self):
+        """The models' current parameters in free_pars order (host array)."""
+        return np.array([float(p) for m in self.rank1 if isinstance(m, (Lecavelier, CCSgray))
+                         for p in m.pars], float)
+
+    def batch_unsupported(self):
+        """Names of the models the batched form does not take (a cloud deck changes the optical-depth
+        integration, the alkali Voigt values are computed on the host)."""
+        return [getattr(m, 'name', type(m).__name__) for m in self.deck + self.alkali]
+
+    def batch_operands(self, order=None):
+        """The device-side operands for eval_bands (BatchOperands), in grid order or permuted to
+        `order` (a column order of TableSpectrum.set_column_order); cached per order."""
+        for o, ops in self._batch:
+            if o is order:
+                return ops
+        ops = BatchOperands(self, order)
+        # (grid order and the latest column order are kept)
+        self._batch = [b for b in self._batch if b[0] is None] + [(order, ops)]
+        return ops
 
     def add(self, ec, temperature, density):
         """ec[L,W] (device, float64) += every term.  temperature[L] and the number
@@ -421,3 +464,144 @@ class Continuum:
                  nlayers, self.nwave, _stream())
         del keep        # stream-ordered allocator: safe to release after the launches
         return ec
+
+
+# ---------------------------------------------------------------------------------------------
+# Batched form (TableSpectrum.eval_bands): every walker has its own temperatures, densities and
+# free continuum parameters; the terms are added by the batched interpolation before it stores ec
+# (pb_interp_ec_batch_cont), in the order of Continuum.add.
+# ---------------------------------------------------------------------------------------------
+_MAX_RANK1, _MAX_CIA = 8, 4
+
+
+class ContBatchStruct(C.Structure):
+    """pb_cont_batch of include/pbhip.h."""
+    _fields_ = [
+        ('nrank1', C.c_int),
+        ('rank1_kind', C.c_int * _MAX_RANK1),
+        ('rank1_species', C.c_int * _MAX_RANK1),
+        ('rank1_par', C.c_int * _MAX_RANK1),
+        ('rank1_s0', C.c_double * _MAX_RANK1),
+        ('rank1_l0', C.c_double * _MAX_RANK1),
+        ('rank1_cs_d', C.c_void_p * _MAX_RANK1),
+        ('rank1_pressure_d', C.c_void_p * _MAX_RANK1),
+        ('ncia', C.c_int),
+        ('cia_ntemp', C.c_int * _MAX_CIA),
+        ('cia_nspec', C.c_int * _MAX_CIA),
+        ('cia_species', (C.c_int * _MAX_CIA) * _MAX_CIA),
+        ('cia_tab_d', C.c_void_p * _MAX_CIA),
+        ('cia_temps_d', C.c_void_p * _MAX_CIA),
+        ('cia_mask_d', C.c_void_p),
+        ('hminus', C.c_int),
+        ('hm_species', C.c_int * 2),
+        ('hm_sigma_bf_d', C.c_void_p),
+        ('hm_ff_d', C.c_void_p),
+        ('wn_d', C.c_void_p),
+        ('density_d', C.c_void_p),
+        ('ncs', C.c_int),
+        ('pars_d', C.c_void_p),
+        ('npars', C.c_int),
+        ('pars_stride', C.c_int),
+    ]
+
+
+class BatchOperands:
+    """The device-side operands of a Continuum for pb_interp_ec_batch_cont, every per-sample one
+    (Rayleigh cross sections, CIA rows and validity mask, H- rows, wn) in one column order."""
+
+    def __init__(self, cont, order=None):
+        idx = None if order is None else torch.as_tensor(order, device='cuda').to(torch.int64)
+
+        def cols(t):
+            return t.contiguous() if idx is None else t.index_select(-1, idx).contiguous()
+        species = cont.species
+        st = ContBatchStruct()
+        keep = []
+        st.nrank1 = len(cont.rank1)
+        offsets = cont._par_offsets()
+        for m, model in enumerate(cont.rank1):
+            if isinstance(model, Kurucz):
+                st.rank1_kind[m] = 0
+                st.rank1_species[m] = species.index(model.species)
+                cs = cols(dev(model.cross_section))
+                keep.append(cs)
+                st.rank1_cs_d[m] = cs.data_ptr()
+            else:
+                st.rank1_kind[m] = 1 if isinstance(model, Lecavelier) else 2
+                st.rank1_par[m] = offsets[m]
+                st.rank1_s0[m] = float(model.s0)
+                st.rank1_l0[m] = float(getattr(model, 'l0', 0.0))
+                pr = dev(model.pressure)
+                keep.append(pr)
+                st.rank1_pressure_d[m] = pr.data_ptr()
+        st.ncia = len(cont.cia)
+        mask = np.zeros(cont.nwave, np.uint8)
+        for c, model in enumerate(cont.cia):
+            tab = cols(cont.cia_tab[c])
+            keep += [tab, cont.cia_temps[c]]
+            st.cia_tab_d[c] = tab.data_ptr()
+            st.cia_temps_d[c] = cont.cia_temps[c].data_ptr()
+            st.cia_ntemp[c] = model.ntemp
+            st.cia_nspec[c] = len(model.species)
+            for j, sp in enumerate(model.species):
+                st.cia_species[c][j] = species.index(sp)
+            mask[model._wn_lo_idx:model._wn_hi_idx] |= np.uint8(1 << c)
+        self.mask = cols(dev(mask, torch.int64).to(torch.uint8))
+        st.cia_mask_d = self.mask.data_ptr()
+        st.hminus = len(cont.hminus)
+        if cont.hminus:
+            st.hm_species[0] = species.index('H')
+            st.hm_species[1] = species.index('e-')
+            self.hm_sigma_bf = cols(cont.hm_sigma_bf)
+            self.hm_ff = cols(cont.hm_ff)
+            st.hm_sigma_bf_d = self.hm_sigma_bf.data_ptr()
+            st.hm_ff_d = self.hm_ff.data_ptr()
+        self.wn = cols(cont.wn)
+        st.wn_d = self.wn.data_ptr()
+        st.ncs = len(species)
+        st.npars = len(cont.free_pars)
+        self._keep = keep
+        self.struct = st
+        self.ncs, self.npars = len(species), len(cont.free_pars)
+        self.nlec = sum(isinstance(m, Lecavelier) for m in cont.rank1)
+        self.cont = cont
+
+    def default_pars(self):
+        """[1, npars] device tensor of the models' current parameters (uploaded again only when
+        they change)."""
+        key = tuple(self.cont.current_pars().tolist())
+        if key != getattr(self, '_pars_key', None):
+            self._pars_d = dev(np.array(key, float)).view(1, -1)
+            self._pars_key = key
+        return self._pars_d
+
+    def default_pars(self):
+        """[1, npars] device tensor of the models' current parameters (uploaded again only when
+        they change)."""
+        key = tuple(self.cont.current_pars().tolist())
+        if key != getattr(self, '_pars_key', None):
+            self._pars_d = dev(np.array(key, float)).view(1, -1)
+            self._pars_key = key
+        return self._pars_d
+
+    def args(self, density, pars):
+        """The pb_cont_batch of one call: density[nw, L, ncs], pars[nw, npars] or [1, npars]."""
+        st = self.struct
+        st.density_d = density.data_ptr() if density is not None else None
+        st.pars_d = pars.data_ptr() if pars is not None else None
+        st.pars_stride = 0 if pars is None or pars.shape[0] == 1 else self.npars
+        return C.byref(st)
+
+    def work_doubles(self, nlayers, nwave, nwalkers):
+        from ._capi import lib
+        return int(lib().pb_interp_ec_batch_cont_work_doubles(C.byref(self.struct), nlayers,
+                                                              nwave, nwalkers))
+
+
+def _species_of(models):
+    out = []
+    for m in models:
+        names = ([m.species] if isinstance(m, Kurucz) else list(m.species)
+                 if isinstance(m, (Collision_Induced, Hydrogen_Ion)) else [])
+        out += [s for s in names if s not in out]
+    return out

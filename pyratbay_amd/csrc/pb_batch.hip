@@ -106,6 +106,218 @@ using pb::uniform_i32;
 using pb::layer_wanted;
 
 // ---------------------------------------------------------------------------
+// Continuum terms in the store of the batched interpolation (TableSpectrum.eval_bands with a
+// Continuum).  A separate ec += continuum pass would read and write ec again (4.1 GB per 64
+// walkers at C5's shape); instead the terms are added to `acc` in registers before it is stored.
+// k_cont_plan writes per (walker, layer) the scalars of every term -- the rank-1 factors, the CIA
+// brackets and density products, the H- temperature factors -- which the epilogue reads as
+// wave-uniform scalar loads; k_cont_rows writes the one term that depends on both the sample and
+// the walker's parameters, the Lecavelier cross section, once per walker.  The arithmetic and the
+// order of the additions are those of Continuum.add -> k_continuum (pb_continuum.hip): rank-1
+// models in list order, CIA tables in order, H-; per walker the result equals
+// pb_interp_ec_batch followed by pb_continuum bit for bit for Rayleigh, CIA and H- (the
+// Lecavelier / gray 10^x and pow run on the device, not in NumPy: within an ulp or two).
+// kCont = 0: no continuum (the kernels compile to what they were); 1: continuum; 2: with H-.
+// ---------------------------------------------------------------------------
+constexpr int kCbRank1 = PB_CONT_MAX_RANK1;
+constexpr int kCbCia = PB_CONT_MAX_CIA;
+constexpr int kCbRank1Reg = 4;     // Rayleigh cross sections kept in registers (more: re-read)
+constexpr double kCbBar = 1e6;
+constexpr double kCbK = 1.380649e-16, kCbH = 6.62607015e-27, kCbC = 29979245800.0;
+constexpr double kCbWn0Bf = 6090.5;
+
+struct ContEpi {
+    int nrank1, ncia, nrec;
+    int kind[kCbRank1];
+    const double *row[kCbRank1];     // kind 0: [nwave]; kind 1: the walker rows [nwalkers][nwave]
+    const double *cia_tab[kCbCia];   // [ntemp][nwave]
+    const uint8_t *cia_mask;         // [nwave]
+    const double *wn, *hm_sigma_bf, *hm_ff;
+    const double *rec;               // [nwalkers * nlayers][nrec], written by k_cont_plan
+};
+
+// the operands of a thread's sample that do not depend on the walker, kept across the walker loop
+template <int kCont>
+struct ContState {
+    double cs[kCbRank1Reg];
+    unsigned mask;
+    int cidx[kCbCia];                // wave-uniform: the CIA bracket whose rows are held
+    double y0[kCbCia], sl[kCbCia];
+    double wn, sig, ff[6];           // (kCont == 2)
+};
+
+template <int kCont>
+__device__ __forceinline__ void cont_init(ContState<kCont> &st, const ContEpi &a, int col,
+                                          int nwave)
+{
+#pragma unroll
+    for (int m = 0; m < kCbRank1Reg; m++)
+        st.cs[m] = m < a.nrank1 && a.kind[m] == 0 ? a.row[m][col] : 0.0;
+    st.mask = a.ncia ? a.cia_mask[col] : 0u;
+    if constexpr (kCont == 2) {
+        st.wn = a.wn[col];
+        st.sig = a.hm_sigma_bf[col];
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+            st.ff[i] = a.hm_ff[(int64_t)i * nwave + col];
+    }
+#pragma unroll
+    for (int c = 0; c < kCbCia; c++)
+        st.cidx[c] = -1;
+}
+
+// acc (the interpolated value of walker w, sample col) + every term, in Continuum.add's order
+template <int kCont>
+__device__ __forceinline__ double cont_apply(double acc, ContState<kCont> &st, const ContEpi &a,
+                                             int col, int w, int64_t wk, int nwave)
+{
+    typedef const double __attribute__((address_space(4))) *crec_t;
+    const crec_t r = (crec_t)(unsigned long long)(a.rec + wk * a.nrec);
+    // rank-1: cross section x factor (k_continuum: ec += csv[m] * f[m][l])
+#pragma unroll
+    for (int m = 0; m < kCbRank1; m++) {
+        if (m >= a.nrank1)
+            break;
+        const double f = r[m];
+        const int kind = a.kind[m];
+        double cs;
+        if (kind == 0)
+            cs = m < kCbRank1Reg ? st.cs[m] : a.row[m][col];
+        else if (kind == 1)
+            cs = a.row[m][(int64_t)w * nwave + col];
+        else
+            cs = 1.0;                       // (CCSgray: a row of ones in Continuum.add)
+        acc += cs * f;
+    }
+    // CIA: the rows of the walker's bracket, held while the next walker shares it
+    const crec_t rc = r + a.nrank1;
+#pragma unroll
+    for (int c = 0; c < kCbCia; c++) {
+        if (c >= a.ncia)
+            break;
+        const int idx = (int)rc[4 * c];
+        const double dt = rc[4 * c + 1], gap = rc[4 * c + 2], fp = rc[4 * c + 3];
+        if (idx != st.cidx[c]) {                        // wave-uniform
+            st.cidx[c] = idx;
+            const double *t0 = a.cia_tab[c] + (int64_t)idx * nwave + col;
+            const double y0 = t0[0], y1 = t0[nwave];
+            st.y0[c] = y0;
+            st.sl[c] = (y1 - y0) / gap;                 // (k_continuum: (y1 - y0) / inv)
+        }
+        if (st.mask >> c & 1u) {
+            // a temperature on a node takes that row unchanged (dt = 0 there)
+            const double cs = dt != 0.0 ? st.y0[c] + dt * st.sl[c] : st.y0[c];
+            acc += cs * fp;
+        }
+    }
+    if constexpr (kCont == 2) {
+        const crec_t rh = rc + 4 * a.ncia;
+        const double bfpre = rh[6], ffpost = rh[7], temp = rh[8], hf = rh[9];
+        const double alpha = kCbH * kCbC / kCbK;
+        const double bf = bfpre * (1.0 - exp(-st.wn * alpha / temp)) * st.sig;
+        double ff = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+            if (st.ff[i] != 0.0)
+                ff += rh[i] * st.ff[i];
+        ff *= ffpost;
+        acc += (bf + ff) * hf;
+    }
+    return acc;
+}
+
+struct ContPlanArgs {
+    double *rec;
+    const double *temps, *density, *pars;
+    int nlayers, ncs, pars_stride, nrec;
+    int64_t n;
+    pb_cont_batch c;
+};
+
+// per (walker, layer): the scalars the epilogue reads (layout: rank-1 factors | per CIA table
+// bracket, dt, node gap, density product | H- beta[6], bf prefactor, ff postfactor, T, n_H n_e)
+__global__ __launch_bounds__(kBlock) void k_cont_plan(ContPlanArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n)
+        return;
+    const int l = (int)(i % a.nlayers);
+    const int64_t w = i / a.nlayers;
+    const double t = a.temps[i];
+    const double *d = a.density + i * a.ncs;
+    const double *p = a.pars + w * a.pars_stride;
+    double *r = a.rec + i * a.nrec;
+    for (int m = 0; m < a.c.nrank1; m++) {
+        const int kind = a.c.rank1_kind[m];
+        if (kind == 0) {
+            r[m] = d[a.c.rank1_species[m]];
+            continue;
+        }
+        const double pr = a.c.rank1_pressure_d[m][l];
+        const double nominal = pr * kCbBar / t / kCbK;      // lecavelier.py / gray.py: p BAR/T/K
+        if (kind == 1) {
+            r[m] = nominal;
+        } else {
+            const int q = a.c.rank1_par[m];
+            const double p_top = pow(10.0, p[q + 2]), p_bottom = pow(10.0, p[q + 1]);
+            const double cs = pr >= p_bottom && pr <= p_top ? pow(10.0, p[q]) * a.c.rank1_s0[m]
+                                                            : 0.0;
+            r[m] = cs * nominal;
+        }
+    }
+    double *rc = r + a.c.nrank1;
+    for (int c = 0; c < a.c.ncia; c++) {
+        // k_continuum's bracket rule (_spline.c:235-251) on the temperature clamped to the table
+        const double *tt = a.c.cia_temps_d[c];
+        const int n = a.c.cia_ntemp[c];
+        const double temp = fmin(fmax(t, tt[0]), tt[n - 1]);
+        int idx = pb::nearest_index(tt, temp, 0, n - 1);
+        if (idx == n - 1 || temp < tt[idx])
+            idx--;
+        rc[4 * c] = (double)idx;
+        rc[4 * c + 1] = tt[idx] != temp ? temp - tt[idx] : 0.0;
+        rc[4 * c + 2] = tt[idx + 1] - tt[idx];
+        double prod = d[a.c.cia_species[c][0]];          // np.prod over the species, in order
+        for (int j = 1; j < a.c.cia_nspec[c]; j++)
+            prod = prod * d[a.c.cia_species[c][j]];
+        rc[4 * c + 3] = prod;
+    }
+    if (a.c.hminus) {
+        double *rh = rc + 4 * a.c.ncia;
+        const double tc = fmin(fmax(t, 1000.0), 10080.0);
+        // (a loop the compiler keeps: the same pow() calls as k_continuum, no constant folding)
+#pragma nounroll
+        for (int k = 0; k < 6; k++)
+            rh[k] = pow(sqrt(5040.0 / tc), (double)(k + 2));
+        const double alpha = kCbH * kCbC / kCbK;
+        rh[6] = 0.75 * pow(t, -1.5) * kCbK * exp(kCbWn0Bf * alpha / t);
+        rh[7] = kCbK * tc;
+        rh[8] = t;
+        rh[9] = d[a.c.hm_species[0]] * d[a.c.hm_species[1]];
+    }
+}
+
+struct ContRowsArgs {
+    double *rows;                    // [nlec][nwalkers][nwave]
+    const double *wn, *pars;
+    int nwave, nwalkers, pars_stride, nlec;
+    int par[kCbRank1];
+    double s0[kCbRank1], l0[kCbRank1];
+};
+
+// Lecavelier.calc_cross_section per walker: 10**p0 * s0 * (wn * l0)**(-p1)
+__global__ __launch_bounds__(kBlock) void k_cont_rows(ContRowsArgs a)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const int w = blockIdx.y, j = blockIdx.z;
+    if (i >= a.nwave)
+        return;
+    const double *p = a.pars + (int64_t)w * a.pars_stride + a.par[j];
+    a.rows[((int64_t)j * a.nwalkers + w) * a.nwave + i] =
+        pow(10.0, p[0]) * a.s0[j] * pow(a.wn[i] * a.l0[j], -p[1]);
+}
+
+// ---------------------------------------------------------------------------
 // interp_ec for a batch of walkers, assigning form.  Workgroup = (256 wavenumbers, layer,
 // chunk of walkers).  Walkers of a chunk that share a temperature bracket share its two table
 // slices: the brackets the chunk uses at this layer are walked in ascending order, the upper
@@ -140,10 +352,10 @@ __global__ __launch_bounds__(kBlock) void k_interp_weights(
 
 // kFull: nmol == kS, no per-species predicate (the coefficient loads of a walker then merge into
 // one scalar load and one wait)
-template <int kS, bool kFull>
+template <int kS, bool kFull, int kCont = 0>
 __global__ __launch_bounds__(kBlock) void k_interp_ec_batch(
     double *ec, const double *etable, const int32_t *tlo, const double *coef, int nmol,
-    int ntemp, int nlayers, int nwave, int nwalkers, int chunk, TileLimit lim)
+    int ntemp, int nlayers, int nwave, int nwalkers, int chunk, TileLimit lim, ContEpi cont = {})
 {
     if (!layer_wanted(lim, blockIdx.y, blockIdx.x * kBlock, blockIdx.x * kBlock + kBlock, nwave))
         return;
@@ -170,6 +382,9 @@ __global__ __launch_bounds__(kBlock) void k_interp_ec_batch(
 #pragma unroll
     for (int j = 0; j < kS; j++)
         hi[j] = kFull || j < nmol ? tab[((int64_t)j * ntemp + bmin) * slice] : 0.0;
+    ContState<kCont> cst;
+    if constexpr (kCont != 0)
+        cont_init(cst, cont, i, nwave);
     for (int b = bmin; b <= bmax; b++) {
 #pragma unroll
         for (int j = 0; j < kS; j++) {
@@ -188,6 +403,8 @@ __global__ __launch_bounds__(kBlock) void k_interp_ec_batch(
             for (int j = 0; j < kS; j++)
                 if (kFull || j < nmol)
                     acc += lo[j] * co[j] + hi[j] * co[kS + j];
+            if constexpr (kCont != 0)
+                acc = cont_apply(acc, cst, cont, i, w, wk, nwave);
             ec[wk * nwave + i] = acc;
         }
     }
@@ -1969,10 +2186,89 @@ int pb_iso_partition(double *z_d, int64_t z_iso_stride, int64_t z_t_stride,
     return PB_OK;
 }
 
+// the continuum's per-(walker, layer) record length (ContEpi::nrec), or -1 if `c` is invalid
+static int cont_nrec(const pb_cont_batch *c)
+{
+    if (!c || c->nrank1 < 0 || c->nrank1 > kCbRank1 || c->ncia < 0 || c->ncia > kCbCia ||
+        c->hminus < 0 || c->hminus > 1)
+        return -1;
+    return c->nrank1 + 4 * c->ncia + 10 * c->hminus;
+}
+
+static int cont_nlec(const pb_cont_batch *c)
+{
+    int n = 0;
+    for (int m = 0; m < c->nrank1; m++)
+        n += c->rank1_kind[m] == 1;
+    return n;
+}
+
+// workspace of the continuum calls, in doubles: coef[n][16] | tlo[n] (int32) | rec[n][nrec] |
+// Lecavelier rows [nlec][nwalkers][nwave]
+static int64_t cont_rec_offset(int64_t n) { return n * 16 + (n + 1) / 2 + 1; }
+
+static int cont_check(const pb_cont_batch *c)
+{
+    PB_REQUIRE(c, "pb_interp_ec_batch_cont: null continuum struct");
+    PB_REQUIRE(c->nrank1 >= 0 && c->nrank1 <= kCbRank1,
+               "pb_interp_ec_batch_cont: 0-%d rank-1 models, not %d", kCbRank1, c->nrank1);
+    PB_REQUIRE(c->ncia >= 0 && c->ncia <= kCbCia,
+               "pb_interp_ec_batch_cont: at most %d CIA tables, not %d", kCbCia, c->ncia);
+    PB_REQUIRE(c->hminus == 0 || c->hminus == 1,
+               "pb_interp_ec_batch_cont: at most one H- model, not %d", c->hminus);
+    PB_REQUIRE(c->ncs >= 0 && c->npars >= 0 && (c->pars_stride == 0 || c->pars_stride == c->npars),
+               "pb_interp_ec_batch_cont: bad counts (ncs %d, npars %d, pars_stride %d)", c->ncs,
+               c->npars, c->pars_stride);
+    bool need_dens = c->ncia > 0 || c->hminus;
+    bool need_pars = false;
+    for (int m = 0; m < c->nrank1; m++) {
+        const int kind = c->rank1_kind[m];
+        PB_REQUIRE(kind >= 0 && kind <= 2, "pb_interp_ec_batch_cont: rank-1 model %d: kind %d",
+                   m, kind);
+        if (kind == 0) {
+            PB_REQUIRE(c->rank1_cs_d[m], "pb_interp_ec_batch_cont: null cross section (model %d)", m);
+            PB_REQUIRE(c->rank1_species[m] >= 0 && c->rank1_species[m] < c->ncs,
+                       "pb_interp_ec_batch_cont: rank-1 model %d: species %d of %d", m,
+                       c->rank1_species[m], c->ncs);
+            need_dens = true;
+        } else {
+            PB_REQUIRE(c->rank1_pressure_d[m], "pb_interp_ec_batch_cont: null pressure (model %d)", m);
+            PB_REQUIRE(c->rank1_par[m] >= 0 && c->rank1_par[m] + (kind == 1 ? 2 : 3) <= c->npars,
+                       "pb_interp_ec_batch_cont: rank-1 model %d: parameters %d.. of %d", m,
+                       c->rank1_par[m], c->npars);
+            need_pars = true;
+        }
+    }
+    for (int k = 0; k < c->ncia; k++) {
+        PB_REQUIRE(c->cia_tab_d[k] && c->cia_temps_d[k],
+                   "pb_interp_ec_batch_cont: null CIA table %d", k);
+        PB_REQUIRE(c->cia_ntemp[k] >= 2, "pb_interp_ec_batch_cont: CIA table %d: %d temperatures",
+                   k, c->cia_ntemp[k]);
+        PB_REQUIRE(c->cia_nspec[k] >= 1 && c->cia_nspec[k] <= kCbCia,
+                   "pb_interp_ec_batch_cont: CIA table %d: 1-%d species, not %d", k, kCbCia,
+                   c->cia_nspec[k]);
+        for (int j = 0; j < c->cia_nspec[k]; j++)
+            PB_REQUIRE(c->cia_species[k][j] >= 0 && c->cia_species[k][j] < c->ncs,
+                       "pb_interp_ec_batch_cont: CIA table %d: species %d of %d", k,
+                       c->cia_species[k][j], c->ncs);
+    }
+    PB_REQUIRE(c->ncia == 0 || c->cia_mask_d, "pb_interp_ec_batch_cont: null CIA mask");
+    if (c->hminus) {
+        PB_REQUIRE(c->hm_sigma_bf_d && c->hm_ff_d, "pb_interp_ec_batch_cont: null H- arrays");
+        for (int j = 0; j < 2; j++)
+            PB_REQUIRE(c->hm_species[j] >= 0 && c->hm_species[j] < c->ncs,
+                       "pb_interp_ec_batch_cont: H- species %d of %d", c->hm_species[j], c->ncs);
+    }
+    PB_REQUIRE(!(c->hminus || cont_nlec(c)) || c->wn_d, "pb_interp_ec_batch_cont: null wn");
+    PB_REQUIRE(!need_dens || c->density_d, "pb_interp_ec_batch_cont: null continuum density");
+    PB_REQUIRE(!need_pars || c->pars_d, "pb_interp_ec_batch_cont: null continuum parameters");
+    return PB_OK;
+}
+
 static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const double *ttable_d,
                                   const double *temps_d, const double *density_d, void *work_d,
                                   int nmol, int ntemp, int nlayers, int nwave, int nwalkers,
-                                  TileLimit lim, void *stream);
+                                  TileLimit lim, void *stream, const pb_cont_batch *cont = nullptr);
 
 int pb_interp_ec_batch(double *ec_d, const double *etable_d, const double *ttable_d,
                        const double *temps_d, const double *density_d, void *work_d, int nmol,
@@ -1994,10 +2290,49 @@ int pb_interp_ec_batch_limited(double *ec_d, const double *etable_d, const doubl
                                   stream);
 }
 
+int64_t pb_interp_ec_batch_cont_work_doubles(const pb_cont_batch *cont, int nlayers, int nwave,
+                                             int nwalkers)
+{
+    const int nrec = cont_nrec(cont);
+    if (nrec < 0 || nlayers < 0 || nwave < 0 || nwalkers < 0)
+        return -1;
+    const int64_t n = (int64_t)nwalkers * nlayers;
+    return cont_rec_offset(n) + n * nrec + (int64_t)cont_nlec(cont) * nwalkers * nwave + 8;
+}
+
+int pb_interp_ec_batch_cont(double *ec_d, const double *etable_d, const double *ttable_d,
+                            const double *temps_d, const double *density_d, void *work_d,
+                            int nmol, int ntemp, int nlayers, int nwave, int nwalkers,
+                            const pb_cont_batch *cont, void *stream)
+{
+    const int rc = cont_check(cont);
+    if (rc != PB_OK)
+        return rc;
+    return interp_ec_batch_launch(ec_d, etable_d, ttable_d, temps_d, density_d, work_d, nmol, ntemp,
+                                  nlayers, nwave, nwalkers, TileLimit{nullptr, 0, nullptr}, stream,
+                                  cont);
+}
+
+int pb_interp_ec_batch_cont_limited(double *ec_d, const double *etable_d, const double *ttable_d,
+                                    const double *temps_d, const double *density_d, void *work_d,
+                                    int nmol, int ntemp, int nlayers, int nwave, int nwalkers,
+                                    const pb_cont_batch *cont, const int32_t *tile_limit_d,
+                                    int row0, const int32_t *gate_d, void *stream)
+{
+    const int rc = cont_check(cont);
+    if (rc != PB_OK)
+        return rc;
+    PB_REQUIRE(row0 >= 0 && row0 < std::max(nlayers, 1),
+               "pb_interp_ec_batch_cont_limited: row0 out of range");
+    return interp_ec_batch_launch(ec_d, etable_d, ttable_d, temps_d, density_d, work_d, nmol, ntemp,
+                                  nlayers, nwave, nwalkers, TileLimit{tile_limit_d, row0, gate_d},
+                                  stream, cont);
+}
+
 static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const double *ttable_d,
                                   const double *temps_d, const double *density_d, void *work_d,
                                   int nmol, int ntemp, int nlayers, int nwave, int nwalkers,
-                                  TileLimit lim, void *stream)
+                                  TileLimit lim, void *stream, const pb_cont_batch *cont)
 {
     PB_REQUIRE(nmol >= 1 && nmol <= 8 && ntemp >= 2 && nlayers >= 1 && nwave >= 0 &&
                    nwalkers >= 0,
@@ -2017,6 +2352,70 @@ static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const do
         k_interp_weights<<<pb::div_up(n, kBlock), kBlock, 0, s>>>(tlo, coef, ttable_d, temps_d,
                                                                 density_d, nmol, ncoef, ntemp, n);
         PB_LAUNCH_CHECK();
+    }
+    // continuum: per-(walker, layer) scalars and per-walker Lecavelier rows behind the weights
+    // (in the same workspace: a gated repair reuses them too)
+    ContEpi epi{};
+    int kcont = 0;
+    if (cont) {
+        const int nrec = cont_nrec(cont);
+        double *rec = reinterpret_cast<double *>(work_d) + cont_rec_offset(n);
+        double *rows = rec + n * nrec;
+        const int nlec = cont_nlec(cont);
+        if (!lim.gate) {
+            if (nrec > 0) {
+                ContPlanArgs pa{};
+                pa.rec = rec;
+                pa.temps = temps_d;
+                pa.density = cont->density_d;
+                pa.pars = cont->pars_d;
+                pa.nlayers = nlayers;
+                pa.ncs = cont->ncs;
+                pa.pars_stride = cont->pars_stride;
+                pa.nrec = nrec;
+                pa.n = n;
+                pa.c = *cont;
+                k_cont_plan<<<pb::div_up(n, kBlock), kBlock, 0, s>>>(pa);
+                PB_LAUNCH_CHECK();
+            }
+            if (nlec > 0) {
+                ContRowsArgs ra{};
+                ra.rows = rows;
+                ra.wn = cont->wn_d;
+                ra.pars = cont->pars_d;
+                ra.nwave = nwave;
+                ra.nwalkers = nwalkers;
+                ra.pars_stride = cont->pars_stride;
+                ra.nlec = nlec;
+                for (int m = 0, j = 0; m < cont->nrank1; m++)
+                    if (cont->rank1_kind[m] == 1) {
+                        ra.par[j] = cont->rank1_par[m];
+                        ra.s0[j] = cont->rank1_s0[m];
+                        ra.l0[j] = cont->rank1_l0[m];
+                        j++;
+                    }
+                k_cont_rows<<<dim3(pb::div_up(nwave, kBlock), nwalkers, nlec), kBlock, 0, s>>>(ra);
+                PB_LAUNCH_CHECK();
+            }
+        }
+        epi.nrank1 = cont->nrank1;
+        epi.ncia = cont->ncia;
+        epi.nrec = nrec;
+        for (int m = 0, j = 0; m < cont->nrank1; m++) {
+            epi.kind[m] = cont->rank1_kind[m];
+            if (epi.kind[m] == 0)
+                epi.row[m] = cont->rank1_cs_d[m];
+            else if (epi.kind[m] == 1)
+                epi.row[m] = rows + (int64_t)(j++) * nwalkers * nwave;
+        }
+        for (int c = 0; c < cont->ncia; c++)
+            epi.cia_tab[c] = cont->cia_tab_d[c];
+        epi.cia_mask = cont->cia_mask_d;
+        epi.wn = cont->wn_d;
+        epi.hm_sigma_bf = cont->hm_sigma_bf_d;
+        epi.hm_ff = cont->hm_ff_d;
+        epi.rec = rec;
+        kcont = cont->hminus ? 2 : 1;
     }
     // walkers per chunk: every chunk reads the table slices its walkers bracket again, so as many
     // as the launch can afford while it still fills the chip (C5, 64 walkers: 1.40 ms in chunks
@@ -2040,11 +2439,21 @@ static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const do
         np = 2;
     if (const char *e = getenv("PB_INTERP_NP"))
         np = atoi(e) == 2 ? 2 : 1;
-    if (pairs)
+    // with a continuum: one sample per thread.  The pair kernel with the epilogue needs 181 / 234
+    // VGPRs (continuum / + H-: two wavefronts per SIMD) and ran slower at C5's shape: 1.48 against
+    // 1.10 ms mean per launch, 4.35 against 3.69 ms per 64-walker transit step
+    if (pairs && !kcont)
         grid.x = pb::div_up(nwave / 2 + 2, kBlock * np);
+#define PB_INTERP_CONT(S, FULL, K)                                                             \
+    k_interp_ec_batch<S, FULL, K><<<grid, kBlock, 0, s>>>(ec_d, etable_d, tlo, coef, nmol, ntemp, \
+                                                          nlayers, nwave, nwalkers, chunk, lim, epi)
 #define PB_INTERP(S, FULL)                                                                     \
     do {                                                                                       \
-        if (pairs && np == 2)                                                                  \
+        if (kcont == 1)                                                                        \
+            PB_INTERP_CONT(S, FULL, 1);                                                        \
+        else if (kcont == 2)                                                                   \
+            PB_INTERP_CONT(S, FULL, 2);                                                        \
+        else if (pairs && np == 2)                                                                  \
             k_interp_ec_batch2<S, FULL, 2><<<grid, kBlock, 0, s>>>(ec_d, etable_d, tlo, coef,  \
                                                                    nmol, ntemp, nlayers, nwave, \
                                                                    nwalkers, chunk, lim);      \
@@ -2066,6 +2475,7 @@ static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const do
     else
         PB_INTERP(8, false);
 #undef PB_INTERP
+#undef PB_INTERP_CONT
     PB_LAUNCH_CHECK();
     return PB_OK;
 }

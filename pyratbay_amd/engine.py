@@ -518,17 +518,40 @@ def transit_path_device(radius, itop=0):
 
 
 def interp_ec_batch(etable, ttable, temps, dens, out=None, tile_limit=None, row0=0, gate=None,
-                    work=None):
+                    work=None, continuum=None, continuum_density=None, continuum_pars=None):
     """interp_ec for a batch of walkers (assigning): temps[nw, L], dens[nw, L, S] ->
     ec[nw, L, W]; the table is read once per chunk of walkers.  tile_limit (int32[ceil(W/256)],
     device) / row0: only the layers a block of 256 columns can need are written
     (pb_interp_ec_batch_limited); gate (int32[1], device): the launch does nothing unless the
-    flag is set, and runs on the `work` buffer its first pass filled."""
+    flag is set, and runs on the `work` buffer its first pass filled.
+    continuum: a continuum.Continuum (grid order) or its batch_operands(order) (the table's column
+    order): its terms are added to every sample before it is stored (pb_interp_ec_batch_cont),
+    with continuum_density[nw, L, len(continuum.species)] and continuum_pars[nw, npars] (None:
+    the models' current parameters) as device tensors."""
     nmol, ntemp, nlayers, nwave = etable.shape
     nw = temps.shape[0]
     assert temps.shape == (nw, nlayers) and dens.shape == (nw, nlayers, nmol)
     if out is None:
         out = torch.empty((nw, nlayers, nwave), dtype=torch.float64, device=etable.device)
+    if continuum is not None:
+        ops = continuum.batch_operands() if hasattr(continuum, 'batch_operands') else continuum
+        if continuum_pars is None and ops.npars:
+            continuum_pars = ops.default_pars()
+        cd = None if continuum_density is None else continuum_density.contiguous()
+        cp = None if continuum_pars is None else continuum_pars.contiguous()
+        if work is None:
+            work = torch.empty(ops.work_doubles(nlayers, nwave, nw), dtype=torch.float64,
+                               device=etable.device)
+        args = ops.args(cd, cp)
+        if tile_limit is None and gate is None:
+            call('pb_interp_ec_batch_cont', _ptr(out), _ptr(etable), _ptr(ttable),
+                 _ptr(temps.contiguous()), _ptr(dens.contiguous()), _ptr(work), nmol, ntemp,
+                 nlayers, nwave, nw, args, _stream())
+        else:
+            call('pb_interp_ec_batch_cont_limited', _ptr(out), _ptr(etable), _ptr(ttable),
+                 _ptr(temps.contiguous()), _ptr(dens.contiguous()), _ptr(work), nmol, ntemp,
+                 nlayers, nwave, nw, args, _ptr(tile_limit), int(row0), _ptr(gate), _stream())
+        return out
     if work is None:
         work = torch.empty(nw * nlayers * 17 + 8, dtype=torch.float64, device=etable.device)
     if tile_limit is None and gate is None:
@@ -1644,7 +1667,7 @@ class TableSpectrum:
         return self._timer.read()
 
     def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
-                   f_dilution=None):
+                   f_dilution=None, continuum_density=None, continuum_pars=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
         without the parameter mapping): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
@@ -1655,19 +1678,47 @@ class TableSpectrum:
         whose temperatures leave the table's range get +inf, like eval()'s reject path
         (pyrat_obj.py:302-320, 378-380).  Emission geometry: f_dilution[nw] = the walkers'
         dilution factors (pyrat_obj.py:296-297), and bands.set_eclipse(...) for the planet-to-star
-        flux ratios of an eclipse retrieval (pyrat_obj.py:662-665)."""
-        assert self.rt_path in ('transit', 'emission') and self.continuum is None, \
+        flux ratios of an eclipse retrieval (pyrat_obj.py:662-665).
+
+        With a Continuum attached (TableSpectrum(..., continuum=cont)) its terms are added in the
+        store of the interpolation (pb_interp_ec_batch_cont): continuum_density[nw, L, ncs] holds
+        the number densities of cont.species, continuum_pars[nw, npars] the free parameters in
+        cont.free_pars order (None: every walker uses the models' current pars).  A walker outside
+        a CIA table's temperatures is rejected like one outside the table.  A cloud deck and the
+        alkali models are refused in this form (ValueError); eval() takes them."""
+        assert self.rt_path in ('transit', 'emission'), \
             'eval_bands: transit or emission geometry on sampled cross sections'
         assert f_dilution is None or self.rt_path == 'emission', 'f_dilution: emission geometry'
         assert f_dilution is None or f_dilution.shape == (temps.shape[0],)
         nw = temps.shape[0]
+        tmin, tmax = self.tmin, self.tmax
+        cont = self.continuum
+        if cont is not None:
+            bad = cont.batch_unsupported()
+            if bad:
+                raise ValueError(f'eval_bands: continuum models {bad} are not supported in '
+                                 'batched form (cloud deck, alkali); use eval()')
+            shape = (nw, self.nlayers, len(cont.species))
+            got = None if continuum_density is None else tuple(continuum_density.shape)
+            if got != shape:
+                raise ValueError(f'eval_bands: continuum_density must be a device tensor of shape '
+                                 f'{shape} (species {cont.species}), got {got}')
+            npars = len(cont.free_pars)
+            if continuum_pars is not None and tuple(continuum_pars.shape) != (nw, npars):
+                raise ValueError(f'eval_bands: continuum_pars must have shape {(nw, npars)} '
+                                 f'({cont.free_pars}), got {tuple(continuum_pars.shape)}')
+            for m in cont.cia:
+                tmin, tmax = max(tmin, float(m.tmin)), min(tmax, float(m.tmax))
+        elif continuum_density is not None or continuum_pars is not None:
+            raise ValueError('eval_bands: continuum arguments without a Continuum')
+        cargs = (continuum_density, continuum_pars)
         out = torch.empty((nw, bands.nbands), dtype=torch.float64, device='cuda')
         if radius is None:
             radius = self.radius.view(1, -1)
         shared_radius = radius.shape[0] == 1
         transit = self.rt_path == 'transit'
         if self._auto_order and self.column_order is None and nw > 0 and self.nwave >= 64 and \
-                not (transit and self._one_pass()):
+                not (transit and self._one_pass() and cont is None):
             # ONE-TIME set-up of the first batch (class docstring): a host read-back, a sort and a
             # permuted second copy of the table.  Skipped -- grid order, nothing else changes --
             # where the ordered kernels do not exist for the shape, while the stream is being
@@ -1702,14 +1753,15 @@ class TableSpectrum:
             if streams > 1:
                 with torch.cuda.stream(self._eval_streams[ci % streams]):
                     self._eval_chunk(temps, dens, bands, radius, shared_radius, path1, out, w0,
-                                     min(w0 + chunk, nw), f_dilution)
+                                     min(w0 + chunk, nw), f_dilution, cargs)
             else:
                 self._eval_chunk(temps, dens, bands, radius, shared_radius, path1, out, w0,
-                                 min(w0 + chunk, nw), f_dilution)
+                                 min(w0 + chunk, nw), f_dilution, cargs)
         if streams > 1:
             for st in self._eval_streams[:streams]:
                 caller.wait_stream(st)
-        call('pb_reject_walkers', _ptr(out), _ptr(temps.contiguous()), self.tmin, self.tmax,
+        # (with CIA tables: the intersection of their temperature ranges and the table's)
+        call('pb_reject_walkers', _ptr(out), _ptr(temps.contiguous()), tmin, tmax,
              self.nlayers, bands.nbands, nw, _stream())
         return out
 
@@ -1735,10 +1787,12 @@ class TableSpectrum:
                                                       self.itop, self.nlayers, self.nwave)
 
     def _eval_chunk(self, temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
-                    f_dilution=None):
+                    f_dilution=None, cargs=(None, None)):
         """One chunk of eval_bands: walkers [w0, w1) through every stage, one launch each."""
         n = w1 - w0
-        if self.rt_path == 'transit' and self._one_pass():
+        cont = self.continuum
+        # (the one-pass transit takes no continuum: with one attached, the two passes)
+        if self.rt_path == 'transit' and self._one_pass() and cont is None:
             # interpolation + optical depth + transmission in one pass: ec is never stored
             if shared_radius:
                 rad = radius.expand(n, -1).contiguous()
@@ -1756,21 +1810,28 @@ class TableSpectrum:
         ordered = self.column_order is not None and self._ordered_supported()
         table = self.etable_ordered if ordered else self.etable
         limited = ordered and self.tile_limit is not None
+        # the continuum's operands in the table's column order, this chunk's walkers
+        ckw = {}
+        if cont is not None:
+            ckw = dict(continuum=cont.batch_operands(self.column_order if ordered else None),
+                       continuum_density=cargs[0][w0:w1],
+                       continuum_pars=None if cargs[1] is None else cargs[1][w0:w1])
         if limited:
             # (ec keeps whatever an earlier batch left in the layers that are not written: they are
             # read by no one, or the walker is flagged and repaired)
             flags = torch.zeros(n + 1, dtype=torch.int32, device=table.device)
-            iwork = torch.empty(n * self.nlayers * 17 + 8, dtype=torch.float64,
-                                device=table.device)
+            iwork = torch.empty(n * self.nlayers * 17 + 8 if cont is None else
+                                ckw['continuum'].work_doubles(self.nlayers, self.nwave, n),
+                                dtype=torch.float64, device=table.device)
             twork = None
             if self.rt_path == 'transit':
                 twork = torch.empty(_capi.lib().pb_transit_work_doubles(
                     self.nlayers, int(self.itop), int(self.nlayers), self.nwave, n),
                     dtype=torch.float64, device=table.device)
             ec = interp_ec_batch(table, self.ttable, temps[w0:w1], dens[w0:w1],
-                                 tile_limit=self.tile_limit, row0=self.itop, work=iwork)
+                                 tile_limit=self.tile_limit, row0=self.itop, work=iwork, **ckw)
         else:
-            ec = interp_ec_batch(table, self.ttable, temps[w0:w1], dens[w0:w1])
+            ec = interp_ec_batch(table, self.ttable, temps[w0:w1], dens[w0:w1], **ckw)
         if self.rt_path != 'transit':
             rad = radius.expand(n, -1) if shared_radius else radius[w0:w1]
             intervals = (rad[:, :-1] - rad[:, 1:]).contiguous()            # -diff(radius)
@@ -1781,7 +1842,7 @@ class TableSpectrum:
                                               tile_limit=self.tile_limit, flags=flags)
                 # (device-gated repair, as in the transit branch below)
                 interp_ec_batch(table, self.ttable, temps[w0:w1], dens[w0:w1], out=ec,
-                                gate=flags[n:n + 1], work=iwork)
+                                gate=flags[n:n + 1], work=iwork, **ckw)
                 emission_flux_batch(ec, intervals, self.wn_ordered, temps[w0:w1], self.mu,
                                     self.weights, self.itop, self.nlayers, self.maxdepth,
                                     self.column_order, gate=flags, out=spectra)
@@ -1808,7 +1869,7 @@ class TableSpectrum:
             # limit, then the transit of the flagged walkers -- two launches of workgroups that
             # return at once otherwise, no host round trip
             interp_ec_batch(table, self.ttable, temps[w0:w1], dens[w0:w1], out=ec,
-                            gate=flags[n:n + 1], work=iwork)
+                            gate=flags[n:n + 1], work=iwork, **ckw)
             transit_spectrum_ordered(ec, path, rad, self.column_order, self.rstar, self.itop,
                                      self.nlayers, self.maxdepth, gate=flags, out=spectra,
                                      work=twork)

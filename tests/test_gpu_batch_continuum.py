@@ -1,0 +1,378 @@
+"""The retrieval batch with continuum opacity (TableSpectrum.eval_bands with a Continuum, per-walker
+densities and free parameters; pb_interp_ec_batch_cont): band fluxes against the oracle chain, the
+one-walker eval(), and the fused kernel against the interpolation followed by Continuum.add.
+Reference: pyratbay/pyrat/pyrat_obj.py:277-283 (per-walker pars), opacity.py:206-257 (every model
+adds to one ec), opacity.py:310-337 + pyrat_obj.py:189-196, 376-380 (CIA temperature range ->
+reject).  CIA tables, temperatures and the grid come from fixture G7."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def eng():
+    from pyratbay_amd import engine
+    engine.require_gpu()
+    return engine
+
+
+@pytest.fixture(scope='module')
+def g(golden):
+    return golden('g7_continuum')
+
+
+@pytest.fixture(scope='module')
+def oc():
+    from oracle import continuum
+    return continuum
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def hydro_radius(rng, nlayers, scale):
+    base = np.linspace(8.0e9, 7.0e9, nlayers)
+    return base * (1.0 + scale * rng.uniform(-1, 1)) + np.linspace(0, 1, nlayers) * 2e7 * rng.uniform(-1, 1)
+
+
+def cia_models(g, ct):
+    out = []
+    for tag, species in (('h2h2', ['H2', 'H2']), ('h2he', ['H2', 'He'])):
+        m = ct.Collision_Induced.__new__(ct.Collision_Induced)
+        m.species, m.nspec = species, 2
+        m.name = 'CIA ' + '-'.join(species)
+        m.tab_cross_section, m.temps = g[f'cia_{tag}_tab'], g[f'cia_{tag}_temps']
+        m.ntemp, m.tmin, m.tmax = len(m.temps), m.temps.min(), m.temps.max()
+        m._wn_lo_idx, m._wn_hi_idx = (int(v) for v in g[f'cia_{tag}_lohi'])
+        out.append(m)
+    return out
+
+
+def setup(g, nw, L=None, seed=3, hminus=False, clouds=True):
+    """A synthetic table on G7's grid, walkers around G7's atmosphere, and the continuum:
+    Rayleigh H2 + He, [Lecavelier + CCSgray,] CIA H2-H2 + H2-He[, H-]."""
+    from pyratbay_amd import continuum as ct
+    rng = np.random.default_rng(seed)
+    wn = g['wn']
+    W = len(wn)
+    if L is None:
+        pressure, tbase = g['pressure'], g['temp']
+    else:
+        pressure = np.logspace(-6, 2, L)
+        tbase = np.interp(np.log(pressure), np.log(g['pressure']), g['temp'])
+    L = len(pressure)
+    nspec, ntemp = 3, 11
+    ttable = np.linspace(40.0, 3240.0, ntemp)         # (reaches below the CIA tables' 50 / 60 K)
+    etable = 10.0**rng.uniform(-27, -22, (nspec, ntemp, L, 1)) * \
+        10.0**rng.uniform(-1, 1, (nspec, 1, 1, W))
+    temps = tbase * (1 + 0.05 * rng.uniform(-1, 1, (nw, 1)))
+    ntot = pressure * 1e6 / temps / 1.380649e-16
+    dens = ntot[:, :, None] * 10.0**rng.uniform(-7, -4, (nw, 1, nspec))
+    models = [ct.Kurucz(wn, 'H2'), ct.Kurucz(wn, 'He')]
+    if clouds:
+        models += [ct.Lecavelier(pressure, wn=wn), ct.CCSgray(pressure, wn)]
+    models += cia_models(g, ct)
+    if hminus:
+        models.append(ct.Hydrogen_Ion(wn))
+    cont = ct.Continuum(wn, pressure, models)
+    vmr = {'H2': 0.85, 'He': 0.149, 'H': 1e-3, 'e-': 1e-6}
+    cdens = np.stack([ntot * vmr[s] * (1 + 0.1 * rng.uniform(-1, 1, (nw, 1)))
+                      for s in cont.species], axis=-1)
+    pars = None
+    if clouds:
+        pars = np.stack([rng.uniform(-1, 1, nw), rng.uniform(-6, -2, nw),          # Lecavelier
+                         rng.uniform(-1, 1, nw), rng.uniform(-4, -1, nw),
+                         rng.uniform(0, 1.5, nw)], axis=1)                          # CCSgray
+    return dict(wn=wn, pressure=pressure, ttable=ttable, etable=etable, temps=temps, dens=dens,
+                cont=cont, cdens=cdens, pars=pars, rng=rng, models=models)
+
+
+def set_pars(s, w):
+    """The walker's parameters on the models (what eval() and Continuum.add read)."""
+    if s['pars'] is None:
+        return
+    for m in s['cont'].rank1:
+        if m.name == 'lecavelier':
+            m.pars[:] = list(s['pars'][w, :2])
+        elif m.name == 'ccsgray':
+            m.pars[:] = list(s['pars'][w, 2:5])
+
+
+def density_dict(s, w):
+    return {sp: s['cdens'][w, :, i].copy() for i, sp in enumerate(s['cont'].species)}
+
+
+def oracle_ec(orc, oc, s, w, g):
+    """interp_ec + every continuum term of walker w, from the oracle's functions."""
+    L, W = len(s['pressure']), len(s['wn'])
+    ec = np.zeros((L, W))
+    orc.interp_ec(ec, s['etable'], s['ttable'], s['temps'][w], s['dens'][w], 0, L)
+    t, d = s['temps'][w], density_dict(s, w)
+    nominal = oc.nominal_density(s['pressure'], t)
+    for m in s['cont'].rank1:
+        if m.name == 'lecavelier':
+            ec += oc.lecavelier_cross_section(s['wn'], s['pars'][w, :2]) * nominal[:, None]
+        elif m.name == 'ccsgray':
+            ec += (oc.gray_layer_cross_section(s['pressure'], s['pars'][w, 2:5]) * nominal)[:, None]
+        else:
+            ec += oc.rayleigh_cross_section(s['wn'], m.species) * d[m.species][:, None]
+    for m, tag in zip(s['cont'].cia, ('h2h2', 'h2he')):
+        lo, hi = g[f'cia_{tag}_lohi']
+        cs = oc.cia_cross_section(g[f'cia_{tag}_tab'], g[f'cia_{tag}_temps'], t, int(lo), int(hi))
+        ec += cs * (d[m.species[0]] * d[m.species[1]])[:, None]
+    if s['cont'].hminus:
+        bf, ff = oc.hminus_cross_sections(s['wn'], t)
+        ec += (bf + ff) * (d['H'] * d['e-'])[:, None]
+    return ec
+
+
+def make_bands(eng, wn):
+    bands = []
+    for lo, hi in ((20, 300), (250, 700), (650, 990)):
+        resp = np.exp(-np.linspace(-1.5, 1.5, hi - lo)**2)
+        bands.append((lo, resp, 1.0 / np.trapezoid(resp, wn[lo:hi])))
+    return bands, eng.PassBands(wn, bands)
+
+
+def split_ec(eng, s, cont, pars, nw):
+    """Today's two steps: interp_ec_batch, then Continuum.add (k_continuum) walker by walker."""
+    ec = eng.interp_ec_batch(eng.dev(s['etable']), eng.dev(s['ttable']),
+                             eng.dev(s['temps'][:nw]), eng.dev(s['dens'][:nw]))
+    for w in range(nw):
+        if pars is not None:
+            set_pars(s, w)
+        cont.add(ec[w], s['temps'][w], density_dict(s, w))
+    return host(ec)
+
+
+def fused_ec(eng, s, cont, pars, nw):
+    return host(eng.interp_ec_batch(eng.dev(s['etable']), eng.dev(s['ttable']),
+                                    eng.dev(s['temps'][:nw]), eng.dev(s['dens'][:nw]),
+                                    continuum=cont, continuum_density=eng.dev(s['cdens'][:nw]),
+                                    continuum_pars=None if pars is None else eng.dev(pars[:nw])))
+
+
+def test_fused_kernel_equals_interpolation_plus_continuum(eng, g):
+    """The epilogue adds what Continuum.add adds, in its order: bit for bit for Rayleigh, CIA and H-
+    (same IEEE operations, same bracket rule); the Lecavelier / gray 10**x and pow on the device
+    instead of NumPy: 1e-14."""
+    from pyratbay_amd import continuum as ct
+    nw = 20
+    s = setup(g, nw, hminus=True, clouds=False)
+    want = split_ec(eng, s, s['cont'], None, nw)
+    got = fused_ec(eng, s, s['cont'], None, nw)
+    assert np.array_equal(got, want)
+    # and with the clouds (per-walker parameters)
+    s = setup(g, nw, hminus=True, clouds=True, seed=8)
+    want = split_ec(eng, s, s['cont'], s['pars'], nw)
+    got = fused_ec(eng, s, s['cont'], s['pars'], nw)
+    np.testing.assert_allclose(got, want, rtol=1e-14)
+    # the models' current parameters when continuum_pars is None
+    set_pars(s, 5)
+    one = host(eng.interp_ec_batch(eng.dev(s['etable']), eng.dev(s['ttable']),
+                                   eng.dev(s['temps'][:nw]), eng.dev(s['dens'][:nw]),
+                                   continuum=s['cont'],
+                                   continuum_density=eng.dev(s['cdens'][:nw])))
+    np.testing.assert_array_equal(one[5], got[5])
+    # more rank-1 terms than the epilogue keeps in registers (the sixth is re-read per walker)
+    wn = s['wn']
+    models = [ct.Kurucz(wn, sp) for sp in ('H2', 'He', 'H', 'e-', 'H2', 'He')] + cia_models(g, ct)
+    s2 = setup(g, 6, clouds=False, seed=9)
+    s2['cont'] = ct.Continuum(wn, s2['pressure'], models)
+    s2['cdens'] = s2['cdens'][:, :, [0, 1, 0, 1]] * np.array([1, 1, 1e-3, 1e-6])
+    assert s2['cont'].species == ['H2', 'He', 'H', 'e-']
+    assert np.array_equal(fused_ec(eng, s2, s2['cont'], None, 6),
+                          split_ec(eng, s2, s2['cont'], None, 6))
+
+
+def test_transit_64_walkers(eng, orc, oc, g):
+    """64 walkers, per-walker radius and cloud parameters, chunk=24: band fluxes against the
+    oracle chain (1e-11) and the one-walker eval() (1e-13)."""
+    nw = 64
+    s = setup(g, nw, seed=21)
+    cont, wn = s['cont'], s['wn']
+    L = len(s['pressure'])
+    assert cont.species == ['H2', 'He']
+    assert cont.free_pars == [('lecavelier', 0), ('lecavelier', 1), ('ccsgray', 0),
+                              ('ccsgray', 1), ('ccsgray', 2)]
+    rstar = 8.8e10
+    base_radius = np.linspace(8.0e9, 7.0e9, L)
+    model = eng.TableSpectrum(s['etable'], s['ttable'], wn, base_radius, rstar, continuum=cont)
+    bands, pb = make_bands(eng, wn)
+    radius = np.array([hydro_radius(s['rng'], L, 0.01) for _ in range(nw)])
+    got = host(model.eval_bands(eng.dev(s['temps']), eng.dev(s['dens']), pb,
+                                radius=eng.dev(radius), chunk=24,
+                                continuum_density=eng.dev(s['cdens']),
+                                continuum_pars=eng.dev(s['pars'])))
+    assert np.all(np.isfinite(got))
+    for w in range(0, nw, 9):
+        ec = oracle_ec(orc, oc, s, w, g)
+        depth, ideep = orc.optical_depth_transit(ec, radius[w], 0, L, 10.0)
+        spec = orc.transmission(depth, radius[w], rstar, ideep, 0)
+        want = [np.trapezoid(spec[a:a + len(r)] * r, wn[a:a + len(r)]) * h for a, r, h in bands]
+        np.testing.assert_allclose(got[w], want, rtol=1e-11)
+    for w in (0, 33, 63):
+        set_pars(s, w)
+        model.set_radius(radius[w])
+        spec = model.eval(s['temps'][w], eng.dev(s['dens'][w]), density_dict(s, w))
+        one = host(pb.partial_integrate(spec) * pb.heights)
+        np.testing.assert_allclose(got[w], one, rtol=1e-13)
+    # shared radius, the models' current parameters
+    model.set_radius(base_radius)
+    set_pars(s, 7)
+    got2 = host(model.eval_bands(eng.dev(s['temps'][:8]), eng.dev(s['dens'][:8]), pb,
+                                 continuum_density=eng.dev(s['cdens'][:8])))
+    spec = model.eval(s['temps'][7], eng.dev(s['dens'][7]), density_dict(s, 7))
+    np.testing.assert_allclose(got2[7], host(pb.partial_integrate(spec) * pb.heights), rtol=1e-13)
+
+
+def test_emission_hminus_eclipse(eng, orc, oc, g):
+    """Emission with H- + CIA + Rayleigh, f_dilution per walker and eclipse bands: against the
+    oracle chain, eval(), and the fused kernel against the two steps bit for bit."""
+    nw = 21
+    s = setup(g, nw, seed=5, hminus=True, clouds=False)
+    cont, wn = s['cont'], s['wn']
+    L = len(s['pressure'])
+    assert cont.species == ['H2', 'He', 'H', 'e-'] and cont.free_pars == []
+    assert np.array_equal(fused_ec(eng, s, cont, None, nw), split_ec(eng, s, cont, None, nw))
+    rstar, rplanet = 8.8e10, 7.4e9
+    base_radius = np.linspace(8.0e9, 7.0e9, L)
+    model = eng.TableSpectrum(s['etable'], s['ttable'], wn, base_radius, rstar,
+                              rt_path='emission', continuum=cont)
+    bands, pb = make_bands(eng, wn)
+    starflux = 2.0e6 * (1.0 + 0.1 * np.sin(wn / 70.0))
+    star = pb.star_bandflux(starflux)
+    pb.set_eclipse(rplanet, rstar, star)
+    fd = s['rng'].uniform(0.5, 1.0, nw)
+    radius = np.array([hydro_radius(s['rng'], L, 0.01) for _ in range(nw)])
+    got = host(model.eval_bands(eng.dev(s['temps']), eng.dev(s['dens']), pb,
+                                radius=eng.dev(radius), chunk=8, f_dilution=eng.dev(fd),
+                                continuum_density=eng.dev(s['cdens'])))
+    assert np.all(np.isfinite(got))
+    mu, weights = eng.default_quadrature()
+    for w in (0, 7, 20):
+        ec = oracle_ec(orc, oc, s, w, g)
+        depth, ideep = np.zeros((L, len(wn))), np.full(len(wn), L - 1, np.int32)
+        orc.plane_parallel_optical_depth(depth, ideep, ec, -orc.ediff(radius[w]), 10.0, 0, L)
+        flux = orc.emission_deck(depth, ideep, wn, s['temps'][w], mu, weights, 0)
+        _, fplanet = orc.emission_observables(flux, 'eclipse', starflux, rplanet, rstar, fd[w])
+        bf = [np.trapezoid(fplanet[a:a + len(r)] * r, wn[a:a + len(r)]) * h for a, r, h in bands]
+        np.testing.assert_allclose(got[w], orc.eclipse_bandflux(bf, rplanet, rstar, star),
+                                   rtol=1e-11)
+        model.set_radius(radius[w])
+        spec = model.eval(s['temps'][w], eng.dev(s['dens'][w]), density_dict(s, w))
+        pb_plain = eng.PassBands(wn, bands)
+        one = host(pb_plain.partial_integrate(spec) * pb_plain.heights) * fd[w]
+        np.testing.assert_allclose(got[w], orc.eclipse_bandflux(one, rplanet, rstar, star),
+                                   rtol=1e-13)
+
+
+@pytest.mark.parametrize('rt_path', ['transit', 'emission'])
+def test_column_order_and_tile_limits(eng, g, rt_path):
+    """column_order='auto', an explicit permutation, and tile limits low enough to need the gated
+    repair: band fluxes bit for bit those of the grid order."""
+    import torch
+    nw, L = 12, 40
+    s = setup(g, nw, L=L, seed=77, hminus=rt_path == 'emission')
+    wn = s['wn']
+    radius0 = np.linspace(8.0e9, 7.0e9, L)
+    radius = radius0[None] * (1 + 0.01 * s['rng'].uniform(-1, 1, (nw, 1)))
+    _, pb = make_bands(eng, wn)
+    args = [eng.dev(x) for x in (s['temps'], s['dens'])]
+    kw = dict(radius=eng.dev(radius), continuum_density=eng.dev(s['cdens']),
+              continuum_pars=eng.dev(s['pars']), chunk=8)
+    out = {}
+    for name, order, margin in (('grid', None, 4), ('auto', 'auto', 4), ('tight', 'auto', 0),
+                                ('given', s['rng'].permutation(len(wn)), 4)):
+        model = eng.TableSpectrum(s['etable'], s['ttable'], wn, radius0, 8.8e10, rt_path=rt_path,
+                                  column_order=order, continuum=s['cont'])
+        model.tile_margin = margin
+        out[name] = model.eval_bands(*args, pb, **kw).clone()
+        assert (model.column_order is None) == (name == 'grid')
+        if name == 'tight' and rt_path == 'transit':
+            assert model.tile_limit is not None
+    for name in ('auto', 'tight', 'given'):
+        assert torch.equal(out[name], out['grid']), name
+    assert bool(torch.isfinite(out['grid']).all())
+
+
+def test_limited_and_gated_repair_add_the_terms(eng, g):
+    """pb_interp_ec_batch_cont_limited writes the layers a block may need, with the terms; the
+    gated repair on the same workspace completes ec to the unlimited result bit for bit."""
+    import torch
+    nw, L = 6, 40
+    s = setup(g, nw, L=L, seed=12, hminus=True)
+    ops = s['cont'].batch_operands()
+    et, tt = eng.dev(s['etable']), eng.dev(s['ttable'])
+    td, dd = eng.dev(s['temps']), eng.dev(s['dens'])
+    ckw = dict(continuum=ops, continuum_density=eng.dev(s['cdens']),
+               continuum_pars=eng.dev(s['pars']))
+    full = eng.interp_ec_batch(et, tt, td, dd, **ckw)
+    W = len(s['wn'])
+    tile = torch.zeros(-(-W // 256), dtype=torch.int32, device='cuda')     # 16 layers only
+    work = torch.empty(ops.work_doubles(L, W, nw), dtype=torch.float64, device='cuda')
+    ec = torch.full_like(full, -1.0)
+    eng.interp_ec_batch(et, tt, td, dd, out=ec, tile_limit=tile, row0=2, work=work, **ckw)
+    assert torch.equal(ec[:, 2:18], full[:, 2:18])
+    assert bool((ec[:, :2] == -1).all()) and bool((ec[:, 18:] == -1).all())
+    flags = torch.zeros(nw + 1, dtype=torch.int32, device='cuda')
+    eng.interp_ec_batch(et, tt, td, dd, out=ec, gate=flags[nw:], work=work, **ckw)
+    assert bool((ec[:, 18:] == -1).all())                       # gate closed: nothing written
+    flags[nw] = 1
+    eng.interp_ec_batch(et, tt, td, dd, out=ec, gate=flags[nw:], work=work, **ckw)
+    assert torch.equal(ec, full)
+
+
+def test_walker_outside_a_cia_table(eng, g):
+    """A walker inside the table's temperatures but below a CIA table's tmin gets +inf (the
+    reference's check_temp_bounds -> reject); every other walker keeps its bits."""
+    import torch
+    nw = 10
+    s = setup(g, nw, seed=31)
+    model = eng.TableSpectrum(s['etable'], s['ttable'], s['wn'], np.linspace(8.0e9, 7.0e9, 12),
+                              8.8e10, continuum=s['cont'])
+    _, pb = make_bands(eng, s['wn'])
+    kw = dict(continuum_density=eng.dev(s['cdens']), continuum_pars=eng.dev(s['pars']))
+    ref = model.eval_bands(eng.dev(s['temps']), eng.dev(s['dens']), pb, **kw).clone()
+    temps = s['temps'].copy()
+    temps[4, 0] = 45.0                  # table from 40 K, CIA tables from 50 / 60 K
+    assert s['ttable'][0] < 45.0 < min(m.tmin for m in s['cont'].cia)
+    got = model.eval_bands(eng.dev(temps), eng.dev(s['dens']), pb, **kw)
+    assert bool(torch.isinf(got[4]).all()) and bool((got[4] > 0).all())
+    keep = [w for w in range(nw) if w != 4]
+    assert torch.equal(got[keep], ref[keep])
+
+
+def test_refusals(eng, g):
+    """Deck and alkali models, a missing or misshaped continuum_density and misshaped
+    continuum_pars raise ValueError before any launch; eval() with a Deck still works."""
+    from pyratbay_amd import continuum as ct
+    nw = 4
+    s = setup(g, nw, seed=2)
+    wn, pressure = s['wn'], s['pressure']
+    L = len(pressure)
+    radius = np.linspace(8.0e9, 7.0e9, L)
+    _, pb = make_bands(eng, wn)
+    td, dd = eng.dev(s['temps']), eng.dev(s['dens'])
+    cd, cp = eng.dev(s['cdens']), eng.dev(s['pars'])
+    for extra in (ct.Deck(pressure, wn), ct.SodiumVdW(pressure, wn=wn)):
+        cont = ct.Continuum(wn, pressure, s['models'] + [extra])
+        model = eng.TableSpectrum(s['etable'], s['ttable'], wn, radius, 8.8e10, continuum=cont)
+        with pytest.raises(ValueError, match='not supported in batched form'):
+            model.eval_bands(td, dd, pb, continuum_density=cd, continuum_pars=cp)
+    model = eng.TableSpectrum(s['etable'], s['ttable'], wn, radius, 8.8e10, continuum=s['cont'])
+    with pytest.raises(ValueError, match='continuum_density'):
+        model.eval_bands(td, dd, pb)
+    with pytest.raises(ValueError, match='continuum_density'):
+        model.eval_bands(td, dd, pb, continuum_density=cd[:, :, :1].contiguous())
+    with pytest.raises(ValueError, match='continuum_pars'):
+        model.eval_bands(td, dd, pb, continuum_density=cd, continuum_pars=cp[:, :4].contiguous())
+    with pytest.raises(ValueError, match='continuum_pars'):
+        model.eval_bands(td, dd, pb, continuum_density=cd, continuum_pars=cp[:2].contiguous())
+    # eval() keeps taking a Deck (it adds nothing to ec there)
+    cont = ct.Continuum(wn, pressure, s['models'] + [ct.Deck(pressure, wn)])
+    model = eng.TableSpectrum(s['etable'], s['ttable'], wn, radius, 8.8e10, continuum=cont)
+    spec = host(model.eval(s['temps'][0], dd[0], density_dict(s, 0)))
+    assert np.all(np.isfinite(spec))
