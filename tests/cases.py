@@ -1,6 +1,7 @@
 """Seeded small inputs shared by the golden-vector generator and the parity tests.
 
-Pure NumPy; nothing here computes expected values."""
+Pure NumPy; the only expected values computed here are the oracle's Voigt tables
+(oracle_voigt_table, oracle_voigt_rows), built by the oracle passed in."""
 import os
 
 import numpy as np
@@ -146,3 +147,206 @@ def table_case(seed=11):
     temps = np.array([300.0, 450.0, 700.0, 1099.999, 1800.0, 2999.0, 3000.0])
     dens = 10.0**rng.uniform(8, 18, (nlayers, nmol))
     return dict(etable=etable, ttable=ttable, temps=temps, dens=dens)
+
+
+# ---------------------------------------------------------------------------
+# Voigt tables: the planner's regime decisions, a boundary grid, independent tables
+# ---------------------------------------------------------------------------
+def voigt_plan(half, dwn, alphaD):
+    """(regime, over) of one table cell of half-size `half`: the decisions voigtn takes before
+    it evaluates (voigt.h:235-262), restated in binary64 like pb_voigt.hip's plan_cell and the
+    oracle.  'quick' = point samples (more than 99 999 samples), 'mean' = mean of the two
+    bounding points (the step resolves the Doppler core), 'simpson' = Simpson mean over `over`
+    sub-intervals (`over` is rounded up to an even number, so the trapezoid form with
+    over > 1 never runs)."""
+    nwn = 2 * int(half) + 1
+    halfwidth = dwn * (nwn // 2)
+    step = 2.0 * halfwidth / (nwn - 1)
+    fine = alphaD / (50 - 1)
+    if nwn > 99999:
+        return 'quick', 1
+    if step < fine:
+        return 'mean', 1
+    over = int(step / fine) + 1
+    if over & 1:
+        over += 1
+    return 'simpson', over
+
+
+def voigt_regimes(doppler, size, dwn):
+    """Regime of every cell of a width grid ('' for the aliased cells, size 0)."""
+    out = np.full(np.shape(size), '', dtype=object)
+    for (m, n), half in np.ndenumerate(np.asarray(size)):
+        if half:
+            out[m, n] = voigt_plan(half, dwn, float(doppler[n]))[0]
+    return out
+
+
+def _doppler_at_ratio(step, k):
+    """Doppler widths a with step / (a / 49) == k exactly and with the largest quotient below k
+    (searched over the doubles next to 49 * step / k, evaluated as the planner does)."""
+    a0 = 49.0 * step / k
+    cands = [a0]
+    up = down = a0
+    for _ in range(256):
+        up, down = np.nextafter(up, np.inf), np.nextafter(down, 0.0)
+        cands += [float(up), float(down)]
+    ratio = {a: step / (a / 49) for a in cands}
+    at = [a for a in cands if ratio[a] == k]
+    below = max((a for a in cands if ratio[a] < k), key=lambda a: ratio[a])
+    assert at, f'no Doppler width puts step/fine at {k}'
+    return at[0], below
+
+
+def voigt_boundary_case():
+    """A hand-made width grid whose cells sit exactly on the switches of voigtn (voigt.h:147-359):
+
+    * half 49 999 / 50 000: 99 999 samples (oversampled) / 100 001 samples (QUICK);
+    * half 1: the 3-sample minimum;
+    * step / fine = 1, 2, 3 exactly and just below each (two-point mean vs Simpson at 1;
+      over = 2 vs 4 at 2; the odd over = 3 rounded up to 4 at 3);
+    * a Doppler width 5 000 times below the step (over in the thousands);
+    * y = sqrt(ln 2) alphaL / alphaD within 1e-12 on either side of 1.8 and of 5 (the switches
+      between the series (Region I), the 3-term and the 2-term rational forms);
+    * a row whose Doppler columns after the first are all aliased (size 0).
+
+    Returns dict(lorentz, doppler, dwn, size, ratio_cols, y): ratio_cols[n] = (k, 'at' | 'below')
+    for the columns placed on step / fine = k (at half-size 40), y[m, n] the cells' y."""
+    dwn = 1.0e-3
+    hb = 40                                   # half-size of the cells of the step/fine columns
+    step = 2.0 * (dwn * hb) / (2 * hb)
+    doppler = [4.0e-3]                        # column 0: step/fine = 12.25 -> over 14
+    ratio_cols = {}
+    for k in (1, 2, 3):
+        at, below = _doppler_at_ratio(step, k)
+        ratio_cols[len(doppler)] = (k, 'at')
+        ratio_cols[len(doppler) + 1] = (k, 'below')
+        doppler += [at, below]
+    big = len(doppler)
+    doppler.append(1.0e-5)                    # step / fine = 4 900 -> over 4 902
+    doppler.append(0.3)                       # step < fine: two-point mean at any half
+    sq = float(np.sqrt(np.log(2.0)))
+    d0 = doppler[0]
+    # y at column 0 on either side of 1.8 and 5, and two generic rows
+    lorentz = [1.0e-4, 0.02]
+    for yb in (1.8, 5.0):
+        for rel in (-1e-12, 1e-12):
+            lorentz.append(yb * (1.0 + rel) * d0 / sq)
+    nd = len(doppler)
+    size = np.zeros((len(lorentz) + 1, nd), np.int64)
+    lorentz.append(3.0e-3)                    # the aliased row
+    # row 0: the step/fine columns at half hb, the extremes of the half-size elsewhere
+    size[0] = hb
+    size[0, 0] = 1
+    size[0, big] = 12
+    size[0, big + 1] = 50000
+    # row 1: 99 999 samples (Simpson in column 0, two-point mean in the last), 100 001 samples,
+    # a 3-sample cell followed by aliases
+    size[1] = 0
+    size[1, 0] = 49999
+    size[1, big + 1] = 49999
+    size[1, 2] = 50000
+    size[1, 3] = 1
+    size[1, big] = 7
+    # rows 2..5 (y on a switch): the whole row, mixed sizes
+    for m in range(2, 6):
+        size[m] = [300, hb, hb, hb, hb, hb, hb, 9, 2500][:nd]
+    # the last row: every column after the first aliased
+    size[-1, 0] = 777
+    lorentz = np.asarray(lorentz)
+    doppler = np.asarray(doppler)
+    return dict(lorentz=lorentz, doppler=doppler, dwn=dwn, size=size, ratio_cols=ratio_cols,
+                y=sq * lorentz[:, None] / doppler[None, :])
+
+
+# the width grids of the full-size configurations (bench.py WORKLOADS, test_gpu_configs.FULL);
+# the widths do not depend on the line list, so a handful of lines builds them
+C4_SPECIES = ('H2', 'He', 'H2O', 'CO', 'CO2', 'CH4')
+C4_VMR = (0.85, 0.149, 4e-4, 5e-4, 1e-7, 1e-4)
+FULL_GRIDS = {
+    'c2': ((100001, 80), dict(wnstep=0.05, niso=1)),
+    'c3': ((1000001, 80), dict(wnstep=0.005, niso=4)),
+    'c4': ((1000001, 120), dict(wnstep=0.005, niso=4, species=C4_SPECIES, vmr=C4_VMR,
+                                line_species=('H2O', 'CO', 'CO2', 'CH4'))),
+    'c2-res': ((100001, 80), dict(wnstep=0.05, niso=1, resolution=123300.0)),
+}
+
+
+def full_width_grid(name, nlines=16):
+    """synth.lbl_case of a full-size configuration with a short line list."""
+    args, kw = FULL_GRIDS[name]
+    return synth.lbl_case(args[0], args[1], nlines, seed=42, **kw)
+
+
+_ORACLE_TABLE = {}
+
+
+def oracle_voigt_table(orc, voigt, ownstep):
+    """(profile, size, index) of the width grid voigt = dict(lorentz, doppler, size) as the
+    oracle builds it (orc.voigt_grid, the plain-C restatement of vprofile.grid): NumPy arrays,
+    read-only.  Parity tests of the extinction hand THIS table to the oracle, not the one the
+    GPU built, so that a wrong table cell cannot hide behind both sides reading it.  The last
+    grid is kept: configurations that share a width grid reuse it, and at full size one table
+    is up to 1.9 GB."""
+    lorentz = np.ascontiguousarray(voigt['lorentz'], np.float64)
+    doppler = np.ascontiguousarray(voigt['doppler'], np.float64)
+    size_in = np.asarray(voigt['size'])
+    key = (lorentz.tobytes(), doppler.tobytes(), size_in.shape,
+           size_in.astype(np.int64).tobytes(), float(ownstep))
+    if key not in _ORACLE_TABLE:
+        _ORACLE_TABLE.clear()
+        size = size_in.astype(np.int32)
+        index = np.zeros_like(size)
+        profile = np.zeros(int(np.sum(2 * size[size > 0].astype(np.int64) + 1)))
+        orc.voigt_grid(profile, size, index, lorentz, doppler, float(ownstep))
+        for a in (profile, size, index):
+            a.flags.writeable = False
+        _ORACLE_TABLE[key] = (profile, size, index)
+    return _ORACLE_TABLE[key]
+
+
+def oracle_voigt_rows(orc, lorentz, doppler, size, dwn, grid=None):
+    """The oracle's table one Lorentz row at a time (host memory stays near one row):
+    yields (m, start, profile_row, size_row, index_row) with index_row in the whole table's
+    numbering.  grid = orc.voigt_grid or a function of the same signature (the compiled
+    reference's vprofile.grid without its trailing `verb`)."""
+    grid = grid or orc.voigt_grid
+    size = np.asarray(size)
+    start = 0
+    for m in range(size.shape[0]):
+        srow = size[m:m + 1].astype(np.int32)
+        irow = np.zeros_like(srow)
+        prow = np.zeros(int(np.sum(2 * srow[srow > 0].astype(np.int64) + 1)))
+        grid(prow, srow, irow, np.ascontiguousarray(lorentz[m:m + 1], np.float64),
+             np.ascontiguousarray(doppler, np.float64), float(dwn))
+        yield m, start, prow, srow[0], irow[0] + start
+        start += prow.size
+
+
+def compare_voigt_tables(got_row, want_rows, regimes, rtol):
+    """Compare a table with the rows of oracle_voigt_rows: for every row the same size and
+    index, the same zero pattern and every sample within rtol.  got_row(m, start, n) returns
+    (profile_row, size_row, index_row) of the table under test.  Returns the worst relative
+    error and the number of cells per regime (regimes: voigt_regimes of the input sizes) and
+    the number of samples compared."""
+    worst = {'quick': 0.0, 'mean': 0.0, 'simpson': 0.0}
+    count = {'quick': 0, 'mean': 0, 'simpson': 0}
+    total = 0
+    for m, start, want, wsize, windex in want_rows:
+        got, gsize, gindex = got_row(m, start, want.size)
+        assert np.array_equal(gsize, wsize), f'row {m}: size differs'
+        assert np.array_equal(gindex, windex), f'row {m}: index differs'
+        assert got.shape == want.shape, f'row {m}: {got.shape} samples, want {want.shape}'
+        assert np.array_equal(got == 0, want == 0), f'row {m}: zero pattern differs'
+        rel = np.zeros(want.size)
+        nz = want != 0
+        rel[nz] = np.abs(got[nz] - want[nz]) / np.abs(want[nz])
+        cells = np.flatnonzero(regimes[m] != '')
+        per_cell = np.maximum.reduceat(rel, windex[cells] - start)
+        for n, err in zip(cells, per_cell):
+            kind = regimes[m, n]
+            worst[kind] = max(worst[kind], float(err))
+            count[kind] += 1
+            assert err <= rtol, f'cell ({m}, {n}), {kind}: relative error {err:.3e} > {rtol:.0e}'
+        total += want.size
+    return worst, count, total

@@ -11,11 +11,14 @@
 * C5 at FULL size: one 64-walker batch of the retrieval inner loop -- run-to-run bitwise equal,
   independent of how the walkers are chunked, out-of-range temperatures rejected, the one-walker
   eval() chain and the oracle chain on sampled walkers.
+* c2-res at FULL size: the `resolution` mode (dynamic grids and the direct gather), every layer
+  of ec and the transit spectrum against the oracle.
 * C1 (the reference's CPU-runnable tutorial shape: 4 501 wavenumbers x 51 layers, one species):
   the whole path, every layer of ec and the transit / emission spectrum against the oracle.
 
 Tolerance as in test_gpu_extinction.py: rtol 1e-10 against the oracle on every non-zero
-sample and an identical zero pattern."""
+sample and an identical zero pattern.  The oracle reads its own Voigt table
+(cases.oracle_voigt_table), never the one the GPU built."""
 import time
 
 import numpy as np
@@ -42,16 +45,25 @@ def host(t):
     return t.cpu().numpy()
 
 
-def oracle_rows(orc, case, vt, profile, layer, add, ethresh=1e-30):
+def oracle_table(orc, case, vt):
+    """The oracle's own Voigt table of the case's width grid (profile, size, index), never the
+    one the GPU built; its layout is the one the HIP table reports."""
+    table = cases.oracle_voigt_table(orc, case['voigt'], case['grid']['ownstep'])
+    assert np.array_equal(table[1], vt.size) and np.array_equal(table[2], vt.index)
+    return table
+
+
+def oracle_rows(orc, case, table, layer, add, ethresh=1e-30, resolution=0):
     g, atm, ln, iso, vg = (case[k] for k in ('grid', 'atm', 'lines', 'iso', 'voigt'))
+    profile, size, index = table
     rows = 1 if add else int(iso['isoiext'].max()) + 1
     want = np.zeros((rows, g['nwave']))
-    orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'], g['wn'],
+    orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'], g['wn'],
                    g['own'], g['divisors'], atm['dens'][layer], atm['mol_radius'],
                    atm['mol_mass'], iso['isoimol'], iso['isomass'], iso['isoratio'],
                    iso['isoz'][:, layer].copy(), iso['isoiext'], ln['lwn'], ln['elow'],
                    ln['gf'], ln['lid'], vg['cutoff'], ethresh, atm['temp'][layer], 0,
-                   int(add), 0)
+                   int(add), int(resolution))
     return want
 
 
@@ -92,13 +104,13 @@ def test_four_species_vs_oracle(eng, orc, gather, ethresh):
     lbl.set_gather_mode(gather)
     lbl.set_ethresh(ethresh)
     t, d, z = eng.dev(atm['temp']), eng.dev(atm['dens']), eng.dev(iso['isoz'])
-    profile = vt.flat()
+    table = oracle_table(orc, case, vt)
     worst = 0.0
     for add in (False, True):
         ext = host(lbl.extinction(t, d, z, add=add))
         assert ext.shape == (7, 1 if add else 4, case['grid']['nwave'])
         for layer in range(7):
-            want = oracle_rows(orc, case, vt, profile, layer, add, ethresh)
+            want = oracle_rows(orc, case, table, layer, add, ethresh)
             worst = max(worst, check(ext[layer], want, f'{gather} add={add} layer {layer}'))
         if not add:
             # every species row is populated and they differ (per-row kmax and density)
@@ -220,12 +232,12 @@ def test_full_size_config(eng, orc, name, monkeypatch):
     del glob
 
     # (4) oracle parity on sampled layers, full size
-    profile = vt.flat()
+    table = oracle_table(orc, case, vt)
     ec = host(full[list(cfg['layers'])])
     worst = 0.0
     for i, layer in enumerate(cfg['layers']):
         t1 = time.time()
-        want = oracle_rows(orc, case, vt, profile, layer, True)
+        want = oracle_rows(orc, case, table, layer, True)
         worst = max(worst, check(ec[i], want, f'{name} layer {layer}'))
         print(f'{name}: layer {layer} oracle {time.time() - t1:.1f} s')
     print(f'{name}: kernel {kernel}; shards exact; staged vs global {rel:.1e}; '
@@ -243,7 +255,7 @@ def test_full_size_config(eng, orc, name, monkeypatch):
         want = full[sub][:, 0]
         relr = ((total - want).abs() / want.abs().clamp_min(1e-300)).max().item()
         assert relr <= 1e-12, relr
-        want0 = oracle_rows(orc, case, vt, profile, 10, False)
+        want0 = oracle_rows(orc, case, table, 10, False)
         check(host(rows[0]), want0, 'c4 add=0 layer 10')
 
 
@@ -260,10 +272,10 @@ def test_c1_tutorial_shape(eng, orc, rt_path):
     assert (nl, nw) == (51, 4501)
     model = eng.LBLSpectrum(case, rt_path=rt_path)
     spectrum = host(model.run())
-    profile = model.voigt.flat()
+    table = oracle_table(orc, case, model.voigt)
     ec = np.zeros((nl, nw))
     for layer in range(nl):
-        ec[layer] = oracle_rows(orc, case, model.voigt, profile, layer, True, case['ethresh'])[0]
+        ec[layer] = oracle_rows(orc, case, table, layer, True, case['ethresh'])[0]
     check(host(model.ec)[:, 0], ec, f'c1 {rt_path} ec')
     if rt_path == 'transit':
         depth, ideep = orc.optical_depth_transit(ec, atm['radius'], 0, nl, case['maxdepth'])
@@ -279,6 +291,54 @@ def test_c1_tutorial_shape(eng, orc, rt_path):
     assert np.array_equal(host(model.ideep), ideep)
     np.testing.assert_allclose(spectrum, want, rtol=RTOL)
     assert want.max() / want.min() > 1.0005
+
+
+# ---------------------------------------------------------------------------
+# c2-res at FULL size (bench.py --workload c2-res): the `resolution` mode, R = 123 300 over the
+# wnosamp-2520 fine grid, whose spectra go through the layers' dynamic grids and the re-cut tables
+# filled one Lorentz row at a time (pb_voigt_rephase / pb_voigt_ensure_rows)
+# ---------------------------------------------------------------------------
+def test_full_size_c2_res(eng, orc):
+    import torch
+    from pyratbay_amd import synth
+    t0 = time.time()
+    case = synth.lbl_case(100001, 80, 100000, wnstep=0.05, niso=1, resolution=123300.0, seed=42)
+    g, atm = case['grid'], case['atm']
+    nl, nw = atm['nlayers'], g['nwave']
+    assert g['wnosamp'] == 2520 and nw > 99000
+    model = eng.LBLSpectrum(case, rt_path='transit')
+    model.run()
+    spectrum = host(model.run())                    # (a second spectrum: the dynamic grids)
+    assert model.lbl.last_gather_kernel == 'dynamic grids'
+    ec = host(model.ec)[:, 0]
+    t_gpu = time.time() - t0
+    # every layer against the oracle, with the oracle's own table
+    t1 = time.time()
+    table = oracle_table(orc, case, model.voigt)
+    want_ec = np.zeros((nl, nw))
+    for layer in range(nl):
+        want_ec[layer] = oracle_rows(orc, case, table, layer, True, case['ethresh'],
+                                     resolution=1)[0]
+    t_orc = time.time() - t1
+    worst_ec = check(ec, want_ec, 'c2-res ec')
+    assert np.count_nonzero(want_ec) > 0.5 * want_ec.size
+    depth, ideep = orc.optical_depth_transit(want_ec, atm['radius'], 0, nl, case['maxdepth'])
+    want = orc.transmission(depth, atm['radius'], atm['rstar'], ideep, 0)
+    assert np.array_equal(host(model.ideep), ideep)
+    np.testing.assert_allclose(spectrum, want, rtol=RTOL)
+    # the direct gather (k_ext_linterp) on a few layers; two runs bitwise equal
+    t, d, z = model.temp, model.dens, model.isoz
+    model.lbl.set_gather_mode('auto')
+    direct = model.lbl.extinction(t, d, z, add=True)
+    assert model.lbl.last_gather_kernel == 'k_ext_linterp'
+    assert torch.equal(model.lbl.extinction(t, d, z, add=True), direct), 'two runs differ'
+    worst_direct = 0.0
+    for layer in (0, 41, 79):
+        worst_direct = max(worst_direct, check(host(direct[layer]), want_ec[layer:layer + 1],
+                                               f'c2-res direct layer {layer}'))
+    print(f'c2-res: W={nw} L={nl}; GPU set-up + 2 spectra {t_gpu:.1f} s; oracle {t_orc:.1f} s; '
+          f'max rel err vs oracle: ec {worst_ec:.2e}, spectrum '
+          f'{np.max(np.abs(spectrum / want - 1)):.2e}, direct gather {worst_direct:.2e}')
 
 
 # ---------------------------------------------------------------------------
@@ -350,11 +410,11 @@ def test_full_size_c3_emission(eng, orc):
     assert model.depth.shape == (nl, nw) and model.ideep.shape == (nw,)
     ec = host(model.ec)[:, 0]
     # extinction: oracle parity on one sampled layer (test_full_size_config[c3] covers more)
-    profile = model.voigt.flat()
+    table = oracle_table(orc, case, model.voigt)
     layer = 44
-    want_row = oracle_rows(orc, case, model.voigt, profile, layer, True, case['ethresh'])
+    want_row = oracle_rows(orc, case, table, layer, True, case['ethresh'])
     worst_ec = check(ec[layer:layer + 1], want_row, f'c3 emission ec layer {layer}')
-    del profile
+    del table
     # RT stages from the HIP ec, every column, on the host
     t1 = time.time()
     depth = np.zeros((nl, nw))

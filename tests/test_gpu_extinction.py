@@ -3,7 +3,8 @@ golden vectors of the compiled reference and against the oracle.  Needs an MI355
 
 Tolerance: rtol 1e-10 on every non-zero sample and an identical zero pattern.  The
 kernel sums the same terms in the same order with fma (one rounding instead of two)
-and device exp(); the table itself agrees to ~1e-13 (test_gpu_voigt.py)."""
+and device exp(); the table itself agrees to ~1e-13 (test_gpu_voigt.py).  The oracle reads
+its own table (cases.oracle_voigt_table), never the one the GPU built."""
 import numpy as np
 import pytest
 
@@ -142,11 +143,11 @@ def test_synthetic_cases_vs_oracle(eng, orc, nwave, nlines, niso, gather):
     lbl.set_gather_mode(gather)
     ext = host(lbl.extinction(eng.dev(atm['temp']), eng.dev(atm['dens']),
                               eng.dev(iso['isoz']), add=True))
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     worst = 0.0
     for layer in range(6):
         want = np.zeros((1, g['nwave']))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'],
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'],
                        g['wn'], g['own'], g['divisors'], atm['dens'][layer],
                        atm['mol_radius'], atm['mol_mass'], iso['isoimol'], iso['isomass'],
                        iso['isoratio'], iso['isoz'][:, layer].copy(), iso['isoiext'],
@@ -265,11 +266,11 @@ def test_long_rows_vs_oracle(eng, orc, gather):
     t, d, z = eng.dev(atm['temp']), eng.dev(atm['dens']), eng.dev(iso['isoz'])
     ext = host(lbl.extinction(t, d, z, add=True))
     assert lbl.last_gather_kernel == {'staged': 'k_ext_staged', 'global': 'k_ext_resample'}[gather]
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     worst = 0.0
     for layer in range(5):
         want = np.zeros((1, g['nwave']))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'],
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'],
                        g['wn'], g['own'], g['divisors'], atm['dens'][layer],
                        atm['mol_radius'], atm['mol_mass'], iso['isoimol'], iso['isomass'],
                        iso['isoratio'], iso['isoz'][:, layer].copy(), iso['isoiext'],
@@ -408,10 +409,10 @@ def test_random_configurations(eng, orc, seed):
     if 'rounds' in out:
         assert np.array_equal(out['rounds'] == 0, out['global'] == 0)
         np.testing.assert_allclose(out['rounds'], out['global'], rtol=1e-12)
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     for layer in sorted(set([0, nlayers // 2, nlayers - 1])):
         want = np.zeros((1, g['nwave']))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'],
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'],
                        g['wn'], g['own'], g['divisors'], atm['dens'][layer],
                        atm['mol_radius'], atm['mol_mass'], iso['isoimol'], iso['isomass'],
                        iso['isoratio'], iso['isoz'][:, layer].copy(), iso['isoiext'],
@@ -516,10 +517,10 @@ def test_unsorted_lines_fall_back_to_host_grouping(eng, orc):
                   iso['isoimol'], iso['isomass'], iso['isoratio'], iso['isoiext'], vg['cutoff'],
                   case['ethresh'], max_layers=4)
     ext = host(lbl.extinction(eng.dev(atm['temp']), eng.dev(atm['dens']), eng.dev(iso['isoz'])))
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     for layer in range(4):
         want = np.zeros((1, g['nwave']))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'], g['wn'],
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'], g['wn'],
                        g['own'], g['divisors'], atm['dens'][layer], atm['mol_radius'],
                        atm['mol_mass'], iso['isoimol'], iso['isomass'], iso['isoratio'],
                        iso['isoz'][:, layer].copy(), iso['isoiext'], mixed['lwn'], mixed['elow'],
@@ -635,11 +636,11 @@ def test_windows_that_leave_the_grid(eng, orc, gather, short_own, long_rows):
     lbl.set_gather_mode(gather)
     t, d, z = eng.dev(atm['temp']), eng.dev(atm['dens']), eng.dev(iso['isoz'])
     ext = host(lbl.extinction(t, d, z, add=True))
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     worst, touched = 0.0, 0
     for layer in range(nl):
         want = np.zeros((1, g['nwave']))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'],
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'],
                        g['wn'], own, g['divisors'], atm['dens'][layer],
                        atm['mol_radius'], atm['mol_mass'], iso['isoimol'], iso['isomass'],
                        iso['isoratio'], iso['isoz'][:, layer].copy(), iso['isoiext'],
@@ -867,9 +868,9 @@ def test_chunked_line_list_equals_one_call(eng, orc, monkeypatch, long_rows, eth
     # the chunked result against the oracle (one layer)
     cut.set_record_budget(int(total / 4.1))
     got = host(cut.extinction(t, d, z, add=True))[1]
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     want = np.zeros((1, g['nwave']))
-    orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'], g['wn'],
+    orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'], g['wn'],
                    g['own'], g['divisors'], atm['dens'][1], atm['mol_radius'], atm['mol_mass'],
                    iso['isoimol'], iso['isomass'], iso['isoratio'], iso['isoz'][:, 1].copy(),
                    iso['isoiext'], ln['lwn'], ln['elow'], ln['gf'], ln['lid'], vg['cutoff'],
@@ -917,10 +918,10 @@ def test_per_layer_phase_split(eng, orc, monkeypatch, deep):
     monkeypatch.setenv('PB_STAGE_DEEP', '0')
     rows0 = lbl.extinction(t, d, z, add=False)
     assert ((rows - rows0).abs() / rows0.abs().clamp_min(1e-300)).max().item() <= 1e-13
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     for layer in (0, 5, 10):
         want = np.zeros((1, g['nwave']))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'], g['wn'],
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'], g['wn'],
                        g['own'], g['divisors'], atm['dens'][layer], atm['mol_radius'],
                        atm['mol_mass'], iso['isoimol'], iso['isomass'], iso['isoratio'],
                        iso['isoz'][:, layer].copy(), iso['isoiext'], ln['lwn'], ln['elow'],
@@ -1042,10 +1043,10 @@ def test_wavelength_step_grid(eng, orc, gather):
                   resolution=True, max_layers=6)
     lbl.set_gather_mode(gather)
     got = host(lbl.extinction(eng.dev(atm['temp']), eng.dev(atm['dens']), eng.dev(iso['isoz'])))
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     for layer in range(atm['nlayers']):
         want = np.zeros((1, len(wn)))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'], wn,
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'], wn,
                        g['own'], g['divisors'], atm['dens'][layer], atm['mol_radius'],
                        atm['mol_mass'], iso['isoimol'], iso['isomass'], iso['isoratio'],
                        iso['isoz'][:, layer].copy(), iso['isoiext'], ln['lwn'], ln['elow'],
@@ -1085,11 +1086,11 @@ def test_wave_kernel_vs_oracle(eng, orc, monkeypatch, wnosamp, cutoff, extent, n
     wave = lbl.last_wave_layers(8)
     assert wave.sum() >= 2, wave                           # (the upper layers at least)
     assert np.array_equal(host(lbl.extinction(t, d, z, add=True)), ext)
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     worst = 0.0
     for layer in range(8):
         want = np.zeros((1, g['nwave']))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'],
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'],
                        g['wn'], g['own'], g['divisors'], atm['dens'][layer],
                        atm['mol_radius'], atm['mol_mass'], iso['isoimol'], iso['isomass'],
                        iso['isoratio'], iso['isoz'][:, layer].copy(), isoiext,
@@ -1149,11 +1150,11 @@ def test_band_structured_list_vs_oracle(eng, orc, gather):
     lbl.set_gather_mode(gather)
     t, d, z = eng.dev(atm['temp']), eng.dev(atm['dens']), eng.dev(iso['isoz'])
     ext = host(lbl.extinction(t, d, z, add=True))
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     worst = 0.0
     for layer in range(6):
         want = np.zeros((1, g['nwave']))
-        orc.extinction(want, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'],
+        orc.extinction(want, profile, size, index, vg['lorentz'], vg['doppler'],
                        g['wn'], g['own'], g['divisors'], atm['dens'][layer],
                        atm['mol_radius'], atm['mol_mass'], iso['isoimol'], iso['isomass'],
                        iso['isoratio'], iso['isoz'][:, layer].copy(), iso['isoiext'],
@@ -1205,10 +1206,10 @@ def test_mode_switch_on_one_plan_with_resident_layers(eng, orc):
         np.testing.assert_allclose(got, want, rtol=1e-12, err_msg=mode)
         if mode == 'auto':
             assert np.array_equal(got, want), 'automatic mode on a used plan != a fresh plan'
-    profile = vt.flat()
+    profile, size, index = cases.oracle_voigt_table(orc, vg, g['ownstep'])
     for layer in (0, 11):
         ref = np.zeros((1, g['nwave']))
-        orc.extinction(ref, profile, vt.size, vt.index, vg['lorentz'], vg['doppler'], g['wn'],
+        orc.extinction(ref, profile, size, index, vg['lorentz'], vg['doppler'], g['wn'],
                        g['own'], g['divisors'], atm['dens'][layer], atm['mol_radius'],
                        atm['mol_mass'], iso['isoimol'], iso['isomass'], iso['isoratio'],
                        iso['isoz'][:, layer].copy(), iso['isoiext'], ln['lwn'], ln['elow'],
