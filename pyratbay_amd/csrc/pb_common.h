@@ -221,5 +221,14 @@ __device__ __forceinline__ bool layer_wanted(const TileLimit &lim, int k, int s0
     return k <= lim.row0 + 16 * (t + 1) - 1;
 }
 
+// a host array as a new device allocation (at least one element)
+template <typename T>
+int upload(T **dst, const T *src, size_t n)
+{
+    PB_HIP(hipMalloc(dst, (n ? n : 1) * sizeof(T)));
+    if (n)
+        PB_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return PB_OK;
+}
 
 }  // namespace pb

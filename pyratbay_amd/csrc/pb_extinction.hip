@@ -11,13 +11,20 @@
 //               (_extcoeff.c:281-299), so ktmp never exists.  The result is the same
 //               sum, term for term.
 //
-// Launch sequence per call (one stream, no host synchronisation):
+// Launch sequence per call (one stream, no host synchronisation; lbl_extinction() at the end of
+// this file, which launches what plan_gather() chose):
 //   1. k_layer_state : per layer/isotope Lorentz+Doppler widths, width-grid indices,
 //                      dynamic-sampling factor (_extcoeff.c:138-200)
-//   2. k_kmax        : per layer/species maximum line strength (_extcoeff.c:203-226)
-//   3. k_ext_resample / k_ext_linterp : the gather.
+//   2. k_records     : per (layer, group) strength, window and table cell, and with them the per
+//                      layer/species maximum line strength (_extcoeff.c:203-226); `resolution`
+//                      plans, which keep no records: k_kmax
+//   3. the gather    : k_ext_resident for the layers with narrow profiles, and for the others
+//                      k_ext_staged (+ a k_combine_* pass when a tile's phases were split over
+//                      several workgroups), k_ext_resample (global gather) or, `resolution`
+//                      plans, k_ext_linterp / the per-layer dynamic grids of lbl_resolution_dyn().
+//      Line lists beyond the record budget repeat 2 and 3 per chunk of the list (run_chunked).
 //
-// Gather kernel design (MI355X): a workgroup owns (layer, row, tile of 1024 output
+// Global gather design (k_ext_resample, MI355X): a workgroup owns (layer, row, tile of 1024 output
 // samples); a wavefront owns 4 consecutive 64-sample chunks and keeps their sums in
 // registers, so every output is written exactly once, coalesced, without atomics and
 // in a fixed order (bitwise reproducible).  Candidate groups of the tile are found by
@@ -2333,15 +2340,6 @@ __global__ __launch_bounds__(kBlock) void k_interp_ec(
     }
 }
 
-template <typename T>
-int upload(T **dst, const T *src, size_t n)
-{
-    PB_HIP(hipMalloc(dst, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n)
-        PB_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return PB_OK;
-}
-
 }  // namespace
 
 // ===========================================================================
@@ -2381,6 +2379,7 @@ struct pb_lbl {
     int32_t *ls_block = nullptr;      // [max_layers]
     int32_t *ls_wave = nullptr;       // [max_layers] layers of the wave-autonomous kernel
     Rec32 *rec32 = nullptr;           // [max_layers][ngroups], scatter kernel
+    size_t rec32_bytes = 0;
     Rec16 *rec16 = nullptr;           // [layers of the largest call][ngroups][nch_max], staged kernel
     size_t rec16_alloc = 0;
     double *part = nullptr;           // partial sums of a phase-split staged launch
@@ -2391,7 +2390,7 @@ struct pb_lbl {
     std::vector<int64_t> h_ph_start;
     std::vector<int32_t> h_wm;
     int32_t *d_wm = nullptr;
-    size_t wm_cap = 0;
+    size_t wm_bytes = 0;
     int64_t wm_flo = 0, wm_fhi = -1;
     int wm_staged = -1, wm_n0 = 0, wm_n1 = 0;
     int64_t wm_total0 = 0, wm_total1 = 0;
@@ -2413,12 +2412,14 @@ struct pb_lbl {
     int last_chunks = 0;     // chunks of the last call (0 = records of every group at once)
     // per-layer phase split of the staged kernel: device tables and the configuration they hold
     int32_t *d_unit_tab = nullptr, *d_lsplit = nullptr;
+    size_t ut_bytes = 0, ls_bytes = 0;
     // per-tile phase split (uneven line density): device table and what it was made for
     int32_t *d_tsplit = nullptr;
     int32_t *pos2ph = nullptr;                        // [ngroups] (LblArgs::pos2ph)
     bool ts_sparse = false;                           // some tile of the table is the global gather's
     int64_t ts_key[4] = {-1, -1, -1, -1};            // wbegin, wcount, tile, base split
-    int ts_max = 0, ts_tiles = 0;
+    int ts_max = 0;
+    size_t ts_bytes = 0;
     int ut_key[4] = {-1, -1, -1, -1};                 // nlayers, base split, deep layers, deep split
     int ut_units = 0;
     int concurrency = 1;     // independent calls the caller keeps in flight beside this plan's
@@ -2431,13 +2432,14 @@ struct pb_lbl {
     // round-staged gather (pb_rounds.hip): per-unit capacities (cached per launch geometry)
     // and the visit-record / segment / header lists
     int64_t *unit_cap = nullptr;
+    size_t unit_cap_bytes = 0;
     int64_t cap_key[5] = {-1, -1, -1, -1, -1};   // wbegin, wcount, tile, nsplit, total
     VRec *vrec = nullptr;
     VSeg *vseg = nullptr;
     int32_t *vrnd = nullptr;
     size_t vrec_alloc = 0;            // entries
     UnitHdr *uhdr = nullptr;
-    size_t uhdr_alloc = 0;
+    size_t uhdr_bytes = 0;
     struct Pending {                 // call begun with pb_lbl_extinction_begin
         double *ext;
         int64_t wbegin, wcount;
@@ -2492,203 +2494,6 @@ struct pb_lbl {
 };
 
 extern "C" {
-
-// ---------------------------------------------------------------------------
-// line list
-// ---------------------------------------------------------------------------
-int pb_lines_create(pb_lines **out, const double *lwn_h, const double *elow_h,
-                    const double *gf_h, const int32_t *lid_h, int64_t nlines, int niso,
-                    const double *own_h, int64_t onwn, double own0, double ownstep)
-{
-    PB_REQUIRE(out, "pb_lines_create: null out");
-    *out = nullptr;
-    PB_REQUIRE(nlines >= 0 && niso > 0 && onwn >= 2, "pb_lines_create: bad sizes");
-    PB_REQUIRE(nlines == 0 || (lwn_h && elow_h && gf_h && lid_h),
-               "pb_lines_create: null line arrays");
-    PB_REQUIRE(nlines < 2147483647LL && onwn < 2147483647LL,
-               "pb_lines_create: sizes exceed the reference's 32-bit indices");
-    // own[] generated exactly like NumPy (wnlow + arange*ownstep: multiply, then add)
-    auto own_at = [&](int64_t i) -> double {
-        if (own_h)
-            return own_h[i];
-        volatile double prod = (double)i * ownstep;
-        return own0 + prod;
-    };
-    pb_lines *l = new (std::nothrow) pb_lines();
-    if (!l)
-        return PB_ERR_NOMEM;
-    l->nlines = nlines;
-    l->niso = niso;
-    l->onwn = onwn;
-    l->own0 = own_at(0);
-    l->own_last = own_at(onwn - 1);
-    l->ownstep = own_at(1) - own_at(0);
-    const double lo = l->own0, hi = l->own_last, step = l->ownstep;
-
-    l->h_lwn.assign(lwn_h, lwn_h + nlines);
-    l->h_elow.assign(elow_h, elow_h + nlines);
-    l->h_gf.assign(gf_h, gf_h + nlines);
-    int rc = PB_OK;
-    if (rc == PB_OK) rc = upload(&l->d_lwn, lwn_h, (size_t)nlines);
-    if (rc == PB_OK) rc = upload(&l->d_elow, elow_h, (size_t)nlines);
-    if (rc == PB_OK) rc = upload(&l->d_gf, gf_h, (size_t)nlines);
-    if (rc == PB_OK) rc = upload(&l->d_lid, lid_h, (size_t)nlines);
-    if (rc != PB_OK) {
-        pb_lines_destroy(l);
-        return rc;
-    }
-    // Grouping on the device (pb_lines.hip) when the list has the TLI order (isotope, then
-    // wavenumber) and valid isotope ids; PB_LINES_HOST=1 or any other order: the host loop below
-    bool grouped = false;
-    if (nlines > 0 && !getenv("PB_LINES_HOST") && lid_h[0] >= 0 && lid_h[nlines - 1] < niso) {
-        const int grc = pb_lines_group_device(l, lwn_h, lid_h, own_h);
-        if (grc == PB_OK) {
-            grouped = true;
-            l->grouped_on_device = 1;
-        } else if (grc != 1) {
-            pb_lines_destroy(l);
-            return grc;
-        }
-    }
-    if (!grouped) {
-    struct Group {
-        int32_t first, count, iown, iso;
-    };
-    std::vector<Group> groups;
-    groups.reserve((size_t)nlines);
-    // The lines of ONE isotope must come in ascending wavenumber order (isotopes may interleave).
-    // The reference's Doppler-width index is a one-way search from the isotope's previous line
-    // (_extcoeff.c:278, utils.h:45-72: `if (value < array[lo]) return lo`): on a list that steps
-    // back within an isotope it keeps a stale index, a result that depends on the list order and
-    // on which lines the layer's threshold skipped.  The kernels evaluate the nearest index
-    // statelessly -- the same thing on an ordered list, NOT on such a one: refuse it loudly.
-    // (Every TLI reader output is ordered; the reference itself produces an unordered list only
-    // from a TLI FILE holding several databases, whose isotope ids it confuses:
-    // line_by_line.py:114-119, fixture G16 `onefile`.)
-    std::vector<double> last_wn((size_t)niso, -HUGE_VAL);
-    for (int64_t ln = 0; ln < nlines; ln++) {
-        const int i = lid_h[ln];
-        if (i < 0 || i >= niso) {
-            pb::set_error("pb_lines_create: line %lld has isotope id %d outside [0,%d)",
-                          (long long)ln, i, niso);
-            pb_lines_destroy(l);
-            return PB_ERR_ARG;
-        }
-        const double v = lwn_h[ln];
-        if (v < lo || v > hi)
-            continue;
-        if (v < last_wn[(size_t)i]) {
-            pb::set_error("pb_lines_create: line %lld (%.6f cm-1) of isotope %d comes after a "
-                          "line at %.6f cm-1: the lines of an isotope must be in ascending "
-                          "wavenumber order (the reference's Doppler-index search is one-way, "
-                          "_extcoeff.c:278; its result on such a list is order-dependent)",
-                          (long long)ln, v, i, last_wn[(size_t)i]);
-            pb_lines_destroy(l);
-            return PB_ERR_ARG;
-        }
-        last_wn[(size_t)i] = v;
-        l->ninrange++;
-        // nearest fine-grid index (_extcoeff.c:243-245)
-        int64_t iown = (int64_t)((v - lo) / step);
-        if (iown + 1 < onwn && fabs(v - own_at(iown + 1)) < fabs(v - own_at(iown)))
-            iown++;
-        Group g{(int32_t)ln, 1, (int32_t)iown, i};
-        const double centre = own_at(iown);
-        // greedy co-adding of the following lines of the same isotope (:248-262)
-        while (ln + 1 != nlines && lid_h[ln + 1] == i && lwn_h[ln + 1] <= hi) {
-            if (fabs(lwn_h[ln + 1] - centre) < step) {
-                ln++;
-                last_wn[(size_t)i] = std::max(last_wn[(size_t)i], lwn_h[ln]);
-                g.count++;
-                l->nadd++;
-                l->ninrange++;
-            } else
-                break;
-        }
-        groups.push_back(g);
-    }
-    // (isotope, fine index) order; stable, so a sorted TLI keeps its file order
-    std::stable_sort(groups.begin(), groups.end(), [](const Group &x, const Group &y) {
-        return x.iso != y.iso ? x.iso < y.iso : x.iown < y.iown;
-    });
-    l->ngroups = (int64_t)groups.size();
-    l->iso_gstart.assign((size_t)niso + 1, 0);
-    for (const Group &g : groups)
-        l->iso_gstart[(size_t)g.iso + 1]++;
-    for (int i = 0; i < niso; i++)
-        l->iso_gstart[(size_t)i + 1] += l->iso_gstart[(size_t)i];
-    std::vector<int32_t> &gfirst = l->h_gfirst, &gcount = l->h_gcount, &giown = l->h_giown;
-    gfirst.resize(groups.size());
-    gcount.resize(groups.size());
-    giown.resize(groups.size());
-    std::vector<int32_t> giso(groups.size());
-    for (size_t k = 0; k < groups.size(); k++) {
-        gfirst[k] = groups[k].first;
-        gcount[k] = groups[k].count;
-        giown[k] = groups[k].iown;
-        giso[k] = groups[k].iso;
-    }
-    if (rc == PB_OK) rc = upload(&l->d_gfirst, gfirst.data(), gfirst.size());
-    if (rc == PB_OK) rc = upload(&l->d_gcount, gcount.data(), gcount.size());
-    if (rc == PB_OK) rc = upload(&l->d_giown, giown.data(), giown.size());
-    if (rc == PB_OK) rc = upload(&l->d_giso, giso.data(), giso.size());
-    }
-    if (rc == PB_OK) rc = upload(&l->d_iso_gstart, l->iso_gstart.data(), l->iso_gstart.size());
-    if (rc != PB_OK) {
-        pb_lines_destroy(l);
-        return rc;
-    }
-    *out = l;
-    return PB_OK;
-}
-
-int pb_lines_grouped_on_device(const pb_lines *l, int *flag)
-{
-    PB_REQUIRE(l && flag, "pb_lines_grouped_on_device: null pointer");
-    *flag = l->grouped_on_device;
-    return PB_OK;
-}
-
-int pb_lines_groups(const pb_lines *l, int32_t *first_h, int32_t *count_h, int32_t *iown_h,
-                    int64_t *iso_gstart_h)
-{
-    PB_REQUIRE(l, "pb_lines_groups: null handle");
-    const size_t n = (size_t)l->ngroups;
-    if (first_h)
-        std::copy(l->h_gfirst.begin(), l->h_gfirst.begin() + n, first_h);
-    if (count_h)
-        std::copy(l->h_gcount.begin(), l->h_gcount.begin() + n, count_h);
-    if (iown_h)
-        std::copy(l->h_giown.begin(), l->h_giown.begin() + n, iown_h);
-    if (iso_gstart_h)
-        std::copy(l->iso_gstart.begin(), l->iso_gstart.end(), iso_gstart_h);
-    return PB_OK;
-}
-
-int pb_lines_stats(const pb_lines *l, int64_t stats[3])
-{
-    PB_REQUIRE(l && stats, "pb_lines_stats: null pointer");
-    stats[0] = l->ninrange;
-    stats[1] = l->ngroups;
-    stats[2] = l->nadd;
-    return PB_OK;
-}
-
-void pb_lines_destroy(pb_lines *l)
-{
-    if (!l)
-        return;
-    (void)hipFree(l->d_lwn);
-    (void)hipFree(l->d_elow);
-    (void)hipFree(l->d_gf);
-    (void)hipFree(l->d_lid);
-    (void)hipFree(l->d_gfirst);
-    (void)hipFree(l->d_gcount);
-    (void)hipFree(l->d_giown);
-    (void)hipFree(l->d_giso);
-    (void)hipFree(l->d_iso_gstart);
-    delete l;
-}
 
 // ---------------------------------------------------------------------------
 // LBL plan
@@ -2781,14 +2586,14 @@ int pb_lbl_create(pb_lbl **out, pb_voigt *voigt, pb_lines *lines, const double *
     p->kmax_rows = rows;
     const size_t L = (size_t)max_layers, LI = L * (size_t)niso;
     int rc = PB_OK;
-    if (rc == PB_OK) rc = upload(&p->d_wn, wn_h, (size_t)nwave);
-    if (rc == PB_OK) rc = upload(&p->d_divisors, divisors_h, (size_t)ndivs);
-    if (rc == PB_OK) rc = upload(&p->d_molrad, molrad_h, (size_t)nmol);
-    if (rc == PB_OK) rc = upload(&p->d_molmass, molmass_h, (size_t)nmol);
-    if (rc == PB_OK) rc = upload(&p->d_isoimol, isoimol_h, (size_t)niso);
-    if (rc == PB_OK) rc = upload(&p->d_isomass, isomass_h, (size_t)niso);
-    if (rc == PB_OK) rc = upload(&p->d_isoratio, isoratio_h, (size_t)niso);
-    if (rc == PB_OK) rc = upload(&p->d_isoiext, isoiext_h, (size_t)niso);
+    if (rc == PB_OK) rc = pb::upload(&p->d_wn, wn_h, (size_t)nwave);
+    if (rc == PB_OK) rc = pb::upload(&p->d_divisors, divisors_h, (size_t)ndivs);
+    if (rc == PB_OK) rc = pb::upload(&p->d_molrad, molrad_h, (size_t)nmol);
+    if (rc == PB_OK) rc = pb::upload(&p->d_molmass, molmass_h, (size_t)nmol);
+    if (rc == PB_OK) rc = pb::upload(&p->d_isoimol, isoimol_h, (size_t)niso);
+    if (rc == PB_OK) rc = pb::upload(&p->d_isomass, isomass_h, (size_t)niso);
+    if (rc == PB_OK) rc = pb::upload(&p->d_isoratio, isoratio_h, (size_t)niso);
+    if (rc == PB_OK) rc = pb::upload(&p->d_isoiext, isoiext_h, (size_t)niso);
     auto alloc = [&](void **ptr, size_t bytes) {
         if (rc == PB_OK && hipMalloc(ptr, bytes) != hipSuccess) {
             pb::set_error("pb_lbl_create: workspace allocation failed");
@@ -2857,12 +2662,12 @@ int pb_lbl_create(pb_lbl **out, pb_voigt *voigt, pb_lines *lines, const double *
             std::vector<int32_t> inv(ng);                 // position-sorted group -> phase-sorted slot
             for (size_t k = 0; k < ng; k++)
                 inv[(size_t)order[k]] = (int32_t)k;
-            if (rc == PB_OK) rc = upload(&p->pos2ph, inv.data(), ng);
+            if (rc == PB_OK) rc = pb::upload(&p->pos2ph, inv.data(), ng);
         }
-        if (rc == PB_OK) rc = upload(&p->ph_first, f.data(), ng);
-        if (rc == PB_OK) rc = upload(&p->ph_count, c.data(), ng);
-        if (rc == PB_OK) rc = upload(&p->ph_iown, w.data(), ng);
-        if (rc == PB_OK) rc = upload(&p->ph_start, start.data(), start.size());
+        if (rc == PB_OK) rc = pb::upload(&p->ph_first, f.data(), ng);
+        if (rc == PB_OK) rc = pb::upload(&p->ph_count, c.data(), ng);
+        if (rc == PB_OK) rc = pb::upload(&p->ph_iown, w.data(), ng);
+        if (rc == PB_OK) rc = pb::upload(&p->ph_start, start.data(), start.size());
         p->h_ph_iown = w;
         p->h_ph_start = start;
         {
@@ -2883,14 +2688,14 @@ int pb_lbl_create(pb_lbl **out, pb_voigt *voigt, pb_lines *lines, const double *
                     row[nbins] = (int32_t)kend;
                 }
             p->ph_nbins = nbins;
-            if (rc == PB_OK) rc = upload(&p->ph_bin, bins.data(), bins.size());
+            if (rc == PB_OK) rc = pb::upload(&p->ph_bin, bins.data(), bins.size());
         }
         {
             std::vector<int32_t> iso_of(ng);
             for (int i = 0; i < niso; i++)
                 for (int64_t k = lines->iso_gstart[i]; k < lines->iso_gstart[i + 1]; k++)
                     iso_of[(size_t)k] = i;
-            if (rc == PB_OK) rc = upload(&p->ph_iso, iso_of.data(), ng);
+            if (rc == PB_OK) rc = pb::upload(&p->ph_iso, iso_of.data(), ng);
         }
         {
             // leader line of every group in both walk orders (coalesced reads in k_records)
@@ -2906,8 +2711,8 @@ int pb_lbl_create(pb_lbl **out, pb_voigt *voigt, pb_lines *lines, const double *
                 glead[ng + k] = elow_all[gf_];
                 glead[2 * ng + k] = gf_all[gf_];
             }
-            if (rc == PB_OK) rc = upload(&p->ph_lead, lead.data(), lead.size());
-            if (rc == PB_OK) rc = upload(&p->g_lead, glead.data(), glead.size());
+            if (rc == PB_OK) rc = pb::upload(&p->ph_lead, lead.data(), lead.size());
+            if (rc == PB_OK) rc = pb::upload(&p->g_lead, glead.data(), glead.size());
         }
         // per (layer, group) records of k_records: allocated on first use
         int cap = 0, smallest = INT_MAX;
@@ -2933,7 +2738,7 @@ int pb_lbl_create(pb_lbl **out, pb_voigt *voigt, pb_lines *lines, const double *
                     gs[(size_t)i * ((size_t)nwave + 1) + (size_t)w] = (int32_t)g;
                 }
             }
-            if (rc == PB_OK) rc = upload(&p->gs_start, gs.data(), gs.size());
+            if (rc == PB_OK) rc = pb::upload(&p->gs_start, gs.data(), gs.size());
         }
     }
     {
@@ -3024,42 +2829,139 @@ int pb_lbl_set_ethresh(pb_lbl *p, double ethresh)
     return PB_OK;
 }
 
-static int lbl_resolution_dyn(pb_lbl *p, LblArgs &a, double *ext_d, int64_t wbegin, int64_t wcount,
-                              const double *temp_d, const double *dens_d, const double *isoz_d,
-                              int64_t z_iso_stride, int64_t z_layer_stride, int nlayers, int add,
-                              hipStream_t s);
+// ---------------------------------------------------------------------------
+// one extinction call: environment, arguments, plan, then the steps in launch order
+// ---------------------------------------------------------------------------
+using Call = pb_lbl::Pending;        // what the caller asked for
+using GatherKernel = void (*)(LblArgs);
 
-// phase 0: the whole call; 1: up to and including the records, per-row maxima over the shard's
-// own groups only (the caller all-reduces them); 2: the gather of the call begun with phase 1
-static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcount,
-                          const double *temp_d, const double *dens_d, const double *isoz_d,
-                          int64_t z_iso_stride, int64_t z_layer_stride, int nlayers, int add,
-                          void *stream, int phase)
+constexpr int kStagedWaves = 8;
+constexpr int kStagedThreads = kStagedWaves * 64;
+constexpr int64_t kStagedSub = kStagedWaves * kStageSpan;      // samples of one sub-tile
+
+// The PB_* variables a call consults.  Read once at the top of EVERY call, never kept in the
+// handle or in a static: the tests change them between calls of one process.
+struct Tuning {
+    int experiment = 0;            // PB_EXPERIMENT
+    bool dma = true;               // PB_STAGE_DMA=0: rows via registers
+    bool no_long_rows = false;     // PB_NO_LONG_ROWS (set at all)
+    int stage_s = 0;               // PB_STAGE_S as 1, 2 or 4; 0 = not set
+    int stage_split = 0;           // PB_STAGE_SPLIT as 1..8; 0 = not set
+    bool poison = false;           // PB_POISON_RECORDS (set and not 0)
+    bool budget_set = false;       // PB_RECORD_BUDGET
+    size_t budget = 0;
+    bool rec_soa = false;          // PB_REC_SOA (set at all)
+    int wave = -1;                 // PB_WAVE: 0 / 1; -1 = not set
+    bool res_dyn_off = false;      // PB_RES_DYN=0
+    bool rec_layers_1 = false;     // PB_REC_LAYERS=1
+    bool no_window_map = false;    // PB_NO_WINDOW_MAP (set at all)
+    size_t wm_lds_cap = 48 * 1024; // PB_WM_LDS_CAP
+    int scatter_t = 512;           // PB_SCATTER_T as 512, 1024 or 2048
+    int rounds_geom = 2;           // PB_ROUNDS_GEOM as 0..7
+    bool deep_set = false;         // PB_STAGE_DEEP=frac[,factor]
+    double deep_frac = 0.0;
+    int deep_factor = 2;
+    bool tile_split_off = false;   // PB_TILE_SPLIT=0
+    int tile_min = 1;              // PB_TILE_MIN
+    bool tile_debug = false;       // PB_TILE_DEBUG (set at all)
+    bool tile_global_off = false;  // PB_TILE_GLOBAL=0
+    int stage_probe = 0;           // PB_STAGE_PROBE
+    int rsplit = 0;                // PB_RSPLIT as 1, 2, 4 or 16; 0 = not set
+    int dyn_streams = 4;           // PB_RES_DYN_STREAMS as 1..8
+    int dyn_big = 1;               // PB_RES_DYN_BIG as 1..7
+};
+
+static Tuning read_tuning()
 {
-    PB_REQUIRE(p, "pb_lbl_extinction: null handle");
-    PB_REQUIRE(wcount == 0 || (ext_d && temp_d && dens_d && isoz_d),
-               "pb_lbl_extinction: null pointer");
-    PB_REQUIRE(nlayers >= 1 && nlayers <= p->max_layers,
-               "pb_lbl_extinction: nlayers=%d outside [1,%d]", nlayers, p->max_layers);
-    PB_REQUIRE(wbegin >= 0 && wcount >= 0 && wbegin + wcount <= p->nwave,
-               "pb_lbl_extinction: shard [%lld,+%lld) outside the %d-sample grid",
-               (long long)wbegin, (long long)wcount, p->nwave);
-    if (wcount == 0) {
-        // an empty shard of a two-phase call still takes part in the all-reduce(MAX) of the
-        // per-row maxima: it must contribute zeros, not what its previous call left behind
-        if (phase == 1)
-            PB_HIP(hipMemsetAsync(p->kmax_bits, 0, (size_t)p->max_layers * p->kmax_rows * 8,
-                                  pb::as_stream(stream)));
-        return PB_OK;
+    Tuning t;
+    auto is_zero = [](const char *name) {
+        const char *e = getenv(name);
+        return e && atoi(e) == 0;
+    };
+    if (const char *e = getenv("PB_EXPERIMENT"))
+        t.experiment = atoi(e);
+    t.dma = !is_zero("PB_STAGE_DMA");
+    t.no_long_rows = getenv("PB_NO_LONG_ROWS") != nullptr;
+    if (const char *e = getenv("PB_STAGE_S"))
+        t.stage_s = atoi(e) >= 4 ? 4 : atoi(e) >= 2 ? 2 : 1;
+    if (const char *e = getenv("PB_STAGE_SPLIT"))
+        t.stage_split = std::max(1, std::min(8, atoi(e)));
+    if (const char *e = getenv("PB_POISON_RECORDS"))
+        t.poison = atoi(e) != 0;
+    if (const char *e = getenv("PB_RECORD_BUDGET")) {
+        t.budget_set = true;
+        t.budget = (size_t)atoll(e);
     }
+    t.rec_soa = getenv("PB_REC_SOA") != nullptr;
+    t.res_dyn_off = is_zero("PB_RES_DYN");
+    if (const char *e = getenv("PB_REC_LAYERS"))
+        t.rec_layers_1 = atoi(e) == 1;
+    t.no_window_map = getenv("PB_NO_WINDOW_MAP") != nullptr;
+    if (const char *e = getenv("PB_WM_LDS_CAP"))
+        t.wm_lds_cap = (size_t)atol(e);
+    if (const char *e = getenv("PB_STAGE_DEEP")) {
+        t.deep_set = true;
+        t.deep_frac = atof(e);
+        if (const char *c = strchr(e, ','))
+            t.deep_factor = std::max(1, atoi(c + 1));
+    }
+    t.tile_split_off = is_zero("PB_TILE_SPLIT");
+    if (const char *e = getenv("PB_TILE_MIN"))
+        t.tile_min = atoi(e);
+    t.tile_debug = getenv("PB_TILE_DEBUG") != nullptr;
+    t.tile_global_off = is_zero("PB_TILE_GLOBAL");
+    if (const char *e = getenv("PB_RSPLIT")) {
+        const int v = atoi(e);
+        t.rsplit = v >= 16 ? 16 : v >= 4 ? 4 : v >= 2 ? 2 : 1;
+    }
+    if (const char *e = getenv("PB_RES_DYN_STREAMS"))
+        t.dyn_streams = std::max(1, std::min(8, atoi(e)));
+    if (const char *e = getenv("PB_RES_DYN_BIG"))
+        t.dyn_big = std::max(1, std::min(7, atoi(e)));
+    if (kExp) {
+        if (const char *e = getenv("PB_WAVE"))
+            t.wave = atoi(e) != 0 ? 1 : 0;
+        if (const char *e = getenv("PB_SCATTER_T"))
+            t.scatter_t = atoi(e) >= 2048 ? 2048 : atoi(e) >= 1024 ? 1024 : 512;
+        if (const char *e = getenv("PB_ROUNDS_GEOM"))
+            t.rounds_geom = std::max(0, std::min(7, atoi(e)));
+        if (const char *e = getenv("PB_STAGE_PROBE"))
+            t.stage_probe = atoi(e);
+    }
+    return t;
+}
+
+// The largest distance (fine samples) from which a group can reach an output sample, over all
+// layers: the widest profile of the table, or the cutoff where that is shorter.
+static int64_t group_reach(const pb_voigt *v, double cutoff, double ownstep)
+{
+    int64_t hmax_all = 0;
+    for (int32_t h : v->psize)
+        hmax_all = std::max<int64_t>(hmax_all, h);
+    int64_t reach = hmax_all;
+    if (cutoff > 0.0)
+        reach = std::min(reach, (int64_t)(cutoff / ownstep) + 2 * (int64_t)v->osamp + 2);
+    return reach;
+}
+
+// groups (any isotope) at fine positions [flo, fhi]: host copy of the position-sorted list
+static int64_t groups_in_reach(const pb_lines *l, int niso, int64_t flo, int64_t fhi)
+{
+    int64_t n = 0;
+    for (int i = 0; i < niso; i++) {
+        const int32_t *b = l->h_giown.data() + l->iso_gstart[(size_t)i];
+        const int32_t *e = l->h_giown.data() + l->iso_gstart[(size_t)i + 1];
+        n += std::upper_bound(b, e, (int32_t)std::min<int64_t>(fhi, INT_MAX)) -
+             std::lower_bound(b, e, (int32_t)std::max<int64_t>(flo, INT_MIN));
+    }
+    return n;
+}
+
+// the part of LblArgs that follows from the plan and the call alone (everything else is zero)
+static LblArgs fill_args(const pb_lbl *p, const Call &c)
+{
     const pb_voigt *v = p->voigt;
     const pb_lines *l = p->lines;
-    hipStream_t s = pb::as_stream(stream);
-    if (p->resolution) {
-        int rc = pb_voigt_ensure_flat(p->voigt, s);
-        if (rc)
-            return rc;
-    }
     LblArgs a;
     memset(&a, 0, sizeof(a));
     a.pm = v->d_pm;
@@ -3094,7 +2996,6 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
     a.ls_resident = p->ls_resident;
     a.ls_block = p->ls_block;
     a.ls_wave = p->ls_wave;
-    a.wave_cap = 0;
     a.gs_start = p->gs_start;
     a.giso = l->d_giso;
     a.ngroups = l->ngroups;
@@ -3109,11 +3010,11 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
     a.nmol = p->nmol;
     a.niso = p->niso;
     a.ndivs = p->ndivs;
-    a.temp = temp_d;
-    a.dens = dens_d;
-    a.isoz = isoz_d;
-    a.z_iso_stride = z_iso_stride;
-    a.z_layer_stride = z_layer_stride;
+    a.temp = c.temp;
+    a.dens = c.dens;
+    a.isoz = c.isoz;
+    a.z_iso_stride = c.zs0;
+    a.z_layer_stride = c.zs1;
     a.ls_ofactor = p->ls_ofactor;
     a.ls_scale = p->ls_scale;
     a.ls_dnwn = p->ls_dnwn;
@@ -3141,71 +3042,211 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
     a.onwn = l->onwn;
     a.cutoff = p->cutoff;
     a.ethresh = p->ethresh;
-    a.add = add ? 1 : 0;
-    a.nrows = add ? 1 : p->nrows_sep;
-    a.nlayers = nlayers;
+    a.add = c.add ? 1 : 0;
+    a.nrows = c.add ? 1 : p->nrows_sep;
+    a.nlayers = c.nlayers;
     a.nwave = p->nwave;
-    a.wbegin = wbegin;
-    a.wcount = wcount;
-    a.ext = ext_d;
-    {
-        // records are needed for the groups within reach of the shard only.  The window must hold
-        // every group ANY gather kernel may examine: the staged / global / round kernels bracket
-        // their candidates by fine position (within min(hmax, cutoff) + osamp + ofactor of a tile),
-        // the resident and scatter kernels through the per-sample index gs_start, which examines
-        // up to two more output samples' worth of groups on either side -- hence 6 (not 2) x osamp
-        // of margin.  A group examined but never written would be whatever the allocation held
-        // (round 2: garbage records of a long-lived process sent the resident kernel out of
-        // bounds; found by tools/fuzz_pipeline.py); the buffers are also zeroed when allocated, so
-        // a record never written is a dead record.
-        int64_t hmax_all = 0;
-        for (int32_t h : v->psize)
-            hmax_all = std::max<int64_t>(hmax_all, h);
-        int64_t reach = hmax_all;
-        if (a.cutoff > 0.0)
-            reach = std::min(reach, (int64_t)(a.cutoff / a.ownstep) + 2 * (int64_t)v->osamp + 2);
-        reach += 6 * (int64_t)v->osamp;
-        const bool whole = wbegin == 0 && wcount == p->nwave;
-        a.rec_flo = whole ? INT64_MIN : wbegin * (int64_t)v->osamp - reach;
-        a.rec_fhi = whole ? INT64_MAX : (wbegin + wcount - 1) * (int64_t)v->osamp + reach;
-        a.kmax_local = phase != 0 ? 1 : 0;
-    }
-    {
-        const char *e = getenv("PB_EXPERIMENT");
-        a.experiment = e ? atoi(e) : 0;
-        a.probe = nullptr;
-    }
+    a.wbegin = c.wbegin;
+    a.wcount = c.wcount;
+    a.ext = c.ext;
+    // records are needed for the groups within reach of the shard only.  The window must hold
+    // every group ANY gather kernel may examine: the staged / global / round kernels bracket
+    // their candidates by fine position (within min(hmax, cutoff) + osamp + ofactor of a tile),
+    // the resident and scatter kernels through the per-sample index gs_start, which examines
+    // up to two more output samples' worth of groups on either side -- hence 6 (not 2) x osamp
+    // of margin.  A group examined but never written would be whatever the allocation held
+    // (round 2: garbage records of a long-lived process sent the resident kernel out of
+    // bounds; found by tools/fuzz_pipeline.py); the buffers are also zeroed when allocated, so
+    // a record never written is a dead record.
+    const int64_t reach = group_reach(v, a.cutoff, a.ownstep) + 6 * (int64_t)v->osamp;
+    const bool whole = c.wbegin == 0 && c.wcount == p->nwave;
+    a.rec_flo = whole ? INT64_MIN : c.wbegin * (int64_t)v->osamp - reach;
+    a.rec_fhi = whole ? INT64_MAX : (c.wbegin + c.wcount - 1) * (int64_t)v->osamp + reach;
+    // every group in one piece, one workgroup per tile: the chunked walk and the phase splits
+    // narrow these
+    a.grp_hi = l->ngroups;
+    a.rec_pitch = l->ngroups;
+    a.key_hi = a.niso * v->osamp;
+    a.nsplit = 1;
+    return a;
+}
 
+// Grow *ptr to `need` bytes (*have = its size so far); what it held is lost.  sync_first: an
+// earlier call on the stream may still read the old block.  Running out of memory is
+// PB_ERR_NOMEM "cannot allocate <need> B of <what>"; without `what`, the runtime's own error.
+static int ensure_bytes(void **ptr, size_t *have, size_t need, hipStream_t s, bool sync_first,
+                        const char *what)
+{
+    if (need <= *have)
+        return PB_OK;
+    if (*ptr) {
+        if (sync_first)
+            PB_HIP(hipStreamSynchronize(s));
+        (void)hipFree(*ptr);
+        *ptr = nullptr;
+        *have = 0;
+    }
+    if (!what)
+        PB_HIP(hipMalloc(ptr, need));
+    else if (hipMalloc(ptr, need) != hipSuccess) {
+        pb::set_error("pb_lbl_extinction: cannot allocate %zu B of %s", need, what);
+        return PB_ERR_NOMEM;
+    }
+    *have = need;
+    return PB_OK;
+}
+
+// bytes of one plane of partial sums, and the largest split <= n (>= least) whose planes beside
+// ext stay below 1 GiB
+static int64_t plane_bytes(const LblArgs &a)
+{
+    return (int64_t)a.nlayers * a.nrows * a.wcount * 8;
+}
+
+static int cap_split_to_planes(int n, int64_t plane, int least = 1)
+{
+    while (n > least && (n - 1) * plane > ((int64_t)1 << 30))
+        n--;
+    return n;
+}
+
+// partial sums of a launch split into `nplanes` pieces (the first piece writes ext itself)
+static int ensure_part(pb_lbl *p, LblArgs &a, int nplanes, hipStream_t s)
+{
+    if (nplanes <= 1)
+        return PB_OK;
+    const size_t need = (size_t)(nplanes - 1) * a.nlayers * a.nrows * a.wcount * 8;
+    if (int rc = ensure_bytes((void **)&p->part, &p->part_bytes, need, s, false, "partial sums"))
+        return rc;
+    a.part = p->part;
+    return PB_OK;
+}
+
+static GatherKernel staged_kernel(int S, bool dma)
+{
+    return dma ? (S == 4   ? k_ext_staged<kStagedWaves, 4, true>
+                  : S == 2 ? k_ext_staged<kStagedWaves, 2, true>
+                           : k_ext_staged<kStagedWaves, 1, true>)
+               : (S == 4   ? k_ext_staged<kStagedWaves, 4, false>
+                  : S == 2 ? k_ext_staged<kStagedWaves, 2, false>
+                           : k_ext_staged<kStagedWaves, 1, false>);
+}
+
+// a kernel that asks for more than 64 KiB of dynamic LDS has to say so first
+static int allow_lds(const void *kern, size_t lds)
+{
+    if (lds > 64 * 1024)
+        PB_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return PB_OK;
+}
+
+static int launch_layer_state(const LblArgs &a, hipStream_t s)
+{
+    k_layer_state<<<a.nlayers, 64, ((size_t)a.nlor + a.ndop) * 8 + (size_t)a.ndivs * 4, s>>>(a);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+static int launch_kmax(const LblArgs &a, hipStream_t s)
+{
+    const int lines_per_block = 4096;
+    dim3 grid(pb::div_up(a.nlines, lines_per_block), a.nlayers);
+    k_kmax<<<grid, kBlock, (size_t)a.nrows * 8, s>>>(a, lines_per_block);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+// LDS bytes of k_records with `per` layers per thread, before its window-map words
+static size_t records_lds(const LblArgs &a, int per)
+{
+    return (size_t)per * a.nrows * 8 + (size_t)a.ndop * 8 +
+           (size_t)per * a.niso * (8 + 8 + 8 + 4) + (size_t)a.niso * (8 + 4) + 16;
+}
+
+// fmt: 0 SoA records, 1 packed, 2 packed with row chunks, 3 the scatter kernel's.  (The kernels
+// lie in the code object in the order they are first named: the packed formats of the usual
+// call first, as they always did, so that the device code stays byte for byte the same.)
+static int launch_records(const LblArgs &a, int fmt, int per, dim3 grid, size_t lds, hipStream_t s)
+{
+    GatherKernel krec;
+    if (per == kRecLayers && (fmt == 1 || fmt == 2))
+        krec = fmt == 2 ? k_records<2, kRecLayers> : k_records<1, kRecLayers>;
+    else
+        krec = per == 1 ? (fmt == 3   ? k_records<3, 1>
+                           : fmt == 2 ? k_records<2, 1>
+                           : fmt == 1 ? k_records<1, 1>
+                                      : k_records<0, 1>)
+                        : (fmt == 0 ? k_records<0, kRecLayers> : k_records<3, kRecLayers>);
+    krec<<<grid, kBlock, lds, s>>>(a);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+// What a call will launch, decided from the plan, the arguments and the environment alone.
+struct Chunk {
+    int key_lo, key_hi;
+    int64_t g_lo, g_hi;
+};
+
+struct GatherPlan {
+    int rc = PB_OK;                  // the call cannot be planned (pb_last_error says why)
+    bool staged = false, rounds = false, scatter = false;
+    bool use_records = false, packable = false;
+    // resident-profile kernel.  plan_gather() says whether the plan and the mode allow it
+    // (resident) and whether the layers' own decision counts too (res_auto); resident_probe()
+    // then settles `resident` and `res_look` (read the layers' decision back after this call)
+    bool resident = false, res_auto = false, res_look = false;
+    bool dma = true;                 // rows by LDS-DMA (k_ext_staged); PB_STAGE_DMA=0: via registers
+    bool shared_chip = false;
+    int S = 2, nsplit = 1;
+    int nch_max = 1, rowlds = 0;     // LblArgs::nch_max, rowlds
+    size_t lds = 0;                  // dynamic LDS of the staged kernel
+    double per_phase = 0.0;          // groups per (2048-sample tile, phase)
+    // out-of-core line lists: the chunks of the phase-sorted group list (empty: one piece), the
+    // bytes of packed records the call needs, whether it uses packed records at all, and the
+    // format k_records writes (launch_records)
+    std::vector<Chunk> chunks;
+    size_t rec16_need = 0;
+    bool packed = false;
+    int fmt = 0;
+};
+
+// Makes no HIP call and does not write to *p.  The two pieces of state the choice touches are
+// applied by the caller (resident_probe): whether the stream is being captured, and the plan's
+// probe counter and pending decision (res_calls, res_on_pending, res_look_pending).
+static GatherPlan plan_gather(const pb_lbl *p, const LblArgs &a, const Tuning &tn, int phase)
+{
+    const pb_voigt *v = p->voigt;
+    const pb_lines *l = p->lines;
+    const int nlayers = a.nlayers;
+    const int64_t wcount = a.wcount;
+    GatherPlan g;
     // Kernel choice (constant-step grids): the LDS-staged kernel when several groups share
     // a (tile, phase) row, else the global gather.  Every kernel adds the terms of a sample in
     // one fixed order, so a call is bitwise reproducible and shards of ONE configuration
     // concatenate exactly; the choice of kernel and the phase split below do depend on the size
     // of the call (shard width, layers), and a different choice changes the association of the
     // per-sample sums: results of different configurations agree to ~1e-13, not bit for bit.
-    constexpr int kStagedWaves = 8;
-    constexpr int kStagedThreads = kStagedWaves * 64;
     // rows longer than kStageRowMax samples are staged in chunks: (phase, chunk) pairs act as
     // phases; k_records writes one packed record per group, clipped to the chunk by the gather
-    const int nch_max = (int)pb::div_up((int64_t)a.rowcap, (int64_t)kChunkRow);
-    a.nch_max = std::max(1, nch_max);
-    a.rowlds = (std::min(a.rowcap, kStageRowMax) + 1) & ~1;     // even: 16-byte aligned buffers
+    const int nch_max = std::max(1, (int)pb::div_up((int64_t)a.rowcap, (int64_t)kChunkRow));
+    g.rowlds = (std::min(a.rowcap, kStageRowMax) + 1) & ~1;     // even: 16-byte aligned buffers
     const size_t lds_fixed = (size_t)kStagedThreads * (16 + 8 + 4) + kStagedWaves * 12 +
                              (size_t)a.ndop * 16 +
-                             (size_t)(2 * v->osamp * a.nch_max + 1) * 4 + 64;
-    bool dma = true;                     // rows by LDS-DMA (k_ext_staged); PB_STAGE_DMA=0: via registers
-    if (const char *e = getenv("PB_STAGE_DMA"))
-        dma = atoi(e) != 0;
-    const size_t lds = (2 * ((size_t)a.rowlds + kStagePad) + kStagePad) * 8 + lds_fixed;
+                             (size_t)(2 * v->osamp * nch_max + 1) * 4 + 64;
+    g.dma = tn.dma;
+    g.lds = (2 * ((size_t)g.rowlds + kStagePad) + kStagePad) * 8 + lds_fixed;
     const double per_phase = (double)l->ngroups / std::max(1, p->nwave) * 2048.0 / v->osamp;
+    g.per_phase = per_phase;
     // table cell and window length share 32 bits of a packed record: 20 + 12, for long rows
     // 18 + kLongLenBits (windows of up to 16 383 samples)
-    const bool packable = v->nlor * v->ndop < (a.nch_max > 1 ? (1 << (32 - kLongLenBits)) : (1 << 20)) &&
+    const bool packable = v->nlor * v->ndop < (nch_max > 1 ? (1 << (32 - kLongLenBits)) : (1 << 20)) &&
                           a.rowcap < (1 << kLongLenBits);
+    g.packable = packable;
     // sized for the layers of this call (a layer shard of a multi-GPU run holds few of them)
     const size_t rec16_bytes = (size_t)nlayers * (size_t)l->ngroups * sizeof(Rec16);
-    const bool can_stage = !p->resolution && lds <= 160 * 1024 && l->ngroups > 0 &&
-                           (a.nch_max == 1 ||
-                            (a.nch_max <= 16 && packable && !getenv("PB_NO_LONG_ROWS")));
+    const bool can_stage = !p->resolution && g.lds <= 160 * 1024 && l->ngroups > 0 &&
+                           (nch_max == 1 || (nch_max <= 16 && packable && !tn.no_long_rows));
     // the staged kernel needs enough workgroups to hide its per-segment latency; launches that
     // stay below 750 even when split eight ways go to the global gather with record splitting.
     // Tiling of the staged kernel: S = 2 sub-tiles of 2048 samples per workgroup (1 measured
@@ -3221,7 +3262,7 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
     //    a workgroup then runs for milliseconds): aim for ~8000.  1e6 lines, 80 layers:
     //    8.13 ms unsplit, 7.33 in four; a 10-layer shard 2.03 -> 1.13 in eight.
     // The partial sums stay below 1 GB.
-    const int64_t sub = kStagedWaves * kStageSpan;
+    const int64_t sub = kStagedSub;
     const int64_t blocks2 = pb::div_up(wcount, 2 * sub) * (int64_t)nlayers;
     // With other spectra in flight on other streams (pb_lbl_set_concurrency: the walkers of a
     // retrieval, the pipelined shards of a multi-GPU rank) a launch need not fill the chip by
@@ -3230,6 +3271,7 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
     // ms whatever the split; two in flight 0.211 (3 workgroups per 4096-sample tile = 960, one round; 4 per tile: 0.232) against
     // 0.240 (7 per 2048-sample tile, the one-at-a-time rule); three in flight 0.190 against 0.236.
     const bool shared_chip = p->concurrency > 1 && per_phase < 64.0;
+    g.shared_chip = shared_chip;
     int S = 2;
     int nsplit = (int)std::min<int64_t>(
         8, pb::div_up((int64_t)(per_phase >= 64.0 ? 8000 : 2000), std::max<int64_t>(1, blocks2)));
@@ -3242,11 +3284,7 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
         const int64_t inflight = blocks2 * std::max(1, p->concurrency);
         nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(8, (2000 + inflight / 2) / std::max<int64_t>(1, inflight)));
     }
-    {
-        const int64_t plane = (int64_t)nlayers * a.nrows * wcount * 8;
-        while (nsplit > 1 && (nsplit - 1) * plane > ((int64_t)1 << 30))
-            nsplit--;
-    }
+    nsplit = cap_split_to_planes(nsplit, plane_bytes(a));
     {
         // tile quantisation of a narrow shard: 12 500 samples are 3.05 tiles of 4096 (31 % of
         // the workgroups' rows staged for nothing) but 6.1 of 2048 (15 %); one span per
@@ -3258,15 +3296,17 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
         if (w2 - w1 > 0.12 && !shared_chip)
             S = 1;
     }
-    if (const char *e = getenv("PB_STAGE_S"))
-        S = atoi(e) >= 4 ? 4 : atoi(e) >= 2 ? 2 : 1;
-    if (const char *e = getenv("PB_STAGE_SPLIT"))
-        nsplit = std::max(1, std::min(8, atoi(e)));
+    if (tn.stage_s)
+        S = tn.stage_s;
+    if (tn.stage_split)
+        nsplit = tn.stage_split;
+    g.S = S;
+    g.nsplit = nsplit;
     // (with other spectra in flight the launches of all of them count towards filling the chip)
     const bool enough_blocks = pb::div_up(wcount, S * sub) * (int64_t)nlayers * nsplit *
                                    (shared_chip ? p->concurrency : 1) >= 750;
     // round-staged kernel (pb_rounds.hip): rows of one piece (<= 1024 samples), packed records
-    const bool rounds = kExp && can_stage && a.nch_max == 1 && packable && p->gather_mode == 5;
+    const bool rounds = kExp && can_stage && nch_max == 1 && packable && p->gather_mode == 5;
     const bool staged = can_stage && (p->gather_mode == 2 || p->gather_mode == 7 || rounds ||
                                       (p->gather_mode == 0 && enough_blocks &&
                                        per_phase >= p->stage_threshold));
@@ -3274,56 +3314,28 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
     // layers with narrow profiles go to the resident-profile kernel (decided per layer on
     // the device, from the layer alone); the kernel chosen above computes the others
     const bool scatter = kExp && use_records && p->gs_start && p->gather_mode == 4;
-    bool resident = use_records && !scatter && p->res_cap > 0 && p->gs_start &&
-                    (p->gather_mode == 0 || p->gather_mode == 3);
-    bool res_look = false;            // read the layers' decision back after this call
-    if (resident && p->gather_mode == 0) {
-        if (phase == 2) {
-            resident = p->res_on_pending;
-            res_look = p->res_look_pending;
-        } else {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(s, &cs) == hipSuccess &&
-                                   cs != hipStreamCaptureStatusNone;
-            const bool probe = !capturing && (p->res_seen < 0 || (p->res_calls++ & 255) == 255);
-            if (!probe && p->res_seen == 0)
-                resident = false;
-            res_look = probe && resident;
-            p->res_on_pending = resident;
-            p->res_look_pending = res_look;
-        }
-    }
-    a.res_cap = resident ? p->res_cap : 0;
-    a.rec32 = nullptr;
-    a.rec16 = nullptr;
-    const bool poison = getenv("PB_POISON_RECORDS") && atoi(getenv("PB_POISON_RECORDS")) != 0;
-    if (!staged || scatter)
-        a.nch_max = 1;
-    a.grp_lo = 0;
-    a.grp_hi = l->ngroups;
-    a.rec_pitch = l->ngroups;
-    a.key_lo = 0;
-    a.key_hi = a.niso * v->osamp;
-    a.accumulate = 0;
+    g.rounds = rounds;
+    g.staged = staged;
+    g.use_records = use_records;
+    g.scatter = scatter;
+    g.resident = use_records && !scatter && p->res_cap > 0 && p->gs_start &&
+                 (p->gather_mode == 0 || p->gather_mode == 3);
+    g.res_auto = g.resident && p->gather_mode == 0;
+    // (the LDS of the staged kernel above was sized for the row chunks even so)
+    g.nch_max = !staged || scatter ? 1 : nch_max;
     // Out-of-core line lists (the reference walks any number of lines one after the other,
     // _extcoeff.c:203-309): when the packed records of all groups exceed the record budget, the
     // phase-sorted group list is cut into chunks of consecutive (isotope, phase) keys that fit.
-    size_t budget = p->record_budget;
-    if (const char *e = getenv("PB_RECORD_BUDGET"))
-        budget = (size_t)atoll(e);
-    struct Chunk {
-        int key_lo, key_hi;
-        int64_t g_lo, g_hi;
-    };
-    std::vector<Chunk> chunks;
-    size_t rec16_need = rec16_bytes;
+    const size_t budget = tn.budget_set ? tn.budget : p->record_budget;
+    g.rec16_need = rec16_bytes;
     if (staged && !scatter && rec16_bytes > budget) {
-        if (!packable || rounds || phase != 0 || getenv("PB_REC_SOA")) {
+        if (!packable || rounds || phase != 0 || tn.rec_soa) {
             pb::set_error("pb_lbl_extinction: %zu B of line records exceed the record budget of "
                           "%zu B and this call cannot be chunked (%s)", rec16_bytes, budget,
                           phase != 0 ? "two-phase shard call"
                                      : rounds ? "round gather" : "records are not packable");
-            return PB_ERR_NOMEM;
+            g.rc = PB_ERR_NOMEM;
+            return g;
         }
         const int osamp = v->osamp;
         const int64_t gmax = (int64_t)(budget / ((size_t)nlayers * sizeof(Rec16)));
@@ -3337,10 +3349,11 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
                     pb::set_error("pb_lbl_extinction: the %lld groups of one (isotope, phase) key "
                                   "need more than the record budget of %zu B",
                                   (long long)(g1 - g0), budget);
-                    return PB_ERR_NOMEM;
+                    g.rc = PB_ERR_NOMEM;
+                    return g;
                 }
                 if (g1 - c.g_lo > gmax) {              // close the chunk before this key
-                    chunks.push_back(c);
+                    g.chunks.push_back(c);
                     biggest = std::max(biggest, c.g_hi - c.g_lo);
                     c.key_lo = i * osamp + ph;
                     c.g_lo = g0;
@@ -3348,94 +3361,284 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
                 c.key_hi = i * osamp + ph + 1;
                 c.g_hi = g1;
             }
-        chunks.push_back(c);
+        g.chunks.push_back(c);
         biggest = std::max(biggest, c.g_hi - c.g_lo);
-        rec16_need = (size_t)std::max<int64_t>(1, biggest) * nlayers * sizeof(Rec16);
+        g.rec16_need = (size_t)std::max<int64_t>(1, biggest) * nlayers * sizeof(Rec16);
     }
-    const bool chunked = !chunks.empty();
-    p->last_chunks = (int)chunks.size();
-    if (staged && !scatter && packable && (a.nch_max > 1 || chunked || !getenv("PB_REC_SOA"))) {
-        const size_t rec16_bytes = rec16_need;       // (shadows the whole-list size)
-        if (rec16_bytes > p->rec16_alloc) {
-            if (p->rec16) {
-                PB_HIP(hipStreamSynchronize(s));       // an earlier call may still read it
-                (void)hipFree(p->rec16);
-                p->rec16 = nullptr;
-                p->rec16_alloc = 0;
-            }
-            if (hipMalloc(&p->rec16, rec16_bytes) != hipSuccess) {
-                pb::set_error("pb_lbl_extinction: cannot allocate %zu B of line records",
-                              rec16_bytes);
-                return PB_ERR_NOMEM;
-            }
-            p->rec16_alloc = rec16_bytes;
-            PB_HIP(hipMemsetAsync(p->rec16, 0, rec16_bytes, s));
-            if (poison)
-                k_poison_records<<<1024, kBlock, 0, s>>>(p->rec16, (int64_t)(rec16_bytes / sizeof(Rec16)),
+    g.packed = staged && !scatter && packable &&
+               (g.nch_max > 1 || !g.chunks.empty() || !tn.rec_soa);
+    g.fmt = scatter ? 3 : g.packed ? (g.nch_max > 1 ? 2 : 1) : 0;
+    return g;
+}
+
+// Which layers are resident is decided on the device; whether the resident kernel is launched at
+// all follows what the host last saw of that decision (pb_lbl::res_seen).  This is the part of
+// the plan that needs the stream and the handle's counters.
+static void resident_probe(pb_lbl *p, GatherPlan &g, hipStream_t s, int phase)
+{
+    if (!g.res_auto)
+        return;
+    if (phase == 2) {
+        g.resident = p->res_on_pending;
+        g.res_look = p->res_look_pending;
+        return;
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(s, &cs) == hipSuccess &&
+                           cs != hipStreamCaptureStatusNone;
+    const bool probe = !capturing && (p->res_seen < 0 || (p->res_calls++ & 255) == 255);
+    if (!probe && p->res_seen == 0)
+        g.resident = false;
+    g.res_look = probe && g.resident;
+    p->res_on_pending = g.resident;
+    p->res_look_pending = g.res_look;
+}
+
+static int lbl_resolution_dyn(pb_lbl *p, LblArgs &a, const Call &c, const Tuning &tn, hipStream_t s);
+
+#ifdef PB_EXPERIMENTS
+// ---------------------------------------------------------------------------
+// the measured dead ends (`make EXPERIMENTS=1`): the wave pair, the scatter and round gathers,
+// the probes of the staged kernel.  The default library has the stand-ins of the #else.
+// ---------------------------------------------------------------------------
+// Layers of short phase rows (<= kWvRowMax samples: the Doppler-core layers) go to the
+// wave-autonomous kernel (pb_wave.hip), decided per layer on the device by k_layer_state; the
+// staged kernel computes the others.  Mode 7 selects the pair; modes 0 and 2 keep to the staged
+// kernel alone.  Chunked line lists continue running sums in the staged kernel's order and
+// keep to it.
+static void exp_wave_cap(const pb_lbl *p, LblArgs &a, const GatherPlan &g, const Tuning &tn)
+{
+    // (measured at C2, round 4: the pair takes 1.20 ms per extinction against 1.05 ms for the
+    // staged kernel alone -- profiles/r04_gather_wave.md -- so mode 0 does not use it unless
+    // PB_WAVE=1 asks for it)
+    const bool can = g.staged && !g.rounds && !g.scatter && g.chunks.empty() && a.rec16 != nullptr;
+    bool wave_on = can && p->gather_mode == 7;
+    if (tn.wave >= 0)
+        wave_on = can && (p->gather_mode == 0 || p->gather_mode == 7) && tn.wave != 0;
+    if (wave_on && wave_lds(a) <= 160 * 1024)
+        a.wave_cap = kWvRowMax;
+}
+
+static int exp_scatter_records(pb_lbl *p, LblArgs &a, const Tuning &tn, hipStream_t s)
+{
+    const size_t n = (size_t)p->max_layers * (size_t)p->lines->ngroups;
+    const size_t had = p->rec32_bytes;
+    if (int rc = ensure_bytes((void **)&p->rec32, &p->rec32_bytes, n * sizeof(Rec32), s, false,
+                              "line records"))
+        return rc;
+    if (p->rec32_bytes != had) {
+        PB_HIP(hipMemsetAsync(p->rec32, 0, n * sizeof(Rec32), s));
+        if (tn.poison)
+            k_poison_records<<<1024, kBlock, 0, s>>>(nullptr, 0, p->rec32, (int64_t)n, nullptr,
+                                                    nullptr, 0);
+    }
+    a.rec32 = p->rec32;
+    return PB_OK;
+}
+
+static int exp_launch_scatter(LblArgs &a, const Tuning &tn, hipStream_t s)
+{
+    const int T = tn.scatter_t;
+    a.ntiles = pb::div_up(a.wcount, T);
+    dim3 grid((unsigned)(8 * a.ntiles * ((a.nlayers + 7) / 8)), a.nrows);
+    if (T == 2048)
+        k_ext_scatter<2048><<<grid, 64, 0, s>>>(a);
+    else if (T == 1024)
+        k_ext_scatter<1024><<<grid, 64, 0, s>>>(a);
+    else
+        k_ext_scatter<512><<<grid, 64, 0, s>>>(a);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+static int exp_launch_rounds(pb_lbl *p, LblArgs &a, const GatherPlan &g, const Tuning &tn,
+                             hipStream_t s)
+{
+    const pb_voigt *v = p->voigt;
+    const pb_lines *l = p->lines;
+    const int nlayers = a.nlayers;
+    const int64_t wbegin = a.wbegin, wcount = a.wcount;
+    // geometry: 16 wavefronts x 2 spans of 256 samples (tile 8192, two LDS buffers of 8192
+    // samples, one workgroup per CU) or 8 x 2 (tile 4096, buffers of 4096, two per CU)
+    const int geom = tn.rounds_geom;
+    int T = 0;
+    rounds_geometry(geom, &T, &a.rbuf);
+    a.rtile = T;
+    a.ntiles = pb::div_up(wcount, T);
+    int rsplit = (int)std::min<int64_t>(
+        8, pb::div_up((int64_t)(g.per_phase >= 64.0 ? 4000 : 1000),
+                      std::max<int64_t>(1, (int64_t)a.ntiles * nlayers)));
+    if (tn.stage_split)
+        rsplit = tn.stage_split;
+    rsplit = cap_split_to_planes(rsplit, plane_bytes(a));
+    a.nsplit = rsplit;
+    if (int rc = ensure_part(p, a, rsplit, s))
+        return rc;
+    // the largest distance from which a group can reach a tile, over all layers
+    const int64_t reachmax = group_reach(v, a.cutoff, a.ownstep) + 2 * (int64_t)v->osamp;
+    a.reachmax = reachmax;
+    const int nunits = a.ntiles * rsplit;
+    if (p->cap_key[0] != wbegin || p->cap_key[1] != wcount || p->cap_key[2] != T ||
+        p->cap_key[3] != rsplit) {
+        // capacity of every unit: the groups (any isotope) within reach of its tile
+        std::vector<int64_t> cap((size_t)nunits + 1, 0);
+        for (int t = 0; t < a.ntiles; t++) {
+            const int64_t t0 = wbegin + (int64_t)t * T;
+            const int64_t tend = std::min(t0 + T, wbegin + wcount);
+            int64_t n = groups_in_reach(l, p->niso, t0 * v->osamp - reachmax,
+                                        (tend - 1) * v->osamp + reachmax);
+            n = (n + 3) & ~(int64_t)3;
+            for (int z = 0; z < rsplit; z++)
+                cap[(size_t)t * rsplit + z + 1] = n;
+        }
+        for (int u = 0; u < nunits; u++)
+            cap[(size_t)u + 1] += cap[(size_t)u];
+        PB_HIP(hipStreamSynchronize(s));       // an earlier call may still read the lists
+        if (int rc = ensure_bytes((void **)&p->unit_cap, &p->unit_cap_bytes, cap.size() * 8, s,
+                                  false, nullptr))
+            return rc;
+        PB_HIP(hipMemcpy(p->unit_cap, cap.data(), cap.size() * 8, hipMemcpyHostToDevice));
+        p->cap_key[0] = wbegin;
+        p->cap_key[1] = wcount;
+        p->cap_key[2] = T;
+        p->cap_key[3] = rsplit;
+        p->cap_key[4] = cap.back();
+    }
+    const size_t nent = (size_t)nlayers * a.nrows * (size_t)p->cap_key[4] + 4;
+    if (nent > p->vrec_alloc) {
+        // the three lists grow together (vrec_alloc entries each)
+        size_t b0 = 0, b1 = 0, b2 = 0;
+        p->vrec_alloc = 0;
+        PB_HIP(hipStreamSynchronize(s));
+        int rc = ensure_bytes((void **)&p->vrec, &b0, nent * 16, s, false, "visit records");
+        if (rc == PB_OK)
+            rc = ensure_bytes((void **)&p->vseg, &b1, nent * 16, s, false, "visit records");
+        if (rc == PB_OK)
+            rc = ensure_bytes((void **)&p->vrnd, &b2, nent * 4, s, false, "visit records");
+        if (rc)
+            return rc;
+        p->vrec_alloc = nent;
+    }
+    const size_t nhdr = (size_t)nlayers * a.nrows * nunits;
+    if (int rc = ensure_bytes((void **)&p->uhdr, &p->uhdr_bytes, nhdr * 16, s, true, nullptr))
+        return rc;
+    a.unit_cap = p->unit_cap;
+    a.vrec = p->vrec;
+    a.vseg = p->vseg;
+    a.vrnd = p->vrnd;
+    a.uhdr = p->uhdr;
+    if (int rc = rounds_launch(a, geom, s))
+        return rc;
+    if (rsplit > 1) {
+        const int64_t n = (int64_t)nlayers * a.nrows * wcount;
+        k_combine_parts<<<(unsigned)pb::div_up(n, kBlock), kBlock, 0, s>>>(
+            a.ext, p->part, rsplit - 1, n, nullptr, (int64_t)a.nrows * wcount);
+    }
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+// PB_STAGE_PROBE: instrumented instances of the staged kernel in place of `kern`
+static int exp_stage_probe_begin(LblArgs &a, const GatherPlan &g, const Tuning &tn,
+                                 GatherKernel *kern, hipStream_t s)
+{
+    const int e = tn.stage_probe;
+    if (g.S != 2 || !g.dma)
+        return PB_OK;
+    if (e >= 1 && e <= 3)                                 // 1, 2: timing probes, wrong sums
+        *kern = e == 1   ? k_ext_staged<kStagedWaves, 2, true, 1>
+                : e == 2 ? k_ext_staged<kStagedWaves, 2, true, 2>
+                         : k_ext_staged<kStagedWaves, 2, true, 3>;
+    if (e >= 11 && e <= 12)                               // 11, 12: who requests the row DMA
+        *kern = e == 11 ? k_ext_staged<kStagedWaves, 2, true, 0, 1>
+                        : k_ext_staged<kStagedWaves, 2, true, 0, 2>;
+    if (e == 4) {                                         // the cycle account (valid sums)
+        *kern = k_ext_staged<kStagedWaves, 2, true, 4>;
+        PB_HIP(hipMalloc(&a.probe, (size_t)a.nlayers * 24 * 8));
+        PB_HIP(hipMemsetAsync(a.probe, 0, (size_t)a.nlayers * 24 * 8, s));
+    }
+    return PB_OK;
+}
+
+static int exp_stage_probe_end(LblArgs &a, hipStream_t s)
+{
+    if (!a.probe)
+        return PB_OK;
+    // one line per layer on stderr: layer, rowmax of its first isotope, then the 15 sums
+    std::vector<unsigned long long> h((size_t)a.nlayers * 24);
+    PB_HIP(hipMemcpyAsync(h.data(), a.probe, h.size() * 8, hipMemcpyDeviceToHost, s));
+    std::vector<int32_t> rowmax((size_t)a.nlayers * a.niso);
+    PB_HIP(hipMemcpyAsync(rowmax.data(), a.li_rowmax, rowmax.size() * 4,
+                          hipMemcpyDeviceToHost, s));
+    PB_HIP(hipStreamSynchronize(s));
+    (void)hipFree(a.probe);
+    a.probe = nullptr;
+    for (int layer = 0; layer < a.nlayers; layer++) {
+        fprintf(stderr, "STAGE_PROBE layer %d rowmax %d :", layer,
+                rowmax[(size_t)layer * a.niso]);
+        for (int i = 0; i < 21; i++)
+            fprintf(stderr, " %llu", h[(size_t)layer * 24 + i]);
+        fprintf(stderr, "\n");
+    }
+    return PB_OK;
+}
+
+// the short-row layers first: many short workgroups, then the staged kernel's long ones
+static int exp_launch_wave(const LblArgs &a, int nunits, hipStream_t s)
+{
+    return a.wave_cap > 0 ? wave_launch(a, nunits, s) : PB_OK;
+}
+#else
+static inline void exp_wave_cap(const pb_lbl *, LblArgs &, const GatherPlan &, const Tuning &) {}
+static inline int exp_scatter_records(pb_lbl *, LblArgs &, const Tuning &, hipStream_t) { return PB_OK; }
+static inline int exp_launch_scatter(LblArgs &, const Tuning &, hipStream_t) { return PB_OK; }
+static inline int exp_launch_rounds(pb_lbl *, LblArgs &, const GatherPlan &, const Tuning &,
+                                    hipStream_t) { return PB_OK; }
+static inline int exp_stage_probe_begin(LblArgs &, const GatherPlan &, const Tuning &,
+                                        GatherKernel *, hipStream_t) { return PB_OK; }
+static inline int exp_stage_probe_end(LblArgs &, hipStream_t) { return PB_OK; }
+static inline int exp_launch_wave(const LblArgs &, int, hipStream_t) { return PB_OK; }
+#endif  // PB_EXPERIMENTS
+
+// The record buffers the plan needs, grown on first use and bound to the arguments.  They are
+// zeroed when allocated (fill_args: a record never written is a dead record).
+static int bind_records(pb_lbl *p, LblArgs &a, const GatherPlan &g, const Tuning &tn, hipStream_t s)
+{
+    const pb_lines *l = p->lines;
+    const size_t n = (size_t)p->max_layers * (size_t)l->ngroups;
+    if (g.packed) {
+        const size_t had = p->rec16_alloc;
+        if (int rc = ensure_bytes((void **)&p->rec16, &p->rec16_alloc, g.rec16_need, s, true,
+                                  "line records"))
+            return rc;
+        if (p->rec16_alloc != had) {
+            PB_HIP(hipMemsetAsync(p->rec16, 0, g.rec16_need, s));
+            if (tn.poison)
+                k_poison_records<<<1024, kBlock, 0, s>>>(p->rec16, (int64_t)(g.rec16_need / sizeof(Rec16)),
                                                         nullptr, 0, nullptr, nullptr, 0);
         }
         a.rec16 = p->rec16;
     }
-    // Layers of short phase rows (<= kWvRowMax samples: the Doppler-core layers) go to the
-    // wave-autonomous kernel (pb_wave.hip), decided per layer on the device by k_layer_state; the
-    // staged kernel computes the others.  Mode 7 selects the pair; modes 0 and 2 keep to the staged
-    // kernel alone.  Chunked line lists continue running sums in the staged kernel's order and
-    // keep to it.
-#ifdef PB_EXPERIMENTS
-    {
-        // (measured at C2, round 4: the pair takes 1.20 ms per extinction against 1.05 ms for the
-        // staged kernel alone -- profiles/r04_gather_wave.md -- so mode 0 does not use it unless
-        // PB_WAVE=1 asks for it)
-        bool wave_on = staged && !rounds && !scatter && !chunked && a.rec16 != nullptr &&
-                       p->gather_mode == 7;
-        if (const char *e = getenv("PB_WAVE"))
-            wave_on = staged && !rounds && !scatter && !chunked && a.rec16 != nullptr &&
-                      (p->gather_mode == 0 || p->gather_mode == 7) && atoi(e) != 0;
-        if (wave_on && wave_lds(a) <= 160 * 1024)
-            a.wave_cap = kWvRowMax;
-    }
-#endif  // PB_EXPERIMENTS
-    a.nsplit = 1;
-    a.part = nullptr;
-    a.wm_lo[0] = a.wm_lo[1] = a.wm_off[0] = a.wm_off[1] = nullptr;
-    a.wm_n[0] = a.wm_n[1] = 0;
-    a.wm_total[0] = a.wm_total[1] = 0;
-#ifdef PB_EXPERIMENTS
-    if (scatter) {
-        if (!p->rec32) {
-            const size_t n = (size_t)p->max_layers * (size_t)l->ngroups;
-            if (hipMalloc(&p->rec32, n * sizeof(Rec32)) != hipSuccess) {
-                pb::set_error("pb_lbl_extinction: cannot allocate %zu B of line records",
-                              n * sizeof(Rec32));
-                return PB_ERR_NOMEM;
-            }
-            PB_HIP(hipMemsetAsync(p->rec32, 0, n * sizeof(Rec32), s));
-            if (poison)
-                k_poison_records<<<1024, kBlock, 0, s>>>(nullptr, 0, p->rec32, (int64_t)n, nullptr,
-                                                        nullptr, 0);
-        }
-        a.rec32 = p->rec32;
-    }
-#endif  // PB_EXPERIMENTS
-    if (chunked)
-        a.res_cap = 0;                   // every layer through the staged gather
+    exp_wave_cap(p, a, g, tn);
+    if (g.scatter)
+        if (int rc = exp_scatter_records(p, a, tn, s))
+            return rc;
     // the SoA records serve the global gather, the resident layers and PB_REC_SOA
-    const bool need_soa = use_records && !scatter && (a.rec16 == nullptr || a.res_cap > 0);
+    const bool need_soa = g.use_records && !g.scatter && (a.rec16 == nullptr || a.res_cap > 0);
     if (need_soa && !p->rec_k) {
-        const size_t n = (size_t)p->max_layers * (size_t)l->ngroups;
-        if (hipMalloc(&p->rec_k, n * 8) != hipSuccess ||
-            hipMalloc(&p->rec_i32, n * 4 * 5) != hipSuccess) {
-            pb::set_error("pb_lbl_extinction: cannot allocate %zu B of line records", n * 28);
-            return PB_ERR_NOMEM;
-        }
+        size_t b0 = 0, b1 = 0;
+        int rc = ensure_bytes((void **)&p->rec_k, &b0, n * 8, s, false, "line records");
+        if (rc == PB_OK)
+            rc = ensure_bytes((void **)&p->rec_i32, &b1, n * 4 * 5, s, false, "line records");
+        if (rc)
+            return rc;
         PB_HIP(hipMemsetAsync(p->rec_k, 0, n * 8, s));
         PB_HIP(hipMemsetAsync(p->rec_i32, 0, n * 4 * 5, s));
-        if (poison)
+        if (tn.poison)
             k_poison_records<<<1024, kBlock, 0, s>>>(nullptr, 0, nullptr, 0, p->rec_k, p->rec_i32,
                                                     (int64_t)n);
     }
-    if (use_records) {
-        const size_t n = (size_t)p->max_layers * (size_t)l->ngroups;
+    if (g.use_records) {
         a.rec_k = p->rec_k;
         a.rec_ulo = p->rec_i32;
         a.rec_uhi = p->rec_i32 + n;
@@ -3443,645 +3646,392 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
         a.rec_cell = p->rec_i32 + 3 * n;
         a.rec_phi = p->rec_i32 + 4 * n;
         // records are laid out in the order the chosen gather kernel walks the groups
-        a.rk_first = staged ? p->ph_first : l->d_gfirst;
-        a.rk_count = staged ? p->ph_count : l->d_gcount;
-        a.rk_iown = staged ? p->ph_iown : l->d_giown;
-        a.rk_iso = staged ? p->ph_iso : l->d_giso;
-        const double *lead = staged ? p->ph_lead : p->g_lead;
+        a.rk_first = g.staged ? p->ph_first : l->d_gfirst;
+        a.rk_count = g.staged ? p->ph_count : l->d_gcount;
+        a.rk_iown = g.staged ? p->ph_iown : l->d_giown;
+        a.rk_iso = g.staged ? p->ph_iso : l->d_giso;
+        const double *lead = g.staged ? p->ph_lead : p->g_lead;
         a.rk_lwn = lead;
         a.rk_elow = lead + l->ngroups;
         a.rk_gf = lead + 2 * l->ngroups;
     }
-    a.use_records = use_records ? 1 : 0;
+    a.use_records = g.use_records ? 1 : 0;
+    return PB_OK;
+}
 
-    bool dyn_fall = false;
-    // (a fine grid shorter than two steps of the coarsest dynamic grid has no constant-step form)
-    if (p->resolution && p->gather_mode == 6 && phase == 0 && l->ngroups > 0 &&
-        l->onwn > 2 * (int64_t)v->osamp &&
-        !(getenv("PB_RES_DYN") && atoi(getenv("PB_RES_DYN")) == 0)) {
-        const int rc = lbl_resolution_dyn(p, a, ext_d, wbegin, wcount, temp_d, dens_d, isoz_d,
-                                          z_iso_stride, z_layer_stride, nlayers, add, s);
-        // a re-cut table row that cannot be addressed (pb_voigt_ensure_rows) before any run has
-        // added to ext: the direct gather below computes the call instead
-        if (!(rc == PB_ERR_UNSUPPORTED && p->dyn_runs == 0)) {
-            if (rc != PB_OK || !p->dyn_fallback)
-                return rc;
-            // a call planned from a prediction: the layers the plan did not fit (none, as a
-            // rule: the launches below then end at once) go through the direct gather
-            dyn_fall = true;
-            a.lskip = p->d_ok;
-        }
-    }
-    if (phase != 2 && !dyn_fall) {
-    k_layer_state<<<nlayers, 64, ((size_t)a.nlor + a.ndop) * 8 + (size_t)a.ndivs * 4, s>>>(a);
-    PB_LAUNCH_CHECK();
-    }
-    if (chunked) {
-        // pass 1: the per-row maxima over ALL lines (the threshold of every chunk's gather);
-        // pass 2: per chunk, the records of its groups, then the gather, which continues the
-        // running sums of the earlier chunks.  One workgroup per tile (no phase split): the sums
-        // of a sample are then exactly those of a single launch over every key.
-        {
-            const int lines_per_block = 4096;
-            dim3 grid(pb::div_up(l->nlines, lines_per_block), nlayers);
-            k_kmax<<<grid, kBlock, (size_t)a.nrows * 8, s>>>(a, lines_per_block);
-            PB_LAUNCH_CHECK();
-        }
-        const bool timed = p->ev_used + 2 <= (int)p->ev.size();
-        if (timed)
-            PB_HIP(hipEventRecord(p->ev[p->ev_used], s));
-        const int per = kRecLayers;
-        const size_t rlds = (size_t)per * a.nrows * 8 + (size_t)a.ndop * 8 +
-                            (size_t)per * a.niso * (8 + 8 + 8 + 4) + (size_t)a.niso * (8 + 4) + 16 + 8;
-        PB_REQUIRE(rlds <= 64 * 1024, "pb_lbl_extinction: %zu B of LDS for the record kernel", rlds);
-        a.wm_lds = 0;
-        a.nsplit = 1;
-        a.part = nullptr;
-        a.ntiles = pb::div_up(wcount, S * sub);
-        const int unit_groups = (nlayers + 7) / 8;
-        dim3 ggrid((unsigned)(8 * a.ntiles * unit_groups), a.nrows);
-        void (*kern)(LblArgs) =
-            dma ? (S == 4   ? k_ext_staged<kStagedWaves, 4, true>
-                   : S == 2 ? k_ext_staged<kStagedWaves, 2, true>
-                            : k_ext_staged<kStagedWaves, 1, true>)
-                : (S == 4   ? k_ext_staged<kStagedWaves, 4, false>
-                   : S == 2 ? k_ext_staged<kStagedWaves, 2, false>
-                            : k_ext_staged<kStagedWaves, 1, false>);
-        if (lds > 64 * 1024)
-            PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        for (size_t c = 0; c < chunks.size(); c++) {
-            a.grp_lo = chunks[c].g_lo;
-            a.grp_hi = chunks[c].g_hi;
-            a.rec_pitch = std::max<int64_t>(1, a.grp_hi - a.grp_lo);
-            a.key_lo = chunks[c].key_lo;
-            a.key_hi = chunks[c].key_hi;
-            a.accumulate = c > 0 ? 1 : 0;
-            if (a.grp_hi > a.grp_lo) {
-                dim3 rgrid(pb::div_up(a.grp_hi - a.grp_lo, kBlock), pb::div_up(nlayers, per));
-                if (a.nch_max > 1)
-                    k_records<2, kRecLayers><<<rgrid, kBlock, rlds, s>>>(a);
-                else
-                    k_records<1, kRecLayers><<<rgrid, kBlock, rlds, s>>>(a);
-                PB_LAUNCH_CHECK();
-            }
-            kern<<<ggrid, kStagedThreads, lds, s>>>(a);
-            PB_LAUNCH_CHECK();
-        }
-        p->last_gather = 2;
-        p->last_args = a;
-        p->last_packed = false;
-        if (timed) {
-            PB_HIP(hipEventRecord(p->ev[p->ev_used + 1], s));
-            p->ev_used += 2;
-        }
-        return PB_OK;
-    }
-    if (phase == 2) {
-        // records and maxima are in place
-    } else if (use_records) {
-        // (one layer per thread for launches of few layers measured slower: 10 layers of C2
-        // 49 us against 27 us with four; PB_REC_LAYERS=1 selects it)
-        const int per = getenv("PB_REC_LAYERS") && atoi(getenv("PB_REC_LAYERS")) == 1 ? 1 : kRecLayers;
-        int64_t rec_threads = l->ngroups;
-        if (a.kmax_local && a.rec_flo != INT64_MIN && !p->h_ph_iown.empty() &&
-            !getenv("PB_NO_WINDOW_MAP")) {
-            // two-phase shard call: only the groups within reach of the shard get a thread
-            const int osamp = v->osamp, niso = a.niso;
-            if (p->wm_flo != a.rec_flo || p->wm_fhi != a.rec_fhi || p->wm_staged != (int)staged) {
-                const int n0 = staged ? niso * osamp : niso, n1 = niso;
-                std::vector<int32_t> &h = p->h_wm;
-                h.assign((size_t)2 * n0 + 1 + 2 * n1 + 1, 0);
-                int32_t *lo0 = h.data(), *off0 = lo0 + n0, *lo1 = off0 + n0 + 1, *off1 = lo1 + n1;
-                const int64_t flo = std::max<int64_t>(a.rec_flo, INT32_MIN);
-                const int64_t fhi = std::min<int64_t>(a.rec_fhi, INT32_MAX);
-                auto run = [&](const std::vector<int32_t> &pos, int64_t b, int64_t e, int32_t *lo,
-                               int32_t *off, int r) {
-                    const auto first = pos.begin() + b, last = pos.begin() + e;
-                    const auto x0 = std::lower_bound(first, last, (int32_t)flo);
-                    const auto x1 = std::upper_bound(x0, last, (int32_t)fhi);
-                    lo[r] = (int32_t)(x0 - pos.begin());
-                    off[r + 1] = off[r] + (int32_t)(x1 - x0);
-                };
-                for (int i = 0; i < niso; i++) {
-                    run(l->h_giown, l->iso_gstart[(size_t)i], l->iso_gstart[(size_t)i + 1], lo1, off1, i);
-                    if (staged)
-                        for (int ph = 0; ph < osamp; ph++)
-                            run(p->h_ph_iown, p->h_ph_start[(size_t)i * (osamp + 1) + ph],
-                                p->h_ph_start[(size_t)i * (osamp + 1) + ph + 1], lo0, off0,
-                                i * osamp + ph);
-                    else
-                        run(l->h_giown, l->iso_gstart[(size_t)i], l->iso_gstart[(size_t)i + 1], lo0, off0, i);
-                }
-                if (h.size() > p->wm_cap) {
-                    (void)hipFree(p->d_wm);
-                    p->d_wm = nullptr;
-                    p->wm_cap = 0;
-                    if (hipMalloc(&p->d_wm, h.size() * 4) != hipSuccess) {
-                        pb::set_error("pb_lbl_extinction: cannot allocate the window map");
-                        return PB_ERR_NOMEM;
-                    }
-                    p->wm_cap = h.size();
-                }
-                PB_HIP(hipMemcpyAsync(p->d_wm, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
-                p->wm_flo = a.rec_flo;
-                p->wm_fhi = a.rec_fhi;
-                p->wm_staged = (int)staged;
-                p->wm_n0 = n0;
-                p->wm_n1 = n1;
-                p->wm_total0 = off0[n0];
-                p->wm_total1 = off1[n1];
-            }
-            a.wm_n[0] = p->wm_n0;
-            a.wm_n[1] = p->wm_n1;
-            a.wm_lo[0] = p->d_wm;
-            a.wm_off[0] = p->d_wm + p->wm_n0;
-            a.wm_lo[1] = p->d_wm + 2 * p->wm_n0 + 1;
-            a.wm_off[1] = a.wm_lo[1] + p->wm_n1;
-            a.wm_total[0] = p->wm_total0;
-            a.wm_total[1] = p->wm_total1;
-            rec_threads = std::max<int64_t>(1, std::max(p->wm_total0, p->wm_total1));
-        }
-        dim3 grid(pb::div_up(rec_threads, kBlock), pb::div_up(nlayers, per));
-        // the run offsets of the phase-order window map go to LDS while they fit beside the rest
-        // in 48 KiB (niso * osamp + 1 words: the reference's default wnosamp of 2160 with 8
-        // isotopes is already 69 KiB); larger maps are bisected in global memory
-        const size_t rlds0 = (size_t)per * a.nrows * 8 + (size_t)a.ndop * 8 +
-                             (size_t)per * a.niso * (8 + 8 + 8 + 4) + (size_t)a.niso * (8 + 4) + 16;
-        const size_t wm_bytes = ((size_t)a.wm_n[0] + 2) * 4;
-        size_t wm_cap_lds = 48 * 1024;
-        if (const char *e = getenv("PB_WM_LDS_CAP"))
-            wm_cap_lds = (size_t)atol(e);
-        a.wm_lds = a.wm_off[0] && rlds0 + wm_bytes <= wm_cap_lds ? 1 : 0;
-        const size_t rlds = rlds0 + (a.wm_lds ? wm_bytes : 8);
-        PB_REQUIRE(rlds <= 64 * 1024, "pb_lbl_extinction: %zu B of LDS for the record kernel "
-                   "(too many isotopes / output rows)", rlds);
-        const int fmt = a.rec32 ? 3 : (a.rec16 && a.nch_max > 1) ? 2 : a.rec16 ? 1 : 0;
-        void (*krec)(LblArgs) =
-            per == 1 ? (fmt == 3   ? k_records<3, 1>
-                        : fmt == 2 ? k_records<2, 1>
-                        : fmt == 1 ? k_records<1, 1>
-                                   : k_records<0, 1>)
-                     : (fmt == 3   ? k_records<3, kRecLayers>
-                        : fmt == 2 ? k_records<2, kRecLayers>
-                        : fmt == 1 ? k_records<1, kRecLayers>
-                                   : k_records<0, kRecLayers>);
-        krec<<<grid, kBlock, rlds, s>>>(a);
-        PB_LAUNCH_CHECK();
-    } else if (l->nlines > 0) {
-        const int lines_per_block = 4096;
-        dim3 grid(pb::div_up(l->nlines, lines_per_block), nlayers);
-        k_kmax<<<grid, kBlock, (size_t)a.nrows * 8, s>>>(a, lines_per_block);
-        PB_LAUNCH_CHECK();
-    }
-    if (phase == 1)
-        return PB_OK;
-    const int layer_groups = (nlayers + 7) / 8;
-    const bool timed = !dyn_fall && p->ev_used + 2 <= (int)p->ev.size();
+// An out-of-core line list, chunk by chunk.
+// pass 1: the per-row maxima over ALL lines (the threshold of every chunk's gather);
+// pass 2: per chunk, the records of its groups, then the gather, which continues the
+// running sums of the earlier chunks.  One workgroup per tile (no phase split): the sums
+// of a sample are then exactly those of a single launch over every key.
+static int run_chunked(pb_lbl *p, LblArgs &a, const GatherPlan &g, hipStream_t s)
+{
+    const int nlayers = a.nlayers;
+    if (int rc = launch_kmax(a, s))
+        return rc;
+    const bool timed = p->ev_used + 2 <= (int)p->ev.size();
     if (timed)
         PB_HIP(hipEventRecord(p->ev[p->ev_used], s));
-    p->last_gather = dyn_fall ? 6 : scatter ? 4
-                             : (p->resolution ? 3 : rounds ? 5 : staged ? 2 : 1) +
-                                   (resident ? 8 : 0) + (a.wave_cap > 0 ? 16 : 0);
-#ifdef PB_EXPERIMENTS
-    if (scatter) {
-        int T = 512;
-        if (const char *e = getenv("PB_SCATTER_T"))
-            T = atoi(e);
-        T = T >= 2048 ? 2048 : T >= 1024 ? 1024 : 512;
-        a.ntiles = pb::div_up(wcount, T);
-        dim3 grid((unsigned)(8 * a.ntiles * layer_groups), a.nrows);
-        if (T == 2048)
-            k_ext_scatter<2048><<<grid, 64, 0, s>>>(a);
-        else if (T == 1024)
-            k_ext_scatter<1024><<<grid, 64, 0, s>>>(a);
-        else
-            k_ext_scatter<512><<<grid, 64, 0, s>>>(a);
-        PB_LAUNCH_CHECK();
-    } else
-#endif  // PB_EXPERIMENTS
-    if (resident) {
-        a.ntiles = pb::div_up(wcount, kResTile);
-        dim3 grid((unsigned)(8 * a.ntiles * layer_groups), a.nrows);
-        const size_t rlds = ((size_t)a.res_cap + 2) * 8 + (size_t)kResThreads * (16 + 4) +
-                            kResWaves * 4 + 64;
-        if (rlds > 64 * 1024)
-            PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ext_resident),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-        k_ext_resident<<<grid, kResThreads, rlds, s>>>(a);
-        PB_LAUNCH_CHECK();
-    }
-    if (scatter) {
-        // the scatter kernel computed every layer
-    } else if (p->resolution) {
-        a.ntiles = pb::div_up(wcount, kBlock);
-        dim3 grid((unsigned)(8 * a.ntiles * layer_groups), a.nrows);
-        k_ext_linterp<<<grid, kBlock, 0, s>>>(a);
-    }
-#ifdef PB_EXPERIMENTS
-    else if (rounds) {
-        // geometry: 16 wavefronts x 2 spans of 256 samples (tile 8192, two LDS buffers of 8192
-        // samples, one workgroup per CU) or 8 x 2 (tile 4096, buffers of 4096, two per CU)
-        int geom = 2;
-        if (const char *e = getenv("PB_ROUNDS_GEOM"))
-            geom = std::max(0, std::min(7, atoi(e)));
-        int T = 0;
-        rounds_geometry(geom, &T, &a.rbuf);
-        a.rtile = T;
-        a.ntiles = pb::div_up(wcount, T);
-        int rsplit = (int)std::min<int64_t>(
-            8, pb::div_up((int64_t)(per_phase >= 64.0 ? 4000 : 1000),
-                          std::max<int64_t>(1, (int64_t)a.ntiles * nlayers)));
-        if (const char *e = getenv("PB_STAGE_SPLIT"))
-            rsplit = std::max(1, std::min(8, atoi(e)));
-        {
-            const int64_t plane = (int64_t)nlayers * a.nrows * wcount * 8;
-            while (rsplit > 1 && (rsplit - 1) * plane > ((int64_t)1 << 30))
-                rsplit--;
-        }
-        a.nsplit = rsplit;
-        if (rsplit > 1) {
-            const size_t need = (size_t)(rsplit - 1) * nlayers * a.nrows * wcount * 8;
-            if (need > p->part_bytes) {
-                (void)hipFree(p->part);
-                p->part = nullptr;
-                p->part_bytes = 0;
-                if (hipMalloc(&p->part, need) != hipSuccess) {
-                    pb::set_error("pb_lbl_extinction: cannot allocate %zu B of partial sums", need);
-                    return PB_ERR_NOMEM;
-                }
-                p->part_bytes = need;
-            }
-            a.part = p->part;
-        }
-        // the largest distance from which a group can reach a tile, over all layers
-        int64_t hmax_all = 0;
-        for (int32_t h : v->psize)
-            hmax_all = std::max<int64_t>(hmax_all, h);
-        int64_t reachmax = hmax_all;
-        if (a.cutoff > 0.0)
-            reachmax = std::min(reachmax, (int64_t)(a.cutoff / a.ownstep) + 2 * (int64_t)v->osamp + 2);
-        reachmax += 2 * (int64_t)v->osamp;
-        a.reachmax = reachmax;
-        const int nunits = a.ntiles * rsplit;
-        if (p->cap_key[0] != wbegin || p->cap_key[1] != wcount || p->cap_key[2] != T ||
-            p->cap_key[3] != rsplit) {
-            // capacity of every unit: the groups (any isotope) within reach of its tile
-            std::vector<int64_t> cap((size_t)nunits + 1, 0);
-            for (int t = 0; t < a.ntiles; t++) {
-                const int64_t t0 = wbegin + (int64_t)t * T;
-                const int64_t tend = std::min(t0 + T, wbegin + wcount);
-                const int64_t flo = t0 * v->osamp - reachmax, fhi = (tend - 1) * v->osamp + reachmax;
-                int64_t n = 0;
-                for (int i = 0; i < p->niso; i++) {
-                    const int32_t *b = l->h_giown.data() + l->iso_gstart[i];
-                    const int32_t *e = l->h_giown.data() + l->iso_gstart[i + 1];
-                    n += std::upper_bound(b, e, (int32_t)std::min<int64_t>(fhi, INT_MAX)) -
-                         std::lower_bound(b, e, (int32_t)std::max<int64_t>(flo, INT_MIN));
-                }
-                n = (n + 3) & ~(int64_t)3;
-                for (int z = 0; z < rsplit; z++)
-                    cap[(size_t)t * rsplit + z + 1] = n;
-            }
-            for (int u = 0; u < nunits; u++)
-                cap[(size_t)u + 1] += cap[(size_t)u];
-            PB_HIP(hipStreamSynchronize(s));       // an earlier call may still read the lists
-            (void)hipFree(p->unit_cap);
-            p->unit_cap = nullptr;
-            PB_HIP(hipMalloc(&p->unit_cap, cap.size() * 8));
-            PB_HIP(hipMemcpy(p->unit_cap, cap.data(), cap.size() * 8, hipMemcpyHostToDevice));
-            p->cap_key[0] = wbegin;
-            p->cap_key[1] = wcount;
-            p->cap_key[2] = T;
-            p->cap_key[3] = rsplit;
-            p->cap_key[4] = cap.back();
-        }
-        const size_t nent = (size_t)nlayers * a.nrows * (size_t)p->cap_key[4] + 4;
-        if (nent > p->vrec_alloc) {
-            PB_HIP(hipStreamSynchronize(s));
-            (void)hipFree(p->vrec);
-            (void)hipFree(p->vseg);
-            (void)hipFree(p->vrnd);
-            p->vrec = nullptr;
-            p->vseg = nullptr;
-            p->vrnd = nullptr;
-            p->vrec_alloc = 0;
-            if (hipMalloc(&p->vrec, nent * 16) != hipSuccess ||
-                hipMalloc(&p->vseg, nent * 16) != hipSuccess ||
-                hipMalloc(&p->vrnd, nent * 4) != hipSuccess) {
-                pb::set_error("pb_lbl_extinction: cannot allocate %zu B of visit records", nent * 32);
-                return PB_ERR_NOMEM;
-            }
-            p->vrec_alloc = nent;
-        }
-        const size_t nhdr = (size_t)nlayers * a.nrows * nunits;
-        if (nhdr > p->uhdr_alloc) {
-            PB_HIP(hipStreamSynchronize(s));
-            (void)hipFree(p->uhdr);
-            p->uhdr = nullptr;
-            PB_HIP(hipMalloc(&p->uhdr, nhdr * 16));
-            p->uhdr_alloc = nhdr;
-        }
-        a.unit_cap = p->unit_cap;
-        a.vrec = p->vrec;
-        a.vseg = p->vseg;
-        a.vrnd = p->vrnd;
-        a.uhdr = p->uhdr;
-        int rc = rounds_launch(a, geom, s);
-        if (rc != PB_OK)
-            return rc;
-        if (rsplit > 1) {
-            const int64_t n = (int64_t)nlayers * a.nrows * wcount;
-            k_combine_parts<<<(unsigned)pb::div_up(n, kBlock), kBlock, 0, s>>>(
-                ext_d, p->part, rsplit - 1, n, nullptr, (int64_t)a.nrows * wcount);
-        }
-    }
-#endif  // PB_EXPERIMENTS
-    else if (staged) {
-        // Per-layer split.  A launch ends when its slowest workgroup does, and the slowest are the
-        // tiles of the deepest layers (cutoff-limited windows of ~1000 samples against 200-300
-        // higher up: 0.7-0.9 ms of a 0.88-ms C2 launch, profiles/r02_gather_ab.md), which the
-        // dispatch order puts first.  The deepest `deep` layers are cut into more pieces than the
-        // others, so that no single workgroup spans the launch.  Pieces of a tile add their sums in
-        // a fixed order (k_combine_layer_parts): bitwise reproducible; against an unsplit launch
-        // the association of a sample's terms differs (~1e-16).  PB_STAGE_SPLIT pins one split for
-        // every layer (the exactness tests), PB_STAGE_DEEP=frac[,factor] tunes the rule.
-        // Measured (profiles/r03_gather_ab.md): C3 44.1 -> 42.3 ms (-4 %), the 1e6-line list -1 %,
-        // C2 +4 % (one spectrum at a time) / +3 % (pipelined): the second prologue and the combine
-        // pass cost a light launch more than its tail does.  On by default only for long rows.
-        int deep = 0, deep_split = nsplit;
-        if (!getenv("PB_STAGE_SPLIT") && nsplit < 8 && nlayers >= 8) {
-            double frac = a.nch_max > 1 ? 0.3 : 0.0;
-            int factor = 2;
-            if (const char *e = getenv("PB_STAGE_DEEP")) {
-                frac = atof(e);
-                if (const char *c = strchr(e, ','))
-                    factor = std::max(1, atoi(c + 1));
-            }
-            deep = (int)(frac * nlayers + 0.5);
-            deep_split = std::min(8, nsplit * factor);
-            const int64_t plane = (int64_t)nlayers * a.nrows * wcount * 8;
-            while (deep_split > nsplit && (deep_split - 1) * plane > ((int64_t)1 << 30))
-                deep_split--;
-            if (deep <= 0 || deep_split <= nsplit)
-                deep = 0, deep_split = nsplit;
-        }
-        a.unit_tab = nullptr;
-        a.lsplit = nullptr;
-        a.nunits = 0;
-        a.tsplit = nullptr;
-        // Per-tile split.  A uniform line list gives every tile the same number of records; a
-        // real one has band heads (10^2-10^3 x the line density of the gaps): the few tiles under
-        // a head run 10 x as long as the others and end the launch alone (the C2 grid with 8 band
-        // heads per isotope at 300 x contrast: gather 1.90 ms unsplit, 1.34 ms with every tile in
-        // four pieces -- profiles/r04_bands.md).  From the groups within reach of every tile (host
-        // copy of the group positions, cached per tiling) the tiles above 1.5 x the median count
-        // get more pieces, up to 8; the others keep the launch's.  Automatic mode only: a forced
-        // mode adds the terms of a sample in one order whatever the tiling (pbhip.h).
-        if (deep == 0 && a.nch_max == 1 && p->gather_mode == 0 && a.wave_cap == 0 &&
-            !getenv("PB_STAGE_SPLIT") && !(getenv("PB_TILE_SPLIT") && atoi(getenv("PB_TILE_SPLIT")) == 0) &&
-            !l->h_giown.empty()) {
-            const int tile = S * (int)sub;
-            const int nt = pb::div_up(wcount, tile);
-            if (p->ts_key[0] != wbegin || p->ts_key[1] != wcount || p->ts_key[2] != tile ||
-                p->ts_key[3] != nsplit) {
-                int64_t hmax_all = 0;
-                for (int32_t h : v->psize)
-                    hmax_all = std::max<int64_t>(hmax_all, h);
-                int64_t reach = hmax_all;
-                if (a.cutoff > 0.0)
-                    reach = std::min(reach, (int64_t)(a.cutoff / a.ownstep) + 2 * (int64_t)v->osamp + 2);
-                std::vector<int64_t> cnt((size_t)nt, 0);
-                for (int t = 0; t < nt; t++) {
-                    const int64_t t0 = wbegin + (int64_t)t * tile;
-                    const int64_t tend = std::min<int64_t>(t0 + tile, wbegin + wcount);
-                    const int64_t flo = t0 * v->osamp - reach, fhi = (tend - 1) * v->osamp + reach;
-                    for (int i = 0; i < p->niso; i++) {
-                        const int32_t *b = l->h_giown.data() + l->iso_gstart[(size_t)i];
-                        const int32_t *e = l->h_giown.data() + l->iso_gstart[(size_t)i + 1];
-                        cnt[(size_t)t] += std::upper_bound(b, e, (int32_t)std::min<int64_t>(fhi, INT_MAX)) -
-                                          std::lower_bound(b, e, (int32_t)std::max<int64_t>(flo, INT_MIN));
-                    }
-                }
-                std::vector<int64_t> sorted(cnt);
-                std::nth_element(sorted.begin(), sorted.begin() + nt / 2, sorted.end());
-                const double median = (double)std::max<int64_t>(1, sorted[(size_t)nt / 2]);
-                std::vector<int32_t> ts((size_t)nt);
-                int tmax = nsplit;
-                const int tmin = getenv("PB_TILE_MIN") ? atoi(getenv("PB_TILE_MIN")) : 1;
-                if (getenv("PB_TILE_DEBUG")) {
-                    fprintf(stderr, "tile counts (median %.0f):", median);
-                    for (int t = 0; t < nt; t++)
-                        fprintf(stderr, " %lld", (long long)cnt[(size_t)t]);
-                    fprintf(stderr, "\n");
-                }
-                // groups per (2048 samples, phase row) of a tile against the threshold that sends a
-                // whole launch to the global gather: a tile below it is visit-starved in the staged
-                // kernel (~300 barrier steps of one or two records: as long as a full tile) -- once
-                // SOME tile is dense enough to be split, the sparse ones go to the global gather
-                bool sparse = false, dense = false;
-                for (int t = 0; t < nt; t++) {
-                    const int k = std::max(tmin, (int)std::ceil((double)cnt[(size_t)t] / (1.5 * median)));
-                    ts[(size_t)t] = std::max(nsplit, std::min(8, nsplit * std::max(1, k)));
-                    tmax = std::max(tmax, ts[(size_t)t]);
-                    dense = dense || ts[(size_t)t] > nsplit;
-                }
-                if (dense && packable && p->pos2ph &&
-                    !(getenv("PB_TILE_GLOBAL") && atoi(getenv("PB_TILE_GLOBAL")) == 0))
-                    for (int t = 0; t < nt; t++) {
-                        const double per =
-                            (double)cnt[(size_t)t] * 2048.0 / (double)tile / (double)v->osamp;
-                        if (per < p->stage_threshold) {
-                            ts[(size_t)t] = 0;
-                            sparse = true;
-                        }
-                    }
-                p->ts_sparse = sparse;
-                PB_HIP(hipStreamSynchronize(s));       // an earlier call may still read the table
-                if (nt > p->ts_tiles) {
-                    (void)hipFree(p->d_tsplit);
-                    p->d_tsplit = nullptr;
-                    PB_HIP(hipMalloc(&p->d_tsplit, (size_t)nt * 4));
-                    p->ts_tiles = nt;
-                }
-                PB_HIP(hipMemcpy(p->d_tsplit, ts.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
-                p->ts_key[0] = wbegin;
-                p->ts_key[1] = wcount;
-                p->ts_key[2] = tile;
-                p->ts_key[3] = nsplit;
-                p->ts_max = tmax;
-            }
-            if (p->ts_max > nsplit) {
-                const int64_t plane = (int64_t)nlayers * a.nrows * wcount * 8;
-                if ((int64_t)(p->ts_max - 1) * plane <= ((int64_t)1 << 30)) {
-                    a.tsplit = p->d_tsplit;
-                    a.ts_tile = tile;
-                    a.pos2ph = p->pos2ph;
-                    nsplit = deep_split = p->ts_max;
-                }
-            }
-        }
-        if (deep > 0) {
-            if (p->ut_key[0] != nlayers || p->ut_key[1] != nsplit || p->ut_key[2] != deep ||
-                p->ut_key[3] != deep_split) {
-                std::vector<int32_t> tab, ls((size_t)nlayers);
-                for (int layer = nlayers - 1; layer >= 0; layer--) {
-                    const int n = layer >= nlayers - deep ? deep_split : nsplit;
-                    ls[(size_t)layer] = n;
-                    for (int z = 0; z < n; z++)
-                        tab.push_back((layer << 8) | z);
-                }
-                PB_HIP(hipStreamSynchronize(s));       // an earlier call may still read the tables
-                (void)hipFree(p->d_unit_tab);
-                (void)hipFree(p->d_lsplit);
-                p->d_unit_tab = p->d_lsplit = nullptr;
-                PB_HIP(hipMalloc(&p->d_unit_tab, tab.size() * 4));
-                PB_HIP(hipMalloc(&p->d_lsplit, ls.size() * 4));
-                PB_HIP(hipMemcpy(p->d_unit_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-                PB_HIP(hipMemcpy(p->d_lsplit, ls.data(), ls.size() * 4, hipMemcpyHostToDevice));
-                p->ut_key[0] = nlayers;
-                p->ut_key[1] = nsplit;
-                p->ut_key[2] = deep;
-                p->ut_key[3] = deep_split;
-                p->ut_units = (int)tab.size();
-            }
-            a.unit_tab = p->d_unit_tab;
-            a.lsplit = p->d_lsplit;
-            a.nunits = p->ut_units;
-        }
-        const int nunits = deep > 0 ? p->ut_units : nlayers * nsplit;
-        const int nplanes = deep > 0 ? deep_split : nsplit;
-        a.nsplit = nsplit;
-        if (nplanes > 1) {
-            const size_t need = (size_t)(nplanes - 1) * nlayers * a.nrows * wcount * 8;
-            if (need > p->part_bytes) {
-                (void)hipFree(p->part);
-                p->part = nullptr;
-                p->part_bytes = 0;
-                if (hipMalloc(&p->part, need) != hipSuccess) {
-                    pb::set_error("pb_lbl_extinction: cannot allocate %zu B of partial sums", need);
-                    return PB_ERR_NOMEM;
-                }
-                p->part_bytes = need;
-            }
-            a.part = p->part;
-        }
-        a.ntiles = pb::div_up(wcount, S * sub);
-        const int unit_groups = (nunits + 7) / 8;               // (layer, split) units per XCD
-        dim3 grid((unsigned)(8 * a.ntiles * unit_groups), a.nrows);
-        void (*kern)(LblArgs) =
-            dma ? (S == 4   ? k_ext_staged<kStagedWaves, 4, true>
-                   : S == 2 ? k_ext_staged<kStagedWaves, 2, true>
-                            : k_ext_staged<kStagedWaves, 1, true>)
-                : (S == 4   ? k_ext_staged<kStagedWaves, 4, false>
-                   : S == 2 ? k_ext_staged<kStagedWaves, 2, false>
-                            : k_ext_staged<kStagedWaves, 1, false>);
-#ifdef PB_EXPERIMENTS
-        unsigned long long *probe_d = nullptr;
-        if (const char *e = getenv("PB_STAGE_PROBE")) {
-            if (atoi(e) >= 1 && atoi(e) <= 3 && S == 2 && dma)    // 1, 2: timing probes, wrong sums
-                kern = atoi(e) == 1   ? k_ext_staged<kStagedWaves, 2, true, 1>
-                       : atoi(e) == 2 ? k_ext_staged<kStagedWaves, 2, true, 2>
-                                      : k_ext_staged<kStagedWaves, 2, true, 3>;
-            if (atoi(e) >= 11 && atoi(e) <= 12 && S == 2 && dma)  // 11, 12: who requests the row DMA
-                kern = atoi(e) == 11 ? k_ext_staged<kStagedWaves, 2, true, 0, 1>
-                                     : k_ext_staged<kStagedWaves, 2, true, 0, 2>;
-            if (atoi(e) == 4 && S == 2 && dma) {                  // the cycle account (valid sums)
-                kern = k_ext_staged<kStagedWaves, 2, true, 4>;
-                PB_HIP(hipMalloc(&probe_d, (size_t)nlayers * 24 * 8));
-                PB_HIP(hipMemsetAsync(probe_d, 0, (size_t)nlayers * 24 * 8, s));
-                a.probe = probe_d;
-            }
-        }
-#endif
-        if (lds > 64 * 1024)
-            PB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#ifdef PB_EXPERIMENTS
-        if (a.wave_cap > 0) {
-            // the short-row layers first: many short workgroups, then the staged kernel's long ones
-            const int rc = wave_launch(a, nunits, s);
-            if (rc != PB_OK)
+    const int per = kRecLayers;
+    const size_t rlds = records_lds(a, per) + 8;
+    PB_REQUIRE(rlds <= 64 * 1024, "pb_lbl_extinction: %zu B of LDS for the record kernel", rlds);
+    a.ntiles = pb::div_up(a.wcount, g.S * kStagedSub);
+    const int unit_groups = (nlayers + 7) / 8;
+    dim3 ggrid((unsigned)(8 * a.ntiles * unit_groups), a.nrows);
+    GatherKernel kern = staged_kernel(g.S, g.dma);
+    if (int rc = allow_lds(reinterpret_cast<const void *>(kern), g.lds))
+        return rc;
+    for (size_t c = 0; c < g.chunks.size(); c++) {
+        a.grp_lo = g.chunks[c].g_lo;
+        a.grp_hi = g.chunks[c].g_hi;
+        a.rec_pitch = std::max<int64_t>(1, a.grp_hi - a.grp_lo);
+        a.key_lo = g.chunks[c].key_lo;
+        a.key_hi = g.chunks[c].key_hi;
+        a.accumulate = c > 0 ? 1 : 0;
+        if (a.grp_hi > a.grp_lo) {
+            dim3 rgrid(pb::div_up(a.grp_hi - a.grp_lo, kBlock), pb::div_up(nlayers, per));
+            if (int rc = launch_records(a, g.fmt, per, rgrid, rlds, s))
                 return rc;
         }
-#endif
-        kern<<<grid, kStagedThreads, lds, s>>>(a);
-#ifdef PB_EXPERIMENTS
-        if (probe_d) {
-            // one line per layer on stderr: layer, rowmax of its first isotope, then the 15 sums
-            std::vector<unsigned long long> h((size_t)nlayers * 24);
-            PB_HIP(hipMemcpyAsync(h.data(), probe_d, h.size() * 8, hipMemcpyDeviceToHost, s));
-            std::vector<int32_t> rowmax((size_t)nlayers * a.niso);
-            PB_HIP(hipMemcpyAsync(rowmax.data(), a.li_rowmax, rowmax.size() * 4,
-                                  hipMemcpyDeviceToHost, s));
-            PB_HIP(hipStreamSynchronize(s));
-            (void)hipFree(probe_d);
-            a.probe = nullptr;
-            for (int layer = 0; layer < nlayers; layer++) {
-                fprintf(stderr, "STAGE_PROBE layer %d rowmax %d :", layer,
-                        rowmax[(size_t)layer * a.niso]);
-                for (int i = 0; i < 21; i++)
-                    fprintf(stderr, " %llu", h[(size_t)layer * 24 + i]);
-                fprintf(stderr, "\n");
+        kern<<<ggrid, kStagedThreads, g.lds, s>>>(a);
+        PB_LAUNCH_CHECK();
+    }
+    p->last_gather = 2;
+    p->last_args = a;
+    p->last_packed = false;
+    if (timed) {
+        PB_HIP(hipEventRecord(p->ev[p->ev_used + 1], s));
+        p->ev_used += 2;
+    }
+    return PB_OK;
+}
+
+// Window map of a two-phase shard call: only the groups within reach of the shard get a thread
+// of k_records (LblArgs::wm_*).  Cached for the window and the walk order it was built for.
+static int window_map(pb_lbl *p, LblArgs &a, bool staged, hipStream_t s)
+{
+    const pb_lines *l = p->lines;
+    const int osamp = p->voigt->osamp, niso = a.niso;
+    if (p->wm_flo != a.rec_flo || p->wm_fhi != a.rec_fhi || p->wm_staged != (int)staged) {
+        const int n0 = staged ? niso * osamp : niso, n1 = niso;
+        std::vector<int32_t> &h = p->h_wm;
+        h.assign((size_t)2 * n0 + 1 + 2 * n1 + 1, 0);
+        int32_t *lo0 = h.data(), *off0 = lo0 + n0, *lo1 = off0 + n0 + 1, *off1 = lo1 + n1;
+        const int64_t flo = std::max<int64_t>(a.rec_flo, INT32_MIN);
+        const int64_t fhi = std::min<int64_t>(a.rec_fhi, INT32_MAX);
+        auto run = [&](const std::vector<int32_t> &pos, int64_t b, int64_t e, int32_t *lo,
+                       int32_t *off, int r) {
+            const auto first = pos.begin() + b, last = pos.begin() + e;
+            const auto x0 = std::lower_bound(first, last, (int32_t)flo);
+            const auto x1 = std::upper_bound(x0, last, (int32_t)fhi);
+            lo[r] = (int32_t)(x0 - pos.begin());
+            off[r + 1] = off[r] + (int32_t)(x1 - x0);
+        };
+        for (int i = 0; i < niso; i++) {
+            run(l->h_giown, l->iso_gstart[(size_t)i], l->iso_gstart[(size_t)i + 1], lo1, off1, i);
+            if (staged)
+                for (int ph = 0; ph < osamp; ph++)
+                    run(p->h_ph_iown, p->h_ph_start[(size_t)i * (osamp + 1) + ph],
+                        p->h_ph_start[(size_t)i * (osamp + 1) + ph + 1], lo0, off0,
+                        i * osamp + ph);
+            else
+                run(l->h_giown, l->iso_gstart[(size_t)i], l->iso_gstart[(size_t)i + 1], lo0, off0, i);
+        }
+        if (int rc = ensure_bytes((void **)&p->d_wm, &p->wm_bytes, h.size() * 4, s, false,
+                                  "the window map"))
+            return rc;
+        PB_HIP(hipMemcpyAsync(p->d_wm, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+        p->wm_flo = a.rec_flo;
+        p->wm_fhi = a.rec_fhi;
+        p->wm_staged = (int)staged;
+        p->wm_n0 = n0;
+        p->wm_n1 = n1;
+        p->wm_total0 = off0[n0];
+        p->wm_total1 = off1[n1];
+    }
+    a.wm_n[0] = p->wm_n0;
+    a.wm_n[1] = p->wm_n1;
+    a.wm_lo[0] = p->d_wm;
+    a.wm_off[0] = p->d_wm + p->wm_n0;
+    a.wm_lo[1] = p->d_wm + 2 * p->wm_n0 + 1;
+    a.wm_off[1] = a.wm_lo[1] + p->wm_n1;
+    a.wm_total[0] = p->wm_total0;
+    a.wm_total[1] = p->wm_total1;
+    return PB_OK;
+}
+
+// the records (and with them the per-row maxima) of every layer of the call
+static int make_records(pb_lbl *p, LblArgs &a, const GatherPlan &g, const Tuning &tn, hipStream_t s)
+{
+    // (one layer per thread for launches of few layers measured slower: 10 layers of C2
+    // 49 us against 27 us with four; PB_REC_LAYERS=1 selects it)
+    const int per = tn.rec_layers_1 ? 1 : kRecLayers;
+    int64_t rec_threads = a.ngroups;
+    if (a.kmax_local && a.rec_flo != INT64_MIN && !p->h_ph_iown.empty() && !tn.no_window_map) {
+        if (int rc = window_map(p, a, g.staged, s))
+            return rc;
+        rec_threads = std::max<int64_t>(1, std::max(p->wm_total0, p->wm_total1));
+    }
+    dim3 grid(pb::div_up(rec_threads, kBlock), pb::div_up(a.nlayers, per));
+    // the run offsets of the phase-order window map go to LDS while they fit beside the rest
+    // in 48 KiB (niso * osamp + 1 words: the reference's default wnosamp of 2160 with 8
+    // isotopes is already 69 KiB); larger maps are bisected in global memory
+    const size_t rlds0 = records_lds(a, per);
+    const size_t wm_bytes = ((size_t)a.wm_n[0] + 2) * 4;
+    a.wm_lds = a.wm_off[0] && rlds0 + wm_bytes <= tn.wm_lds_cap ? 1 : 0;
+    const size_t rlds = rlds0 + (a.wm_lds ? wm_bytes : 8);
+    PB_REQUIRE(rlds <= 64 * 1024, "pb_lbl_extinction: %zu B of LDS for the record kernel "
+               "(too many isotopes / output rows)", rlds);
+    return launch_records(a, g.fmt, per, grid, rlds, s);
+}
+
+// Per-tile split table of the staged kernel (LblArgs::tsplit), cached per tiling: from the
+// groups within reach of every tile the tiles above 1.5 x the median count get more pieces, up
+// to 8; the others keep the launch's `nsplit`.
+static int tile_split_table(pb_lbl *p, const LblArgs &a, const GatherPlan &g, const Tuning &tn,
+                            int nsplit, hipStream_t s)
+{
+    const pb_voigt *v = p->voigt;
+    const pb_lines *l = p->lines;
+    const int64_t wbegin = a.wbegin, wcount = a.wcount;
+    const int tile = g.S * (int)kStagedSub;
+    const int nt = pb::div_up(wcount, tile);
+    if (p->ts_key[0] == wbegin && p->ts_key[1] == wcount && p->ts_key[2] == tile &&
+        p->ts_key[3] == nsplit)
+        return PB_OK;
+    const int64_t reach = group_reach(v, a.cutoff, a.ownstep);
+    std::vector<int64_t> cnt((size_t)nt, 0);
+    for (int t = 0; t < nt; t++) {
+        const int64_t t0 = wbegin + (int64_t)t * tile;
+        const int64_t tend = std::min<int64_t>(t0 + tile, wbegin + wcount);
+        cnt[(size_t)t] = groups_in_reach(l, p->niso, t0 * v->osamp - reach,
+                                         (tend - 1) * v->osamp + reach);
+    }
+    std::vector<int64_t> sorted(cnt);
+    std::nth_element(sorted.begin(), sorted.begin() + nt / 2, sorted.end());
+    const double median = (double)std::max<int64_t>(1, sorted[(size_t)nt / 2]);
+    std::vector<int32_t> ts((size_t)nt);
+    int tmax = nsplit;
+    if (tn.tile_debug) {
+        fprintf(stderr, "tile counts (median %.0f):", median);
+        for (int t = 0; t < nt; t++)
+            fprintf(stderr, " %lld", (long long)cnt[(size_t)t]);
+        fprintf(stderr, "\n");
+    }
+    // groups per (2048 samples, phase row) of a tile against the threshold that sends a
+    // whole launch to the global gather: a tile below it is visit-starved in the staged
+    // kernel (~300 barrier steps of one or two records: as long as a full tile) -- once
+    // SOME tile is dense enough to be split, the sparse ones go to the global gather
+    bool sparse = false, dense = false;
+    for (int t = 0; t < nt; t++) {
+        const int k = std::max(tn.tile_min, (int)std::ceil((double)cnt[(size_t)t] / (1.5 * median)));
+        ts[(size_t)t] = std::max(nsplit, std::min(8, nsplit * std::max(1, k)));
+        tmax = std::max(tmax, ts[(size_t)t]);
+        dense = dense || ts[(size_t)t] > nsplit;
+    }
+    if (dense && g.packable && p->pos2ph && !tn.tile_global_off)
+        for (int t = 0; t < nt; t++) {
+            const double per =
+                (double)cnt[(size_t)t] * 2048.0 / (double)tile / (double)v->osamp;
+            if (per < p->stage_threshold) {
+                ts[(size_t)t] = 0;
+                sparse = true;
             }
         }
-#endif
-        if (deep > 0) {
-            PB_LAUNCH_CHECK();
-            const int64_t per_layer = (int64_t)a.nrows * wcount;
-            dim3 cgrid((unsigned)pb::div_up(per_layer, kBlock), nlayers);
-            k_combine_layer_parts<<<cgrid, kBlock, 0, s>>>(ext_d, p->part, p->d_lsplit, per_layer,
-                                                          (int64_t)nlayers * per_layer,
-                                                          a.res_cap > 0 ? a.ls_resident : nullptr);
-        } else if (a.tsplit) {
-            PB_LAUNCH_CHECK();
-            if (p->ts_sparse) {
-                // the sparse tiles through the global gather (RS = 1: its own 1024-sample tiles;
-                // the tiles of the staged kernel end at once there, and the other way round)
-                LblArgs g = a;
-                g.ntiles = pb::div_up(wcount, kTile);
-                dim3 ggrid((unsigned)(8 * g.ntiles * layer_groups), a.nrows);
-                k_ext_resample<1, 4><<<ggrid, kBlock, 0, s>>>(g);
-                PB_LAUNCH_CHECK();
-            }
-            const int64_t n = (int64_t)nlayers * a.nrows * wcount;
-            k_combine_tile_parts<<<(unsigned)pb::div_up(n, kBlock), kBlock, 0, s>>>(
-                ext_d, p->part, a.tsplit, S * (int)sub, wcount, n,
-                a.res_cap > 0 ? a.ls_resident : nullptr, (int64_t)a.nrows * wcount);
-        } else if (nsplit > 1) {
-            PB_LAUNCH_CHECK();
-            const int64_t n = (int64_t)nlayers * a.nrows * wcount;
-            k_combine_parts<<<(unsigned)pb::div_up(n, kBlock), kBlock, 0, s>>>(
-                ext_d, p->part, nsplit - 1, n, a.res_cap > 0 ? a.ls_resident : nullptr,
-                (int64_t)a.nrows * wcount);
+    p->ts_sparse = sparse;
+    PB_HIP(hipStreamSynchronize(s));       // an earlier call may still read the table
+    if (int rc = ensure_bytes((void **)&p->d_tsplit, &p->ts_bytes, (size_t)nt * 4, s, false, nullptr))
+        return rc;
+    PB_HIP(hipMemcpy(p->d_tsplit, ts.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+    p->ts_key[0] = wbegin;
+    p->ts_key[1] = wcount;
+    p->ts_key[2] = tile;
+    p->ts_key[3] = nsplit;
+    p->ts_max = tmax;
+    return PB_OK;
+}
+
+// Per-layer split tables of the staged kernel (LblArgs::unit_tab, lsplit), cached: the deepest
+// `deep` layers in `deep_split` pieces, the others in `nsplit`, in dispatch order.
+static int layer_split_table(pb_lbl *p, int nlayers, int nsplit, int deep, int deep_split,
+                             hipStream_t s)
+{
+    if (p->ut_key[0] == nlayers && p->ut_key[1] == nsplit && p->ut_key[2] == deep &&
+        p->ut_key[3] == deep_split)
+        return PB_OK;
+    std::vector<int32_t> tab, ls((size_t)nlayers);
+    for (int layer = nlayers - 1; layer >= 0; layer--) {
+        const int n = layer >= nlayers - deep ? deep_split : nsplit;
+        ls[(size_t)layer] = n;
+        for (int z = 0; z < n; z++)
+            tab.push_back((layer << 8) | z);
+    }
+    PB_HIP(hipStreamSynchronize(s));       // an earlier call may still read the tables
+    if (int rc = ensure_bytes((void **)&p->d_unit_tab, &p->ut_bytes, tab.size() * 4, s, false, nullptr))
+        return rc;
+    if (int rc = ensure_bytes((void **)&p->d_lsplit, &p->ls_bytes, ls.size() * 4, s, false, nullptr))
+        return rc;
+    PB_HIP(hipMemcpy(p->d_unit_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    PB_HIP(hipMemcpy(p->d_lsplit, ls.data(), ls.size() * 4, hipMemcpyHostToDevice));
+    p->ut_key[0] = nlayers;
+    p->ut_key[1] = nsplit;
+    p->ut_key[2] = deep;
+    p->ut_key[3] = deep_split;
+    p->ut_units = (int)tab.size();
+    return PB_OK;
+}
+
+static int launch_staged(pb_lbl *p, LblArgs &a, const GatherPlan &g, const Tuning &tn, hipStream_t s)
+{
+    const int nlayers = a.nlayers;
+    const int64_t wcount = a.wcount;
+    const int64_t plane = plane_bytes(a);
+    int nsplit = g.nsplit;
+    // Per-layer split.  A launch ends when its slowest workgroup does, and the slowest are the
+    // tiles of the deepest layers (cutoff-limited windows of ~1000 samples against 200-300
+    // higher up: 0.7-0.9 ms of a 0.88-ms C2 launch, profiles/r02_gather_ab.md), which the
+    // dispatch order puts first.  The deepest `deep` layers are cut into more pieces than the
+    // others, so that no single workgroup spans the launch.  Pieces of a tile add their sums in
+    // a fixed order (k_combine_layer_parts): bitwise reproducible; against an unsplit launch
+    // the association of a sample's terms differs (~1e-16).  PB_STAGE_SPLIT pins one split for
+    // every layer (the exactness tests), PB_STAGE_DEEP=frac[,factor] tunes the rule.
+    // Measured (profiles/r03_gather_ab.md): C3 44.1 -> 42.3 ms (-4 %), the 1e6-line list -1 %,
+    // C2 +4 % (one spectrum at a time) / +3 % (pipelined): the second prologue and the combine
+    // pass cost a light launch more than its tail does.  On by default only for long rows.
+    int deep = 0, deep_split = nsplit;
+    if (!tn.stage_split && nsplit < 8 && nlayers >= 8) {
+        const double frac = tn.deep_set ? tn.deep_frac : a.nch_max > 1 ? 0.3 : 0.0;
+        const int factor = tn.deep_set ? tn.deep_factor : 2;
+        deep = (int)(frac * nlayers + 0.5);
+        deep_split = cap_split_to_planes(std::min(8, nsplit * factor), plane, nsplit);
+        if (deep <= 0 || deep_split <= nsplit)
+            deep = 0, deep_split = nsplit;
+    }
+    // Per-tile split.  A uniform line list gives every tile the same number of records; a
+    // real one has band heads (10^2-10^3 x the line density of the gaps): the few tiles under
+    // a head run 10 x as long as the others and end the launch alone (the C2 grid with 8 band
+    // heads per isotope at 300 x contrast: gather 1.90 ms unsplit, 1.34 ms with every tile in
+    // four pieces -- profiles/r04_bands.md).  From the groups within reach of every tile (host
+    // copy of the group positions, cached per tiling) the tiles above 1.5 x the median count
+    // get more pieces, up to 8; the others keep the launch's.  Automatic mode only: a forced
+    // mode adds the terms of a sample in one order whatever the tiling (pbhip.h).
+    if (deep == 0 && a.nch_max == 1 && p->gather_mode == 0 && a.wave_cap == 0 &&
+        !tn.stage_split && !tn.tile_split_off && !p->lines->h_giown.empty()) {
+        if (int rc = tile_split_table(p, a, g, tn, nsplit, s))
+            return rc;
+        // (only while the planes of the largest split fit)
+        if (p->ts_max > nsplit && cap_split_to_planes(p->ts_max, plane) == p->ts_max) {
+            a.tsplit = p->d_tsplit;
+            a.ts_tile = g.S * (int)kStagedSub;
+            a.pos2ph = p->pos2ph;
+            nsplit = deep_split = p->ts_max;
         }
-    } else {
-        // record splitting when the launch would not fill the chip
-        // (measured at C2: RS=2 beats RS=1 until the launch has ~16k workgroups; a 16-wave
-        // workgroup with a 16-way split, selectable with PB_RSPLIT=16, measured slower than
-        // RS=4: every wavefront still scans every 64-record round for its share)
-        const int64_t tiles1 = pb::div_up(wcount, kTile) * (int64_t)nlayers * a.nrows;
-        int RS = tiles1 >= 16000 ? 1 : tiles1 >= 1500 ? 2 : 4;
-        if (const char *e = getenv("PB_RSPLIT")) {
-            const int v_ = atoi(e);
-            RS = v_ >= 16 ? 16 : v_ >= 4 ? 4 : v_ >= 2 ? 2 : 1;
+    }
+    if (deep > 0) {
+        if (int rc = layer_split_table(p, nlayers, nsplit, deep, deep_split, s))
+            return rc;
+        a.unit_tab = p->d_unit_tab;
+        a.lsplit = p->d_lsplit;
+        a.nunits = p->ut_units;
+    }
+    const int nunits = deep > 0 ? p->ut_units : nlayers * nsplit;
+    a.nsplit = nsplit;
+    if (int rc = ensure_part(p, a, deep > 0 ? deep_split : nsplit, s))
+        return rc;
+    a.ntiles = pb::div_up(wcount, g.S * kStagedSub);
+    const int unit_groups = (nunits + 7) / 8;               // (layer, split) units per XCD
+    dim3 grid((unsigned)(8 * a.ntiles * unit_groups), a.nrows);
+    GatherKernel kern = staged_kernel(g.S, g.dma);
+    if (int rc = exp_stage_probe_begin(a, g, tn, &kern, s))
+        return rc;
+    if (int rc = allow_lds(reinterpret_cast<const void *>(kern), g.lds))
+        return rc;
+    if (int rc = exp_launch_wave(a, nunits, s))
+        return rc;
+    kern<<<grid, kStagedThreads, g.lds, s>>>(a);
+    if (int rc = exp_stage_probe_end(a, s))
+        return rc;
+    const int32_t *resident = a.res_cap > 0 ? a.ls_resident : nullptr;
+    const int64_t per_layer = (int64_t)a.nrows * wcount, n = nlayers * per_layer;
+    if (deep > 0) {
+        PB_LAUNCH_CHECK();
+        dim3 cgrid((unsigned)pb::div_up(per_layer, kBlock), nlayers);
+        k_combine_layer_parts<<<cgrid, kBlock, 0, s>>>(a.ext, p->part, p->d_lsplit, per_layer, n,
+                                                      resident);
+    } else if (a.tsplit) {
+        PB_LAUNCH_CHECK();
+        if (p->ts_sparse) {
+            // the sparse tiles through the global gather (RS = 1: its own 1024-sample tiles;
+            // the tiles of the staged kernel end at once there, and the other way round)
+            LblArgs ga = a;
+            ga.ntiles = pb::div_up(wcount, kTile);
+            dim3 ggrid((unsigned)(8 * ga.ntiles * ((nlayers + 7) / 8)), a.nrows);
+            k_ext_resample<1, 4><<<ggrid, kBlock, 0, s>>>(ga);
+            PB_LAUNCH_CHECK();
         }
-        const int tile = RS == 16 ? kWaveSpan : kTile / RS;
-        a.ntiles = pb::div_up(wcount, tile);
-        dim3 grid((unsigned)(8 * a.ntiles * layer_groups), a.nrows);
-        if (RS == 16)
-            k_ext_resample<16, 16><<<grid, 1024, 0, s>>>(a);
-        else if (RS == 4)
-            k_ext_resample<4, 4><<<grid, kBlock, 0, s>>>(a);
-        else if (RS == 2)
-            k_ext_resample<2, 4><<<grid, kBlock, 0, s>>>(a);
-        else
-            k_ext_resample<1, 4><<<grid, kBlock, 0, s>>>(a);
+        k_combine_tile_parts<<<(unsigned)pb::div_up(n, kBlock), kBlock, 0, s>>>(
+            a.ext, p->part, a.tsplit, g.S * (int)kStagedSub, wcount, n, resident, per_layer);
+    } else if (nsplit > 1) {
+        PB_LAUNCH_CHECK();
+        k_combine_parts<<<(unsigned)pb::div_up(n, kBlock), kBlock, 0, s>>>(
+            a.ext, p->part, nsplit - 1, n, resident, per_layer);
     }
     PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+static int launch_global(LblArgs &a, const Tuning &tn, hipStream_t s)
+{
+    // record splitting when the launch would not fill the chip
+    // (measured at C2: RS=2 beats RS=1 until the launch has ~16k workgroups; a 16-wave
+    // workgroup with a 16-way split, selectable with PB_RSPLIT=16, measured slower than
+    // RS=4: every wavefront still scans every 64-record round for its share)
+    const int64_t tiles1 = pb::div_up(a.wcount, kTile) * (int64_t)a.nlayers * a.nrows;
+    const int RS = tn.rsplit ? tn.rsplit : tiles1 >= 16000 ? 1 : tiles1 >= 1500 ? 2 : 4;
+    const int tile = RS == 16 ? kWaveSpan : kTile / RS;
+    a.ntiles = pb::div_up(a.wcount, tile);
+    dim3 grid((unsigned)(8 * a.ntiles * ((a.nlayers + 7) / 8)), a.nrows);
+    if (RS == 16)
+        k_ext_resample<16, 16><<<grid, 1024, 0, s>>>(a);
+    else if (RS == 4)
+        k_ext_resample<4, 4><<<grid, kBlock, 0, s>>>(a);
+    else if (RS == 2)
+        k_ext_resample<2, 4><<<grid, kBlock, 0, s>>>(a);
+    else
+        k_ext_resample<1, 4><<<grid, kBlock, 0, s>>>(a);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+static int launch_resident(LblArgs &a, hipStream_t s)
+{
+    a.ntiles = pb::div_up(a.wcount, kResTile);
+    dim3 grid((unsigned)(8 * a.ntiles * ((a.nlayers + 7) / 8)), a.nrows);
+    const size_t rlds = ((size_t)a.res_cap + 2) * 8 + (size_t)kResThreads * (16 + 4) +
+                        kResWaves * 4 + 64;
+    if (int rc = allow_lds(reinterpret_cast<const void *>(k_ext_resident), rlds))
+        return rc;
+    k_ext_resident<<<grid, kResThreads, rlds, s>>>(a);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+static int launch_linterp(LblArgs &a, hipStream_t s)
+{
+    a.ntiles = pb::div_up(a.wcount, kBlock);
+    dim3 grid((unsigned)(8 * a.ntiles * ((a.nlayers + 7) / 8)), a.nrows);
+    k_ext_linterp<<<grid, kBlock, 0, s>>>(a);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+// what the call leaves in the handle: the resident decision (when this call looks), the
+// arguments for pb_lbl_last_work, the end of the timed span
+static int finish_call(pb_lbl *p, const LblArgs &a, bool res_look, bool timed, hipStream_t s)
+{
     if (res_look) {
-        std::vector<int32_t> h((size_t)nlayers);
-        PB_HIP(hipMemcpyAsync(h.data(), p->ls_resident, (size_t)nlayers * 4, hipMemcpyDeviceToHost, s));
+        std::vector<int32_t> h((size_t)a.nlayers);
+        PB_HIP(hipMemcpyAsync(h.data(), p->ls_resident, (size_t)a.nlayers * 4, hipMemcpyDeviceToHost, s));
         PB_HIP(hipStreamSynchronize(s));
         p->res_seen = std::any_of(h.begin(), h.end(), [](int32_t v) { return v != 0; }) ? 1 : 0;
     }
@@ -4097,6 +4047,97 @@ static int lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcou
         p->ev_used += 2;
     }
     return PB_OK;
+}
+
+// phase 0: the whole call; 1: up to and including the records, per-row maxima over the shard's
+// own groups only (the caller all-reduces them); 2: the gather of the call begun with phase 1
+static int lbl_extinction(pb_lbl *p, const Call &c, void *stream, int phase)
+{
+    PB_REQUIRE(p, "pb_lbl_extinction: null handle");
+    PB_REQUIRE(c.wcount == 0 || (c.ext && c.temp && c.dens && c.isoz),
+               "pb_lbl_extinction: null pointer");
+    PB_REQUIRE(c.nlayers >= 1 && c.nlayers <= p->max_layers,
+               "pb_lbl_extinction: nlayers=%d outside [1,%d]", c.nlayers, p->max_layers);
+    PB_REQUIRE(c.wbegin >= 0 && c.wcount >= 0 && c.wbegin + c.wcount <= p->nwave,
+               "pb_lbl_extinction: shard [%lld,+%lld) outside the %d-sample grid",
+               (long long)c.wbegin, (long long)c.wcount, p->nwave);
+    hipStream_t s = pb::as_stream(stream);
+    if (c.wcount == 0) {
+        // an empty shard of a two-phase call still takes part in the all-reduce(MAX) of the
+        // per-row maxima: it must contribute zeros, not what its previous call left behind
+        if (phase == 1)
+            PB_HIP(hipMemsetAsync(p->kmax_bits, 0, (size_t)p->max_layers * p->kmax_rows * 8, s));
+        return PB_OK;
+    }
+    const pb_lines *l = p->lines;
+    if (p->resolution)
+        if (int rc = pb_voigt_ensure_flat(p->voigt, s))
+            return rc;
+    const Tuning tn = read_tuning();
+    LblArgs a = fill_args(p, c);
+    a.kmax_local = phase != 0 ? 1 : 0;
+    a.experiment = tn.experiment;
+
+    GatherPlan g = plan_gather(p, a, tn, phase);
+    resident_probe(p, g, s, phase);
+    if (g.rc)
+        return g.rc;
+    const bool chunked = !g.chunks.empty();
+    p->last_chunks = (int)g.chunks.size();
+    a.nch_max = g.nch_max;
+    a.rowlds = g.rowlds;
+    a.res_cap = g.resident && !chunked ? p->res_cap : 0;   // (chunked: every layer through the staged gather)
+    if (int rc = bind_records(p, a, g, tn, s))
+        return rc;
+
+    bool dyn_fall = false;
+    // (a fine grid shorter than two steps of the coarsest dynamic grid has no constant-step form)
+    if (p->resolution && p->gather_mode == 6 && phase == 0 && l->ngroups > 0 &&
+        l->onwn > 2 * (int64_t)p->voigt->osamp && !tn.res_dyn_off) {
+        const int rc = lbl_resolution_dyn(p, a, c, tn, s);
+        // a re-cut table row that cannot be addressed (pb_voigt_ensure_rows) before any run has
+        // added to ext: the direct gather below computes the call instead
+        if (!(rc == PB_ERR_UNSUPPORTED && p->dyn_runs == 0)) {
+            if (rc != PB_OK || !p->dyn_fallback)
+                return rc;
+            // a call planned from a prediction: the layers the plan did not fit (none, as a
+            // rule: the launches below then end at once) go through the direct gather
+            dyn_fall = true;
+            a.lskip = p->d_ok;
+        }
+    }
+    if (phase != 2 && !dyn_fall)
+        if (int rc = launch_layer_state(a, s))
+            return rc;
+    if (chunked)
+        return run_chunked(p, a, g, s);
+    int rc = PB_OK;
+    if (phase != 2)                      // (phase 2: records and maxima are in place)
+        rc = g.use_records ? make_records(p, a, g, tn, s) : l->nlines > 0 ? launch_kmax(a, s) : PB_OK;
+    if (rc || phase == 1)
+        return rc;
+
+    const bool timed = !dyn_fall && p->ev_used + 2 <= (int)p->ev.size();
+    if (timed)
+        PB_HIP(hipEventRecord(p->ev[p->ev_used], s));
+    p->last_gather = dyn_fall ? 6 : g.scatter ? 4
+                             : (p->resolution ? 3 : g.rounds ? 5 : g.staged ? 2 : 1) +
+                                   (g.resident ? 8 : 0) + (a.wave_cap > 0 ? 16 : 0);
+    if (g.scatter) {                     // (computes every layer)
+        rc = exp_launch_scatter(a, tn, s);
+    } else {
+        // the layers with narrow profiles, then the others
+        if (g.resident)
+            rc = launch_resident(a, s);
+        if (rc == PB_OK)
+            rc = p->resolution ? launch_linterp(a, s)
+                 : g.rounds    ? exp_launch_rounds(p, a, g, tn, s)
+                 : g.staged    ? launch_staged(p, a, g, tn, s)
+                               : launch_global(a, tn, s);
+    }
+    if (rc)
+        return rc;
+    return finish_call(p, a, g.res_look, timed, s);
 }
 
 // `resolution` plans, gather mode 6.  The reference accumulates every line of a layer on the
@@ -4141,16 +4182,15 @@ static int dyn_subplan(pb_lbl *p, int f, hipStream_t s, pb_lbl::DynSub **out)
     return PB_OK;
 }
 
-static int lbl_resolution_dyn(pb_lbl *p, LblArgs &a, double *ext_d, int64_t wbegin, int64_t wcount,
-                              const double *temp_d, const double *dens_d, const double *isoz_d,
-                              int64_t z_iso_stride, int64_t z_layer_stride, int nlayers, int add,
-                              hipStream_t s)
+static int lbl_resolution_dyn(pb_lbl *p, LblArgs &a, const Call &c, const Tuning &tn, hipStream_t s)
 {
     const pb_lines *l = p->lines;
+    const int nlayers = c.nlayers;
+    const int64_t wbegin = c.wbegin, wcount = c.wcount;
     PB_REQUIRE(l->onwn < (1LL << 30), "pb_lbl_extinction: fine grid of %lld samples exceeds 2^30",
                (long long)l->onwn);
-    k_layer_state<<<nlayers, 64, ((size_t)a.nlor + a.ndop) * 8 + (size_t)a.ndivs * 4, s>>>(a);
-    PB_LAUNCH_CHECK();
+    if (int rc = launch_layer_state(a, s))
+        return rc;
     const size_t nstate = (size_t)nlayers * (1 + p->niso);
     // a finished read-back of an earlier call: adopt it as the prediction; if it contradicts the
     // prediction that call was planned with, the atmosphere is moving -- synchronise for a while
@@ -4285,9 +4325,7 @@ static int lbl_resolution_dyn(pb_lbl *p, LblArgs &a, double *ext_d, int64_t wbeg
     k_dyn_check<<<pb::div_up(nlayers, 64), 64, 0, s>>>(p->d_ok, p->ls_ofactor, p->li_ilor,
                                                       p->d_pred_f, p->d_pred_mask, nlayers, p->niso);
     PB_LAUNCH_CHECK();
-    int lanes = 4;
-    if (const char *e = getenv("PB_RES_DYN_STREAMS"))
-        lanes = std::max(1, std::min(8, atoi(e)));
+    const int lanes = tn.dyn_streams;
     if (lanes > 1 && p->dyn_streams.empty()) {
         PB_HIP(hipEventCreateWithFlags(&p->dyn_fork, hipEventDisableTiming));
         for (int k = 0; k < 8; k++) {
@@ -4318,9 +4356,7 @@ static int lbl_resolution_dyn(pb_lbl *p, LblArgs &a, double *ext_d, int64_t wbeg
     // (deep layers: one or two layers on a short grid) are dealt to the remaining side streams,
     // least work first, and run in the shadow of the large ones.
     double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int nbig = 1;
-    if (const char *e = getenv("PB_RES_DYN_BIG"))
-        nbig = std::max(1, std::min(7, atoi(e)));
+    const int nbig = tn.dyn_big;
     for (int l0 = 0; l0 < nlayers && rc == PB_OK;) {
         const int f = p->h_ofactor[(size_t)l0];
         // (a run's dynamic-grid sums stay below 1 GiB: fine factors on long fine grids)
@@ -4394,9 +4430,9 @@ static int lbl_resolution_dyn(pb_lbl *p, LblArgs &a, double *ext_d, int64_t wbeg
             }
             sub->ktmp_bytes = need;
         }
-        rc = lbl_extinction(q, sub->ktmp, d0, d1 - d0, temp_d + l0, dens_d + (int64_t)l0 * p->nmol,
-                            isoz_d + (int64_t)l0 * z_layer_stride, z_iso_stride, z_layer_stride,
-                            nl, add, t, 0);
+        const Call run{sub->ktmp, d0, d1 - d0, c.temp + l0, c.dens + (int64_t)l0 * p->nmol,
+                       c.isoz + (int64_t)l0 * c.zs1, c.zs0, c.zs1, nl, c.add, false};
+        rc = lbl_extinction(q, run, t, 0);
         if (rc)
             break;
         // (pb_lbl_last_state / pb_lbl_kmax_buffer of this plan report the run's maxima)
@@ -4408,7 +4444,7 @@ static int lbl_resolution_dyn(pb_lbl *p, LblArgs &a, double *ext_d, int64_t wbeg
             break;
         }
         dim3 grid((unsigned)pb::div_up(wcount, (int64_t)kBlock), (unsigned)(nl * a.nrows));
-        k_dyn_interp<<<grid, kBlock, 0, t>>>(ext_d + (int64_t)l0 * a.nrows * wcount, sub->ktmp,
+        k_dyn_interp<<<grid, kBlock, 0, t>>>(c.ext + (int64_t)l0 * a.nrows * wcount, sub->ktmp,
                                             p->d_wn, p->wn0, p->ls_dwnstep + l0, d0, d1 - d0,
                                             wbegin, wcount, a.nrows, p->d_ok + l0);
         if (hipGetLastError() != hipSuccess) {
@@ -4450,8 +4486,9 @@ int pb_lbl_extinction(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcount,
                       int64_t z_iso_stride, int64_t z_layer_stride, int nlayers, int add,
                       void *stream)
 {
-    return lbl_extinction(p, ext_d, wbegin, wcount, temp_d, dens_d, isoz_d, z_iso_stride,
-                          z_layer_stride, nlayers, add, stream, 0);
+    const Call c{ext_d, wbegin, wcount, temp_d, dens_d, isoz_d, z_iso_stride, z_layer_stride,
+                 nlayers, add, false};
+    return lbl_extinction(p, c, stream, 0);
 }
 
 int pb_lbl_extinction_begin(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wcount,
@@ -4462,17 +4499,14 @@ int pb_lbl_extinction_begin(pb_lbl *p, double *ext_d, int64_t wbegin, int64_t wc
     PB_REQUIRE(p, "pb_lbl_extinction_begin: null handle");
     p->pending = {ext_d, wbegin, wcount, temp_d, dens_d, isoz_d, z_iso_stride, z_layer_stride,
                   nlayers, add, true};
-    return lbl_extinction(p, ext_d, wbegin, wcount, temp_d, dens_d, isoz_d, z_iso_stride,
-                          z_layer_stride, nlayers, add, stream, 1);
+    return lbl_extinction(p, p->pending, stream, 1);
 }
 
 int pb_lbl_extinction_end(pb_lbl *p, void *stream)
 {
     PB_REQUIRE(p && p->pending.open, "pb_lbl_extinction_end: no call was begun");
-    const auto c = p->pending;
     p->pending.open = false;
-    return lbl_extinction(p, c.ext, c.wbegin, c.wcount, c.temp, c.dens, c.isoz, c.zs0, c.zs1,
-                          c.nlayers, c.add, stream, 2);
+    return lbl_extinction(p, p->pending, stream, 2);
 }
 
 int pb_lbl_kmax_buffer(pb_lbl *p, void **kmax_d, int64_t *count)

@@ -19,7 +19,10 @@
 //   scan + k_emit: leaders compacted in file order = (isotope, position) order.
 // Requires the TLI invariant: lines sorted by isotope, then wavenumber (checked on the device;
 // otherwise the host loop of pb_lines_create does the work).
+#include <cmath>
+#include <cstdlib>
 #include <cstring>
+#include <new>
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -341,3 +344,204 @@ int pb_lines_group_device(pb_lines *l, const double *lwn_h, const int32_t *lid_h
     l->nadd = members - ng;
     return PB_OK;
 }
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// line list: the C ABI
+// ---------------------------------------------------------------------------
+int pb_lines_create(pb_lines **out, const double *lwn_h, const double *elow_h,
+                    const double *gf_h, const int32_t *lid_h, int64_t nlines, int niso,
+                    const double *own_h, int64_t onwn, double own0, double ownstep)
+{
+    PB_REQUIRE(out, "pb_lines_create: null out");
+    *out = nullptr;
+    PB_REQUIRE(nlines >= 0 && niso > 0 && onwn >= 2, "pb_lines_create: bad sizes");
+    PB_REQUIRE(nlines == 0 || (lwn_h && elow_h && gf_h && lid_h),
+               "pb_lines_create: null line arrays");
+    PB_REQUIRE(nlines < 2147483647LL && onwn < 2147483647LL,
+               "pb_lines_create: sizes exceed the reference's 32-bit indices");
+    // own[] generated exactly like NumPy (wnlow + arange*ownstep: multiply, then add)
+    auto own_at = [&](int64_t i) -> double {
+        if (own_h)
+            return own_h[i];
+        volatile double prod = (double)i * ownstep;
+        return own0 + prod;
+    };
+    pb_lines *l = new (std::nothrow) pb_lines();
+    if (!l)
+        return PB_ERR_NOMEM;
+    l->nlines = nlines;
+    l->niso = niso;
+    l->onwn = onwn;
+    l->own0 = own_at(0);
+    l->own_last = own_at(onwn - 1);
+    l->ownstep = own_at(1) - own_at(0);
+    const double lo = l->own0, hi = l->own_last, step = l->ownstep;
+
+    l->h_lwn.assign(lwn_h, lwn_h + nlines);
+    l->h_elow.assign(elow_h, elow_h + nlines);
+    l->h_gf.assign(gf_h, gf_h + nlines);
+    int rc = PB_OK;
+    if (rc == PB_OK) rc = pb::upload(&l->d_lwn, lwn_h, (size_t)nlines);
+    if (rc == PB_OK) rc = pb::upload(&l->d_elow, elow_h, (size_t)nlines);
+    if (rc == PB_OK) rc = pb::upload(&l->d_gf, gf_h, (size_t)nlines);
+    if (rc == PB_OK) rc = pb::upload(&l->d_lid, lid_h, (size_t)nlines);
+    if (rc != PB_OK) {
+        pb_lines_destroy(l);
+        return rc;
+    }
+    // Grouping on the device (pb_lines.hip) when the list has the TLI order (isotope, then
+    // wavenumber) and valid isotope ids; PB_LINES_HOST=1 or any other order: the host loop below
+    bool grouped = false;
+    if (nlines > 0 && !getenv("PB_LINES_HOST") && lid_h[0] >= 0 && lid_h[nlines - 1] < niso) {
+        const int grc = pb_lines_group_device(l, lwn_h, lid_h, own_h);
+        if (grc == PB_OK) {
+            grouped = true;
+            l->grouped_on_device = 1;
+        } else if (grc != 1) {
+            pb_lines_destroy(l);
+            return grc;
+        }
+    }
+    if (!grouped) {
+    struct Group {
+        int32_t first, count, iown, iso;
+    };
+    std::vector<Group> groups;
+    groups.reserve((size_t)nlines);
+    // The lines of ONE isotope must come in ascending wavenumber order (isotopes may interleave).
+    // The reference's Doppler-width index is a one-way search from the isotope's previous line
+    // (_extcoeff.c:278, utils.h:45-72: `if (value < array[lo]) return lo`): on a list that steps
+    // back within an isotope it keeps a stale index, a result that depends on the list order and
+    // on which lines the layer's threshold skipped.  The kernels evaluate the nearest index
+    // statelessly -- the same thing on an ordered list, NOT on such a one: refuse it loudly.
+    // (Every TLI reader output is ordered; the reference itself produces an unordered list only
+    // from a TLI FILE holding several databases, whose isotope ids it confuses:
+    // line_by_line.py:114-119, fixture G16 `onefile`.)
+    std::vector<double> last_wn((size_t)niso, -HUGE_VAL);
+    for (int64_t ln = 0; ln < nlines; ln++) {
+        const int i = lid_h[ln];
+        if (i < 0 || i >= niso) {
+            pb::set_error("pb_lines_create: line %lld has isotope id %d outside [0,%d)",
+                          (long long)ln, i, niso);
+            pb_lines_destroy(l);
+            return PB_ERR_ARG;
+        }
+        const double v = lwn_h[ln];
+        if (v < lo || v > hi)
+            continue;
+        if (v < last_wn[(size_t)i]) {
+            pb::set_error("pb_lines_create: line %lld (%.6f cm-1) of isotope %d comes after a "
+                          "line at %.6f cm-1: the lines of an isotope must be in ascending "
+                          "wavenumber order (the reference's Doppler-index search is one-way, "
+                          "_extcoeff.c:278; its result on such a list is order-dependent)",
+                          (long long)ln, v, i, last_wn[(size_t)i]);
+            pb_lines_destroy(l);
+            return PB_ERR_ARG;
+        }
+        last_wn[(size_t)i] = v;
+        l->ninrange++;
+        // nearest fine-grid index (_extcoeff.c:243-245)
+        int64_t iown = (int64_t)((v - lo) / step);
+        if (iown + 1 < onwn && fabs(v - own_at(iown + 1)) < fabs(v - own_at(iown)))
+            iown++;
+        Group g{(int32_t)ln, 1, (int32_t)iown, i};
+        const double centre = own_at(iown);
+        // greedy co-adding of the following lines of the same isotope (:248-262)
+        while (ln + 1 != nlines && lid_h[ln + 1] == i && lwn_h[ln + 1] <= hi) {
+            if (fabs(lwn_h[ln + 1] - centre) < step) {
+                ln++;
+                last_wn[(size_t)i] = std::max(last_wn[(size_t)i], lwn_h[ln]);
+                g.count++;
+                l->nadd++;
+                l->ninrange++;
+            } else
+                break;
+        }
+        groups.push_back(g);
+    }
+    // (isotope, fine index) order; stable, so a sorted TLI keeps its file order
+    std::stable_sort(groups.begin(), groups.end(), [](const Group &x, const Group &y) {
+        return x.iso != y.iso ? x.iso < y.iso : x.iown < y.iown;
+    });
+    l->ngroups = (int64_t)groups.size();
+    l->iso_gstart.assign((size_t)niso + 1, 0);
+    for (const Group &g : groups)
+        l->iso_gstart[(size_t)g.iso + 1]++;
+    for (int i = 0; i < niso; i++)
+        l->iso_gstart[(size_t)i + 1] += l->iso_gstart[(size_t)i];
+    std::vector<int32_t> &gfirst = l->h_gfirst, &gcount = l->h_gcount, &giown = l->h_giown;
+    gfirst.resize(groups.size());
+    gcount.resize(groups.size());
+    giown.resize(groups.size());
+    std::vector<int32_t> giso(groups.size());
+    for (size_t k = 0; k < groups.size(); k++) {
+        gfirst[k] = groups[k].first;
+        gcount[k] = groups[k].count;
+        giown[k] = groups[k].iown;
+        giso[k] = groups[k].iso;
+    }
+    if (rc == PB_OK) rc = pb::upload(&l->d_gfirst, gfirst.data(), gfirst.size());
+    if (rc == PB_OK) rc = pb::upload(&l->d_gcount, gcount.data(), gcount.size());
+    if (rc == PB_OK) rc = pb::upload(&l->d_giown, giown.data(), giown.size());
+    if (rc == PB_OK) rc = pb::upload(&l->d_giso, giso.data(), giso.size());
+    }
+    if (rc == PB_OK) rc = pb::upload(&l->d_iso_gstart, l->iso_gstart.data(), l->iso_gstart.size());
+    if (rc != PB_OK) {
+        pb_lines_destroy(l);
+        return rc;
+    }
+    *out = l;
+    return PB_OK;
+}
+
+int pb_lines_grouped_on_device(const pb_lines *l, int *flag)
+{
+    PB_REQUIRE(l && flag, "pb_lines_grouped_on_device: null pointer");
+    *flag = l->grouped_on_device;
+    return PB_OK;
+}
+
+int pb_lines_groups(const pb_lines *l, int32_t *first_h, int32_t *count_h, int32_t *iown_h,
+                    int64_t *iso_gstart_h)
+{
+    PB_REQUIRE(l, "pb_lines_groups: null handle");
+    const size_t n = (size_t)l->ngroups;
+    if (first_h)
+        std::copy(l->h_gfirst.begin(), l->h_gfirst.begin() + n, first_h);
+    if (count_h)
+        std::copy(l->h_gcount.begin(), l->h_gcount.begin() + n, count_h);
+    if (iown_h)
+        std::copy(l->h_giown.begin(), l->h_giown.begin() + n, iown_h);
+    if (iso_gstart_h)
+        std::copy(l->iso_gstart.begin(), l->iso_gstart.end(), iso_gstart_h);
+    return PB_OK;
+}
+
+int pb_lines_stats(const pb_lines *l, int64_t stats[3])
+{
+    PB_REQUIRE(l && stats, "pb_lines_stats: null pointer");
+    stats[0] = l->ninrange;
+    stats[1] = l->ngroups;
+    stats[2] = l->nadd;
+    return PB_OK;
+}
+
+void pb_lines_destroy(pb_lines *l)
+{
+    if (!l)
+        return;
+    (void)hipFree(l->d_lwn);
+    (void)hipFree(l->d_elow);
+    (void)hipFree(l->d_gf);
+    (void)hipFree(l->d_lid);
+    (void)hipFree(l->d_gfirst);
+    (void)hipFree(l->d_gcount);
+    (void)hipFree(l->d_giown);
+    (void)hipFree(l->d_giso);
+    (void)hipFree(l->d_iso_gstart);
+    delete l;
+}
+
+}  // extern "C"
