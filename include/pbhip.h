@@ -553,6 +553,33 @@ int pb_band_scale(double *bandflux_d, const double *band_scale_d, const double *
 int pb_reject_walkers(double *bandflux_d, const double *temps_d, double tmin, double tmax,
                       int nlayers, int nbands, int nwalkers, void *stream);
 
+/* High-resolution data (eval()'s second exit, pyrat/pyrat_obj.py:331-356).
+ * ps.inst_convolution's last step (spectrum/spec_tools.py:879) for a batch:
+ *   out_d[w] = convolve(spectra_d[w] * sample_scale_d, taps_d, mode='same')
+ * -- the full convolution cut to the grid, zeros beyond both ends; ntaps odd, at most 1025 (a
+ * larger kernel is refused: PB_ERR_ARG, the message names the limit).  sample_scale_d[nwave]
+ * (or NULL) multiplies every sample as it is loaded: the eclipse ratio and the f_lambda factor are
+ * applied before the convolution in the reference.  Not in place. */
+int pb_inst_convolve_batch(double *out_d, const double *spectra_d, const double *taps_d,
+                           const double *sample_scale_d, int ntaps, int nwave, int nwalkers,
+                           void *stream);
+/* Convolution, radial-velocity shift and sampling at the data in one launch, the convolved
+ * spectra never stored: per walker w
+ *   s = spectra_d[w] [* walker_scale_d[w]] [* sample_scale_d]
+ *   c = convolve(s, taps_d, mode='same')                       (only where a data point needs it)
+ *   x = wn_d * sqrt((1 - v/c) / (1 + v/c)), v = rv_kms_d[w] km/s  (spec_tools.py:883-907; NULL: 0)
+ *   out_d[w, data_slot_d[j]] = interp1d(x, c)(data_wn_sorted_d[j]):  idx = searchsorted(x, d,
+ *     'left') clipped to [1, nwave - 1], lo = idx - 1, (c[idx] - c[lo]) / (x[idx] - x[lo]) * (d -
+ *     x[lo]) + c[lo]
+ * data_wn_sorted_d[ndata] ascending, data_slot_d[ndata] a permutation of 0 .. ndata - 1 (the
+ * caller's order).  A walker with |rv| > rv_max (or NaN), or with a data point off its shifted
+ * grid (interp1d raises there), gets +inf in every output.  Same limit on ntaps. */
+int pb_hires_observe_batch(double *out_d, const double *spectra_d, const double *wn_d,
+                           const double *taps_d, const double *sample_scale_d,
+                           const double *data_wn_sorted_d, const int32_t *data_slot_d,
+                           const double *rv_kms_d, const double *walker_scale_d, double rv_max,
+                           int ntaps, int nwave, int ndata, int nwalkers, void *stream);
+
 /* The retrieval batch with continuum terms (pyrat/opacity.py:206-257: every model adds to the
  * one ec), added in registers before pb_interp_ec_batch[_limited] store a sample -- no second
  * pass over ec.  Per walker and layer the terms of Continuum.add / pb_continuum, in its order, on

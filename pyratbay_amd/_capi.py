@@ -91,6 +91,8 @@ _PROTOS = {
     'pb_emission_observables': [vp, vp, vp, vp, vp, i64, i32, i32, f64, f64, vp],
     'pb_band_scale': [vp, vp, vp, i32, i32, vp],
     'pb_reject_walkers': [vp, vp, f64, f64, i32, i32, i32, vp],
+    'pb_inst_convolve_batch': [vp, vp, vp, vp, i32, i32, i32, vp],
+    'pb_hires_observe_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, i32, i32, i32, vp],
     'pb_interp_ec_batch_cont_work_doubles': [vp, i32, i32, i32],
     'pb_interp_ec_batch_cont': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
     'pb_interp_ec_batch_cont_limited': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp,

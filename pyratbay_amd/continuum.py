@@ -29,6 +29,7 @@ BAR = 1e6
 AMU = 1.6605390666e-24
 AMAGAT = 2.6867801117984436e+19
 UM = 1e-4
+KM = 1e5
 
 
 def _grid(wn, wl):

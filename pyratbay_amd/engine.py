@@ -945,6 +945,100 @@ class PassBands:
         return out
 
 
+class HiresData:
+    """High-resolution spectroscopic data as the exit of the batched loop (eval()'s second exit,
+    pyrat/pyrat_obj.py:331-356): the model spectrum convolved with the instrument profile of
+    resolving power inst_resolution (ps.inst_convolution), the grid Doppler-shifted by each
+    walker's radial velocity (ps.rv_shift) and the result sampled at data_wn by interp1d's linear
+    rule.  wn: the model's grid (ascending); sampling_res: the grid's resolving power when it is a
+    constant-resolution grid (the reference's spec.resolution), None: taken from the grid's steps;
+    data_wn: in any order -- sorted once here, integrate_batch() returns the caller's order.
+    rv_max (km/s): walkers beyond it are rejected (+inf, like eval()'s reject path); the
+    constructor refuses data that can leave the shifted grid within +-rv_max (where the
+    reference's interp1d raises); check_data=False leaves that to the device, which rejects a
+    walker whose data leave ITS shifted grid.
+
+    integrate_batch() is ONE fused launch (pb_hires_observe_batch): the convolved spectra
+    [nw, W] are never stored, and only the convolved samples that a data point brackets are
+    computed.  `fused = False` takes the two-launch form instead (convolve() into a [nw, W]
+    buffer, then the same kernel with a single unit tap): the same bits, kept for comparison."""
+
+    def __init__(self, wn, data_wn, inst_resolution, sampling_res=None, rv_max=100.0,
+                 check_data=True):
+        from . import hires
+        wn_host = np.ascontiguousarray(wn.cpu().numpy() if isinstance(wn, torch.Tensor) else wn,
+                                       dtype=np.float64)
+        data_host = np.ascontiguousarray(data_wn, dtype=np.float64)
+        hires.check_data_in_grid(wn_host, data_host, rv_max, span=check_data)
+        taps = hires.inst_kernel(inst_resolution, wn=wn_host, sampling_res=sampling_res)
+        if len(taps) > hires.MAX_TAPS:
+            raise ValueError(f'HiresData: the instrument profile spans {len(taps)} samples of '
+                             f'the grid, at most {hires.MAX_TAPS} are supported')
+        self.inst_resolution, self.sampling_res = inst_resolution, sampling_res
+        self.rv_max = float(rv_max)
+        self.nwave = len(wn_host)
+        self.nbands = self.ndata = len(data_host)
+        self.taps_host = taps
+        order = np.argsort(data_host, kind='stable')
+        self.wn = dev(wn_host)
+        self.taps = dev(taps)
+        self.data_wn_sorted = dev(data_host[order])
+        self.data_slot = dev(order, torch.int32)
+        self.unit_tap = dev(np.ones(1))
+        self.sample_scale = None        # per-sample factor before the convolution
+        self.fused = True
+
+    def set_eclipse(self, rplanet, rstar, starflux):
+        """Eclipse geometry: every sample of fplanet is multiplied by 1/starflux * rprs**2 BEFORE
+        the convolution (pyrat/spectrum.py:401-404 -- pb_emission_observables' mode 1)."""
+        starflux = np.asarray(starflux, float)
+        assert starflux.shape == (self.nwave,)
+        self.sample_scale = dev(1 / starflux * (float(rplanet) / float(rstar))**2)
+        return self
+
+    def set_f_lambda(self, rplanet, distance):
+        """f_lambda geometry: erg s-1 cm-2 cm to W m-2 um-1 per sample before the convolution
+        (pyrat_obj.py:323-329 -- pb_emission_observables' mode 2: 10 (rplanet/distance wn um)^2,
+        here as ONE factor per sample: within an ulp of the reference's two products)."""
+        t = float(rplanet) / float(distance) * self.wn.cpu().numpy() * 1.0e-4
+        self.sample_scale = dev(10.0 * (t * t))
+        return self
+
+    def convolve(self, spectra):
+        """spectra[nw, W] (x the per-sample factor, if set) convolved with the instrument profile
+        -> [nw, W], the reference's spec.spectrum_convolved."""
+        nw, nwave = spectra.shape
+        assert nwave == self.nwave
+        out = torch.empty_like(spectra)
+        call('pb_inst_convolve_batch', _ptr(out), _ptr(spectra), _ptr(self.taps),
+             _ptr(self.sample_scale), len(self.taps_host), nwave, nw, _stream())
+        return out
+
+    def integrate_batch(self, spectra, out=None, f_dilution=None, rv=None):
+        """Model values at the data of full-grid spectra[nw, W] -> [nw, ndata] in the order of
+        data_wn.  rv[nw]: the walkers' radial velocities in km/s (None: no shift); f_dilution[nw]:
+        the walkers' dilution factors, applied per sample first (pyrat/spectrum.py:395-396)."""
+        nw, nwave = spectra.shape
+        assert nwave == self.nwave
+        assert rv is None or rv.shape == (nw,)
+        assert f_dilution is None or f_dilution.shape == (nw,)
+        if out is None:
+            out = torch.empty((nw, self.ndata), dtype=torch.float64, device=spectra.device)
+        rv = None if rv is None else rv.contiguous()
+        if self.fused:
+            call('pb_hires_observe_batch', _ptr(out), _ptr(spectra), _ptr(self.wn),
+                 _ptr(self.taps), _ptr(self.sample_scale), _ptr(self.data_wn_sorted),
+                 _ptr(self.data_slot), _ptr(rv), _ptr(f_dilution), self.rv_max,
+                 len(self.taps_host), nwave, self.ndata, nw, _stream())
+            return out
+        if f_dilution is not None:
+            spectra = spectra * f_dilution.view(-1, 1)
+        call('pb_hires_observe_batch', _ptr(out), _ptr(self.convolve(spectra)), _ptr(self.wn),
+             _ptr(self.unit_tap), None, _ptr(self.data_wn_sorted), _ptr(self.data_slot),
+             _ptr(rv), None, self.rv_max, 1, nwave, self.ndata, nw, _stream())
+        return out
+
+
 def default_quadrature():
     """(mu, weights) of the reference when `quadrature` is unset: raygrid = 0, 20, 40, 60, 80
     degrees, weights = the solid angle between the mid-points (pyrat/spectrum.py:30-58)."""
@@ -1667,7 +1761,7 @@ class TableSpectrum:
         return self._timer.read()
 
     def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
-                   f_dilution=None, continuum_density=None, continuum_pars=None):
+                   f_dilution=None, continuum_density=None, continuum_pars=None, rv=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
         without the parameter mapping): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
@@ -1685,9 +1779,21 @@ class TableSpectrum:
         the number densities of cont.species, continuum_pars[nw, npars] the free parameters in
         cont.free_pars order (None: every walker uses the models' current pars).  A walker outside
         a CIA table's temperatures is rejected like one outside the table.  A cloud deck and the
-        alkali models are refused in this form (ValueError); eval() takes them."""
+        alkali models are refused in this form (ValueError); eval() takes them.
+
+        bands may be a HiresData instead (high-resolution spectroscopy, pyrat_obj.py:331-356):
+        the spectra are convolved with the instrument profile, shifted by the walkers' radial
+        velocities rv[nw] (km/s, a device tensor; None: no shift) and sampled at the data in one
+        launch per chunk -> [nw, ndata].  rv with a PassBands is refused (ValueError)."""
         assert self.rt_path in ('transit', 'emission'), \
             'eval_bands: transit or emission geometry on sampled cross sections'
+        if rv is not None:
+            if not isinstance(bands, HiresData):
+                raise ValueError('eval_bands: rv (a radial-velocity shift) needs a HiresData, '
+                                 'pass bands are integrated on the unshifted grid')
+            if tuple(rv.shape) != (temps.shape[0],):
+                raise ValueError(f'eval_bands: rv must have shape {(temps.shape[0],)}, got '
+                                 f'{tuple(rv.shape)}')
         assert f_dilution is None or self.rt_path == 'emission', 'f_dilution: emission geometry'
         assert f_dilution is None or f_dilution.shape == (temps.shape[0],)
         nw = temps.shape[0]
@@ -1753,10 +1859,10 @@ class TableSpectrum:
             if streams > 1:
                 with torch.cuda.stream(self._eval_streams[ci % streams]):
                     self._eval_chunk(temps, dens, bands, radius, shared_radius, path1, out, w0,
-                                     min(w0 + chunk, nw), f_dilution, cargs)
+                                     min(w0 + chunk, nw), f_dilution, cargs, rv)
             else:
                 self._eval_chunk(temps, dens, bands, radius, shared_radius, path1, out, w0,
-                                 min(w0 + chunk, nw), f_dilution, cargs)
+                                 min(w0 + chunk, nw), f_dilution, cargs, rv)
         if streams > 1:
             for st in self._eval_streams[:streams]:
                 caller.wait_stream(st)
@@ -1787,9 +1893,11 @@ class TableSpectrum:
                                                       self.itop, self.nlayers, self.nwave)
 
     def _eval_chunk(self, temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
-                    f_dilution=None, cargs=(None, None)):
+                    f_dilution=None, cargs=(None, None), rv=None):
         """One chunk of eval_bands: walkers [w0, w1) through every stage, one launch each."""
         n = w1 - w0
+        # (the walkers' radial velocities: HiresData only -- eval_bands has checked)
+        okw = {} if rv is None else {'rv': rv[w0:w1]}
         cont = self.continuum
         # (the one-pass transit takes no continuum: with one attached, the two passes)
         if self.rt_path == 'transit' and self._one_pass() and cont is None:
@@ -1803,7 +1911,7 @@ class TableSpectrum:
             spectra = table_transit_batch(self.etable, self.ttable, temps[w0:w1], dens[w0:w1],
                                           path, rad, self.rstar, self.itop, self.nlayers,
                                           self.maxdepth)
-            bands.integrate_batch(spectra, out[w0:w1])
+            bands.integrate_batch(spectra, out[w0:w1], **okw)
             return
         # (an explicit order on a shape the ordered transit kernel does not take -- more than 128
         # impact parameters -- is worked in grid order: the spectra do not depend on the order)
@@ -1853,7 +1961,8 @@ class TableSpectrum:
                                               self.nlayers, self.maxdepth,
                                               self.column_order if ordered else None)
             bands.integrate_batch(spectra, out[w0:w1],
-                                  None if f_dilution is None else f_dilution[w0:w1].contiguous())
+                                  None if f_dilution is None else f_dilution[w0:w1].contiguous(),
+                                  **okw)
             return
         if shared_radius:
             rad = radius.expand(n, -1).contiguous()
@@ -1880,4 +1989,4 @@ class TableSpectrum:
         else:
             spectra = transit_spectrum_batch(ec, path, rad, self.rstar, self.itop, self.nlayers,
                                              self.maxdepth)
-        bands.integrate_batch(spectra, out[w0:w1])
+        bands.integrate_batch(spectra, out[w0:w1], **okw)
