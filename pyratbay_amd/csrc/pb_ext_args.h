@@ -1,6 +1,8 @@
-// Argument block and record formats shared by the translation units of the line-by-line
-// extinction (pb_extinction.hip: layer state, records, the gather kernels and the C ABI;
-// pb_rounds.hip: the round-staged gather).
+// Argument block, record formats, kernel geometry and __device__ helpers shared by the translation
+// units of the line-by-line extinction: pb_extinction.hip (handle, planner, C ABI),
+// pb_ext_records.hip (layer state and records), pb_ext_gather.hip (the gathers of constant-step
+// grids), pb_ext_resolution.hip (`resolution` plans) and, in the experiments build, pb_rounds.hip /
+// pb_wave.hip.  The host side of the same units is in pb_ext_plan.h.
 #pragma once
 
 #include <cstdint>
@@ -10,10 +12,49 @@
 
 namespace pbx {
 
+// `make EXPERIMENTS=1` (libpbhip_exp.so) keeps the measured dead ends selectable: gather modes 4
+// (scatter), 5 (rounds: pb_rounds.hip) and 7 (wave: pb_wave.hip), the predicted run plans of the
+// `resolution` mode.  The default library compiles none of them.
+#ifdef PB_EXPERIMENTS
+constexpr bool kExp = true;
+#else
+constexpr bool kExp = false;
+#endif
+
+// global gather (k_ext_resample): threads of a workgroup and the samples a wavefront / workgroup owns
+constexpr int kBlock = 256;
+constexpr int kChunks = 2;                       // 128-sample chunks per wavefront
+constexpr int kLaneSamples = 2;                  // consecutive samples per lane (16-B loads)
+constexpr int kChunk = 64 * kLaneSamples;        // samples per chunk
+constexpr int kWaveSpan = kChunks * kChunk;      // samples per wavefront
+constexpr int kTile = 4 * kWaveSpan;             // output samples per workgroup
+constexpr int kRecs = 4;                         // records in flight per wavefront trip
+static_assert(kTile <= kPmPad, "table padding must cover one tile");
+static_assert(kTile < 65536, "window coordinates are packed in 16 bits");
+
+// packed records (k_records writes them; the staged gather and the planner decode them)
+constexpr int kLongLenBits = 14;   // window length in a long-row record (rows of up to 16 x 1024 samples)
+constexpr int kChunkRow = 1024;      // samples per chunk of a long phase row (= kStageRowMax)
+constexpr int kRecLayers = 4;        // layers per thread of k_records (group data loaded once);
+                                     // 1 for launches of few layers (multi-GPU ranks)
+
 constexpr int kBinSamples = 256;     // output samples per bin of the phase-list position index
 constexpr int kStagePad = 256;       // zero samples on either side of a staged row
 constexpr int kStageSpan = 256;      // samples per wavefront and sub-tile (4 chunks of 64)
 constexpr int kStageRowMax = 1024;   // longest phase row the staged kernels keep in one piece
+
+// staged gather (k_ext_staged): wavefronts and threads of a workgroup
+constexpr int kStagedWaves = 8;
+constexpr int kStagedThreads = kStagedWaves * 64;
+constexpr int64_t kStagedSub = kStagedWaves * kStageSpan;      // samples of one sub-tile
+
+// resident-profile gather (k_ext_resident)
+constexpr int kResWaves = 8;
+constexpr int kResThreads = kResWaves * 64;
+constexpr int kResStrips = 2;                              // 64-sample strips per wavefront
+constexpr int kResTile = kResThreads * kResStrips;         // output samples per workgroup
+constexpr int kResCapDefault = 8192;                       // doubles of LDS for one profile block
+static_assert(kResTile < 65536, "window coordinates are packed in 16 bits");
 
 // wave-autonomous gather (pb_wave.hip): output samples per workgroup (every wavefront keeps all
 // of them) and the longest phase row / window it stages (three LDS-DMA pieces of 128 samples)
@@ -250,6 +291,131 @@ __device__ inline void lower_bound2_i32(const int32_t *a, int64_t lo0, int64_t h
 __device__ inline int floor_div_inv(int a, double inv)
 {
     return (int)floor(((double)a + 0.5) * inv);
+}
+
+// Line strength divided by the abundance (_extcoeff.c:219-224), same operation order; the three
+// divisions by per-layer values through pb::quot(), the exponentials through pb::exp_s (the device
+// library's exp arithmetic with its coefficients in scalar registers: same bits).  k_records
+// evaluates this once per (layer, line): 2 exp + 3 divisions were 0.11 ms of every C2 spectrum.
+__device__ inline double line_strength(double ratio, double gf, double elow, double wavn,
+                                       double temp, double inv_temp, double z, double inv_z)
+{
+    const double k = pb::quot_fast(pb::kSigCte * ratio * gf *
+                                       pb::exp_s(pb::quot_fast(-pb::kExpCte * elow, temp, inv_temp)) *
+                                       (1 - pb::exp_s(pb::quot_fast(-pb::kExpCte * wavn, temp, inv_temp))),
+                                   z, inv_z);
+    // one test of the END result instead of one per quotient: a special value in any of the three
+    // (temp or z zero / infinite, an infinite numerator) ends as NaN or 0 here -- then, and when
+    // the strength has really underflowed, the reference's own divisions decide
+    if (__builtin_expect(!(fabs(k) > 0.0), 0))
+        return pb::kSigCte * ratio * gf * pb::exp_s(-pb::kExpCte * elow / temp) *
+               (1 - pb::exp_s(-pb::kExpCte * wavn / temp)) / z;
+    return k;
+}
+
+// a wave-uniform int written by an earlier kernel, by a scalar load
+__device__ __forceinline__ int uniform_load_i32(const int32_t *p, int64_t i)
+{
+    typedef const int32_t __attribute__((address_space(4))) *cptr;
+    return ((cptr)(unsigned long long)p)[i];
+}
+
+// A wave-uniform element of a device array written by an EARLIER kernel: read through the constant
+// address space, i.e. by a scalar load (a plain load of a uniform address is a vector load that
+// every lane waits for).
+template <class T>
+__device__ __forceinline__ T uniform_load(const T *p, int64_t i)
+{
+    typedef const T __attribute__((address_space(4))) *cptr;
+    return ((cptr)(unsigned long long)p)[i];
+}
+
+// ---------------------------------------------------------------------------
+// helpers for the gather kernels
+// ---------------------------------------------------------------------------
+__device__ inline double bcast(double v, int lane)
+{
+    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+// Window of one group on the dynamic grid, exactly as _extcoeff.c:274-299.
+struct Window {
+    long minj, maxj;
+    int half, cell;
+};
+
+// a / d truncated toward zero like C's integer division, for |a| < 2^31, 0 < d < 2^20, inv = 1.0/d
+__device__ inline int trunc_div_inv(int a, double inv)
+{
+    return a >= 0 ? floor_div_inv(a, inv) : -floor_div_inv(-a, inv);
+}
+
+// cutsteps = cutoff / dwnstep and inv_ofactor = 1.0 / ofactor are per-layer values prepared by
+// k_layer_state (the same quotients the reference forms per line, _extcoeff.c:281-299)
+__device__ inline Window group_window(const LblArgs &a, double wavn, int iown, int ilor,
+                                      double alphad, int ofactor, double dwnstep,
+                                      int64_t dnwn, int idop_lo, int idop_hi,
+                                      const double *doppler, double cutsteps,
+                                      double inv_ofactor, bool clip_lo = true,
+                                      bool clip_hi = true)
+{
+    // [idop_lo, idop_hi] brackets the answer (nearest index is monotonic in wavn), which
+    // turns the bisection over the whole Doppler grid into 0-2 steps; `doppler` may point
+    // to an LDS copy of the grid
+    Window w;
+    const int idwn = (int)((wavn - a.own0) / dwnstep);
+    const int idop = idop_lo == idop_hi
+                         ? idop_lo
+                         : pb::nearest_index(doppler ? doppler : a.doppler, alphad * wavn,
+                                             idop_lo, idop_hi);
+    w.cell = ilor * a.ndop + idop;
+    w.half = a.psize[w.cell];
+    const int subw = iown - idwn * ofactor;
+    w.minj = idwn - trunc_div_inv(w.half - subw, inv_ofactor);
+    w.maxj = idwn + trunc_div_inv(w.half + subw, inv_ofactor);
+    // (the packed records of the staged gathers keep a window that leaves the grid unclipped:
+    // see k_records)
+    if (clip_lo && w.minj < 0)
+        w.minj = 0;
+    if (clip_hi && w.maxj > dnwn)
+        w.maxj = dnwn;
+    if (a.cutoff > 0.0) {
+        const int mincut = (int)(idwn - cutsteps);
+        const int maxcut = (int)(idwn + cutsteps);
+        if (mincut > w.minj)
+            w.minj = mincut;
+        if (maxcut < w.maxj)
+            w.maxj = maxcut;
+    }
+    return w;
+}
+
+// Co-added strength of a group (left-to-right sum of its members, _extcoeff.c:248-262)
+__device__ inline double group_strength(const LblArgs &a, int first, int count, double ratio,
+                                        double temp, double inv_temp, double z, double inv_z)
+{
+    double k = line_strength(ratio, a.gf[first], a.elow[first], a.lwn[first], temp, inv_temp, z,
+                             inv_z);
+    for (int m = 1; m < count; m++)
+        k += line_strength(ratio, a.gf[first + m], a.elow[first + m], a.lwn[first + m],
+                           temp, inv_temp, z, inv_z);
+    return k;
+}
+
+__device__ inline void decode_block(const LblArgs &a, int &tile, int &layer)
+{
+    // blocks b and b+8 share an XCD: give each XCD its own layers, deepest first
+    const int id = blockIdx.x;
+    const int xcd = id & 7;
+    const int k = id >> 3;
+    tile = k % a.ntiles;
+    const int grp = k / a.ntiles;
+    // dealt to the XCDs in snake order (0..7, 7..0, ...): the cost of a layer falls with height,
+    // and workgroup i always runs on XCD i % 8 -- dealt 0..7 every time, XCD 0 gets the heaviest
+    // layer of every group of eight and finishes last (C3: 44.0 ms of work against 38.4 on XCD 6)
+    const int rank = grp * 8 + ((grp & 1) ? 7 - xcd : xcd);
+    layer = a.nlayers - 1 - rank;      // < 0 for the padding blocks
 }
 
 }  // namespace pbx

@@ -8,7 +8,7 @@
 
 #include "pbhip.h"
 
-constexpr int kPmPad = 1024;   // >= the gather kernel's tile (pb_extinction.hip kTile)
+constexpr int kPmPad = 1024;   // >= the gather kernel's tile (pb_ext_args.h kTile)
 
 struct pb_voigt {
     int nlor = 0, ndop = 0, osamp = 0, ncell = 0, max_half = 0;

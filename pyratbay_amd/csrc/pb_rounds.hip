@@ -1,7 +1,7 @@
 // Round-staged extinction gather (constant-step grids, phase rows of <= 1024 samples).
 //
 // Replaces the profile accumulation + resample of _extcoeff.extinction
-// (src_c/_extcoeff.c:300-332), like k_ext_staged in pb_extinction.hip, with the per-segment
+// (src_c/_extcoeff.c:300-332), like k_ext_staged in pb_ext_gather.hip, with the per-segment
 // machinery of that kernel taken apart into two launches:
 //
 //   k_rounds      one 256-thread workgroup per (layer, tile, phase split).  Walks the tile's

@@ -3,7 +3,7 @@
 // Replaces the profile accumulation + resample of _extcoeff.extinction
 // (src_c/_extcoeff.c:281-332) for the layers whose phase rows are at most kWvRowMax samples
 // long -- the Doppler-core layers of an atmosphere: 49 of the 80 layers of BASELINE config 2,
-// where a line adds ~130-300 samples -- like k_ext_staged (pb_extinction.hip) does for the rest.
+// where a line adds ~130-300 samples -- like k_ext_staged (pb_ext_gather.hip) does for the rest.
 //
 // Why another kernel.  k_ext_staged shares every staged row between the eight wavefronts of a
 // workgroup: one `s_barrier` per phase row, between two barriers a wavefront has one or two
