@@ -645,6 +645,80 @@ int pb_interp_ec_batch_cont_limited(double *ec_d, const double *etable_d, const 
                                     const pb_cont_batch *cont, const int32_t *tile_limit_d,
                                     int row0, const int32_t *gate_d, void *stream);
 
+/* The retrieval batch with clouds: an opaque deck at a per-walker pressure (opacity/clouds/
+ * gray.py:95-154; pyrat_obj.py:135-139; spectrum/radiative_transfer.py:63-67, 125-127) and patchy
+ * clouds (pyrat_obj.py:285-286, opacity/optic_depth.py:94-136, pyrat/spectrum.py:357-384).
+ *
+ * Deck state of every walker, p = 10^logp_d[w] bar on pressure_d[nlayers] (bar, ascending):
+ *   itop  = first layer with pressure >= p; nlayers - 1 if p >= pressure[nlayers-1] (or NaN);
+ *           1 (at most nlayers - 1) if p < pressure[0]
+ *   rsurf, tsurf = radius and temperature at p, linear in pressure, CLAMPED to the end values
+ *           outside the grid (the reference's interp1d raises there)
+ * radius_d[w * radius_stride + l] (radius_stride = 0: one profile for all), temps_d[nwalkers,
+ * nlayers].  One launch, nothing read back. */
+int pb_deck_state_batch(int32_t *itop_d, double *rsurf_d, double *tsurf_d,
+                        const double *pressure_d, const double *logp_d, const double *radius_d,
+                        int64_t radius_stride, const double *temps_d, int nlayers, int nwalkers,
+                        void *stream);
+/* ec_cloud = sum_m cs_m[sample] f_m[walker, layer], m in model order, is never stored: the
+ * kernels below add it to ec as they walk a column.  cs_d[m]: NULL (a row of ones: gray) or the
+ * cross sections in ec's column order at cs_d[m][w * cs_stride[m] + sample] (cs_stride 0: one row
+ * for all walkers; nwave: a row per walker); f_d[nwalkers][nlayers][nr]. */
+#define PB_CLOUD_MAX 8
+typedef struct pb_cloud_terms {
+    int nr;
+    const double *cs_d[PB_CLOUD_MAX];
+    int64_t cs_stride[PB_CLOUD_MAX];
+    const double *f_d;
+} pb_cloud_terms;
+/* The factors of the cloud-type models of a Continuum from the walkers' parameters, as
+ * pb_interp_ec_batch_cont forms them for the same models in ec (kind 1 Lecavelier: f = p BAR/T/K,
+ * cross sections 10^p[par] s0 (wn l0)^-p[par+1] into rows_d[j][nwalkers][nwave], j counting the
+ * Lecavelier models; kind 2 CCSgray: f = 10^p[par] s0 p BAR/T/K between 10^p[par+1] and
+ * 10^p[par+2] bar, else 0).  f_d[nwalkers][nlayers][nr]; pars_stride 0: one row for all. */
+typedef struct pb_cloud_models {
+    int nr;
+    int kind[PB_CLOUD_MAX];
+    int par[PB_CLOUD_MAX];
+    double s0[PB_CLOUD_MAX];
+    double l0[PB_CLOUD_MAX];
+    const double *pressure_d[PB_CLOUD_MAX];
+} pb_cloud_models;
+int pb_cloud_plan(double *f_d, double *rows_d, const pb_cloud_models *models,
+                  const double *temps_d, const double *pars_d, int pars_stride,
+                  const double *wn_d, int nlayers, int nwave, int nwalkers, void *stream);
+/* Transit geometry, one pass over ec_d[nwalkers,nlayers,nwave] for both columns of a walker:
+ *   clear : ec over [itop, nlayers), no deck
+ *   cloudy: ec + ec_cloud over [itop, deck_itop + 1); the interval that ends at the deck ends at
+ *           deck_rsurf with the integrand interpolated linearly in radius (nothing is replaced
+ *           when deck_itop <= itop); no deck (deck_itop_d NULL): down to the last layer
+ *   spectrum = f cloudy + (1 - f) clear, f = f_patchy_d[w] clamped to [0, 1] (NaN stays NaN);
+ *           f_patchy_d NULL: spectrum = cloudy, and the clear column is not walked
+ * With cloud == NULL (or nr = 0) the two optical depths are equal row for row down to the deck and
+ * are summed once.  raypath_d[w * path_stride + .] = pb_transit_path's packed triangle,
+ * radius_d[w * radius_stride + l] (stride 0: shared).  column_d (or NULL): ec_d's columns are in
+ * that order (grid index of each), the outputs in grid order; per column the arithmetic does not
+ * depend on the order.  clear_d / cloudy_d (or NULL): the two parts.  At most 1024 impact
+ * parameters. */
+int pb_cloudy_transit_batch(double *spectrum_d, double *clear_d, double *cloudy_d,
+                            const double *ec_d, const double *raypath_d, int64_t path_stride,
+                            const double *radius_d, int64_t radius_stride,
+                            const int32_t *column_d, double rstar, int itop, double maxdepth,
+                            int nlayers, int nwave, int nwalkers, const int32_t *deck_itop_d,
+                            const double *deck_rsurf_d, const pb_cloud_terms *cloud,
+                            const double *f_patchy_d, void *stream);
+/* Emission geometry (pb_emission_flux_batch's pass): the cloudy column stops at deck_itop (the
+ * reference clips ideep to it), layer deck_itop radiates at deck_tsurf_d[w] -- in the CLEAR
+ * column too: the reference's cloudy pass overwrites that row of its Planck array and the clear
+ * pass reads it (spectrum/radiative_transfer.py:125-126, pyrat/spectrum.py:380-383).  wn_d in
+ * ec_d's column order. */
+int pb_cloudy_emission_batch(double *flux_d, double *clear_d, double *cloudy_d, const double *ec_d,
+                             const double *intervals_d, const double *wn_d, const double *temp_d,
+                             const double *mu_d, const double *weights_d, const int32_t *column_d,
+                             int nmu, double maxdepth, int itop, int nlayers, int nwave,
+                             int nwalkers, const int32_t *deck_itop_d, const double *deck_tsurf_d,
+                             const pb_cloud_terms *cloud, const double *f_patchy_d, void *stream);
+
 /* =========================================================================
  * Experiments -- NOT in libpbhip.so.  `make -C pyratbay_amd/csrc EXPERIMENTS=1` builds
  * libpbhip_exp.so (compiled with -DPB_EXPERIMENTS) = the product library + the variants that were

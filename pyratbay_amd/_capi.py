@@ -97,6 +97,12 @@ _PROTOS = {
     'pb_interp_ec_batch_cont': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
     'pb_interp_ec_batch_cont_limited': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp,
                                         i32, vp, vp],
+    'pb_deck_state_batch': [vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, vp],
+    'pb_cloud_plan': [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp],
+    'pb_cloudy_transit_batch': [vp, vp, vp, vp, vp, i64, vp, i64, vp, f64, i32, f64, i32, i32, i32,
+                                vp, vp, vp, vp, vp],
+    'pb_cloudy_emission_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f64, i32, i32, i32,
+                                 i32, vp, vp, vp, vp, vp],
     'pb_optdepth': [vp, vp, i64, vp, i32, f64, vp, i32, i32, vp],
     'pb_optical_depth_transit': [vp, vp, vp, vp, i32, i32, f64, i32, i32, vp],
     'pb_transit_spectrum': [vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, vp],

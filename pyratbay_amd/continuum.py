@@ -14,6 +14,7 @@ line-by-line or table stage left on the device.
 Reference: pyratbay/opacity/rayleigh/rayleigh.py, clouds/lecavelier.py, clouds/gray.py,
 cia.py, hydrogen_ion.py, alkali/alkali.py; io/io.py:866-950 (read_cs)."""
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -331,12 +332,26 @@ class Continuum:
     """All continuum terms of a run, resident on the device; add(ec, temp, density) is one
     fused pass over ec plus one pass per alkali species."""
 
-    def __init__(self, wn, pressure, models):
+    def __init__(self, wn, pressure, models, cloud_models=()):
+        """cloud_models: the models of `models` (the same objects) that are CLOUD-type -- what the
+        reference lists under `clouds` (pyrat/opacity.py:252-255): in a patchy batch
+        (eval_bands(..., f_patchy=...)) their terms make up ec_cloud, the extinction of the cloudy
+        column only.  Lecavelier, CCSgray (rank-1 terms) and the Deck (always a property of the
+        cloudy column) may be cloud-type; anything else is refused.  Default: none, every term
+        goes into ec.  eval() / add() put every term into the one ec whatever is listed here."""
         self.wn_h = np.asarray(wn, float)
         self.pressure = np.asarray(pressure, float)
         self.nwave = len(self.wn_h)
-        self.wn = dev(self.wn_h)
         self.rank1 = [m for m in models if hasattr(m, 'rank1')]
+        cloud_models = list(cloud_models or ())
+        for m in cloud_models:
+            if not any(m is x for x in models):
+                raise ValueError('cloud_models: every entry must be one of the models')
+            if not isinstance(m, (Lecavelier, CCSgray, Deck)):
+                raise ValueError(f"cloud_models: '{getattr(m, 'name', type(m).__name__)}' cannot "
+                                 'be cloud-type (Lecavelier, CCSgray and the Deck can)')
+        # the rank-1 cloud-type models, in model order
+        self.cloud = [m for m in self.rank1 if any(m is c for c in cloud_models)]
         self.cia = [m for m in models if isinstance(m, Collision_Induced)]
         self.hminus = [m for m in models if isinstance(m, Hydrogen_Ion)]
         self.alkali = [m for m in models if isinstance(m, VanderWaals)]
@@ -348,9 +363,23 @@ class Continuum:
         if self.hminus:
             self.hm_sigma_bf = dev(self.hminus[0].sigma_bf)
             self.hm_ff = dev(self.hminus[0].ff_factors)
-        self.pressure_barye = dev(self.pressure * BAR)
         self._cs_key = None
         self._batch = []         # [(column order, BatchOperands)]
+        self._cloud_batch = []   # [(column order, CloudOperands)]
+        self._pars_key = None    # default_pars
+
+    # (uploaded on first use: the bookkeeping of a Continuum without tables needs no device)
+    @functools.cached_property
+    def wn(self):
+        return dev(self.wn_h)
+
+    @functools.cached_property
+    def pressure_barye(self):
+        return dev(self.pressure * BAR)
+
+    @functools.cached_property
+    def pressure_d(self):
+        return dev(self.pressure)
 
     def _rank1_cross_sections(self):
         """[nrank1, nwave] on the device; uploaded again only when a model's parameters
@@ -391,10 +420,38 @@ class Continuum:
         return np.array([float(p) for m in self.rank1 if isinstance(m, (Lecavelier, CCSgray))
                          for p in m.pars], float)
 
-    def batch_unsupported(self):
-        """Names of the models the batched form does not take (a cloud deck changes the optical-depth
-        integration, the alkali Voigt values are computed on the host)."""
-        return [getattr(m, 'name', type(m).__name__) for m in self.deck + self.alkali]
+    def default_pars(self):
+        """[1, npars] device tensor of current_pars(), shared by BatchOperands and CloudOperands
+        (uploaded again only when a model's parameters change)."""
+        key = tuple(self.current_pars().tolist())
+        if key != self._pars_key:
+            self._pars_d = dev(np.array(key, float)).view(1, -1)
+            self._pars_key = key
+        return self._pars_d
+
+    def is_cloud(self, model):
+        return any(model is c for c in self.cloud)
+
+    def batch_unsupported(self, deck=False):
+        """Names of the models the batched form does not take.  The alkali doublets always: their
+        Voigt values at the detuning distance are computed on the host, a batched form of them is
+        a separate piece of work.  A cloud deck unless `deck` is set: eval_bands takes one only
+        together with the walkers' deck pressures (its deck_logp argument), which put the bottom
+        of each walker's cloudy column (pb_clouds.hip)."""
+        return [getattr(m, 'name', type(m).__name__)
+                for m in ([] if deck else self.deck) + self.alkali]
+
+    def cloud_operands(self, order=None):
+        """The device-side operands of the cloud-type rank-1 models (CloudOperands), in grid order
+        or permuted to `order`; cached per order like batch_operands.  None without such models."""
+        if not self.cloud:
+            return None
+        for o, ops in self._cloud_batch:
+            if o is order:
+                return ops
+        ops = CloudOperands(self, order)
+        self._cloud_batch = [b for b in self._cloud_batch if b[0] is None] + [(order, ops)]
+        return ops
 
     def batch_operands(self, order=None):
         """The device-side operands for eval_bands (BatchOperands), in grid order or permuted to
@@ -518,9 +575,13 @@ class BatchOperands:
         species = cont.species
         st = ContBatchStruct()
         keep = []
-        st.nrank1 = len(cont.rank1)
-        offsets = cont._par_offsets()
-        for m, model in enumerate(cont.rank1):
+        # (cloud-type models are not part of ec: CloudOperands; the parameter offsets are those of
+        # the full list, the walkers' parameter rows do not change with what is cloud-type)
+        clear = [(model, off) for model, off in zip(cont.rank1, cont._par_offsets())
+                 if not cont.is_cloud(model)]
+        st.nrank1 = len(clear)
+        offsets = [off for _, off in clear]
+        for m, (model, _) in enumerate(clear):
             if isinstance(model, Kurucz):
                 st.rank1_kind[m] = 0
                 st.rank1_species[m] = species.index(model.species)
@@ -564,26 +625,8 @@ class BatchOperands:
         self._keep = keep
         self.struct = st
         self.ncs, self.npars = len(species), len(cont.free_pars)
-        self.nlec = sum(isinstance(m, Lecavelier) for m in cont.rank1)
+        self.nlec = sum(isinstance(m, Lecavelier) for m, _ in clear)
         self.cont = cont
-
-    def default_pars(self):
-        """[1, npars] device tensor of the models' current parameters (uploaded again only when
-        they change)."""
-        key = tuple(self.cont.current_pars().tolist())
-        if key != getattr(self, '_pars_key', None):
-            self._pars_d = dev(np.array(key, float)).view(1, -1)
-            self._pars_key = key
-        return self._pars_d
-
-    def default_pars(self):
-        """[1, npars] device tensor of the models' current parameters (uploaded again only when
-        they change)."""
-        key = tuple(self.cont.current_pars().tolist())
-        if key != getattr(self, '_pars_key', None):
-            self._pars_d = dev(np.array(key, float)).view(1, -1)
-            self._pars_key = key
-        return self._pars_d
 
     def args(self, density, pars):
         """The pb_cont_batch of one call: density[nw, L, ncs], pars[nw, npars] or [1, npars]."""
@@ -597,6 +640,138 @@ class BatchOperands:
         from ._capi import lib
         return int(lib().pb_interp_ec_batch_cont_work_doubles(C.byref(self.struct), nlayers,
                                                               nwave, nwalkers))
+
+
+_MAX_CLOUD = 8
+
+
+class CloudTermsStruct(C.Structure):
+    """pb_cloud_terms of include/pbhip.h."""
+    _fields_ = [
+        ('nr', C.c_int),
+        ('cs_d', C.c_void_p * _MAX_CLOUD),
+        ('cs_stride', C.c_int64 * _MAX_CLOUD),
+        ('f_d', C.c_void_p),
+    ]
+
+
+class CloudModelsStruct(C.Structure):
+    """pb_cloud_models of include/pbhip.h."""
+    _fields_ = [
+        ('nr', C.c_int),
+        ('kind', C.c_int * _MAX_CLOUD),
+        ('par', C.c_int * _MAX_CLOUD),
+        ('s0', C.c_double * _MAX_CLOUD),
+        ('l0', C.c_double * _MAX_CLOUD),
+        ('pressure_d', C.c_void_p * _MAX_CLOUD),
+    ]
+
+
+def cloud_terms(cloud_cs, cloud_f):
+    """pb_cloud_terms from explicit factors: cloud_cs[nr, W] (one row per term for all walkers) or
+    [nr, nw, W] (a row per walker), cloud_f[nw, L, nr], device tensors.  -> (struct, keep-alive)."""
+    nr = cloud_f.shape[-1]
+    if not 1 <= nr <= _MAX_CLOUD:
+        raise ValueError(f'1 ... {_MAX_CLOUD} rank-1 cloud terms, got {nr}')
+    if cloud_cs.shape[0] != nr or cloud_cs.dim() not in (2, 3) or \
+            (cloud_cs.dim() == 3 and cloud_cs.shape[1] != cloud_f.shape[0]):
+        raise ValueError(f'cloud_cs must have shape [{nr}, W] or [{nr}, {cloud_f.shape[0]}, W], '
+                         f'got {tuple(cloud_cs.shape)}')
+    cs, f = cloud_cs.contiguous(), cloud_f.contiguous()
+    st = CloudTermsStruct()
+    st.nr = nr
+    for m in range(nr):
+        st.cs_d[m] = cs[m].data_ptr()
+        st.cs_stride[m] = cs.shape[-1] if cs.dim() == 3 else 0
+    st.f_d = f.data_ptr()
+    return st, (cs, f)
+
+
+class CloudOperands:
+    """The cloud-type rank-1 models of a Continuum for pb_cloud_plan: per batch it writes their
+    factors f[nw, L, nr] and the Lecavelier rows [nlec, nw, W] (in one column order) from the
+    walkers' parameters, on the device."""
+
+    def __init__(self, cont, order=None):
+        idx = None if order is None else torch.as_tensor(order, device='cuda').to(torch.int64)
+        self.wn = cont.wn if idx is None else cont.wn.index_select(0, idx).contiguous()
+        st = CloudModelsStruct()
+        self._keep = []
+        pairs = [(model, off) for model, off in zip(cont.rank1, cont._par_offsets())
+                 if cont.is_cloud(model)]
+        if len(pairs) > _MAX_CLOUD:
+            raise ValueError(f'at most {_MAX_CLOUD} cloud-type rank-1 models')
+        st.nr = len(pairs)
+        for m, (model, off) in enumerate(pairs):
+            st.kind[m] = 1 if isinstance(model, Lecavelier) else 2
+            st.par[m] = off
+            st.s0[m] = float(model.s0)
+            st.l0[m] = float(getattr(model, 'l0', 0.0))
+            pr = dev(model.pressure)
+            self._keep.append(pr)
+            st.pressure_d[m] = pr.data_ptr()
+        self.struct = st
+        self.kinds = [st.kind[m] for m in range(st.nr)]
+        self.nr, self.nlec = st.nr, self.kinds.count(1)
+        self.npars = len(cont.free_pars)
+        self.cont = cont
+
+    def plan(self, temps, pars):
+        """temps[nw, L], pars[nw, npars] / [1, npars] / None (the models' current parameters)
+        -> (pb_cloud_terms struct, keep-alive tensors) of this batch."""
+        from ._capi import call
+        nw, nlayers = temps.shape
+        nwave = self.wn.shape[0]
+        if pars is None:
+            pars = self.cont.default_pars()
+        pars = pars.contiguous()
+        f = torch.empty((nw, nlayers, self.nr), dtype=torch.float64, device=temps.device)
+        rows = torch.empty((max(self.nlec, 1), nw, nwave), dtype=torch.float64,
+                           device=temps.device) if self.nlec else None
+        temps = temps.contiguous()
+        call('pb_cloud_plan', f.data_ptr(), None if rows is None else rows.data_ptr(),
+             C.byref(self.struct), temps.data_ptr(), pars.data_ptr(),
+             0 if pars.shape[0] == 1 else self.npars, self.wn.data_ptr(), nlayers, nwave, nw,
+             torch.cuda.current_stream().cuda_stream)
+        st = CloudTermsStruct()
+        st.nr = self.nr
+        j = 0
+        for m, kind in enumerate(self.kinds):
+            if kind == 1:
+                st.cs_d[m] = rows[j].data_ptr()
+                st.cs_stride[m] = nwave
+                j += 1
+            else:
+                st.cs_d[m] = None            # (CCSgray: a row of ones)
+                st.cs_stride[m] = 0
+        st.f_d = f.data_ptr()
+        return st, (f, rows, temps, pars)
+
+
+def deck_state(pressure, logp, radius, temps):
+    """NumPy mirror of pb_deck_state_batch: the state of an opaque deck at 10**logp[w] bar for every
+    walker, by Deck.calc_extinction_coefficient's rule (gray.py:129-150).  pressure[L] (bar),
+    logp[nw], radius[nw or 1, L], temps[nw, L] -> (itop int32[nw], rsurf[nw], tsurf[nw]).
+    rsurf / tsurf are CLAMPED to the end values when the deck lies outside the pressure grid (the
+    reference's interp1d raises there); a NaN pressure gives itop = L - 1 and NaN."""
+    pressure = np.asarray(pressure, float)
+    logp = np.atleast_1d(np.asarray(logp, float))
+    temps = np.atleast_2d(np.asarray(temps, float))
+    radius = np.atleast_2d(np.asarray(radius, float))
+    nw, nlayers = len(logp), len(pressure)
+    itop = np.empty(nw, np.int32)
+    rsurf, tsurf = np.empty(nw), np.empty(nw)
+    for w in range(nw):
+        ptop = 10**logp[w]
+        if ptop >= pressure[-1] or np.isnan(ptop):
+            itop[w] = nlayers - 1
+        elif ptop < pressure[0]:
+            itop[w] = min(1, nlayers - 1)
+        else:
+            itop[w] = int(np.where(pressure >= ptop)[0][0])
+        rsurf[w] = np.interp(ptop, pressure, radius[w if radius.shape[0] > 1 else 0])
+        tsurf[w] = np.interp(ptop, pressure, temps[w])
+    return itop, rsurf, tsurf
 
 
 def _species_of(models):

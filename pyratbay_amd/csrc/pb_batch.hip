@@ -546,12 +546,7 @@ __global__ __launch_bounds__(kBlock) void k_path_blocks(double *blocked, const d
 // of the two-kernel form went (every row of every column, then a second pass to find the exit).
 // depth and ideep are optional outputs (a retrieval needs neither).
 // ---------------------------------------------------------------------------
-__device__ inline double deck_integrand(double f_above, double f_below, double r_above,
-                                        double r_below, double rsurf)
-{
-    const double slope = (f_above - f_below) / (r_above - r_below);
-    return slope * (rsurf - r_below) + f_below;
-}
+using pb::deck_integrand;         // (pb_common.h)
 
 // kFma: tau += path*s as ONE fused multiply-add instead of the reference's product-then-sum
 // (two roundings): half the FP64 instructions, results equal to ~1e-16 relative.  Used only

@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "pb_common.h"
+#include "pb_planck.h"
 
 int pb_transit_fused_launch(double *depth_d, int32_t *ideep_d, double *spectrum_d,
                             const double *ec_d, const double *raypath_d, const double *radius_d,
@@ -180,12 +181,7 @@ __global__ __launch_bounds__(kBlock) void k_transit_tau(double *depth, const dou
 // Opaque cloud deck (radiative_transfer.py:62-66): at row deck_row = deck_itop - itop the
 // interval's far end is the cloud top: h = rsurf - radius[deck_itop-1] and the integrand is
 // the linear interpolation (scipy interp1d) of exp(-tau)*r between the two layers at rsurf.
-__device__ inline double deck_integrand(double f_above, double f_below, double r_above,
-                                        double r_below, double rsurf)
-{
-    const double slope = (f_above - f_below) / (r_above - r_below);
-    return slope * (rsurf - r_below) + f_below;
-}
+using pb::deck_integrand;         // (pb_common.h)
 
 __global__ __launch_bounds__(kBlock) void k_transit_finish(
     double *depth, int32_t *ideep, double *spectrum, const double *radius_g, double rstar,
@@ -406,38 +402,11 @@ __global__ void k_transmission(double *spectrum, const double *depth,
 // ---------------------------------------------------------------------------
 // Planck function (src_c/_blackbody.c:35-130)
 // ---------------------------------------------------------------------------
-__device__ inline double planck_factor(double wn)
-{
-    return 2 * pb::kH * pb::kLS * pb::kLS * pow(wn, 3.0);
-}
-// kt = kKB * temp and its rounded reciprocal: the same for every sample of a layer, so the
-// column kernels prepare them once per (workgroup, layer) in LDS (planck_terms) and the exponent's
-// division is pb::quot's three instructions; every kernel forms B this way (same bits)
-__device__ inline double planck_q(double factor, double wn, double kt, double inv_kt)
-{
-    return factor / (pb::exp_s(pb::quot_fast(pb::kH * pb::kLS * wn, kt, inv_kt)) - 1.0);
-}
-__device__ inline double planck(double factor, double wn, double temp)
-{
-    double kt, inv_kt;
-    pb::sane_divisor(pb::kKB * temp, kt, inv_kt);      // (T = 0 -> B = 0 like the reference)
-    return planck_q(factor, wn, kt, inv_kt);
-}
-// s_kt[0 .. 2 nlayers): kKB * temp[k] and 1 / (kKB * temp[k]) of one temperature profile, then
-// 1 / mu[m] for the nmu quadrature angles (the angles themselves stay scalar loads)
-__device__ inline void planck_terms(double *s_kt, const double *temp, int nlayers,
-                                    const double *mu = nullptr, int nmu = 0)
-{
-    // (sane_divisor: a layer at T = 0 or a ray at mu = 0 keeps pb::quot_fast finite; the results
-    // are those of the true divisions)
-    for (int k = threadIdx.x; k < nlayers; k += blockDim.x)
-        pb::sane_divisor(pb::kKB * temp[k], s_kt[k], s_kt[nlayers + k]);
-    for (int m = threadIdx.x; m < nmu; m += blockDim.x) {
-        double ms;
-        pb::sane_divisor(mu[m], ms, s_kt[2 * nlayers + m]);
-    }
-    __syncthreads();
-}
+// (pb_planck.h: shared with pb_clouds.hip)
+using pb::planck;
+using pb::planck_factor;
+using pb::planck_q;
+using pb::planck_terms;
 
 __global__ void k_blackbody2d(double *B, const double *wn, int nwave, const double *temp,
                               int nlayers, const int32_t *last)

@@ -191,6 +191,15 @@ __device__ __forceinline__ double exp_s(double x)
     return x < -1075.0 ? 0.0 : v;
 }
 
+// Transit with an opaque cloud deck (radiative_transfer.py:63-67): the integrand exp(-tau) r at the
+// deck's radius, interpolated linearly in radius between the layers above and below it.
+__device__ inline double deck_integrand(double f_above, double f_below, double r_above,
+                                        double r_below, double rsurf)
+{
+    const double slope = (f_above - f_below) / (r_above - r_below);
+    return slope * (rsurf - r_below) + f_below;
+}
+
 // The layers nobody reads of a retrieval batch with ordered columns (pb_batch.hip, above
 // k_interp_ec_batch): limits per block of 256 columns, the repair pass's gate.
 struct TileLimit {

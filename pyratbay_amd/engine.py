@@ -536,7 +536,7 @@ def interp_ec_batch(etable, ttable, temps, dens, out=None, tile_limit=None, row0
     if continuum is not None:
         ops = continuum.batch_operands() if hasattr(continuum, 'batch_operands') else continuum
         if continuum_pars is None and ops.npars:
-            continuum_pars = ops.default_pars()
+            continuum_pars = ops.cont.default_pars()
         cd = None if continuum_density is None else continuum_density.contiguous()
         cp = None if continuum_pars is None else continuum_pars.contiguous()
         if work is None:
@@ -663,6 +663,135 @@ def emission_flux_batch(ec, intervals, wn, temps, mu, weights, itop, ibottom, ma
          _ptr(temps.contiguous()), _ptr(mu), _ptr(weights), len(mu), float(maxdepth), int(itop),
          int(ibottom), nlayers, nwave, nw, _stream())
     return flux
+
+
+# --------------------------------------------------------------------------
+# Cloud deck and patchy clouds for a batch (pb_clouds.hip)
+# --------------------------------------------------------------------------
+def deck_state_batch(pressure, logp, radius, temps):
+    """The state of an opaque cloud deck at 10**logp[w] bar for every walker
+    (opacity/clouds/gray.py:129-150), on the device in one launch, nothing read back:
+    pressure[L] (bar), logp[nw], radius[nw, L] or [1, L] / [L] (shared), temps[nw, L] ->
+    (itop int32[nw], rsurf[nw], tsurf[nw]).  itop = the first layer with pressure >= the deck's
+    (L - 1 beyond the bottom of the grid, 1 above its top); rsurf / tsurf are linear in pressure
+    and CLAMPED to the end values outside the grid, as continuum.Deck does (the reference's
+    interp1d raises there).  continuum.deck_state is the NumPy mirror."""
+    nw, nlayers = temps.shape
+    rad = radius if radius.dim() == 2 else radius.view(1, -1)
+    if tuple(pressure.shape) != (nlayers,) or tuple(logp.shape) != (nw,) or \
+            rad.shape[1] != nlayers or rad.shape[0] not in (1, nw):
+        raise ValueError(f'deck_state_batch: pressure[{nlayers}], logp[{nw}], radius[{nw} or 1, '
+                         f'{nlayers}] wanted, got {tuple(pressure.shape)}, {tuple(logp.shape)}, '
+                         f'{tuple(radius.shape)}')
+    itop = torch.empty(nw, dtype=torch.int32, device=temps.device)
+    rsurf = torch.empty(nw, dtype=torch.float64, device=temps.device)
+    tsurf = torch.empty(nw, dtype=torch.float64, device=temps.device)
+    rad = rad.contiguous()
+    call('pb_deck_state_batch', _ptr(itop), _ptr(rsurf), _ptr(tsurf), _ptr(pressure.contiguous()),
+         _ptr(logp.contiguous()), _ptr(rad), 0 if rad.shape[0] == 1 else nlayers,
+         _ptr(temps.contiguous()), nlayers, nw, _stream())
+    return itop, rsurf, tsurf
+
+
+def _check_walker_tensor(name, t, nw, dtype=torch.float64):
+    """A per-walker argument of the cloud path: None, or a device tensor [nw] of `dtype` (its
+    data pointer goes to a kernel as that element type)."""
+    if t is None:
+        return
+    kind = str(dtype).replace('torch.', '')
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or \
+            tuple(t.shape) != (nw,):
+        raise ValueError(f'{name} must be a {kind} device tensor of shape {(nw,)}, got '
+                         f'{type(t).__name__} {getattr(t, "dtype", "")} '
+                         f'{tuple(getattr(t, "shape", ()))} on {getattr(t, "device", "the host")}')
+
+
+def _cloud_call_args(nw, nwave, device, deck, surf, cloud_cs, cloud_f, f_patchy, want_parts,
+                     terms, out):
+    """What cloudy_transit_batch and cloudy_emission_batch share: outputs, the deck's tensors, the
+    pb_cloud_terms struct and the tensors that must outlive the launch."""
+    import ctypes as C
+    from . import continuum as ct
+    for name, t, dtype in (('f_patchy', f_patchy, torch.float64),) + \
+            (() if deck is None else (('deck itop', deck[0], torch.int32),
+                                      ('deck surface', deck[surf], torch.float64))):
+        _check_walker_tensor(name, t, nw, dtype)
+    keep = []
+    if terms is None and cloud_cs is not None:
+        if cloud_f is None or cloud_f.dim() != 3 or cloud_f.shape[0] != nw:
+            raise ValueError('cloud_cs needs cloud_f[nw, L, nr]')
+        terms, keep = ct.cloud_terms(cloud_cs, cloud_f)
+    spectrum = out if out is not None else torch.empty((nw, nwave), dtype=torch.float64,
+                                                       device=device)
+    clear = torch.empty_like(spectrum) if want_parts else None
+    cloudy = torch.empty_like(spectrum) if want_parts else None
+    ditop = None if deck is None else deck[0].contiguous()
+    dsurf = None if deck is None else deck[surf].contiguous()
+    fp = None if f_patchy is None else f_patchy.contiguous()
+    tail = (_ptr(ditop), _ptr(dsurf), None if terms is None else C.byref(terms), _ptr(fp),
+            _stream())
+    return spectrum, clear, cloudy, tail, (keep, ditop, dsurf, fp)
+
+
+def cloudy_transit_batch(ec, raypath, radius, rstar, itop, maxdepth, deck=None, cloud_cs=None,
+                         cloud_f=None, f_patchy=None, want_parts=False, column=None, out=None,
+                         _terms=None):
+    """Transit spectra of a batch with a cloud deck and / or patchy clouds, ONE pass over
+    ec[nw, L, W] (opacity/optic_depth.py:94-121, spectrum/radiative_transfer.py:57-71,
+    pyrat/spectrum.py:350-363):
+      clear   ec over all layers from itop, no deck
+      cloudy  ec + ec_cloud down to the deck: deck = deck_state_batch()'s (itop[nw], rsurf[nw],
+              tsurf[nw]); None: down to the last layer
+      spectrum = f_patchy[w] cloudy + (1 - f_patchy[w]) clear; f_patchy None: the cloudy column
+    ec_cloud = sum_m cloud_cs[m] x cloud_f[:, :, m] is never stored: cloud_cs[nr, W] (or
+    [nr, nw, W], a row per walker), cloud_f[nw, L, nr], nr <= 8; None: no cloud opacity, the two
+    columns then share one optical-depth sum down to the deck.  f_patchy is CLAMPED to [0, 1] on
+    the device (NaN gives NaN).  raypath[nw, npath] or [1, npath] / [npath] (shared; the packed
+    triangle of transit_path_device), radius[nw, L] or [1, L] / [L].  column (int32[W]): ec's
+    columns are in that order, the spectra come in grid order (same bits).
+    -> spectrum[nw, W], or (spectrum, clear, cloudy) with want_parts."""
+    nw, nlayers, nwave = ec.shape
+    path = raypath if raypath.dim() == 2 else raypath.view(1, -1)
+    rad = radius if radius.dim() == 2 else radius.view(1, -1)
+    nrow = nlayers - int(itop)
+    if rad.shape[1] != nlayers or rad.shape[0] not in (1, nw) or path.shape[0] not in (1, nw) or \
+            path.shape[1] != (nrow * (nrow - 1)) // 2:
+        raise ValueError(f'cloudy_transit_batch: radius[{nw} or 1, {nlayers}] and raypath[{nw} or '
+                         f'1, {(nrow * (nrow - 1)) // 2}] wanted, got {tuple(radius.shape)}, '
+                         f'{tuple(raypath.shape)}')
+    spectrum, clear, cloudy, tail, keep = _cloud_call_args(
+        nw, nwave, ec.device, deck, 1, cloud_cs, cloud_f, f_patchy, want_parts, _terms, out)
+    path, rad = path.contiguous(), rad.contiguous()
+    call('pb_cloudy_transit_batch', _ptr(spectrum), _ptr(clear), _ptr(cloudy), _ptr(ec),
+         _ptr(path) if path.numel() else None, 0 if path.shape[0] == 1 else path.shape[1],
+         _ptr(rad), 0 if rad.shape[0] == 1 else nlayers, _ptr(column), float(rstar), int(itop),
+         float(maxdepth), nlayers, nwave, nw, *tail)
+    del keep
+    return (spectrum, clear, cloudy) if want_parts else spectrum
+
+
+def cloudy_emission_batch(ec, intervals, wn, temps, mu, weights, itop, maxdepth, deck=None,
+                          cloud_cs=None, cloud_f=None, f_patchy=None, want_parts=False,
+                          column=None, out=None, _terms=None):
+    """The emission counterpart of cloudy_transit_batch (opacity/optic_depth.py:123-136,
+    spectrum/radiative_transfer.py:74-139, pyrat/spectrum.py:366-385): intervals[nw, L-1],
+    temps[nw, L], wn[W] in ec's column order.  The cloudy column's deepest layer is the deck's
+    itop, which radiates at the deck's tsurf -- in the clear column too: the reference's cloudy
+    pass overwrites that row of its Planck array and its clear pass reads it (reproduced, like
+    patchy_emission_flux does)."""
+    nw, nlayers, nwave = ec.shape
+    if tuple(intervals.shape) != (nw, nlayers - 1) or tuple(temps.shape) != (nw, nlayers) or \
+            tuple(wn.shape) != (nwave,):
+        raise ValueError(f'cloudy_emission_batch: intervals[{nw}, {nlayers - 1}], temps[{nw}, '
+                         f'{nlayers}], wn[{nwave}] wanted, got {tuple(intervals.shape)}, '
+                         f'{tuple(temps.shape)}, {tuple(wn.shape)}')
+    flux, clear, cloudy, tail, keep = _cloud_call_args(
+        nw, nwave, ec.device, deck, 2, cloud_cs, cloud_f, f_patchy, want_parts, _terms, out)
+    call('pb_cloudy_emission_batch', _ptr(flux), _ptr(clear), _ptr(cloudy), _ptr(ec),
+         _ptr(intervals.contiguous()), _ptr(wn), _ptr(temps.contiguous()), _ptr(mu), _ptr(weights),
+         _ptr(column), len(mu), float(maxdepth), int(itop), nlayers, nwave, nw, *tail)
+    del keep
+    return (flux, clear, cloudy) if want_parts else flux
 
 
 # --------------------------------------------------------------------------
@@ -1761,7 +1890,8 @@ class TableSpectrum:
         return self._timer.read()
 
     def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
-                   f_dilution=None, continuum_density=None, continuum_pars=None, rv=None):
+                   f_dilution=None, continuum_density=None, continuum_pars=None, rv=None,
+                   deck_logp=None, f_patchy=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
         without the parameter mapping): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
@@ -1778,8 +1908,24 @@ class TableSpectrum:
         store of the interpolation (pb_interp_ec_batch_cont): continuum_density[nw, L, ncs] holds
         the number densities of cont.species, continuum_pars[nw, npars] the free parameters in
         cont.free_pars order (None: every walker uses the models' current pars).  A walker outside
-        a CIA table's temperatures is rejected like one outside the table.  A cloud deck and the
-        alkali models are refused in this form (ValueError); eval() takes them.
+        a CIA table's temperatures is rejected like one outside the table.  The alkali models are
+        refused in this form (ValueError; their Voigt values at the detuning distance are
+        computed on the host: a batched form is a separate piece of work), and so is a Deck
+        without deck_logp; eval() takes them.
+
+        Clouds (pb_clouds.hip; both arguments are device tensors of shape [nw]):
+        deck_logp = log10 of each walker's cloud-deck pressure in bar (needs a Deck in the
+        Continuum; the pressure grid is cont.pressure): the deck's layer, radius and temperature
+        are found on the device (deck_state_batch: clamped at the ends of the grid) and the
+        column ends there.  f_patchy = each walker's cloudy fraction: the spectrum is
+        f cloudy + (1 - f) clear, combined per sample BEFORE the band integration / the
+        instrument profile, where the cloudy column is ec + the terms of the Continuum's
+        cloud_models down to the deck (if any) and the clear column has neither.  f_patchy is
+        CLAMPED to [0, 1] on the device (no host check; NaN gives NaN).  Without f_patchy a deck
+        alone gives the cloudy column; cloud_models without f_patchy likewise.  Both columns come
+        from one kernel on the clear ec (no second ec buffer); it runs in the column order in use
+        but without its layer limits (tile_limit), whatever column_order is: the spectra do not
+        depend on it bit for bit.
 
         bands may be a HiresData instead (high-resolution spectroscopy, pyrat_obj.py:331-356):
         the spectra are convolved with the instrument profile, shifted by the walkers' radial
@@ -1799,8 +1945,21 @@ class TableSpectrum:
         nw = temps.shape[0]
         tmin, tmax = self.tmin, self.tmax
         cont = self.continuum
+        _check_walker_tensor('eval_bands: deck_logp', deck_logp, nw)
+        _check_walker_tensor('eval_bands: f_patchy', f_patchy, nw)
+        if deck_logp is not None and (cont is None or not cont.deck):
+            raise ValueError('eval_bands: deck_logp needs a Deck among the models of the '
+                             'attached Continuum')
+        # (cloud-type models alone take the cloud path too: the cloudy column is the spectrum)
+        cloudy = deck_logp is not None or f_patchy is not None or \
+            (cont is not None and bool(cont.cloud))
+        if cloudy and radius is not None and (radius.dim() != 2 or
+                                              radius.shape[1] != self.nlayers or
+                                              radius.shape[0] not in (1, nw)):
+            raise ValueError(f'eval_bands: radius must have shape ({nw} or 1, {self.nlayers}), '
+                             f'got {tuple(radius.shape)}')
         if cont is not None:
-            bad = cont.batch_unsupported()
+            bad = cont.batch_unsupported(deck=deck_logp is not None)
             if bad:
                 raise ValueError(f'eval_bands: continuum models {bad} are not supported in '
                                  'batched form (cloud deck, alkali); use eval()')
@@ -1818,6 +1977,7 @@ class TableSpectrum:
         elif continuum_density is not None or continuum_pars is not None:
             raise ValueError('eval_bands: continuum arguments without a Continuum')
         cargs = (continuum_density, continuum_pars)
+        clouds = (deck_logp, f_patchy) if cloudy else None
         out = torch.empty((nw, bands.nbands), dtype=torch.float64, device='cuda')
         if radius is None:
             radius = self.radius.view(1, -1)
@@ -1859,10 +2019,10 @@ class TableSpectrum:
             if streams > 1:
                 with torch.cuda.stream(self._eval_streams[ci % streams]):
                     self._eval_chunk(temps, dens, bands, radius, shared_radius, path1, out, w0,
-                                     min(w0 + chunk, nw), f_dilution, cargs, rv)
+                                     min(w0 + chunk, nw), f_dilution, cargs, rv, clouds)
             else:
                 self._eval_chunk(temps, dens, bands, radius, shared_radius, path1, out, w0,
-                                 min(w0 + chunk, nw), f_dilution, cargs, rv)
+                                 min(w0 + chunk, nw), f_dilution, cargs, rv, clouds)
         if streams > 1:
             for st in self._eval_streams[:streams]:
                 caller.wait_stream(st)
@@ -1893,12 +2053,16 @@ class TableSpectrum:
                                                       self.itop, self.nlayers, self.nwave)
 
     def _eval_chunk(self, temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
-                    f_dilution=None, cargs=(None, None), rv=None):
+                    f_dilution=None, cargs=(None, None), rv=None, clouds=None):
         """One chunk of eval_bands: walkers [w0, w1) through every stage, one launch each."""
         n = w1 - w0
         # (the walkers' radial velocities: HiresData only -- eval_bands has checked)
         okw = {} if rv is None else {'rv': rv[w0:w1]}
         cont = self.continuum
+        if clouds is not None:
+            self._eval_chunk_clouds(temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
+                                    f_dilution, cargs, okw, clouds)
+            return
         # (the one-pass transit takes no continuum: with one attached, the two passes)
         if self.rt_path == 'transit' and self._one_pass() and cont is None:
             # interpolation + optical depth + transmission in one pass: ec is never stored
@@ -1990,3 +2154,44 @@ class TableSpectrum:
             spectra = transit_spectrum_batch(ec, path, rad, self.rstar, self.itop, self.nlayers,
                                              self.maxdepth)
         bands.integrate_batch(spectra, out[w0:w1], **okw)
+
+    def _eval_chunk_clouds(self, temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
+                           f_dilution, cargs, okw, clouds):
+        """_eval_chunk with a cloud deck and / or patchy clouds: the interpolation writes the
+        CLEAR ec (every layer: the clear column of a patchy walker may run below any limit taken
+        from a cloud-free base model), the deck state and the cloud-type models' factors are one
+        small launch each, and one pass over ec gives f cloudy + (1 - f) clear."""
+        deck_logp, f_patchy = clouds
+        cont = self.continuum
+        ordered = self.column_order is not None and self._ordered_supported()
+        order = self.column_order if ordered else None
+        table = self.etable_ordered if ordered else self.etable
+        ckw = {}
+        if cont is not None:
+            ckw = dict(continuum=cont.batch_operands(order), continuum_density=cargs[0][w0:w1],
+                       continuum_pars=None if cargs[1] is None else cargs[1][w0:w1])
+        t = temps[w0:w1].contiguous()
+        ec = interp_ec_batch(table, self.ttable, t, dens[w0:w1], **ckw)
+        rad = radius if shared_radius else radius[w0:w1]
+        deck = None if deck_logp is None else \
+            deck_state_batch(cont.pressure_d, deck_logp[w0:w1], rad, t)
+        terms = keep = None
+        cops = None if cont is None else cont.cloud_operands(order)
+        if cops is not None:
+            terms, keep = cops.plan(t, None if cargs[1] is None else cargs[1][w0:w1])
+        fp = None if f_patchy is None else f_patchy[w0:w1]
+        if self.rt_path == 'transit':
+            path = path1 if shared_radius else transit_path_device(rad.contiguous(), self.itop)
+            spectra = cloudy_transit_batch(ec, path, rad, self.rstar, self.itop, self.maxdepth,
+                                           deck=deck, f_patchy=fp, column=order, _terms=terms)
+            bands.integrate_batch(spectra, out[w0:w1], **okw)
+        else:
+            radn = rad.expand(w1 - w0, -1)
+            intervals = (radn[:, :-1] - radn[:, 1:]).contiguous()          # -diff(radius)
+            spectra = cloudy_emission_batch(ec, intervals, self.wn_ordered if ordered else self.wn,
+                                            t, self.mu, self.weights, self.itop, self.maxdepth,
+                                            deck=deck, f_patchy=fp, column=order, _terms=terms)
+            bands.integrate_batch(spectra, out[w0:w1],
+                                  None if f_dilution is None else f_dilution[w0:w1].contiguous(),
+                                  **okw)
+        del keep
