@@ -597,9 +597,19 @@ int pb_hires_observe_batch(double *out_d, const double *spectra_d, const double 
  * (one row for all).  Every per-sample operand (rank1_cs_d, cia_tab_d rows, cia_mask_d, wn_d,
  * hm_sigma_bf_d, hm_ff_d rows) is in the column order of etable_d / ec_d.  At most
  * PB_CONT_MAX_RANK1 rank-1 models, PB_CONT_MAX_CIA tables of at most PB_CONT_MAX_CIA species,
- * one H- model. */
+ * one H- model.
+ *   Alkali resonance doublets (alkali.py:28-262, _alkali.c:58-104) after H-, nalkali models in
+ *     order, the lines of a model in order: per sample inside |wn - wn0| <= cutoff the power-law
+ *     wing voigt_det (|dwn|/dsigma)^-1.5 C3 gf/Z exp(-C2 (|dwn| - dsigma)/T) where |dwn| >=
+ *     dsigma, else the Lorentz core; the sum over a model's lines x alkali_density_d[w][l][model].
+ *     lorentz, dsigma and voigt_det are formed per (walker, layer) on the device
+ *     (pb_alkali_voigt_det_batch's arithmetic) from alkali_pressure_d[nlayers] (barye).  At most
+ *     PB_CONT_MAX_ALKALI models with PB_CONT_MAX_ALKALI_LINES lines in all; nalkali = 0: none,
+ *     the alkali fields are not read. */
 #define PB_CONT_MAX_RANK1 8
 #define PB_CONT_MAX_CIA 4
+#define PB_CONT_MAX_ALKALI 2
+#define PB_CONT_MAX_ALKALI_LINES 4
 typedef struct pb_cont_batch {
     int nrank1;
     int rank1_kind[PB_CONT_MAX_RANK1];
@@ -626,6 +636,18 @@ typedef struct pb_cont_batch {
     const double *pars_d;
     int npars;
     int pars_stride;
+    /* alkali doublets (appended: the layout above is unchanged) */
+    int nalkali;
+    int alkali_nlines[PB_CONT_MAX_ALKALI];
+    double alkali_wn0[PB_CONT_MAX_ALKALI][PB_CONT_MAX_ALKALI_LINES];
+    double alkali_gf[PB_CONT_MAX_ALKALI][PB_CONT_MAX_ALKALI_LINES];
+    double alkali_detuning[PB_CONT_MAX_ALKALI];
+    double alkali_mass[PB_CONT_MAX_ALKALI];
+    double alkali_lpar[PB_CONT_MAX_ALKALI];
+    double alkali_part_func[PB_CONT_MAX_ALKALI];
+    double alkali_cutoff[PB_CONT_MAX_ALKALI];
+    const double *alkali_pressure_d;
+    const double *alkali_density_d;
 } pb_cont_batch;
 /* Device scratch (doubles) of the two calls below: the interpolation weights, the per-(walker,
  * layer) continuum scalars and the per-walker Lecavelier rows [nlec][nwalkers][nwave]; -1 when
@@ -644,6 +666,19 @@ int pb_interp_ec_batch_cont_limited(double *ec_d, const double *etable_d, const 
                                     int nmol, int ntemp, int nlayers, int nwave, int nwalkers,
                                     const pb_cont_batch *cont, const int32_t *tile_limit_d,
                                     int row0, const int32_t *gate_d, void *stream);
+
+/* The Voigt value of every line of an alkali model at the detuning distance, for a batch of
+ * walkers (VanderWaals.voigt_det, alkali.py:48-82 -> broadening.py:231-260), one launch:
+ *   dsigma = detuning (T/500)^0.6, lorentz = lpar (T/2000)^-0.7 p/1.01e6, hwhm_G of `mass` at T
+ *   out_d[w][l][j] = Voigt(wn0[j] + dsigma): Re w(z)/(sigma sqrt(pi)), z = (dsigma + i lorentz)/sigma
+ *     where lorentz/hwhm_G < 0.1, else the four-term rational approximation.
+ * Re w(z) is the Laplace continued fraction with 6 levels: exact to 8e-15 for Re z >= 20 (the
+ * shipped models: 570 ... 1069); the caller keeps a model out whose Re z is smaller.
+ * temps_d[nwalkers][nlayers], pressure_d[nlayers] (barye), wn0_h[nlines] (host, at most
+ * PB_CONT_MAX_ALKALI_LINES). */
+int pb_alkali_voigt_det_batch(double *out_d, const double *temps_d, const double *pressure_d,
+                              double detuning, double mass, double lpar, const double *wn0_h,
+                              int nlines, int nlayers, int nwalkers, void *stream);
 
 /* The retrieval batch with clouds: an opaque deck at a per-walker pressure (opacity/clouds/
  * gray.py:95-154; pyrat_obj.py:135-139; spectrum/radiative_transfer.py:63-67, 125-127) and patchy

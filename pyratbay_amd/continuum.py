@@ -5,7 +5,8 @@ parameters -- and keeps what depends only on the spectral grid (cross sections, 
 resampled to the grid) resident in HBM.  What depends on the atmosphere is evaluated by
 ONE fused kernel (pb_continuum) plus one windowed kernel per alkali species
 (pb_alkali_cross_section), accumulating into the extinction coefficient that the
-line-by-line or table stage left on the device.
+line-by-line or table stage left on the device.  The batched form (TableSpectrum.eval_bands)
+adds every term, the alkali doublets included, in the store of the batched interpolation.
 
     models = [Kurucz(wn, 'H2'), Lecavelier(pressure, wn), Collision_Induced(path, wn=wn), ...]
     cont = Continuum(wn, pressure, models)
@@ -311,6 +312,21 @@ class VanderWaals:
             out[:, j] = np.where(lor / hg < 0.1, faddeeva, rational)
         return out
 
+    def detuning_x(self, temperature):
+        """Re z of voigt_det's Faddeeva argument, dsigma / sigma, at `temperature`: the smallest
+        over the lines.  It grows as T**0.1 (Na: 570 at 40 K, 941 at 6000 K), so its minimum over
+        a range of temperatures is at the lowest.  The device form of voigt_det
+        (pb_alkali_voigt_det_batch, eval_bands) evaluates w(z) by a continued fraction that needs
+        Re z >= BATCH_MIN_X."""
+        temperature = float(temperature)
+        dsigma = self.detuning * (temperature / 500.0)**0.6
+        hg = np.sqrt(2 * K * temperature / (self.mass * AMU)) * np.asarray(self.wn0, float) / LS
+        return float(np.min(dsigma * np.sqrt(np.log(2)) / hg))
+
+
+# the regime of the device's Faddeeva function (csrc/pb_alkali_voigt.h: kFaddeevaMinX)
+BATCH_MIN_X = 20.0
+
 
 class SodiumVdW(VanderWaals):
     def __init__(self, pressure, *, wn=None, wl=None, cutoff=4500.0):
@@ -330,7 +346,8 @@ class PotassiumVdW(VanderWaals):
 
 class Continuum:
     """All continuum terms of a run, resident on the device; add(ec, temp, density) is one
-    fused pass over ec plus one pass per alkali species."""
+    fused pass over ec plus one pass per alkali species.  The batched form
+    (TableSpectrum.eval_bands, BatchOperands) adds them all in the interpolation's store."""
 
     def __init__(self, wn, pressure, models, cloud_models=()):
         """cloud_models: the models of `models` (the same objects) that are CLOUD-type -- what the
@@ -401,6 +418,12 @@ class Continuum:
         return _species_of(self.rank1 + self.cia + self.hminus)
 
     @property
+    def alkali_species(self):
+        """The species of the [nw, L, len(alkali)] alkali density tensor of eval_bands: one per
+        alkali model, in model order (a species two models share is listed twice)."""
+        return [m.species for m in self.alkali]
+
+    @property
     def free_pars(self):
         """(model name, index) of every free parameter, models in order: Lecavelier has 2
         (log10 scale, exponent), CCSgray 3 (log10 cross section, log10 bottom / top pressure)."""
@@ -432,14 +455,32 @@ class Continuum:
     def is_cloud(self, model):
         return any(model is c for c in self.cloud)
 
-    def batch_unsupported(self, deck=False):
-        """Names of the models the batched form does not take.  The alkali doublets always: their
-        Voigt values at the detuning distance are computed on the host, a batched form of them is
-        a separate piece of work.  A cloud deck unless `deck` is set: eval_bands takes one only
-        together with the walkers' deck pressures (its deck_logp argument), which put the bottom
-        of each walker's cloudy column (pb_clouds.hip)."""
+    def batch_unsupported(self, deck=False, alkali=False):
+        """Names of the models the batched form does not take.  The alkali doublets unless
+        `alkali` is set: eval_bands takes them only together with the walkers' alkali densities
+        (its alkali_density argument), and then at most _MAX_ALKALI models with
+        _MAX_ALKALI_LINES lines in all (more: every alkali model is listed).  A cloud deck unless
+        `deck` is set: eval_bands takes one only together with the walkers' deck pressures (its
+        deck_logp argument), which put the bottom of each walker's cloudy column
+        (pb_clouds.hip)."""
+        fits = len(self.alkali) <= _MAX_ALKALI and \
+            sum(m.nlines for m in self.alkali) <= _MAX_ALKALI_LINES
         return [getattr(m, 'name', type(m).__name__)
-                for m in ([] if deck else self.deck) + self.alkali]
+                for m in ([] if deck else self.deck) + ([] if alkali and fits else self.alkali)]
+
+    def check_alkali_batch(self, tmin):
+        """The batched form's conditions on the alkali models, on the host, once per model: its
+        pressures are the Continuum's, and Re z of the Faddeeva argument at the lowest temperature
+        of the table, `tmin`, is in the regime of the device's continued fraction."""
+        for m in self.alkali:
+            if not np.array_equal(m.pressure, self.pressure):
+                raise ValueError(f"eval_bands: alkali model '{m.name}' has a pressure grid of its "
+                                 "own, not the Continuum's; use eval()")
+            x = m.detuning_x(tmin)
+            if not x >= BATCH_MIN_X:
+                raise ValueError(f"eval_bands: alkali model '{m.name}': detuning / Gaussian width "
+                                 f'= {x:.3g} at {tmin:.1f} K is below {BATCH_MIN_X:g}, outside '
+                                 "the regime of the device's Faddeeva function; use eval()")
 
     def cloud_operands(self, order=None):
         """The device-side operands of the cloud-type rank-1 models (CloudOperands), in grid order
@@ -530,6 +571,7 @@ class Continuum:
 # (pb_interp_ec_batch_cont), in the order of Continuum.add.
 # ---------------------------------------------------------------------------------------------
 _MAX_RANK1, _MAX_CIA = 8, 4
+_MAX_ALKALI, _MAX_ALKALI_LINES = 2, 4
 
 
 class ContBatchStruct(C.Structure):
@@ -560,12 +602,25 @@ class ContBatchStruct(C.Structure):
         ('pars_d', C.c_void_p),
         ('npars', C.c_int),
         ('pars_stride', C.c_int),
+        ('nalkali', C.c_int),
+        ('alkali_nlines', C.c_int * _MAX_ALKALI),
+        ('alkali_wn0', (C.c_double * _MAX_ALKALI_LINES) * _MAX_ALKALI),
+        ('alkali_gf', (C.c_double * _MAX_ALKALI_LINES) * _MAX_ALKALI),
+        ('alkali_detuning', C.c_double * _MAX_ALKALI),
+        ('alkali_mass', C.c_double * _MAX_ALKALI),
+        ('alkali_lpar', C.c_double * _MAX_ALKALI),
+        ('alkali_part_func', C.c_double * _MAX_ALKALI),
+        ('alkali_cutoff', C.c_double * _MAX_ALKALI),
+        ('alkali_pressure_d', C.c_void_p),
+        ('alkali_density_d', C.c_void_p),
     ]
 
 
 class BatchOperands:
     """The device-side operands of a Continuum for pb_interp_ec_batch_cont, every per-sample one
-    (Rayleigh cross sections, CIA rows and validity mask, H- rows, wn) in one column order."""
+    (Rayleigh cross sections, CIA rows and validity mask, H- rows, wn) in one column order.  The
+    alkali models' constants are carried along; they take part in a call that has the walkers'
+    alkali densities (args(..., alkali_density))."""
 
     def __init__(self, cont, order=None):
         idx = None if order is None else torch.as_tensor(order, device='cuda').to(torch.int64)
@@ -627,17 +682,42 @@ class BatchOperands:
         self.ncs, self.npars = len(species), len(cont.free_pars)
         self.nlec = sum(isinstance(m, Lecavelier) for m, _ in clear)
         self.cont = cont
+        # the alkali models (None: more than the batched form takes)
+        self.nalkali = None
+        if not cont.batch_unsupported(deck=True, alkali=True):
+            self.nalkali = len(cont.alkali)
+            for m, model in enumerate(cont.alkali):
+                st.alkali_nlines[m] = model.nlines
+                for j in range(model.nlines):
+                    st.alkali_wn0[m][j] = float(model.wn0[j])
+                    st.alkali_gf[m][j] = float(model.gf[j])
+                st.alkali_detuning[m] = float(model.detuning)
+                st.alkali_mass[m] = float(model.mass)
+                st.alkali_lpar[m] = float(model.lpar)
+                st.alkali_part_func[m] = float(model.Z)
+                st.alkali_cutoff[m] = float(model.cutoff)
+            if self.nalkali:
+                st.alkali_pressure_d = cont.pressure_barye.data_ptr()
 
-    def args(self, density, pars):
-        """The pb_cont_batch of one call: density[nw, L, ncs], pars[nw, npars] or [1, npars]."""
+    def args(self, density, pars, alkali_density=None):
+        """The pb_cont_batch of one call: density[nw, L, ncs], pars[nw, npars] or [1, npars],
+        alkali_density[nw, L, nalkali] or None (the alkali models add nothing)."""
         st = self.struct
         st.density_d = density.data_ptr() if density is not None else None
         st.pars_d = pars.data_ptr() if pars is not None else None
         st.pars_stride = 0 if pars is None or pars.shape[0] == 1 else self.npars
+        if alkali_density is not None and not self.nalkali:
+            raise ValueError('alkali_density: the Continuum has no alkali model, or more than '
+                             f'{_MAX_ALKALI} models / {_MAX_ALKALI_LINES} lines in all')
+        st.nalkali = self.nalkali if alkali_density is not None else 0
+        st.alkali_density_d = alkali_density.data_ptr() if alkali_density is not None else None
         return C.byref(st)
 
     def work_doubles(self, nlayers, nwave, nwalkers):
+        """Scratch of a call, in doubles (with room for the alkali records whether or not the
+        call has alkali densities: args() decides that per call)."""
         from ._capi import lib
+        self.struct.nalkali = self.nalkali or 0
         return int(lib().pb_interp_ec_batch_cont_work_doubles(C.byref(self.struct), nlayers,
                                                               nwave, nwalkers))
 

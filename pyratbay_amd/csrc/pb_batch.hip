@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "pb_common.h"
+#include "pb_alkali_voigt.h"
 
 namespace {
 
@@ -118,9 +119,23 @@ using pb::layer_wanted;
 // pb_interp_ec_batch followed by pb_continuum bit for bit for Rayleigh, CIA and H- (the
 // Lecavelier / gray 10^x and pow run on the device, not in NumPy: within an ulp or two).
 // kCont = 0: no continuum (the kernels compile to what they were); 1: continuum; 2: with H-.
+//
+// Alkali resonance doublets (kAlk, after H-: models in order, lines in order -- Continuum.add's
+// pb_alkali_cross_section calls).  What made them a host job, the Voigt value at the detuning
+// distance, is formed by k_cont_plan per (walker, layer, line) (pb_alkali_voigt.h: Re w(z) by a
+// continued fraction, valid for Re z >= 20, which the caller guarantees).  Per line the record
+// holds dsigma, lorentz^2, -C2/T, the wing prefactor voigt_det C3 gf/Z dsigma^1.5 exp(C2 dsigma/T),
+// the core prefactor lorentz/pi C3 gf/Z and the species density; a thread keeps |wn - wn0|,
+// |wn - wn0|^-1.5 and the inside-cutoff bit of its sample across the walker loop.  Per (walker,
+// layer, sample, line) that leaves one exp (wing) or one division (core), no pow; k_alkali's
+// branches exactly (_alkali.c:74-100), its values to rounding (the factors are grouped
+// differently: a few ulp).  kAlk = false: the kernels compile to what they were.
 // ---------------------------------------------------------------------------
 constexpr int kCbRank1 = PB_CONT_MAX_RANK1;
 constexpr int kCbCia = PB_CONT_MAX_CIA;
+constexpr int kCbAlk = PB_CONT_MAX_ALKALI;
+constexpr int kCbAlkLines = PB_CONT_MAX_ALKALI_LINES;
+constexpr int kCbAlkRec = 6;       // doubles per (walker, layer, line)
 constexpr int kCbRank1Reg = 4;     // Rayleigh cross sections kept in registers (more: re-read)
 constexpr double kCbBar = 1e6;
 constexpr double kCbK = 1.380649e-16, kCbH = 6.62607015e-27, kCbC = 29979245800.0;
@@ -134,22 +149,50 @@ struct ContEpi {
     const uint8_t *cia_mask;         // [nwave]
     const double *wn, *hm_sigma_bf, *hm_ff;
     const double *rec;               // [nwalkers * nlayers][nrec], written by k_cont_plan
+    // alkali (kAlk): every model's lines in one list
+    int alk_nl, alk_off;             // lines in all; where their records start in a rec row
+    unsigned alk_end;                // bit j: line j is the last of its model
+    double alk_wn0[kCbAlkLines], alk_cutoff[kCbAlkLines];
+};
+
+template <bool kAlk>
+struct AlkState {};
+template <>
+struct AlkState<true> {
+    double adwn[kCbAlkLines];        // |wn - wn0|
+    double pw[kCbAlkLines];          // |wn - wn0|^-1.5
+    unsigned in;                     // bit j: inside line j's cutoff
 };
 
 // the operands of a thread's sample that do not depend on the walker, kept across the walker loop
-template <int kCont>
+template <int kCont, bool kAlk = false>
 struct ContState {
     double cs[kCbRank1Reg];
     unsigned mask;
     int cidx[kCbCia];                // wave-uniform: the CIA bracket whose rows are held
     double y0[kCbCia], sl[kCbCia];
     double wn, sig, ff[6];           // (kCont == 2)
+    AlkState<kAlk> alk;
 };
 
-template <int kCont>
-__device__ __forceinline__ void cont_init(ContState<kCont> &st, const ContEpi &a, int col,
+template <int kCont, bool kAlk>
+__device__ __forceinline__ void cont_init(ContState<kCont, kAlk> &st, const ContEpi &a, int col,
                                           int nwave)
 {
+    if constexpr (kAlk) {
+        const double wn = a.wn[col];
+        st.alk.in = 0u;
+#pragma unroll
+        for (int j = 0; j < kCbAlkLines; j++) {
+            const double dwn = j < a.alk_nl ? wn - a.alk_wn0[j] : 0.0;
+            const double ad = fabs(dwn);
+            st.alk.adwn[j] = ad;
+            st.alk.pw[j] = 1.0 / (ad * sqrt(ad));
+            // (_alkali.c:83: a sample beyond the cutoff on either side is skipped)
+            if (j < a.alk_nl && !(dwn < -a.alk_cutoff[j] || dwn > a.alk_cutoff[j]))
+                st.alk.in |= 1u << j;
+        }
+    }
 #pragma unroll
     for (int m = 0; m < kCbRank1Reg; m++)
         st.cs[m] = m < a.nrank1 && a.kind[m] == 0 ? a.row[m][col] : 0.0;
@@ -167,9 +210,10 @@ __device__ __forceinline__ void cont_init(ContState<kCont> &st, const ContEpi &a
 }
 
 // acc (the interpolated value of walker w, sample col) + every term, in Continuum.add's order
-template <int kCont>
-__device__ __forceinline__ double cont_apply(double acc, ContState<kCont> &st, const ContEpi &a,
-                                             int col, int w, int64_t wk, int nwave)
+template <int kCont, bool kAlk>
+__device__ __forceinline__ double cont_apply(double acc, ContState<kCont, kAlk> &st,
+                                             const ContEpi &a, int col, int w, int64_t wk,
+                                             int nwave)
 {
     typedef const double __attribute__((address_space(4))) *crec_t;
     const crec_t r = (crec_t)(unsigned long long)(a.rec + wk * a.nrec);
@@ -223,6 +267,30 @@ __device__ __forceinline__ double cont_apply(double acc, ContState<kCont> &st, c
         ff *= ffpost;
         acc += (bf + ff) * hf;
     }
+    if constexpr (kAlk) {
+        // per line: dsigma, lorentz^2, -C2/T, wing prefactor, core prefactor, density
+        const crec_t ra = r + a.alk_off;
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j < kCbAlkLines; j++) {
+            if (j >= a.alk_nl)
+                break;
+            const crec_t q = ra + kCbAlkRec * j;
+            if (st.alk.in >> j & 1u) {
+                const double d = st.alk.adwn[j];
+                if (d >= q[0])
+                    sum += q[3] * st.alk.pw[j] * exp(q[2] * d);
+                else
+                    sum += q[4] / (q[1] + d * d);
+            }
+            if (a.alk_end >> j & 1u) {
+                // (k_alkali: ec += acc * density, only where a line contributed)
+                if (sum != 0.0)
+                    acc += sum * q[5];
+                sum = 0.0;
+            }
+        }
+    }
     return acc;
 }
 
@@ -232,10 +300,12 @@ struct ContPlanArgs {
     int nlayers, ncs, pars_stride, nrec;
     int64_t n;
     pb_cont_batch c;
+    int alk_off;
 };
 
 // per (walker, layer): the scalars the epilogue reads (layout: rank-1 factors | per CIA table
-// bracket, dt, node gap, density product | H- beta[6], bf prefactor, ff postfactor, T, n_H n_e)
+// bracket, dt, node gap, density product | H- beta[6], bf prefactor, ff postfactor, T, n_H n_e |
+// per alkali line dsigma, lorentz^2, -C2/T, wing prefactor, core prefactor, species density)
 __global__ __launch_bounds__(kBlock) void k_cont_plan(ContPlanArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -295,6 +365,24 @@ __global__ __launch_bounds__(kBlock) void k_cont_plan(ContPlanArgs a)
         rh[8] = t;
         rh[9] = d[a.c.hm_species[0]] * d[a.c.hm_species[1]];
     }
+    double *ra = r + a.alk_off;
+    for (int m = 0; m < a.c.nalkali; m++) {
+        const double kC2 = 1.4387768775039338, kC3 = 8.852821681767784e-13;    // _alkali.c
+        const pb::AlkaliLayer al = pb::alkali_layer(t, a.c.alkali_pressure_d[l],
+                                                    a.c.alkali_detuning[m], a.c.alkali_lpar[m]);
+        const double dens = a.c.alkali_density_d[i * a.c.nalkali + m];
+        const double wing = al.dsigma * sqrt(al.dsigma) * exp(kC2 * al.dsigma / t);
+        for (int j = 0; j < a.c.alkali_nlines[m]; j++, ra += kCbAlkRec) {
+            const double vd = pb::alkali_voigt_det(t, al, a.c.alkali_mass[m], a.c.alkali_wn0[m][j]);
+            const double g = kC3 * a.c.alkali_gf[m][j] / a.c.alkali_part_func[m];
+            ra[0] = al.dsigma;
+            ra[1] = al.lorentz * al.lorentz;
+            ra[2] = -kC2 / t;
+            ra[3] = vd * g * wing;
+            ra[4] = al.lorentz / pb::kPi * g;
+            ra[5] = dens;
+        }
+    }
 }
 
 struct ContRowsArgs {
@@ -352,7 +440,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_weights(
 
 // kFull: nmol == kS, no per-species predicate (the coefficient loads of a walker then merge into
 // one scalar load and one wait)
-template <int kS, bool kFull, int kCont = 0>
+template <int kS, bool kFull, int kCont = 0, bool kAlk = false>
 __global__ __launch_bounds__(kBlock) void k_interp_ec_batch(
     double *ec, const double *etable, const int32_t *tlo, const double *coef, int nmol,
     int ntemp, int nlayers, int nwave, int nwalkers, int chunk, TileLimit lim, ContEpi cont = {})
@@ -382,7 +470,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_ec_batch(
 #pragma unroll
     for (int j = 0; j < kS; j++)
         hi[j] = kFull || j < nmol ? tab[((int64_t)j * ntemp + bmin) * slice] : 0.0;
-    ContState<kCont> cst;
+    ContState<kCont, kAlk> cst;
     if constexpr (kCont != 0)
         cont_init(cst, cont, i, nwave);
     for (int b = bmin; b <= bmax; b++) {
@@ -2181,13 +2269,36 @@ int pb_iso_partition(double *z_d, int64_t z_iso_stride, int64_t z_t_stride,
     return PB_OK;
 }
 
+// the alkali models' lines in all, or -1 if the counts are invalid
+static int cont_alkali_lines(const pb_cont_batch *c)
+{
+    if (c->nalkali < 0 || c->nalkali > kCbAlk)
+        return -1;
+    int nl = 0;
+    for (int m = 0; m < c->nalkali; m++) {
+        if (c->alkali_nlines[m] < 1 || c->alkali_nlines[m] > kCbAlkLines)
+            return -1;
+        nl += c->alkali_nlines[m];
+    }
+    return nl <= kCbAlkLines ? nl : -1;
+}
+
+// where the alkali lines' records start in a (walker, layer) record
+static int cont_alkali_offset(const pb_cont_batch *c)
+{
+    return c->nrank1 + 4 * c->ncia + 10 * c->hminus;
+}
+
 // the continuum's per-(walker, layer) record length (ContEpi::nrec), or -1 if `c` is invalid
 static int cont_nrec(const pb_cont_batch *c)
 {
     if (!c || c->nrank1 < 0 || c->nrank1 > kCbRank1 || c->ncia < 0 || c->ncia > kCbCia ||
         c->hminus < 0 || c->hminus > 1)
         return -1;
-    return c->nrank1 + 4 * c->ncia + 10 * c->hminus;
+    const int nl = cont_alkali_lines(c);
+    if (nl < 0)
+        return -1;
+    return cont_alkali_offset(c) + kCbAlkRec * nl;
 }
 
 static int cont_nlec(const pb_cont_batch *c)
@@ -2254,7 +2365,30 @@ static int cont_check(const pb_cont_batch *c)
             PB_REQUIRE(c->hm_species[j] >= 0 && c->hm_species[j] < c->ncs,
                        "pb_interp_ec_batch_cont: H- species %d of %d", c->hm_species[j], c->ncs);
     }
-    PB_REQUIRE(!(c->hminus || cont_nlec(c)) || c->wn_d, "pb_interp_ec_batch_cont: null wn");
+    PB_REQUIRE(c->nalkali >= 0 && c->nalkali <= kCbAlk,
+               "pb_interp_ec_batch_cont: at most %d alkali models, not %d", kCbAlk, c->nalkali);
+    int nlines = 0;
+    for (int m = 0; m < c->nalkali; m++) {
+        PB_REQUIRE(c->alkali_nlines[m] >= 1 && c->alkali_nlines[m] <= kCbAlkLines,
+                   "pb_interp_ec_batch_cont: alkali model %d: 1-%d lines, not %d", m, kCbAlkLines,
+                   c->alkali_nlines[m]);
+        nlines += c->alkali_nlines[m];
+        PB_REQUIRE(c->alkali_cutoff[m] > 0.0,
+                   "pb_interp_ec_batch_cont: alkali model %d: cutoff %g (must be positive)", m,
+                   c->alkali_cutoff[m]);
+        PB_REQUIRE(c->alkali_part_func[m] > 0.0 && c->alkali_mass[m] > 0.0,
+                   "pb_interp_ec_batch_cont: alkali model %d: partition function %g, mass %g", m,
+                   c->alkali_part_func[m], c->alkali_mass[m]);
+    }
+    PB_REQUIRE(nlines <= kCbAlkLines,
+               "pb_interp_ec_batch_cont: at most %d alkali lines in all, not %d", kCbAlkLines,
+               nlines);
+    if (c->nalkali) {
+        PB_REQUIRE(c->alkali_pressure_d, "pb_interp_ec_batch_cont: null alkali pressure");
+        PB_REQUIRE(c->alkali_density_d, "pb_interp_ec_batch_cont: null alkali density");
+    }
+    PB_REQUIRE(!(c->hminus || cont_nlec(c) || c->nalkali) || c->wn_d,
+               "pb_interp_ec_batch_cont: null wn");
     PB_REQUIRE(!need_dens || c->density_d, "pb_interp_ec_batch_cont: null continuum density");
     PB_REQUIRE(!need_pars || c->pars_d, "pb_interp_ec_batch_cont: null continuum parameters");
     return PB_OK;
@@ -2352,6 +2486,7 @@ static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const do
     // (in the same workspace: a gated repair reuses them too)
     ContEpi epi{};
     int kcont = 0;
+    bool kalk = false;
     if (cont) {
         const int nrec = cont_nrec(cont);
         double *rec = reinterpret_cast<double *>(work_d) + cont_rec_offset(n);
@@ -2370,6 +2505,7 @@ static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const do
                 pa.nrec = nrec;
                 pa.n = n;
                 pa.c = *cont;
+                pa.alk_off = cont_alkali_offset(cont);
                 k_cont_plan<<<pb::div_up(n, kBlock), kBlock, 0, s>>>(pa);
                 PB_LAUNCH_CHECK();
             }
@@ -2410,7 +2546,16 @@ static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const do
         epi.hm_sigma_bf = cont->hm_sigma_bf_d;
         epi.hm_ff = cont->hm_ff_d;
         epi.rec = rec;
+        epi.alk_off = cont_alkali_offset(cont);
+        for (int m = 0; m < cont->nalkali; m++)
+            for (int j = 0; j < cont->alkali_nlines[m]; j++, epi.alk_nl++) {
+                epi.alk_wn0[epi.alk_nl] = cont->alkali_wn0[m][j];
+                epi.alk_cutoff[epi.alk_nl] = cont->alkali_cutoff[m];
+                if (j == cont->alkali_nlines[m] - 1)
+                    epi.alk_end |= 1u << epi.alk_nl;
+            }
         kcont = cont->hminus ? 2 : 1;
+        kalk = cont->nalkali > 0;
     }
     // walkers per chunk: every chunk reads the table slices its walkers bracket again, so as many
     // as the launch can afford while it still fills the chip (C5, 64 walkers: 1.40 ms in chunks
@@ -2440,8 +2585,14 @@ static int interp_ec_batch_launch(double *ec_d, const double *etable_d, const do
     if (pairs && !kcont)
         grid.x = pb::div_up(nwave / 2 + 2, kBlock * np);
 #define PB_INTERP_CONT(S, FULL, K)                                                             \
-    k_interp_ec_batch<S, FULL, K><<<grid, kBlock, 0, s>>>(ec_d, etable_d, tlo, coef, nmol, ntemp, \
-                                                          nlayers, nwave, nwalkers, chunk, lim, epi)
+    do {                                                                                       \
+        if (kalk)                                                                              \
+            k_interp_ec_batch<S, FULL, K, true><<<grid, kBlock, 0, s>>>(                       \
+                ec_d, etable_d, tlo, coef, nmol, ntemp, nlayers, nwave, nwalkers, chunk, lim, epi); \
+        else                                                                                   \
+            k_interp_ec_batch<S, FULL, K><<<grid, kBlock, 0, s>>>(                             \
+                ec_d, etable_d, tlo, coef, nmol, ntemp, nlayers, nwave, nwalkers, chunk, lim, epi); \
+    } while (0)
 #define PB_INTERP(S, FULL)                                                                     \
     do {                                                                                       \
         if (kcont == 1)                                                                        \

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "pb_common.h"
+#include "pb_alkali_voigt.h"
 #include "pbhip.h"
 
 namespace {
@@ -204,6 +205,27 @@ __global__ __launch_bounds__(kBlock) void k_alkali(AlkaliArgs a)
     }
 }
 
+struct VoigtDetArgs {
+    double *out;
+    const double *temps, *pressure;
+    double detuning, mass, lpar;
+    double wn0[PB_CONT_MAX_ALKALI_LINES];
+    int nlines, nlayers;
+    int64_t n;
+};
+
+// VanderWaals.voigt_det for a batch: thread = (walker, layer), its lines in order
+__global__ __launch_bounds__(kBlock) void k_alkali_voigt_det(VoigtDetArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n)
+        return;
+    const double t = a.temps[i];
+    const pb::AlkaliLayer al = pb::alkali_layer(t, a.pressure[i % a.nlayers], a.detuning, a.lpar);
+    for (int j = 0; j < a.nlines; j++)
+        a.out[i * a.nlines + j] = pb::alkali_voigt_det(t, al, a.mass, a.wn0[j]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -290,6 +312,35 @@ int pb_alkali_cross_section(double *ec_d, const double *pressure_d, const double
     a.nwave = nwave;
     dim3 grid((unsigned)pb::div_up(nwave, kBlock), (unsigned)nlayers);
     k_alkali<<<grid, kBlock, 0, pb::as_stream(stream)>>>(a);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+int pb_alkali_voigt_det_batch(double *out_d, const double *temps_d, const double *pressure_d,
+                              double detuning, double mass, double lpar, const double *wn0_h,
+                              int nlines, int nlayers, int nwalkers, void *stream)
+{
+    PB_REQUIRE(nlayers >= 0 && nwalkers >= 0, "pb_alkali_voigt_det_batch: bad shape");
+    PB_REQUIRE(nlines >= 0 && nlines <= PB_CONT_MAX_ALKALI_LINES,
+               "pb_alkali_voigt_det_batch: at most %d lines, not %d", PB_CONT_MAX_ALKALI_LINES,
+               nlines);
+    if (nlayers == 0 || nwalkers == 0 || nlines == 0)
+        return PB_OK;
+    PB_REQUIRE(out_d && temps_d && pressure_d && wn0_h, "pb_alkali_voigt_det_batch: null pointer");
+    PB_REQUIRE(mass > 0.0, "pb_alkali_voigt_det_batch: mass %g (must be positive)", mass);
+    VoigtDetArgs a{};
+    a.out = out_d;
+    a.temps = temps_d;
+    a.pressure = pressure_d;
+    a.detuning = detuning;
+    a.mass = mass;
+    a.lpar = lpar;
+    for (int j = 0; j < nlines; j++)
+        a.wn0[j] = wn0_h[j];
+    a.nlines = nlines;
+    a.nlayers = nlayers;
+    a.n = (int64_t)nwalkers * nlayers;
+    k_alkali_voigt_det<<<(unsigned)pb::div_up(a.n, kBlock), kBlock, 0, pb::as_stream(stream)>>>(a);
     PB_LAUNCH_CHECK();
     return PB_OK;
 }

@@ -518,7 +518,8 @@ def transit_path_device(radius, itop=0):
 
 
 def interp_ec_batch(etable, ttable, temps, dens, out=None, tile_limit=None, row0=0, gate=None,
-                    work=None, continuum=None, continuum_density=None, continuum_pars=None):
+                    work=None, continuum=None, continuum_density=None, continuum_pars=None,
+                    alkali_density=None):
     """interp_ec for a batch of walkers (assigning): temps[nw, L], dens[nw, L, S] ->
     ec[nw, L, W]; the table is read once per chunk of walkers.  tile_limit (int32[ceil(W/256)],
     device) / row0: only the layers a block of 256 columns can need are written
@@ -527,7 +528,11 @@ def interp_ec_batch(etable, ttable, temps, dens, out=None, tile_limit=None, row0
     continuum: a continuum.Continuum (grid order) or its batch_operands(order) (the table's column
     order): its terms are added to every sample before it is stored (pb_interp_ec_batch_cont),
     with continuum_density[nw, L, len(continuum.species)] and continuum_pars[nw, npars] (None:
-    the models' current parameters) as device tensors."""
+    the models' current parameters) as device tensors.  alkali_density[nw, L,
+    len(continuum.alkali)] (device; the densities of continuum.alkali_species): the alkali
+    doublets are added too, their Voigt values at the detuning distance formed on the device
+    (valid while VanderWaals.detuning_x(T) >= continuum.BATCH_MIN_X: the caller's check, see
+    Continuum.check_alkali_batch); None: the alkali models add nothing."""
     nmol, ntemp, nlayers, nwave = etable.shape
     nw = temps.shape[0]
     assert temps.shape == (nw, nlayers) and dens.shape == (nw, nlayers, nmol)
@@ -539,10 +544,11 @@ def interp_ec_batch(etable, ttable, temps, dens, out=None, tile_limit=None, row0
             continuum_pars = ops.cont.default_pars()
         cd = None if continuum_density is None else continuum_density.contiguous()
         cp = None if continuum_pars is None else continuum_pars.contiguous()
+        ad = None if alkali_density is None else alkali_density.contiguous()
         if work is None:
             work = torch.empty(ops.work_doubles(nlayers, nwave, nw), dtype=torch.float64,
                                device=etable.device)
-        args = ops.args(cd, cp)
+        args = ops.args(cd, cp, ad)
         if tile_limit is None and gate is None:
             call('pb_interp_ec_batch_cont', _ptr(out), _ptr(etable), _ptr(ttable),
                  _ptr(temps.contiguous()), _ptr(dens.contiguous()), _ptr(work), nmol, ntemp,
@@ -668,6 +674,23 @@ def emission_flux_batch(ec, intervals, wn, temps, mu, weights, itop, ibottom, ma
 # --------------------------------------------------------------------------
 # Cloud deck and patchy clouds for a batch (pb_clouds.hip)
 # --------------------------------------------------------------------------
+def alkali_voigt_det_batch(model, temps, pressure_barye=None):
+    """VanderWaals.voigt_det for a batch of walkers on the device (pb_alkali_voigt_det_batch):
+    temps[nw, L] (device) -> [nw, L, model.nlines].  pressure_barye[L] (device; None: the
+    model's pressures).  The device's Faddeeva function needs model.detuning_x(T) >=
+    continuum.BATCH_MIN_X at every temperature (it grows with T): not checked here."""
+    nw, nlayers = temps.shape
+    if pressure_barye is None:
+        pressure_barye = dev(np.asarray(model.pressure, float) * 1e6)
+    assert pressure_barye.shape == (nlayers,)
+    out = torch.empty((nw, nlayers, model.nlines), dtype=torch.float64, device=temps.device)
+    wn0 = np.ascontiguousarray(model.wn0, float)
+    call('pb_alkali_voigt_det_batch', _ptr(out), _ptr(temps.contiguous()),
+         _ptr(pressure_barye.contiguous()), float(model.detuning), float(model.mass),
+         float(model.lpar), _capi.hptr(wn0), model.nlines, nlayers, nw, _stream())
+    return out
+
+
 def deck_state_batch(pressure, logp, radius, temps):
     """The state of an opaque cloud deck at 10**logp[w] bar for every walker
     (opacity/clouds/gray.py:129-150), on the device in one launch, nothing read back:
@@ -693,15 +716,16 @@ def deck_state_batch(pressure, logp, radius, temps):
     return itop, rsurf, tsurf
 
 
-def _check_walker_tensor(name, t, nw, dtype=torch.float64):
-    """A per-walker argument of the cloud path: None, or a device tensor [nw] of `dtype` (its
-    data pointer goes to a kernel as that element type)."""
+def _check_walker_tensor(name, t, nw, dtype=torch.float64, shape=None):
+    """A per-walker argument of eval_bands: None, or a device tensor [nw] (or of `shape`) of
+    `dtype` (its data pointer goes to a kernel as that element type)."""
     if t is None:
         return
     kind = str(dtype).replace('torch.', '')
+    shape = (nw,) if shape is None else tuple(shape)
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or \
-            tuple(t.shape) != (nw,):
-        raise ValueError(f'{name} must be a {kind} device tensor of shape {(nw,)}, got '
+            tuple(t.shape) != shape:
+        raise ValueError(f'{name} must be a {kind} device tensor of shape {shape}, got '
                          f'{type(t).__name__} {getattr(t, "dtype", "")} '
                          f'{tuple(getattr(t, "shape", ()))} on {getattr(t, "device", "the host")}')
 
@@ -1745,6 +1769,7 @@ class TableSpectrum:
         else:
             self._pending_order = None
         self.continuum = continuum          # pyratbay_amd.continuum.Continuum or None
+        self._alkali_checked = None         # the Continuum whose alkali models eval_bands has checked
         self.etable = etable if isinstance(etable, torch.Tensor) else dev(etable)
         self.nspec, self.ntemp, self.nlayers, self.nwave = self.etable.shape
         self.ttable = dev(ttable)
@@ -1891,7 +1916,7 @@ class TableSpectrum:
 
     def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
                    f_dilution=None, continuum_density=None, continuum_pars=None, rv=None,
-                   deck_logp=None, f_patchy=None):
+                   deck_logp=None, f_patchy=None, alkali_density=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
         without the parameter mapping): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
@@ -1908,10 +1933,15 @@ class TableSpectrum:
         store of the interpolation (pb_interp_ec_batch_cont): continuum_density[nw, L, ncs] holds
         the number densities of cont.species, continuum_pars[nw, npars] the free parameters in
         cont.free_pars order (None: every walker uses the models' current pars).  A walker outside
-        a CIA table's temperatures is rejected like one outside the table.  The alkali models are
-        refused in this form (ValueError; their Voigt values at the detuning distance are
-        computed on the host: a batched form is a separate piece of work), and so is a Deck
-        without deck_logp; eval() takes them.
+        a CIA table's temperatures is rejected like one outside the table.  Alkali doublets
+        (SodiumVdW, PotassiumVdW) take alkali_density[nw, L, len(cont.alkali)], the number
+        densities of cont.alkali_species in model order (a float64 device tensor): their terms are
+        added in the same store, the Voigt values at the detuning distance formed per walker and
+        layer on the device.  At most 2 alkali models with 4 lines in all; a model whose detuning
+        distance is less than 20 Gaussian widths at the table's lowest temperature (no shipped
+        model: 570 and more) is outside the regime of the device's Faddeeva function.  Both are
+        refused (ValueError), as are alkali models without alkali_density and a Deck without
+        deck_logp; eval() takes them.
 
         Clouds (pb_clouds.hip; both arguments are device tensors of shape [nw]):
         deck_logp = log10 of each walker's cloud-deck pressure in bar (needs a Deck in the
@@ -1959,7 +1989,24 @@ class TableSpectrum:
             raise ValueError(f'eval_bands: radius must have shape ({nw} or 1, {self.nlayers}), '
                              f'got {tuple(radius.shape)}')
         if cont is not None:
-            bad = cont.batch_unsupported(deck=deck_logp is not None)
+            if alkali_density is not None:
+                if not cont.alkali:
+                    raise ValueError('eval_bands: alkali_density needs an alkali model '
+                                     '(SodiumVdW, PotassiumVdW) among the models of the '
+                                     'attached Continuum')
+                if cont.batch_unsupported(deck=True, alkali=True):
+                    raise ValueError(
+                        f'eval_bands: {len(cont.alkali)} alkali models with '
+                        f'{sum(m.nlines for m in cont.alkali)} lines: the batched form takes at '
+                        'most 2 models with 4 lines in all; use eval()')
+                _check_walker_tensor(f'eval_bands: alkali_density (species '
+                                     f'{cont.alkali_species})', alkali_density, nw,
+                                     shape=(nw, self.nlayers, len(cont.alkali)))
+                if self._alkali_checked is not cont:
+                    cont.check_alkali_batch(self.tmin)       # (once per model: host arithmetic)
+                    self._alkali_checked = cont
+            bad = cont.batch_unsupported(deck=deck_logp is not None,
+                                         alkali=alkali_density is not None)
             if bad:
                 raise ValueError(f'eval_bands: continuum models {bad} are not supported in '
                                  'batched form (cloud deck, alkali); use eval()')
@@ -1976,7 +2023,10 @@ class TableSpectrum:
                 tmin, tmax = max(tmin, float(m.tmin)), min(tmax, float(m.tmax))
         elif continuum_density is not None or continuum_pars is not None:
             raise ValueError('eval_bands: continuum arguments without a Continuum')
-        cargs = (continuum_density, continuum_pars)
+        elif alkali_density is not None:
+            raise ValueError('eval_bands: alkali_density without a Continuum that has an alkali '
+                             'model')
+        cargs = (continuum_density, continuum_pars, alkali_density)
         clouds = (deck_logp, f_patchy) if cloudy else None
         out = torch.empty((nw, bands.nbands), dtype=torch.float64, device='cuda')
         if radius is None:
@@ -2053,7 +2103,7 @@ class TableSpectrum:
                                                       self.itop, self.nlayers, self.nwave)
 
     def _eval_chunk(self, temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
-                    f_dilution=None, cargs=(None, None), rv=None, clouds=None):
+                    f_dilution=None, cargs=(None, None, None), rv=None, clouds=None):
         """One chunk of eval_bands: walkers [w0, w1) through every stage, one launch each."""
         n = w1 - w0
         # (the walkers' radial velocities: HiresData only -- eval_bands has checked)
@@ -2087,7 +2137,8 @@ class TableSpectrum:
         if cont is not None:
             ckw = dict(continuum=cont.batch_operands(self.column_order if ordered else None),
                        continuum_density=cargs[0][w0:w1],
-                       continuum_pars=None if cargs[1] is None else cargs[1][w0:w1])
+                       continuum_pars=None if cargs[1] is None else cargs[1][w0:w1],
+                       alkali_density=None if cargs[2] is None else cargs[2][w0:w1])
         if limited:
             # (ec keeps whatever an earlier batch left in the layers that are not written: they are
             # read by no one, or the walker is flagged and repaired)
@@ -2169,7 +2220,8 @@ class TableSpectrum:
         ckw = {}
         if cont is not None:
             ckw = dict(continuum=cont.batch_operands(order), continuum_density=cargs[0][w0:w1],
-                       continuum_pars=None if cargs[1] is None else cargs[1][w0:w1])
+                       continuum_pars=None if cargs[1] is None else cargs[1][w0:w1],
+                       alkali_density=None if cargs[2] is None else cargs[2][w0:w1])
         t = temps[w0:w1].contiguous()
         ec = interp_ec_batch(table, self.ttable, t, dens[w0:w1], **ckw)
         rad = radius if shared_radius else radius[w0:w1]
