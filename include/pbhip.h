@@ -754,6 +754,78 @@ int pb_cloudy_emission_batch(double *flux_d, double *clear_d, double *cloudy_d, 
                              int nwalkers, const int32_t *deck_itop_d, const double *deck_tsurf_d,
                              const pb_cloud_terms *cloud, const double *f_patchy_d, void *stream);
 
+/* The walkers' atmospheres from their parameter vectors: what Atmosphere.calc_profiles
+ * (pyratbay/pyrat/atmosphere.py:399-526) makes of the parameters eval() maps (pyrat_obj.py:258-275),
+ * for a batch, in ONE launch with no host read-back and no allocation (graph-capturable):
+ *   temperature  tmodel 0 isothermal, 1 guillot (src_c/_pt.c:11-15, 88-109; E2 by power series
+ *                for x <= 1 and continued fraction above, 0 for x > log(2^127) like the reference),
+ *                2 madhu (tmodels.py:301-325; the smoothing of gaussian_filter1d(mode='nearest')
+ *                as a clamped-index correlation with the 2 madhu_radius + 1 host-made weights)
+ *   abundances   nvmr models on species vmr_species[i]: kind 0 IsoVMR, 1 ScaleVMR (its vmr0 in row
+ *                i of vmr0_d[nvmr][nlayers]), 2 SlantVMR (vmr_models.py:129-347), parameters from
+ *                column vmr_par[i]; then the bulk balance of vmr_scale (vmr_scaling.py:69-126,
+ *                259-278, qsat = None) with bulk_ratio_d[nlayers][nbulk], invsrat_d[nlayers]
+ *   density      ((vmr (p / T)) bar) / k (atmosphere.py:664), mean mass sum(vmr mass) (:626, in
+ *                NumPy's pairwise order)
+ *   radius       rmodel 0 hydro_m (:467-485), 1 hydro_g (:397-415): cumulative trapezoid over ln p
+ *                summed left to right, the value at the reference pressure by SciPy's first-order
+ *                spline, radius(p0) = r0
+ * Free scalars: column par_rplanet (cm), par_log_refpressure (log10 bar), par_mplanet (g) of
+ * params_d, or -1: the struct's constant.  All arithmetic in binary64.
+ * CONSTANTS: this kernel uses those of pyratbay.constants, which the reference's Python code runs
+ * with (CODATA 2018: k = 1.380649e-23 * 1e7 erg/K, G = 6.67430e-11 * 1e3, N_A = 6.02214076e23;
+ * bar = 1e6) -- NOT the legacy values of the C extensions (pb_common.h), which every other kernel
+ * of this library keeps.
+ * Outputs, each written once: temps_d[nw][L], dens_d[nw][L][ntab] (species tab_map_d[j]),
+ * radius_d[nw][L], mm_d[nw][L], cont_dens_d[nw][L][ncont] and alk_dens_d[nw][L][nalk] (or NULL with
+ * a count of 0), reject_d[nw]: a bit mask, 0 = accepted.  A rejected walker gets temps = 0 (which
+ * pb_reject_walkers turns into +inf band fluxes), densities and mean masses of 0 and
+ * base_radius_d[L] as its radius.  The divergent hydro_m case deviates from the reference, which
+ * would carry on above the layer where the profile turns over. */
+#define PB_ATM_MAX_SPECIES 32
+#define PB_ATM_MAX_VMR 16
+#define PB_ATM_MAX_BULK 4
+#define PB_ATM_MAX_LAYERS 1024
+#define PB_ATM_REJECT_TEMP 1        /* a temperature <= 0 or not finite                     */
+#define PB_ATM_REJECT_MADHU 2       /* madhu: log_p1 > log_p3                               */
+#define PB_ATM_REJECT_QCAP 4        /* trace VMRs sum above qcap in a layer (:52-66)        */
+#define PB_ATM_REJECT_REFPRESSURE 8 /* reference pressure outside the grid (interp1d raises) */
+#define PB_ATM_REJECT_DIVERGENT 16  /* hydro_m: the radius does not decrease with index; either
+                                       model: a radius <= 0 or not finite (a free rplanet or
+                                       mplanet that is NaN, zero or negative)              */
+typedef struct pb_atm_model {
+    int nlayers, nspecies, npar;
+    int tmodel;
+    double guillot_gravity;             /* 1.0 for gravity = None */
+    int madhu_radius;
+    double madhu_logp0, madhu_loge;
+    const double *madhu_weights_d;
+    int nvmr;
+    int vmr_kind[PB_ATM_MAX_VMR];
+    int vmr_species[PB_ATM_MAX_VMR];
+    int vmr_par[PB_ATM_MAX_VMR];
+    const double *vmr0_d;
+    int nbulk;
+    int bulk_species[PB_ATM_MAX_BULK];
+    const double *bulk_ratio_d, *invsrat_d;
+    const double *base_vmr_d;           /* [nlayers][nspecies] */
+    const double *pressure_d;           /* [nlayers] bar, ascending */
+    const double *log10p_d, *lnp_d;     /* NumPy's log10 and log of it */
+    const double *mass_d;               /* [nspecies] g mol-1 */
+    int rmodel;
+    double mplanet, gplanet, rplanet, refpressure;
+    int par_rplanet, par_log_refpressure, par_mplanet;
+    int has_qcap;
+    double qcap;
+    const double *base_radius_d;
+    int ntab, ncont, nalk;
+    const int32_t *tab_map_d, *cont_map_d, *alk_map_d;
+} pb_atm_model;
+/* The model struct (a host struct) is checked before any HIP call. */
+int pb_walker_atmosphere(const pb_atm_model *model, const double *params_d, int nwalkers,
+                         double *temps_d, double *dens_d, double *radius_d, double *mm_d,
+                         double *cont_dens_d, double *alk_dens_d, int32_t *reject_d, void *stream);
+
 /* =========================================================================
  * Experiments -- NOT in libpbhip.so.  `make -C pyratbay_amd/csrc EXPERIMENTS=1` builds
  * libpbhip_exp.so (compiled with -DPB_EXPERIMENTS) = the product library + the variants that were

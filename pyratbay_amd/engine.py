@@ -1918,7 +1918,7 @@ class TableSpectrum:
                    f_dilution=None, continuum_density=None, continuum_pars=None, rv=None,
                    deck_logp=None, f_patchy=None, alkali_density=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
-        without the parameter mapping): temps[nw, L], dens[nw, L, nspec] device tensors,
+        without the parameter mapping -- eval_params adds it): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
         bands: PassBands on this model's grid -> bandflux[nw, nbands].  Every stage is ONE
         launch per chunk of walkers -- interp_ec, transit_path, optical depth + transmission,
@@ -2080,6 +2080,26 @@ class TableSpectrum:
         call('pb_reject_walkers', _ptr(out), _ptr(temps.contiguous()), tmin, tmax,
              self.nlayers, bands.nbands, nw, _stream())
         return out
+
+    def eval_params(self, atmosphere, params, bands, **kw):
+        """The batched loop from the walkers' parameter vectors (pyrat_obj.py:225-385 WITH the
+        parameter mapping of :258-275 and Atmosphere.calc_profiles): atmosphere, a bound
+        pyratbay_amd.atmosphere.WalkerAtmosphere, turns params[nw, npar] into temps, dens, radius
+        and the continuum / alkali densities in one launch (WalkerAtmosphere.evaluate), and those
+        tensors go to eval_bands unchanged; kw: everything else eval_bands takes (continuum_pars,
+        rv, deck_logp, f_patchy, f_dilution, chunk, streams).  Walkers the atmosphere rejects
+        (non-positive temperature, trace abundances above qcap, ...: WalkerAtmosphere) come out
+        as +inf like those outside the table's temperatures."""
+        for name in ('temps', 'dens', 'radius', 'continuum_density', 'alkali_density'):
+            if name in kw:
+                raise ValueError(f'eval_params: {name} comes from the atmosphere, not from the '
+                                 'caller')
+        prof = atmosphere.evaluate(params)
+        if prof.continuum_density is not None:
+            kw['continuum_density'] = prof.continuum_density
+        if prof.alkali_density is not None:
+            kw['alkali_density'] = prof.alkali_density
+        return self.eval_bands(prof.temps, prof.dens, bands, radius=prof.radius, **kw)
 
     def _ordered_supported(self):
         """Whether the depth-ordered kernels exist for this model's shape: the transit form is the
