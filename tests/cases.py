@@ -139,6 +139,85 @@ def column_case(seed=3, nlayers=24, nwave=96):
                 nlayers=nlayers, nwave=nwave)
 
 
+def emission_oracle(orc, ec, intervals, wn, temp, mu, weights, itop, ibottom, maxdepth):
+    """The oracle chain of the emission geometry for one walker: plane-parallel optical depth ->
+    Planck -> intensity per mu -> weighted sum.  Returns (flux[W], stop[W], depth[L, W]); stop is
+    the layer at which the depth loop left each column (nlayers where there is no interval below
+    itop: the reference clips it to the last layer before it forms the intensity)."""
+    ec = np.ascontiguousarray(ec, np.float64)
+    L, W = ec.shape
+    depth = np.zeros((L, W))
+    stop = np.zeros(W, np.int32)
+    orc.plane_parallel_optical_depth(depth, stop, ec, intervals, maxdepth, itop, ibottom)
+    B = orc.blackbody_wn_2D(wn, temp)
+    inten = orc.intensity(depth, np.minimum(stop, L - 1), B, mu, itop)
+    return np.sum(inten * np.asarray(weights)[:, None], axis=0), stop, depth
+
+
+def block_tiles(stop, itop, nlayers, margin=0):
+    """The last row tile (16 layers from itop) each block of 256 columns can need, from the layers
+    `stop` at which its columns end (in the order the columns are worked in) -- derived as
+    TableSpectrum.order_columns does: the ragged last block padded with the last column."""
+    stop = np.asarray(stop, np.int64)
+    nblk = -(-len(stop) // 256)
+    padded = np.concatenate([stop, np.full(nblk * 256 - len(stop), stop[-1])])
+    ntiles = -(-(nlayers - itop) // 16)
+    return np.clip((padded.reshape(nblk, 256).max(axis=1) - itop + margin) // 16, 0,
+                   ntiles - 1).astype(np.int32)
+
+
+def limit_layer(tile, itop, nwave):
+    """The last layer available to each column under the per-block limits `tile`."""
+    return itop + 16 * (np.asarray(tile, np.int64)[np.arange(nwave) // 256] + 1) - 1
+
+
+def limited_table_model(L, itop, W, nw=9, opacity=1.0):
+    """The small retrieval model of test_gpu_batch.test_tile_limited_batch: 3 species, 6 table
+    temperatures, columns over six decades of opacity, nw walkers of which walker 3 is 30 times
+    more opaque and walker 5 30 times more transparent than the rest.  opacity: a factor on every
+    density (the emission geometry looks down the column, not along the slant path of a transit,
+    and finds the same atmosphere some 50 times thinner)."""
+    rng = np.random.default_rng(1000 + L + W)
+    nspec, ntemp = 3, 6
+    ttable = np.linspace(300.0, 3000.0, ntemp)
+    press = np.logspace(-6, 2, L)
+    etable = 10.0**rng.uniform(-27, -21, (nspec, ntemp, L, 1)) * \
+        10.0**rng.uniform(-3, 3, (nspec, 1, 1, W))
+    radius0 = np.linspace(8.0e9, 7.0e9, L)
+    temps = 1500.0 * (1 + 0.1 * rng.uniform(-1, 1, (nw, 1))) * np.linspace(0.8, 1.2, L)
+    dens = (press / temps)[:, :, None] * 7.2e21 * 10.0**rng.uniform(-7, -3, (nw, 1, nspec))
+    dens[3] *= 30.0
+    dens[5] /= 30.0
+    dens *= opacity
+    g = synth.spectral_grid(4000.0, 4000.0 + (W - 1) * 0.05 + 0.01, 0.05, 12)
+    # per-walker radius profiles (strictly decreasing) for the rows that want them
+    radius = radius0[None] * (1 + 0.01 * rng.uniform(-1, 1, (nw, 1))) + \
+        np.linspace(0, 1, L)[None] * 2e7 * rng.uniform(-1, 1, (nw, 1))
+    bands = [(1, np.ones(W - 2), 1.0),
+             (W // 3, np.exp(-np.linspace(-1.5, 1.5, W // 2)**2), 0.5)]
+    return dict(etable=etable, ttable=ttable, temps=temps, dens=dens, radius0=radius0,
+                radius=radius, wn=g['wn'], bands=bands, rstar=8.8e10, nlayers=L, itop=itop,
+                nwave=W, nw=nw)
+
+
+def table_bandflux_oracle(orc, m, rt_path, temp, dens, radius, maxdepth=10.0, mu=None,
+                          weights=None):
+    """Band fluxes of one walker of limited_table_model through the oracle chain (interp_ec ->
+    optical depth -> transmission, or -> Planck -> intensity -> weighted sum; bands by
+    np.trapezoid) and the layer at which each column stopped."""
+    L, W, itop, wn = m['nlayers'], m['nwave'], m['itop'], m['wn']
+    ec = np.zeros((L, W))
+    orc.interp_ec(ec, m['etable'], m['ttable'], temp, dens, 0, L)
+    if rt_path == 'transit':
+        depth, stop = orc.optical_depth_transit(ec, radius, itop, L, maxdepth)
+        spec = orc.transmission(depth, radius, m['rstar'], stop, itop)
+    else:
+        spec, stop, _ = emission_oracle(orc, ec, -np.diff(radius), wn, temp, mu, weights, itop,
+                                        L, maxdepth)
+    flux = [np.trapezoid(spec[s:s + len(r)] * r, wn[s:s + len(r)]) * h for s, r, h in m['bands']]
+    return np.array(flux), np.asarray(stop)
+
+
 def table_case(seed=11):
     rng = np.random.default_rng(seed)
     nmol, ntemp, nlayers, nwave = 3, 5, 7, 50
