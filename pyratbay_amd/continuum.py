@@ -849,6 +849,9 @@ def deck_state(pressure, logp, radius, temps):
             itop[w] = min(1, nlayers - 1)
         else:
             itop[w] = int(np.where(pressure >= ptop)[0][0])
+        if np.isnan(ptop):                 # (np.interp returns the node's value at one layer)
+            rsurf[w] = tsurf[w] = np.nan
+            continue
         rsurf[w] = np.interp(ptop, pressure, radius[w if radius.shape[0] > 1 else 0])
         tsurf[w] = np.interp(ptop, pressure, temps[w])
     return itop, rsurf, tsurf

@@ -227,6 +227,12 @@ __device__ __forceinline__ void cloud_store(const CloudArgs &a, int w, int col, 
 // cloudy column has optical depths of its own; else the rows of one sum serve both columns.
 // Row r of the cloudy column exists for r < deck_itop + 1 - itop; its last interval ends at the
 // deck's radius (deck_integrand, as in k_transit_fused).
+// Infinite opacity: the fma over the rows of a block is predicate-free, and the staged zeros of
+// the rows ABOVE a layer would meet an infinite sum of that layer as 0 * inf = NaN, where the
+// reference never touches the layer for those rows.  The sum of a segment's two layers is
+// therefore capped at the largest finite double (finite_sum): 0 * it = 0 for the rows above, and
+// the rows that do include the layer still get an optical depth beyond any maxdepth whose
+// exp(-depth) is 0, as with +inf.  Every finite sum keeps its bits; NaN stays NaN.
 // ---------------------------------------------------------------------------
 struct TransitGeom {
     const double *raypath, *radius;
@@ -235,6 +241,11 @@ struct TransitGeom {
 };
 
 using pb::deck_integrand;         // (pb_common.h)
+
+__device__ __forceinline__ double finite_sum(double s)
+{
+    return s > 0x1.fffffffffffffp+1023 ? 0x1.fffffffffffffp+1023 : s;
+}
 
 template <int kRows, bool kTwo>
 __global__ __launch_bounds__(kBlock) void k_cloudy_transit(CloudArgs a, TransitGeom g)
@@ -289,12 +300,12 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_transit(CloudArgs a, TransitG
 #pragma unroll 2
             for (int i = 0; i < nseg; i++) {
                 const double next = src[(int64_t)(i + 1) * nwave];
-                const double s = next + prev;
+                const double s = finite_sum(next + prev);
                 prev = next;
                 const double *pk = s_path + i * kRows;      // LDS broadcast reads
                 if constexpr (kTwo) {
                     const double next_c = next + cloud_at(cs, a, w, itop + i + 1);
-                    const double s_c = next_c + prev_c;
+                    const double s_c = finite_sum(next_c + prev_c);
                     prev_c = next_c;
 #pragma unroll
                     for (int k = 0; k < kRows; k++) {

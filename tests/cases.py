@@ -429,3 +429,249 @@ def compare_voigt_tables(got_row, want_rows, regimes, rtol):
             assert err <= rtol, f'cell ({m}, {n}), {kind}: relative error {err:.3e} > {rtol:.0e}'
         total += want.size
     return worst, count, total
+
+
+# ---------------------------------------------------------------------------
+# The cloud walker batch (pb_clouds.hip) at the kernel boundary: test_gpu_batch_clouds_boundary.py
+# runs these cases on the device, test_batch_clouds_cases_cpu.py checks on the oracle alone that
+# they are the situations their names say
+# ---------------------------------------------------------------------------
+CLOUD_RSTAR = 8.8e10
+CLOUD_MAXDEPTH = 10.0
+# (L, itop, W)
+CLOUD_TRANSIT_SHAPES = [(1, 0, 1), (2, 1, 256), (2, 0, 255), (17, 0, 257), (33, 2, 700),
+                        (80, 0, 600), (384, 0, 130), (385, 0, 130), (400, 15, 130), (1024, 0, 64)]
+CLOUD_EMISSION_SHAPES = [(1, 0, 1), (2, 1, 256), (2, 0, 255), (17, 0, 257), (51, 3, 402),
+                         (130, 0, 300)]
+CLOUD_NMU = [1, 5, 8, 9, 16]
+
+
+def oracle_patchy(orc, geom, ec, ec_cloud, radius, itop, maxdepth, deck, temp=None, wn=None,
+                  mu=None, weights=None, rstar=CLOUD_RSTAR):
+    """The oracle chain of one walker with a deck and / or patchy clouds
+    (test_patchy_golden.py::test_oracle_patchy): optical_depth_transit -> transmission_deck, or
+    plane_parallel_optical_depth -> emission_deck with the deck's temperature in row deck_itop
+    for both columns.  -> (clear, cloudy, ideep_clear, ideep_cloudy); deck = (itop, rsurf or
+    tsurf ...) as (itop, rsurf, tsurf), or None."""
+    L, W = ec.shape
+    ec_cloudy = ec.copy()
+    if ec_cloud is not None:
+        ec_cloudy[itop:] += ec_cloud[itop:]
+    ibottom = L if deck is None else int(deck[0]) + 1
+    if geom == 'transit':
+        depth, ideep = orc.optical_depth_transit(ec_cloudy, radius, itop, ibottom, maxdepth)
+        cloudy = orc.transmission_deck(depth, radius, rstar, ideep, itop,
+                                       None if deck is None else float(deck[1]),
+                                       None if deck is None else int(deck[0]))
+        depth_c, ideep_c = orc.optical_depth_transit(ec, radius, itop, L, maxdepth)
+        clear = orc.transmission_deck(depth_c, radius, rstar, ideep_c, itop, None, None)
+        return clear, cloudy, ideep_c, ideep
+    h = -orc.ediff(radius)
+    depth, ideep = np.zeros((L, W)), np.full(W, L - 1, np.int32)
+    orc.plane_parallel_optical_depth(depth, ideep, ec_cloudy, h, maxdepth, itop, ibottom)
+    depth_c, ideep_c = np.zeros((L, W)), np.full(W, L - 1, np.int32)
+    orc.plane_parallel_optical_depth(depth_c, ideep_c, ec, h, maxdepth, itop, L)
+    # (itop == L - 1: the depth loop leaves at L; the reference clips to the last layer before it
+    # forms the intensity, as cases.emission_oracle does)
+    ideep, ideep_c = np.minimum(ideep, L - 1), np.minimum(ideep_c, L - 1)
+    if deck is None:
+        cloudy = orc.emission_deck(depth, ideep, wn, temp, mu, weights, itop, None, None)
+        clear = orc.emission_deck(depth_c, ideep_c, wn, temp, mu, weights, itop, None, None)
+        return clear, cloudy, ideep_c, ideep
+    cloudy = orc.emission_deck(depth, ideep, wn, temp, mu, weights, itop, float(deck[2]),
+                               int(deck[0]))
+    # the reference's cloudy pass has overwritten row deck_itop of its Planck array in place
+    # (spectrum/radiative_transfer.py:125-126); its clear pass integrates that array
+    temp_clear = temp.copy()
+    temp_clear[int(deck[0])] = float(deck[2])
+    clear = orc.emission_deck(depth_c, ideep_c, wn, temp_clear, mu, weights, itop, None, None)
+    return clear, cloudy, ideep_c, ideep
+
+
+def cloud_row_block(nrow):
+    """Rows of ray path per block of k_cloudy_transit: 16 while 16 rows of nrow segments fit in
+    48 KiB of LDS (nrow <= 384), else 8."""
+    return 16 if nrow * 16 * 8 <= 48 * 1024 else 8
+
+
+def cloud_decks(L, itop, krows):
+    """The deck layers of a batch of six walkers: at itop (row 0 of the first row block); above
+    itop (itop = 0: inside the first row block instead); on each side of the first row-block
+    boundary (rows krows - 1, the last of the first block, and krows); inside the last row block;
+    at L - 1.  Clipped to the grid where the shape is smaller than that."""
+    nrow = L - itop
+    last_block = itop + ((nrow - 1) // krows) * krows
+    want = [itop, itop - 1 if itop > 0 else itop + 2, itop + krows - 1, itop + krows,
+            min(last_block + 1, L - 2), L - 1]
+    return np.clip(want, 0, L - 1).astype(np.int32)
+
+
+_CLOUD_CASES, _CLOUD_ORACLE = {}, {}
+
+
+def cloud_case(orc, geom, L, itop, W, nr, nw=6, cache=True):
+    """nw walkers for cloudy_transit_batch / cloudy_emission_batch at one shape: per-walker ec,
+    radius, temperatures, deck (cloud_decks) and patchy fraction, nr rank-1 cloud terms (nr = 1:
+    one cross-section row for all walkers; nr = 2: a row per walker, the second term confined to
+    the middle half of the layers like a gray cloud).
+
+    The opacities are scaled column by column from the oracle's own depths of walker 0 (maxdepth =
+    inf): column j crosses CLOUD_MAXDEPTH at row 1 + (7 j + 3) mod (nrow - 1) -- every row block
+    gets crossings -- and every fifth column stays below 0.2 CLOUD_MAXDEPTH down to the bottom
+    (0.3 with the most opaque walker: it never crosses).  The other walkers are up to 1.4 times
+    more or less opaque.  Transit (80, 0, 600): columns 0 ... 255, the first workgroup, cross at
+    rows 2 ... 9 instead, so that it alone leaves before the second row block.
+    ec, radius and temperatures do not depend on nr.  The arrays are read-only."""
+    key = (geom, L, itop, W, nr, nw)
+    if cache and key in _CLOUD_CASES:
+        return _CLOUD_CASES[key]
+    rng = np.random.default_rng([L, itop, W, geom == 'emission'])
+    nrow = L - itop
+    press = np.logspace(-6, 2, L) if L > 1 else np.ones(1)
+    radius = np.linspace(8.0e9, 7.0e9, L)[None] * (1 + 0.01 * rng.uniform(-1, 1, (nw, 1))) + \
+        np.linspace(0, 1, L)[None] * 2e7 * rng.uniform(-1, 1, (nw, 1))
+    assert np.all(np.diff(radius, axis=1) < 0)
+    temps = np.linspace(900.0, 1900.0, L)[None] * (1 + 0.1 * rng.uniform(-1, 1, (nw, 1))) + \
+        rng.uniform(-20, 20, (nw, L))
+    wn = np.linspace(2000.0, 9000.0, W) if W > 1 else np.array([2000.0])
+    profile = press**0.9
+    base = profile[:, None] * rng.uniform(0.8, 1.2, (L, W))
+    colscale = np.full(W, 1e-10)
+    first_group = geom == 'transit' and (L, itop, W) == (80, 0, 600)
+    if nrow > 1:
+        if geom == 'transit':
+            depth, _ = orc.optical_depth_transit(base, radius[0], itop, L, np.inf)
+        else:
+            depth, stop = np.zeros((L, W)), np.zeros(W, np.int32)
+            orc.plane_parallel_optical_depth(depth, stop, base, -orc.ediff(radius[0]), np.inf,
+                                             itop, L)
+        cols = np.arange(W)
+        target = itop + 1 + (7 * cols + 3) % (nrow - 1)
+        never = cols % 5 == 4
+        if first_group:
+            target[:256] = itop + 2 + cols[:256] % 8
+            never[:256] = False
+        colscale = np.where(never, 0.2 * CLOUD_MAXDEPTH / depth[L - 1, cols],
+                            1.05 * CLOUD_MAXDEPTH / depth[target, cols])
+    wscale = 10.0**rng.uniform(-0.15, 0.15, nw)
+    wscale[0] = 1.0
+    ec = base[None] * colscale[None, None, :] * wscale[:, None, None]
+    krows = cloud_row_block(nrow) if geom == 'transit' else 16
+    deck_itop = cloud_decks(L, itop, krows)[:nw]
+    up = np.maximum(deck_itop - 1, 0)
+    walkers = np.arange(nw)
+    rsurf = radius[walkers, deck_itop] + 0.4 * (radius[walkers, up] - radius[walkers, deck_itop])
+    tsurf = temps[walkers, deck_itop] + 0.4 * (temps[walkers, up] - temps[walkers, deck_itop])
+    fpatchy = rng.uniform(0.05, 0.95, nw)
+    cs = cf = None
+    if nr:
+        crng = np.random.default_rng([L, itop, W, geom == 'emission', nr])
+        shape = (nr, W) if nr == 1 else (nr, nw, W)
+        cs = crng.uniform(0.5, 1.5, shape) * colscale
+        cf = profile[None, :, None] * crng.uniform(0.2, 1.0, (nw, 1, nr))
+        if nr > 1:
+            cf[:, :L // 4, 1] = 0.0
+            cf[:, L - L // 4:, 1] = 0.0
+    c = dict(key=key, geom=geom, L=L, itop=itop, W=W, nr=nr, nw=nw, krows=krows, ec=ec,
+             radius=radius, temps=temps, wn=wn, deck_itop=deck_itop, rsurf=rsurf, tsurf=tsurf,
+             fpatchy=fpatchy, cs=cs, cf=cf, rstar=CLOUD_RSTAR, first_group=first_group)
+    for a in c.values():
+        if isinstance(a, np.ndarray):
+            a.flags.writeable = False
+    if cache:
+        _CLOUD_CASES[key] = c
+    return c
+
+
+def cloud_ec(c, w):
+    """ec_cloud[L, W] of walker w: sum_m cs_m (x) f_m in the models' order, or None."""
+    if c['cs'] is None:
+        return None
+    out = np.zeros(c['ec'].shape[1:])
+    for m in range(c['cf'].shape[2]):
+        row = c['cs'][m] if c['cs'].ndim == 2 else c['cs'][m, w]
+        out += np.outer(c['cf'][w, :, m], row)
+    return out
+
+
+def cloud_oracle(orc, c, maxdepth, use_deck, mu=None, weights=None, walkers=None):
+    """oracle_patchy for the walkers of a cloud_case -> dict w -> (clear[W], cloudy[W],
+    ideep_clear[W], ideep_cloudy[W]).  Kept per (case, maxdepth, deck, quadrature) when the case
+    is one of cloud_case's own (c['key']); a modified copy drops its key and is computed anew."""
+    key = None
+    if c.get('key') is not None:
+        key = (c['key'], float(maxdepth), bool(use_deck),
+               None if mu is None else (tuple(mu), tuple(weights)))
+    have = _CLOUD_ORACLE.setdefault(key, {}) if key is not None else {}
+    out = {}
+    for w in range(c['nw']) if walkers is None else walkers:
+        if w not in have:
+            deck = (c['deck_itop'][w], c['rsurf'][w], c['tsurf'][w]) if use_deck else None
+            with np.errstate(all='ignore'):
+                have[w] = oracle_patchy(orc, c['geom'], c['ec'][w], cloud_ec(c, w), c['radius'][w],
+                                        c['itop'], maxdepth, deck, c['temps'][w], c['wn'], mu,
+                                        weights, c['rstar'])
+        out[w] = have[w]
+    return out
+
+
+def cloud_regimes(ideep_clear, deck_itop):
+    """Per walker: does the deck decide 'all', 'some' or 'none' of its columns (it lies above every
+    clear crossing, above some, below all)?  ideep_clear: dict w -> ideep[W]."""
+    out = []
+    for w, ideep in ideep_clear.items():
+        above = deck_itop[w] < ideep
+        out.append('all' if above.all() else 'some' if above.any() else 'none')
+    return out
+
+
+def cloud_modified(c, **arrays):
+    """A writable copy of a cloud_case with some arrays replaced (no key: not cached)."""
+    out = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+    out.update(arrays)
+    out['key'] = None
+    return out
+
+
+def cloud_quadrature9(mu8, weights8):
+    """The eight nodes with a ninth of weight zero (mu = 0.5): k_cloudy_emission<16> on the same
+    sums as k_cloudy_emission<8>."""
+    return np.append(mu8, 0.5), np.append(weights8, 0.0)
+
+
+# test_special_values: (name, maxdepth); the special walker is walker 2 of six
+CLOUD_SPECIAL_EMISSION = [('ec_inf', CLOUD_MAXDEPTH), ('deep', np.inf), ('t_zero', CLOUD_MAXDEPTH),
+                          ('tsurf_zero', CLOUD_MAXDEPTH), ('tsurf_nan', CLOUD_MAXDEPTH)]
+CLOUD_SPECIAL_TRANSIT = [('ec_inf', 0), ('cloud_inf', 1)]          # (name, nr)
+CLOUD_SPECIAL_SHAPE = (33, 2, 300)
+CLOUD_SPECIAL_WALKER = 2
+CLOUD_SPECIAL_LAYER = 9         # row 7 of the first row block of 16 (itop = 2)
+
+
+def cloud_special_case(orc, geom, name):
+    """-> (base case, the case with walker CLOUD_SPECIAL_WALKER made special).  Emission (nr = 2):
+    'ec_inf' a layer of ec = +inf; 'deep' ec x 1e7, depths far above 1e5 (run with maxdepth =
+    inf, the kernel's clamp_depth); 't_zero' a layer at T = 0; 'tsurf_zero' / 'tsurf_nan' the
+    deck's temperature (the walker's deck lies inside the grid, above most clear crossings).
+    Transit: 'ec_inf' (nr = 0) ec = +inf in a layer in the middle of a row block; 'cloud_inf'
+    (nr = 1) one infinite cloud factor there."""
+    L, itop, W = CLOUD_SPECIAL_SHAPE
+    nr = dict(CLOUD_SPECIAL_TRANSIT)[name] if geom == 'transit' else 2
+    base = cloud_case(orc, geom, L, itop, W, nr)
+    w, lay = CLOUD_SPECIAL_WALKER, CLOUD_SPECIAL_LAYER
+    c = cloud_modified(base)
+    if name == 'ec_inf':
+        c['ec'][w, lay] = np.inf
+    elif name == 'cloud_inf':
+        c['cf'][w, lay, 0] = np.inf
+    elif name == 'deep':
+        c['ec'][w] *= 1e7
+    elif name == 't_zero':
+        c['temps'][w, lay] = 0.0
+    elif name == 'tsurf_zero':
+        c['tsurf'][w] = 0.0
+    elif name == 'tsurf_nan':
+        c['tsurf'][w] = np.nan
+    else:
+        raise ValueError(name)
+    return base, c

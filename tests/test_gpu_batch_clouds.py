@@ -8,6 +8,9 @@ oracle/continuum.py terms; rtol 1e-11, the figure those tests use for this chain
 import numpy as np
 import pytest
 
+# the oracle chain (test_patchy_golden.py::test_oracle_patchy) for one walker
+from cases import oracle_patchy
+
 pytestmark = pytest.mark.gpu
 
 RTS = ['transit', 'emission', 'eclipse']
@@ -30,44 +33,6 @@ def oc():
 
 def host(t):
     return t.cpu().numpy()
-
-
-# ---------------------------------------------------------------------------------------------
-# The oracle chain (test_patchy_golden.py::test_oracle_patchy) for one walker
-# ---------------------------------------------------------------------------------------------
-def oracle_patchy(orc, geom, ec, ec_cloud, radius, itop, maxdepth, deck, temp=None, wn=None,
-                  mu=None, weights=None, rstar=RSTAR):
-    """-> (clear, cloudy, ideep_clear, ideep_cloudy); deck = (itop, rsurf, tsurf) or None."""
-    L, W = ec.shape
-    ec_cloudy = ec.copy()
-    if ec_cloud is not None:
-        ec_cloudy[itop:] += ec_cloud[itop:]
-    ibottom = L if deck is None else int(deck[0]) + 1
-    if geom == 'transit':
-        depth, ideep = orc.optical_depth_transit(ec_cloudy, radius, itop, ibottom, maxdepth)
-        cloudy = orc.transmission_deck(depth, radius, rstar, ideep, itop,
-                                       None if deck is None else float(deck[1]),
-                                       None if deck is None else int(deck[0]))
-        depth_c, ideep_c = orc.optical_depth_transit(ec, radius, itop, L, maxdepth)
-        clear = orc.transmission_deck(depth_c, radius, rstar, ideep_c, itop, None, None)
-        return clear, cloudy, ideep_c, ideep
-    h = -orc.ediff(radius)
-    depth, ideep = np.zeros((L, W)), np.full(W, L - 1, np.int32)
-    orc.plane_parallel_optical_depth(depth, ideep, ec_cloudy, h, maxdepth, itop, ibottom)
-    depth_c, ideep_c = np.zeros((L, W)), np.full(W, L - 1, np.int32)
-    orc.plane_parallel_optical_depth(depth_c, ideep_c, ec, h, maxdepth, itop, L)
-    if deck is None:
-        cloudy = orc.emission_deck(depth, ideep, wn, temp, mu, weights, itop, None, None)
-        clear = orc.emission_deck(depth_c, ideep_c, wn, temp, mu, weights, itop, None, None)
-        return clear, cloudy, ideep_c, ideep
-    cloudy = orc.emission_deck(depth, ideep, wn, temp, mu, weights, itop, float(deck[2]),
-                               int(deck[0]))
-    # the reference's cloudy pass has overwritten row deck_itop of its Planck array in place
-    # (spectrum/radiative_transfer.py:125-126); its clear pass integrates that array
-    temp_clear = temp.copy()
-    temp_clear[int(deck[0])] = float(deck[2])
-    clear = orc.emission_deck(depth_c, ideep_c, wn, temp_clear, mu, weights, itop, None, None)
-    return clear, cloudy, ideep_c, ideep
 
 
 # ---------------------------------------------------------------------------------------------
