@@ -379,6 +379,23 @@ int pb_loglike(double *loglike_d, const double *bandflux_d, const double *data_d
 int pb_two_stream(double *flux_down_d, double *flux_up_d, const double *depth_d,
                   const double *wn_d, const double *temp_d, const double *f_int_d,
                   const double *flux_top_d, int rtop, int nlayers, int nwave, void *stream);
+/* The same for a batch of walkers in ONE pass (the retrieval loop in two-stream geometry):
+ * per walker w the plane-parallel optical depth of ec_d[w] without a stop (maxdepth = inf,
+ * itop = 0, opacity/optic_depth.py:124-126), the transmissions and both sweeps of pb_two_stream,
+ * of which only flux_up row 0 is stored: flux_d[nwalkers,nwave].  ec_d[nwalkers,nlayers,nwave]
+ * is DESTROYED (the downward sweep leaves each interval's optical depth in it for the upward
+ * one); intervals_d[nwalkers,nlayers-1] = -diff(radius) (NULL allowed when nlayers == 1),
+ * temps_d[nwalkers,nlayers]; wn_d, f_int_d, flux_top_d [nwave] are shared by the walkers
+ * (NULL = no internal flux / no irradiation).  work_d: pb_two_stream_batch_work_doubles(...)
+ * doubles of device scratch, written before it is read (NULL when that is 0).  nlayers == 1:
+ * flux = flux_top + f_int.  Same operations in the same order as
+ * pb_plane_parallel_optical_depth + pb_two_stream per walker: same bits.  nwalkers == 0 or
+ * nwave == 0: nothing is launched. */
+int pb_two_stream_batch(double *flux_d, double *ec_d, const double *intervals_d,
+                        const double *wn_d, const double *temps_d, const double *f_int_d,
+                        const double *flux_top_d, double *work_d, int nlayers, int nwave,
+                        int nwalkers, void *stream);
+int64_t pb_two_stream_batch_work_doubles(int nlayers, int nwave, int nwalkers);
 /* f_int of spectrum.py:475-478: Planck at tint scaled to a bolometric sigma*tint^4. */
 int pb_internal_flux(double *f_int_d, const double *wn_d, double tint, int nwave, void *stream);
 

@@ -122,6 +122,8 @@ _PROTOS = {
     'pb_alkali_voigt_det_batch': [vp, vp, vp, f64, f64, f64, vp, i32, i32, i32, vp],
     'pb_loglike': [vp, vp, vp, vp, i32, i32, vp],
     'pb_two_stream': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    'pb_two_stream_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    'pb_two_stream_batch_work_doubles': [i32, i32, i32],
     'pb_internal_flux': [vp, vp, f64, i32, vp],
     'pb_simps2D': [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp],
     'pb_ediff': [vp, vp, i32, vp],
@@ -137,7 +139,7 @@ _EXP_PROTOS = {
     'pb_table_transit_batch': [vp, vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, i32, i32,
                                i32, vp, vp],
 }
-_RESTYPES = {'pb_transit_work_doubles': C.c_int64,
+_RESTYPES = {'pb_transit_work_doubles': C.c_int64, 'pb_two_stream_batch_work_doubles': C.c_int64,
              'pb_interp_ec_batch_cont_work_doubles': C.c_int64, 'pb_table_transit_work_doubles': C.c_int64,
              'pb_table_transit_supported': C.c_int, 'pb_voigt_destroy': None, 'pb_lines_destroy': None, 'pb_lbl_destroy': None,
              'pb_voigt_device_bytes': i64, 'pb_timer_destroy': None}

@@ -13,6 +13,7 @@
 
 #include "pb_common.h"
 #include "pb_planck.h"
+#include "pb_two_stream.h"
 
 int pb_transit_fused_launch(double *depth_d, int32_t *ideep_d, double *spectrum_d,
                             const double *ec_d, const double *raypath_d, const double *radius_d,
@@ -710,31 +711,12 @@ __global__ __launch_bounds__(kBlock) void k_band_integrate(
 
 // ---------------------------------------------------------------------------
 // Two-stream fluxes (pyratbay/pyrat/spectrum.py:454-522; Heng et al. 2014 Eqs. B5-B6).
-// exp1 = scipy.special.exp1 for real arguments (xsf/expint.h:22-52, the E1XB routine of
-// Zhang & Jin 1996): power series for x <= 1, backward continued fraction otherwise.
+// exp1 and the statements of one layer interval: pb_two_stream.h, shared with the walker batch
+// (pb_two_stream.hip).
 // ---------------------------------------------------------------------------
-__device__ inline double exp1_real(double x)
-{
-    const double ga = 0.5772156649015328606065120900824024;
-    if (x == 0.0)
-        return INFINITY;
-    if (x <= 1.0) {
-        double e1 = 1.0, r = 1.0;
-        for (int k = 1; k < 26; k++) {
-            const double k1 = k + 1.0;
-            r = -r * k * x / (k1 * k1);
-            e1 += r;
-            if (fabs(r) <= fabs(e1) * 1e-15)
-                break;
-        }
-        return -ga - log(x) + x * e1;
-    }
-    const int m = 20 + (int)(80.0 / x);
-    double t0 = 0.0;
-    for (int k = m; k > 0; k--)
-        t0 = k / (1.0 + k / (x + t0));
-    return pb::exp_s(-x) * (1.0 / (x + t0));
-}
+using pb::two_stream_down;
+using pb::two_stream_trans;
+using pb::two_stream_up;
 
 // The diffusivity transmission of every (layer interval, sample), trans[i][j] written to
 // flux_up[i][j]: the expensive part of the two-stream solver (exp1: a series or a continued
@@ -749,8 +731,7 @@ __global__ __launch_bounds__(kBlock) void k_two_stream_trans(double *flux_up, co
     if (j >= nwave || i >= nlayers - 1)
         return;
     const double dtau0 = depth[(int64_t)(i + 1) * nwave + j] - depth[(int64_t)i * nwave + j];
-    flux_up[(int64_t)i * nwave + j] =
-        (1 - dtau0) * pb::exp_s(-dtau0) + dtau0 * dtau0 * exp1_real(dtau0);
+    flux_up[(int64_t)i * nwave + j] = two_stream_trans(dtau0);
 }
 
 // One column per thread.  trans[i] comes from k_two_stream_trans (parked in flux_up[i], which
@@ -763,7 +744,6 @@ __global__ __launch_bounds__(kBlock) void k_two_stream(
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= nwave)
         return;
-    const double pi = 3.141592653589793;
     const double w = wn[j];
     const double factor = planck_factor(w);
     // the irradiation is written into row rtop and the sweep overwrites rows 1..L-1
@@ -777,9 +757,7 @@ __global__ __launch_bounds__(kBlock) void k_two_stream(
         const double bnext = planck(factor, w, temp[i + 1]);
         const double dtau0 = dnext - dprev;
         const double trans = flux_up[(int64_t)i * nwave + j];
-        const double bp = (bnext - bprev) / dtau0;
-        down = trans * down + pi * bprev * (1 - trans) +
-               pi * bp * (-2.0 / 3 * (1 - pb::exp_s(-dtau0)) + dtau0 * (1 - trans / 3));
+        down = two_stream_down(down, trans, dtau0, bprev, bnext);
         flux_down[(int64_t)(i + 1) * nwave + j] = down;
         dprev = dnext;
         bprev = bnext;
@@ -792,9 +770,7 @@ __global__ __launch_bounds__(kBlock) void k_two_stream(
         const double blo = planck(factor, w, temp[i]);
         const double dtau0 = dprev - dlo;
         const double trans = flux_up[(int64_t)i * nwave + j];
-        const double bp = (bprev - blo) / dtau0;
-        up = trans * up + pi * bprev * (1 - trans) +
-             pi * bp * (2.0 / 3 * (1 - pb::exp_s(-dtau0)) - dtau0 * (1 - trans / 3));
+        up = two_stream_up(up, trans, dtau0, blo, bprev);
         flux_up[(int64_t)i * nwave + j] = up;
         dprev = dlo;
         bprev = blo;

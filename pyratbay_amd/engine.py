@@ -671,6 +671,27 @@ def emission_flux_batch(ec, intervals, wn, temps, mu, weights, itop, ibottom, ma
     return flux
 
 
+def two_stream_batch(ec, intervals, wn, temps, f_int=None, flux_top=None, out=None, work=None):
+    """plane-parallel optical depth without a stop + two-stream fluxes for a batch, itop = 0:
+    ec[nw, L, W], intervals[nw, L-1], temps[nw, L], f_int[W] / flux_top[W] (shared by the walkers;
+    None: none) -> flux_up[0] of every walker, [nw, W].  ec is CONSUMED: the kernel leaves each
+    interval's optical depth in it (pb_two_stream_batch).  work: at least
+    pb_two_stream_batch_work_doubles(L, W, nw) doubles of scratch (None: allocated here)."""
+    nw, nlayers, nwave = ec.shape
+    assert ec.is_contiguous() and ec.dtype == torch.float64
+    flux = out if out is not None else torch.empty((nw, nwave), dtype=torch.float64,
+                                                   device=ec.device)
+    need = _capi.lib().pb_two_stream_batch_work_doubles(nlayers, nwave, nw)
+    if work is None:
+        work = torch.empty(need, dtype=torch.float64, device=ec.device) if need else None
+    elif work.numel() < need or work.dtype != torch.float64 or not work.is_contiguous():
+        raise ValueError(f'two_stream_batch: work must hold {need} contiguous doubles')
+    call('pb_two_stream_batch', _ptr(flux), _ptr(ec), _ptr(intervals.contiguous()), _ptr(wn),
+         _ptr(temps.contiguous()), _ptr(f_int), _ptr(flux_top), _ptr(work), nlayers, nwave, nw,
+         _stream())
+    return flux
+
+
 # --------------------------------------------------------------------------
 # Cloud deck and patchy clouds for a batch (pb_clouds.hip)
 # --------------------------------------------------------------------------
@@ -1747,8 +1768,25 @@ class TableSpectrum:
 
     def __init__(self, etable, ttable, wn, radius, rstar, rt_path='transit', itop=0,
                  maxdepth=10.0, quadrature_mu=None, quadrature_weights=None, continuum=None,
-                 timestamps=True, column_order='auto'):
+                 timestamps=True, column_order='auto', tint=0.0, flux_top=None):
         require_gpu()
+        # rt_path 'two_stream' / 'emission_two_stream' / 'eclipse_two_stream' (RT_PATHS, as in
+        # LBLSpectrum): the geometry 'two_stream' (pyrat/spectrum.py:454-522) with the internal
+        # flux of tint (K) added at the bottom and flux_top[W], the irradiation
+        # beta_irr * (rstar / smaxis)**2 * starflux the caller forms (host or device; None: none),
+        # at the top.  The optical depth has no maxdepth stop (opacity/optic_depth.py:124-126).
+        self.rt_path_name = rt_path
+        self.observable = None
+        if rt_path in ('two_stream', 'emission_two_stream', 'eclipse_two_stream'):
+            rt_path, self.observable = RT_PATHS[rt_path]
+            if itop != 0:
+                # (layers above itop have dtau0 = 0 and the reference's own statement then gives
+                # 0 * exp1(0) = NaN in every column)
+                raise ValueError(f'rt_path {self.rt_path_name!r}: itop must be 0, got {itop}')
+            maxdepth = float('inf')
+            column_order = None               # (no early exit to order the columns for)
+        elif tint != 0.0 or flux_top is not None:
+            raise ValueError('tint and flux_top belong to the two-stream geometries')
         self._timer = StageTimer() if timestamps else None
         # eval_bands: the order the columns are worked in (see order_columns).
         # 'auto': taken from the first walker of the first batch; None: grid order
@@ -1778,7 +1816,13 @@ class TableSpectrum:
         self.rt_path, self.itop, self.maxdepth = rt_path, itop, maxdepth
         self.rstar = float(rstar)
         self.set_radius(radius)
-        if rt_path != 'transit':
+        if rt_path == 'two_stream':
+            self.f_int = internal_flux(self.wn, tint)
+            self.flux_top = None if flux_top is None else dev(flux_top)
+            if self.flux_top is not None and self.flux_top.shape != (self.nwave,):
+                raise ValueError(f'flux_top must have shape ({self.nwave},), got '
+                                 f'{tuple(self.flux_top.shape)}')
+        elif rt_path != 'transit':
             if quadrature_mu is None:
                 quadrature_mu, quadrature_weights = default_quadrature()
             elif quadrature_weights is None:
@@ -1900,8 +1944,13 @@ class TableSpectrum:
                 self.ec, self.intervals, self.itop, self.nlayers, self.maxdepth)
             if t is not None:
                 t.mark('odepth', 'spectrum')
-            self.spectrum = emission_flux(self.depth, self.ideep, self.wn, self.temp, self.mu,
-                                          self.weights, self.itop)
+            if self.rt_path == 'two_stream':
+                self.flux_down, self.flux_up = two_stream(self.depth, self.wn, self.temp,
+                                                          self.f_int, self.flux_top, 0)
+                self.spectrum = self.flux_up[0]
+            else:
+                self.spectrum = emission_flux(self.depth, self.ideep, self.wn, self.temp,
+                                              self.mu, self.weights, self.itop)
         if t is not None:
             t.mark('spectrum')
         return self.spectrum
@@ -1928,6 +1977,15 @@ class TableSpectrum:
         (pyrat_obj.py:302-320, 378-380).  Emission geometry: f_dilution[nw] = the walkers'
         dilution factors (pyrat_obj.py:296-297), and bands.set_eclipse(...) for the planet-to-star
         flux ratios of an eclipse retrieval (pyrat_obj.py:662-665).
+
+        Two-stream geometry (rt_path 'two_stream' / 'emission_two_stream' / 'eclipse_two_stream',
+        pyrat/spectrum.py:454-522): interpolation, then ONE launch for the optical depth without a
+        stop and both sweeps (two_stream_batch), then the bands; f_dilution, set_eclipse, a
+        HiresData with rv, radius[nw, L] and the Continuum's terms and alkali doublets work as in
+        emission geometry.  Always grid order (there is no stop to order the columns for:
+        column_order orders nothing and copies no table); deck_logp, f_patchy and a Continuum with
+        cloud-type models are refused (ValueError: the reference's two-stream ignores the clear
+        column and its deck leaves zero rows below it) -- eval() takes them.
 
         With a Continuum attached (TableSpectrum(..., continuum=cont)) its terms are added in the
         store of the interpolation (pb_interp_ec_batch_cont): continuum_density[nw, L, ncs] holds
@@ -1961,8 +2019,9 @@ class TableSpectrum:
         the spectra are convolved with the instrument profile, shifted by the walkers' radial
         velocities rv[nw] (km/s, a device tensor; None: no shift) and sampled at the data in one
         launch per chunk -> [nw, ndata].  rv with a PassBands is refused (ValueError)."""
-        assert self.rt_path in ('transit', 'emission'), \
-            'eval_bands: transit or emission geometry on sampled cross sections'
+        assert self.rt_path in ('transit', 'emission', 'two_stream'), \
+            'eval_bands: transit, emission or two-stream geometry on sampled cross sections'
+        two_stream_rt = self.rt_path == 'two_stream'
         if rv is not None:
             if not isinstance(bands, HiresData):
                 raise ValueError('eval_bands: rv (a radial-velocity shift) needs a HiresData, '
@@ -1970,7 +2029,8 @@ class TableSpectrum:
             if tuple(rv.shape) != (temps.shape[0],):
                 raise ValueError(f'eval_bands: rv must have shape {(temps.shape[0],)}, got '
                                  f'{tuple(rv.shape)}')
-        assert f_dilution is None or self.rt_path == 'emission', 'f_dilution: emission geometry'
+        assert f_dilution is None or self.rt_path in ('emission', 'two_stream'), \
+            'f_dilution: emission geometry'
         assert f_dilution is None or f_dilution.shape == (temps.shape[0],)
         nw = temps.shape[0]
         tmin, tmax = self.tmin, self.tmax
@@ -1980,6 +2040,16 @@ class TableSpectrum:
         if deck_logp is not None and (cont is None or not cont.deck):
             raise ValueError('eval_bands: deck_logp needs a Deck among the models of the '
                              'attached Continuum')
+        if two_stream_rt:
+            # (the reference's two-stream ignores the clear column of a patchy model, and its deck
+            # leaves zero rows below the deck's layer)
+            for name, given in (('deck_logp', deck_logp is not None),
+                                ('f_patchy', f_patchy is not None),
+                                ('a Continuum with cloud-type models',
+                                 cont is not None and bool(cont.cloud))):
+                if given:
+                    raise ValueError(f'eval_bands: {name}: clouds are not supported in batched '
+                                     'form in two-stream geometry; use eval()')
         # (cloud-type models alone take the cloud path too: the cloudy column is the spectrum)
         cloudy = deck_logp is not None or f_patchy is not None or \
             (cont is not None and bool(cont.cloud))
@@ -2034,7 +2104,7 @@ class TableSpectrum:
         shared_radius = radius.shape[0] == 1
         transit = self.rt_path == 'transit'
         if self._auto_order and self.column_order is None and nw > 0 and self.nwave >= 64 and \
-                not (transit and self._one_pass() and cont is None):
+                not two_stream_rt and not (transit and self._one_pass() and cont is None):
             # ONE-TIME set-up of the first batch (class docstring): a host read-back, a sort and a
             # permuted second copy of the table.  Skipped -- grid order, nothing else changes --
             # where the ordered kernels do not exist for the shape, while the stream is being
@@ -2149,7 +2219,9 @@ class TableSpectrum:
             return
         # (an explicit order on a shape the ordered transit kernel does not take -- more than 128
         # impact parameters -- is worked in grid order: the spectra do not depend on the order)
-        ordered = self.column_order is not None and self._ordered_supported()
+        # (two-stream geometry: always grid order -- no stop, nothing to order for)
+        ordered = self.column_order is not None and self._ordered_supported() and \
+            self.rt_path != 'two_stream'
         table = self.etable_ordered if ordered else self.etable
         limited = ordered and self.tile_limit is not None
         # the continuum's operands in the table's column order, this chunk's walkers
@@ -2178,7 +2250,11 @@ class TableSpectrum:
         if self.rt_path != 'transit':
             rad = radius.expand(n, -1) if shared_radius else radius[w0:w1]
             intervals = (rad[:, :-1] - rad[:, 1:]).contiguous()            # -diff(radius)
-            if limited:
+            if self.rt_path == 'two_stream':
+                # depth without a stop + both sweeps in one launch; ec is consumed
+                spectra = two_stream_batch(ec, intervals, self.wn, temps[w0:w1], self.f_int,
+                                           self.flux_top)
+            elif limited:
                 spectra = emission_flux_batch(ec, intervals, self.wn_ordered, temps[w0:w1],
                                               self.mu, self.weights, self.itop, self.nlayers,
                                               self.maxdepth, self.column_order,
