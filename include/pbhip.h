@@ -399,6 +399,83 @@ int64_t pb_two_stream_batch_work_doubles(int nlayers, int nwave, int nwalkers);
 /* f_int of spectrum.py:475-478: Planck at tint scaled to a bolometric sigma*tint^4. */
 int pb_internal_flux(double *f_int_d, const double *wn_d, double tint, int nwave, void *stream);
 
+/* ---- Radiative equilibrium (Pyrat.radiative_equilibrium, pyrat/pyrat_obj.py:559-646 ->
+ * spectrum/radiative_transfer.py:141-270) for a batch of profiles, at fixed volume mixing ratios
+ * and without convection: pb_radeq.hip.  One iteration is pb_interp_ec_batch[_cont],
+ * pb_two_stream_net_batch, pb_radeq_update; nothing is read back.
+ *
+ * pb_two_stream_net_batch = pb_two_stream_batch (same arguments, same bits in flux_d, ec_d
+ * DESTROYED) that also integrates flux_up and flux_down of EVERY layer over wavenumber with the
+ * trapezoid weights trapz_weights_d[nwave] (half the neighbouring gaps of the grid, one-sided at
+ * its ends; a single sample: 0): parts_d[nwalkers, nparts, 2, nlayers], nparts =
+ * pb_two_stream_net_parts(nwave), holds the sums over the columns of one part (a workgroup of 256
+ * columns), [.., 0, ..] of flux_up and [.., 1, ..] of flux_down; the parts added up are
+ * Qup[nlayers] and Qdown[nlayers] (radiative_transfer.py:208-209).  No atomics: two runs give
+ * the same bits.  At most 744 layers (LDS).  flux_down[0] is the irradiation, flux_up[nlayers-1] = flux_down[nlayers-1] +
+ * f_int.  f_int_d / flux_top_d: [nwave] shared by the profiles (stride 0) or [nwalkers, nwave]
+ * (stride nwave); NULL = none. */
+int pb_two_stream_net_parts(int nwave);
+int64_t pb_two_stream_net_work_doubles(int nlayers, int nwave, int nwalkers);
+int pb_two_stream_net_batch(double *flux_d, double *parts_d, double *ec_d,
+                            const double *intervals_d, const double *wn_d,
+                            const double *trapz_weights_d, const double *temps_d,
+                            const double *f_int_d, int f_int_stride, const double *flux_top_d,
+                            int flux_top_stride, double *work_d, int nlayers, int nwave,
+                            int nwalkers, void *stream);
+
+/* The state of pb_radeq_update; every pointer is device memory.  Iteration k = iter_d[w] of
+ * profile w reads temp_d[w] (= row k of temps_d[w]) and the parts of its fluxes, and writes row
+ * k + 1, temp_d[w], dt_scale_d[w], row k % 4 of signs_d[w], q_up_d[w], q_down_d[w], iter_d[w] =
+ * k + 1 and the atmosphere of the next evaluation.  A launch with k + 1 >= nrows does nothing. */
+typedef struct pb_radeq {
+    int nlayers, nwalkers;
+    int nparts;                    /* pb_two_stream_net_parts(nwave) */
+    int nrows;                     /* rows of temps_d per profile: 1 + nsamples */
+    double tmin, tmax;             /* np.clip of the new temperatures */
+    const double *parts_d;         /* [nwalkers, nparts, 2, nlayers] */
+    const double *dpress_d;        /* [nlayers] ediff1d(log p), element 0 = element 1 */
+    double *temps_d;               /* [nwalkers, nrows, nlayers] history */
+    double *temp_d;                /* [nwalkers, nlayers] the profile to evaluate next */
+    double *dt_scale_d;            /* [nwalkers, nlayers] */
+    double *signs_d;               /* [nwalkers, 4, nlayers] sign(dF) of iteration k in row k % 4 */
+    int32_t *iter_d;               /* [nwalkers] */
+    double *q_up_d, *q_down_d;     /* [nwalkers, nlayers] bolometric fluxes of the evaluated profile */
+    /* (diagnostics, for tests: nothing in the loop reads them) */
+    int32_t *wobble_d;             /* [nwalkers, nlayers] the wobbling layers, or NULL */
+    double *sigma_d;               /* [nwalkers] sigma of the temperature filter, or NULL */
+    /* the atmosphere: n = vmr p / (k T) (atmosphere.ideal_gas_density, pyratbay.constants) */
+    const double *pressure_d;      /* [nlayers] bar, ascending */
+    const double *lnp_d;           /* [nlayers] log(pressure); radius models only */
+    const double *vmr_d;           /* [nwalkers or 1, nlayers, nspecies] */
+    int64_t vmr_stride;            /* 0 (shared) or nlayers * nspecies */
+    int nspecies;
+    const double *mm_d;            /* [nwalkers or 1, nlayers] mean molecular mass; radius models only */
+    int mm_stride;                 /* 0 or nlayers */
+    int ntab, ncont;               /* species of dens_d / cdens_d */
+    const int32_t *tab_map_d, *cont_map_d;     /* their indices among the nspecies */
+    double *dens_d;                /* [nwalkers, nlayers, ntab] */
+    double *cdens_d;               /* [nwalkers, nlayers, ncont] (ncont > 0) */
+    int rmodel;                    /* -1: radius_d, intervals_d are not touched; 0 hydro_m; 1 hydro_g */
+    int has_ref;                   /* p0, r0 given (hydro_m: always; hydro_g without: radius[-1] = 0) */
+    double mplanet, gplanet;       /* g (hydro_m), cm s-2 (hydro_g) */
+    double p0, r0;                 /* bar within the pressure grid (the caller's check), cm */
+    double *radius_d;              /* [nwalkers, nlayers] */
+    double *intervals_d;           /* [nwalkers, nlayers - 1] radius[i] - radius[i + 1] */
+} pb_radeq;
+
+/* One update of every profile (radiative_transfer.py:207-237, convection=False), one workgroup per
+ * profile: Qup, Qdown from the parts in a fixed order (with G = max(1, min(256 / nlayers, nparts))
+ * for nlayers <= 256, else 1: G groups of ceil(nparts / G) consecutive parts, each added left to
+ * right, then the groups left to right); dF = ediff1d(Qup - Qdown, to_begin=0); wobble = a
+ * sign of dF that differs from one of the up to four previous iterations; dt_scale * 0.5 / 1.15,
+ * clipped to [1, 1e8], gaussian_filter1d(sigma = 1.5); dT = dt_scale sign(dF) |dF|**0.1 /
+ * (pc.sigma T**3 dpress); isothermal top; gaussian_filter1d(sigma = clip(mean|dT| / 10, 0.75, 2))
+ * of all but the last layer; clip to [tmin, tmax]; then the densities, radius and intervals of the
+ * new profile.  gaussian_filter1d is SciPy's (radius int(4 sigma + 0.5), mode 'reflect').
+ * init_only != 0: only the atmosphere of temp_d (before the first evaluation).  2 <= nlayers <=
+ * PB_ATM_MAX_LAYERS. */
+int pb_radeq_update(const pb_radeq *state, int init_only, void *stream);
+
 /* _simpson.simps2D (src_c/_simpson.c:167-203): y_d[ny,nwave] */
 int pb_simps2D(double *out_d, const double *y_d, int ny, int nwave, const double *h_d,
                const int32_t *nint_d, const double *hsum_d, const double *hratio_d,

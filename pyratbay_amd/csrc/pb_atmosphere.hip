@@ -5,18 +5,16 @@
 // Everything in binary64, in the reference's order of operations; the build's -ffp-contract=off
 // keeps products and sums apart like NumPy does.
 //
-// CONSTANTS: pyratbay.constants (CODATA 2018 through scipy.constants, the products NumPy forms),
-// which the reference's Python code -- ideal_gas_density, hydro_m, hydro_g -- runs with; not the
-// legacy set of the C extensions in pb_common.h.
+// CONSTANTS: pyratbay.constants (pb_atm_profile.h, which also holds the ideal-gas and hydrostatic
+// statements the radiative-equilibrium update shares), not the legacy set of the C extensions in
+// pb_common.h.
+#include "pb_atm_profile.h"
 #include "pb_common.h"
 
 namespace {
 
 constexpr int kWave = 64;
-constexpr double kBoltz = 1.380649e-23 * 1e7;    // pc.k = sc.k * 1e7 (erg K-1)
-constexpr double kGrav = 6.67430e-11 * 1e3;      // pc.G = sc.G * 1e3 (dyne cm2 g-2)
-constexpr double kAvogadro = 6.02214076e23;      // sc.N_A
-constexpr double kBar = 1e6;                     // pc.bar (barye)
+using pb::atm::kBar;
 constexpr double kEuler = 0.57721566490153286061;
 constexpr double kE2Cutoff = 88.029691931113054296;   // log(2^127): E2 = 0 above, like the reference
 
@@ -151,7 +149,7 @@ __device__ void gather_density(double *out, int64_t base, const int32_t *map, in
         double v = 0.0;
         if (!rejected) {
             const int l = l0 + ll;
-            v = ((s_vmr[map[j] * kWave + ll] * (pressure[l] / s_temp[l])) * kBar) / kBoltz;
+            v = pb::atm::ideal_gas_density(s_vmr[map[j] * kWave + ll], pressure[l], s_temp[l]);
         }
         out[base + (int64_t)l0 * ncol + idx] = v;
     }
@@ -258,41 +256,18 @@ __global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
     const double r0 = m.par_rplanet >= 0 ? par[m.par_rplanet] : m.rplanet;
     const double p0 = m.par_log_refpressure >= 0 ? pow(10.0, par[m.par_log_refpressure])
                                                  : m.refpressure;
-    for (int l = lane; l < L; l += kWave) {
-        const double t = s_temp[l], mu = s_mm[l];
-        s_aux[l] = m.rmodel == 0 ? ((kBoltz * kAvogadro) * t) / ((kGrav * mu) * mplanet)
-                                 : ((-kBoltz * kAvogadro) * t) / (mu * m.gplanet);
-    }
+    for (int l = lane; l < L; l += kWave)
+        s_aux[l] = pb::atm::hydro_integrand(m.rmodel, s_temp[l], s_mm[l], mplanet, m.gplanet);
     __syncthreads();
-    if (lane == 0) {
-        // np.cumsum's order: left to right
-        double run = 0.0;
-        s_int[0] = 0.0;
-        for (int l = 1; l < L; l++) {
-            run += (m.lnp_d[l] - m.lnp_d[l - 1]) * (s_aux[l] + s_aux[l - 1]) / 2.0;
-            s_int[l] = run;
-        }
-    }
+    if (lane == 0)
+        pb::atm::hydro_cumulative(s_int, m.lnp_d, s_aux, L);
     __syncthreads();
     if (!(p0 >= pressure[0] && p0 <= pressure[L - 1])) {
         flags |= PB_ATM_REJECT_REFPRESSURE;
     } else {
-        // interp1d(pressure, I, kind='slinear')(p0): SciPy's first-order spline
-        int lo = 0, hi = L;                    // searchsorted(pressure, p0, 'right')
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (pressure[mid] <= p0)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        lo = min(max(lo - 1, 0), L - 2);
-        const double pa = pressure[lo], pb = pressure[lo + 1];
-        const double wgt = 1.0 / (pb - pa);
-        const double i0 = s_int[lo] * (wgt * (pb - p0)) + s_int[lo + 1] * (wgt * (p0 - pa));
+        const double i0 = pb::atm::hydro_reference(pressure, s_int, p0, L);
         for (int l = lane; l < L; l += kWave)
-            s_aux[l] = m.rmodel == 0 ? 1.0 / ((s_int[l] - i0) + 1.0 / r0)
-                                     : s_int[l] + (r0 - i0);
+            s_aux[l] = pb::atm::hydro_radius(m.rmodel, s_int[l], i0, r0);
         __syncthreads();
         // a radius that is not finite and positive is no geometry for either model (a free
         // rplanet or mplanet that is NaN, zero or negative; every <= below is false on NaN)

@@ -2171,6 +2171,14 @@ class TableSpectrum:
             kw['alkali_density'] = prof.alkali_density
         return self.eval_bands(prof.temps, prof.dens, bands, radius=prof.radius, **kw)
 
+    def radiative_equilibrium(self, pressure, vmr, mol_mass, **kw):
+        """The radiative-equilibrium iteration (runmode = radeq, pyrat_obj.py:559-646) of a batch
+        of profiles on this model's table, grid and Continuum, at fixed volume mixing ratios: a
+        pyratbay_amd.radeq.RadiativeEquilibrium (its docstring has the keywords); .run(temp0,
+        nsamples) iterates on the device.  Two-stream geometry only."""
+        from .radeq import RadiativeEquilibrium
+        return RadiativeEquilibrium(self, pressure, vmr, mol_mass, **kw)
+
     def _ordered_supported(self):
         """Whether the depth-ordered kernels exist for this model's shape: the transit form is the
         matrix-core kernel only (pb_transit_spectrum_ordered: 2 ... 128 impact parameters, i.e.
