@@ -920,6 +920,35 @@ int pb_walker_atmosphere(const pb_atm_model *model, const double *params_d, int 
                          double *temps_d, double *dens_d, double *radius_d, double *mm_d,
                          double *cont_dens_d, double *alk_dens_d, int32_t *reject_d, void *stream);
 
+/* ---- Posterior summary: weighted column quantiles (pb_quantiles.hip).  The reduction of
+ * posterior_post_processing (pyratbay/tools/retrieval_tools.py:384-503: np.percentile of
+ * models[uinv] along the samples, per wavenumber / band / layer) on the UNIQUE samples and their
+ * multiplicities; the expansion is never formed.
+ *
+ * values_d[ncol][ld] (sample-minor: a column's n samples are contiguous, ld >= n, the padding is
+ * never read), counts_d[n] >= 0 (how often the chain visited sample i; shared by the columns; a
+ * row with count 0 does not exist; the counts may sum past 2^31).  With a_k = the element of rank
+ * k of column c's samples, each repeated counts[i] times and sorted (N = sum of counts elements):
+ *   out_d[q][c] = lerp(a_{rank_lo[q]}, a_{rank_hi[q]}, gamma[q])
+ * with NumPy's lerp, every operation rounded on its own: d = b - a; a + d t, and b - d (1 - t)
+ * where t >= 0.5.  The caller forms rank_lo_d[nq], rank_hi_d[nq] (0 <= rank < N), gamma_d[nq]
+ * (device memory) the way np.percentile(method='linear') does; the result then has np.percentile's
+ * bits (pyratbay_amd/posterior.py: weighted_quantiles_host is the NumPy statement).  Exact
+ * selection (a weighted radix select on the order-preserving key of the double, integer
+ * histograms in LDS), no floating-point atomics: two runs give the same bits.  Values order by
+ * that key: -0.0 before +0.0, NaNs of positive sign last.  A column whose counts are all zero
+ * (the caller's error), and a quantile with a rank outside [0, N), get NaN.
+ * n <= pb_weighted_quantiles_resident_rows(): the column is read once and kept in LDS; above, every
+ * pass re-reads it.  work_d: pb_weighted_quantiles_work_doubles(n, ncol, nq) doubles of device
+ * scratch (0 today: NULL is then accepted).  Refused before any launch (PB_ERR_ARG): n < 1,
+ * nq < 1, ncol < 0, ld < n, a null pointer; ncol == 0 succeeds and launches nothing. */
+int pb_weighted_quantiles(double *out_d, const double *values_d, int64_t ld,
+                          const int64_t *counts_d, int n, int ncol, const int64_t *rank_lo_d,
+                          const int64_t *rank_hi_d, const double *gamma_d, int nq, double *work_d,
+                          void *stream);
+int64_t pb_weighted_quantiles_work_doubles(int n, int ncol, int nq);
+int pb_weighted_quantiles_resident_rows(void);
+
 /* =========================================================================
  * Experiments -- NOT in libpbhip.so.  `make -C pyratbay_amd/csrc EXPERIMENTS=1` builds
  * libpbhip_exp.so (compiled with -DPB_EXPERIMENTS) = the product library + the variants that were

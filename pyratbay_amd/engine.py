@@ -1965,7 +1965,7 @@ class TableSpectrum:
 
     def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
                    f_dilution=None, continuum_density=None, continuum_pars=None, rv=None,
-                   deck_logp=None, f_patchy=None, alkali_density=None):
+                   deck_logp=None, f_patchy=None, alkali_density=None, spectra_out=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
         without the parameter mapping -- eval_params adds it): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
@@ -2018,7 +2018,15 @@ class TableSpectrum:
         bands may be a HiresData instead (high-resolution spectroscopy, pyrat_obj.py:331-356):
         the spectra are convolved with the instrument profile, shifted by the walkers' radial
         velocities rv[nw] (km/s, a device tensor; None: no shift) and sampled at the data in one
-        launch per chunk -> [nw, ndata].  rv with a PassBands is refused (ValueError)."""
+        launch per chunk -> [nw, ndata].  rv with a PassBands is refused (ValueError).
+
+        spectra_out (a contiguous float64 device tensor [nw, nwave]; None: nothing changes)
+        receives every walker's full-resolution spectrum in GRID order, whatever column order is
+        in use: the spectrum a one-walker eval() of this model returns (transit: the modulation
+        spectrum; emission and two-stream: the planet's flux, before f_dilution, the eclipse ratio
+        and the instrument profile, which belong to the bands) -- one copy per chunk on every
+        branch: one-pass, ordered and limited transit, emission, two-stream and clouds.  The rows
+        of rejected walkers hold whatever the kernels made of their inputs."""
         assert self.rt_path in ('transit', 'emission', 'two_stream'), \
             'eval_bands: transit, emission or two-stream geometry on sampled cross sections'
         two_stream_rt = self.rt_path == 'two_stream'
@@ -2033,6 +2041,11 @@ class TableSpectrum:
             'f_dilution: emission geometry'
         assert f_dilution is None or f_dilution.shape == (temps.shape[0],)
         nw = temps.shape[0]
+        if spectra_out is not None:
+            _check_walker_tensor('eval_bands: spectra_out', spectra_out, nw,
+                                 shape=(nw, self.nwave))
+            if not spectra_out.is_contiguous():
+                raise ValueError('eval_bands: spectra_out must be contiguous')
         tmin, tmax = self.tmin, self.tmax
         cont = self.continuum
         _check_walker_tensor('eval_bands: deck_logp', deck_logp, nw)
@@ -2139,10 +2152,11 @@ class TableSpectrum:
             if streams > 1:
                 with torch.cuda.stream(self._eval_streams[ci % streams]):
                     self._eval_chunk(temps, dens, bands, radius, shared_radius, path1, out, w0,
-                                     min(w0 + chunk, nw), f_dilution, cargs, rv, clouds)
+                                     min(w0 + chunk, nw), f_dilution, cargs, rv, clouds,
+                                     spectra_out)
             else:
                 self._eval_chunk(temps, dens, bands, radius, shared_radius, path1, out, w0,
-                                 min(w0 + chunk, nw), f_dilution, cargs, rv, clouds)
+                                 min(w0 + chunk, nw), f_dilution, cargs, rv, clouds, spectra_out)
         if streams > 1:
             for st in self._eval_streams[:streams]:
                 caller.wait_stream(st)
@@ -2170,6 +2184,34 @@ class TableSpectrum:
         if prof.alkali_density is not None:
             kw['alkali_density'] = prof.alkali_density
         return self.eval_bands(prof.temps, prof.dens, bands, radius=prof.radius, **kw)
+
+    def posterior_summary(self, atmosphere, params, counts, bands, quantiles=None, chunk=64,
+                          **kw):
+        """The summary of a posterior (posterior_post_processing, tools/retrieval_tools.py:384-503):
+        params[n, npar] = the chain's UNIQUE samples (device; posterior.unique_samples gives their
+        rows and counts[n], how often the chain visited each) go through the eval_params path in
+        chunks of `chunk`; each chunk's full-resolution spectra, band fluxes, temperatures and mole
+        fractions are written transposed into sample-minor stores ([nwave, n], [nbands, n],
+        [L, n], [L, nspec, n]) and one pb_weighted_quantiles call per store gives the quantiles
+        (default posterior.QUANTILES: the median and the 1- and 2-sigma bounds, the reference's
+        order) of the chain -- each sample counts[i] times, np.percentile's bits, the expansion
+        never formed.  -> posterior.PosteriorSummary of device tensors: spectrum[nq, nwave],
+        bands[nq, nbands], temperature[nq, L], vmr[nq, L, nspec] (nspec: the table's species, the
+        atmosphere's dens output times k T / p), n_rejected, quantiles, stores (None unless
+        keep_stores=True: the four stores and the counts used).
+
+        DEVIATION: samples the batch rejects (+inf band fluxes: outside the table's temperatures,
+        a radial velocity beyond rv_max; or a reject flag of the atmosphere) get count 0 before the
+        reduction and are reported in n_rejected -- the reference would return NaN / inf
+        quantiles.  Every sample rejected: ValueError.  One read-back (n_rejected and the length
+        of the expansion), otherwise launches only.  The spectrum store takes 8 nwave n bytes: a
+        store that does not fit in free device memory is refused (ValueError) before anything is
+        allocated.  kw: what eval_bands takes per walker (continuum_pars, rv, deck_logp, f_patchy,
+        f_dilution) with one row per sample, and streams."""
+        from . import posterior
+        return posterior.posterior_summary(
+            self, atmosphere, params, counts, bands,
+            quantiles=posterior.QUANTILES if quantiles is None else quantiles, chunk=chunk, **kw)
 
     def radiative_equilibrium(self, pressure, vmr, mol_mass, **kw):
         """The radiative-equilibrium iteration (runmode = radeq, pyrat_obj.py:559-646) of a batch
@@ -2201,7 +2243,8 @@ class TableSpectrum:
                                                       self.itop, self.nlayers, self.nwave)
 
     def _eval_chunk(self, temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
-                    f_dilution=None, cargs=(None, None, None), rv=None, clouds=None):
+                    f_dilution=None, cargs=(None, None, None), rv=None, clouds=None,
+                    spectra_out=None):
         """One chunk of eval_bands: walkers [w0, w1) through every stage, one launch each."""
         n = w1 - w0
         # (the walkers' radial velocities: HiresData only -- eval_bands has checked)
@@ -2209,7 +2252,7 @@ class TableSpectrum:
         cont = self.continuum
         if clouds is not None:
             self._eval_chunk_clouds(temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
-                                    f_dilution, cargs, okw, clouds)
+                                    f_dilution, cargs, okw, clouds, spectra_out)
             return
         # (the one-pass transit takes no continuum: with one attached, the two passes)
         if self.rt_path == 'transit' and self._one_pass() and cont is None:
@@ -2223,6 +2266,8 @@ class TableSpectrum:
             spectra = table_transit_batch(self.etable, self.ttable, temps[w0:w1], dens[w0:w1],
                                           path, rad, self.rstar, self.itop, self.nlayers,
                                           self.maxdepth)
+            if spectra_out is not None:
+                spectra_out[w0:w1].copy_(spectra)
             bands.integrate_batch(spectra, out[w0:w1], **okw)
             return
         # (an explicit order on a shape the ordered transit kernel does not take -- more than 128
@@ -2279,6 +2324,8 @@ class TableSpectrum:
                                               temps[w0:w1], self.mu, self.weights, self.itop,
                                               self.nlayers, self.maxdepth,
                                               self.column_order if ordered else None)
+            if spectra_out is not None:
+                spectra_out[w0:w1].copy_(spectra)
             bands.integrate_batch(spectra, out[w0:w1],
                                   None if f_dilution is None else f_dilution[w0:w1].contiguous(),
                                   **okw)
@@ -2308,10 +2355,12 @@ class TableSpectrum:
         else:
             spectra = transit_spectrum_batch(ec, path, rad, self.rstar, self.itop, self.nlayers,
                                              self.maxdepth)
+        if spectra_out is not None:
+            spectra_out[w0:w1].copy_(spectra)
         bands.integrate_batch(spectra, out[w0:w1], **okw)
 
     def _eval_chunk_clouds(self, temps, dens, bands, radius, shared_radius, path1, out, w0, w1,
-                           f_dilution, cargs, okw, clouds):
+                           f_dilution, cargs, okw, clouds, spectra_out=None):
         """_eval_chunk with a cloud deck and / or patchy clouds: the interpolation writes the
         CLEAR ec (every layer: the clear column of a patchy walker may run below any limit taken
         from a cloud-free base model), the deck state and the cloud-type models' factors are one
@@ -2340,6 +2389,8 @@ class TableSpectrum:
             path = path1 if shared_radius else transit_path_device(rad.contiguous(), self.itop)
             spectra = cloudy_transit_batch(ec, path, rad, self.rstar, self.itop, self.maxdepth,
                                            deck=deck, f_patchy=fp, column=order, _terms=terms)
+            if spectra_out is not None:
+                spectra_out[w0:w1].copy_(spectra)
             bands.integrate_batch(spectra, out[w0:w1], **okw)
         else:
             radn = rad.expand(w1 - w0, -1)
@@ -2347,6 +2398,8 @@ class TableSpectrum:
             spectra = cloudy_emission_batch(ec, intervals, self.wn_ordered if ordered else self.wn,
                                             t, self.mu, self.weights, self.itop, self.maxdepth,
                                             deck=deck, f_patchy=fp, column=order, _terms=terms)
+            if spectra_out is not None:
+                spectra_out[w0:w1].copy_(spectra)
             bands.integrate_batch(spectra, out[w0:w1],
                                   None if f_dilution is None else f_dilution[w0:w1].contiguous(),
                                   **okw)
