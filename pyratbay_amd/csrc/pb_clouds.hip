@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kBlock) void k_deck_state(
 
 // ---------------------------------------------------------------------------
 // The factors of the cloud-type rank-1 models, with the expressions of k_cont_plan / k_cont_rows
-// (pb_batch.hip), which form the same models when they go into ec.
+// (pb_interp.hip), which form the same models when they go into ec.
 // ---------------------------------------------------------------------------
 struct PlanArgs {
     double *f, *rows;
@@ -220,7 +220,7 @@ __device__ __forceinline__ void cloud_store(const CloudArgs &a, int w, int col, 
 }
 
 // ---------------------------------------------------------------------------
-// Transit: the pass of k_transit_fused (pb_batch.hip; optic_depth.py:103-112 with the early exit
+// Transit: the pass of k_transit_fused (pb_transit.hip; optic_depth.py:103-112 with the early exit
 // of _trapezoid.c:259-273, radiative_transfer.py:57-71) for the two columns of a walker.
 // thread = column; the impact parameters are taken kRows at a time, the ray-path segments of the
 // block staged in LDS ([segment][row], zero where segment >= row).  kTwo: ec_cloud != 0, the

@@ -13,17 +13,8 @@
 
 #include "pb_common.h"
 #include "pb_planck.h"
+#include "pb_transit.h"
 #include "pb_two_stream.h"
-
-int pb_transit_fused_launch(double *depth_d, int32_t *ideep_d, double *spectrum_d,
-                            const double *ec_d, const double *raypath_d, const double *radius_d,
-                            int64_t npath, double rstar, int itop, int ibottom, double maxdepth,
-                            int nlayers, int nwave, int nwalkers, int deck_row, double rsurf,
-                            hipStream_t s, double *work_d, const int32_t *scatter_d = nullptr,
-                            const int32_t *tile_limit_d = nullptr, int32_t *flags_d = nullptr,
-                            const int32_t *gate_d = nullptr);
-int pb_path_blocks_launch(double **blocked_d, int64_t *len, const double *raypath_d, int64_t npath,
-                          int rows, int nimpact, hipStream_t s);
 
 namespace {
 
@@ -890,15 +881,30 @@ static int transit_launch(double *depth_d, int32_t *ideep_d, double *spectrum_d,
     const int deck_row0 = deck_itop > itop ? deck_itop - itop : -1;
     // One spectrum: two kernels (tau for every row with grid.y over blocks of impact parameters,
     // then the early exit): a single grid of columns has too few wavefronts for the fused
-    // one-pass kernel of pb_batch.hip (C2: 155 us fused against 97 us), which is what the
+    // one-pass kernel of pb_transit.hip (C2: 155 us fused against 97 us), which is what the
     // walker-batched path uses.  PB_TRANSIT=fused|split forces one form (tests compare them).
     const char *mode = getenv("PB_TRANSIT");
     const bool fused = mode ? !strcmp(mode, "fused") : false;
-    if (fused)
-        return pb_transit_fused_launch(depth_d, ideep_d, spectrum_d, ec_d, raypath_d, radius_d,
-                                       ((int64_t)nrow * (nrow - 1)) / 2, rstar, itop, ibottom,
-                                       maxdepth, nlayers, nwave, 1, deck_row0, deck_rsurf,
-                                       pb::as_stream(stream), nullptr);
+    if (fused) {
+        TransitCall c;
+        c.depth = depth_d;
+        c.ideep = ideep_d;
+        c.spectrum = spectrum_d;
+        c.ec = ec_d;
+        c.raypath = raypath_d;
+        c.radius = radius_d;
+        c.npath = ((int64_t)nrow * (nrow - 1)) / 2;
+        c.rstar = rstar;
+        c.itop = itop;
+        c.ibottom = ibottom;
+        c.maxdepth = maxdepth;
+        c.nlayers = nlayers;
+        c.nwave = nwave;
+        c.nwalkers = 1;
+        c.deck_row = deck_row0;
+        c.rsurf = deck_rsurf;
+        return pb_transit_fused_launch(c, pb::as_stream(stream));
+    }
     const bool narrow = nwave <= kNarrowColumns;
     const int rows = narrow ? kRowsPerThreadNarrow : kRowsPerThread;
     const int threads = narrow ? 64 : kBlock;

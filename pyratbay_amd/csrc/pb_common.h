@@ -200,7 +200,7 @@ __device__ inline double deck_integrand(double f_above, double f_below, double r
     return slope * (rsurf - r_below) + f_below;
 }
 
-// The layers nobody reads of a retrieval batch with ordered columns (pb_batch.hip, above
+// The layers nobody reads of a retrieval batch with ordered columns (pb_interp.hip, above
 // k_interp_ec_batch): limits per block of 256 columns, the repair pass's gate.
 struct TileLimit {
     const int32_t *tile;      // [ceil(nwave / 256)] last row tile available, or null: every layer

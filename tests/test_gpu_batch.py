@@ -533,6 +533,39 @@ def test_transit_on_the_matrix_cores(eng, orc, monkeypatch, nlayers, nwave, itop
         assert len(stops) >= 2          # exits in several row tiles
 
 
+@pytest.mark.parametrize('nwave,pair', [(16384, False), (16385, True)])
+def test_transit_beyond_the_matrix_cores_size_rule(eng, orc, nwave, pair):
+    """More than 128 impact parameters: the default selection leaves the matrix cores, and the size
+    rule of plan_transit decides with no variable set -- up to 32768 columns in all 8 rows per
+    block (k_transit_fused, products then sums), beyond that 16 rows and k_transit_pair (fused
+    multiply-adds).  Both sides of the rule against the oracle's loops and against the call that
+    returns depth (always products then sums: 1e-13 like the other comparisons of the two
+    arithmetics), with columns that leave in different blocks of 16 rows."""
+    rng = np.random.default_rng(17)
+    nlayers, itop, nw = 130, 0, 2
+    assert (nwave * nw > 32768) == pair
+    c = cases.column_case(seed=19, nlayers=nlayers, nwave=nwave)
+    # spread the crossing layer over the whole column: scale every column by its own factor
+    scale = 10.0**rng.uniform(-3, 3, nwave)
+    ecs = np.array([c['ec'] * scale * 10.0**rng.uniform(-0.3, 0.3) for _ in range(nw)])
+    radius = np.array([np.sort(c['radius'] * (1 + 0.01 * rng.uniform(-1, 1)))[::-1]
+                       for _ in range(nw)])
+    rad_d = eng.dev(radius)
+    path = eng.transit_path_device(rad_d, itop)
+    ec_d = eng.dev(ecs)
+    got = host(eng.transit_spectrum_batch(ec_d, path, rad_d, c['rstar'], itop, nlayers, 10.0))
+    spec, _, _ = eng.transit_spectrum_batch(ec_d, path, rad_d, c['rstar'], itop, nlayers, 10.0,
+                                            want_depth=True)
+    np.testing.assert_allclose(got, host(spec), rtol=1e-13)
+    stops = set()
+    for w in range(nw):
+        wd, wi = orc.optical_depth_transit(ecs[w], radius[w], itop, nlayers, 10.0)
+        ws = orc.transmission(wd, radius[w], c['rstar'], wi, itop)
+        np.testing.assert_allclose(got[w], ws, rtol=RTOL)
+        stops |= set(np.unique(wi // 16))
+    assert len(stops) >= 2              # the early exit is taken, in several blocks of rows
+
+
 @pytest.mark.gpu_experiments
 @pytest.mark.parametrize('nlayers,nwave,itop,nmol', [(80, 1000, 0, 4), (80, 131, 2, 4),
                                                       (17, 99, 0, 1), (48, 40, 5, 3),
