@@ -19,6 +19,8 @@ from collections.abc import Iterable
 
 import numpy as np
 
+from ._device import dev, require_gpu
+
 # pyratbay.constants: k = sc.k * 1e7, G = sc.G * 1e3, sc.N_A, bar
 K_BOLTZ = 1.380649e-23 * 1e7
 G_GRAV = 6.67430e-11 * 1e3
@@ -654,7 +656,6 @@ class WalkerAtmosphere:
 
     def _build_struct(self):
         import torch
-        from .engine import dev, require_gpu
         require_gpu()
         if self._dev is None:
             d = {}

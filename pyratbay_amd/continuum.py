@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ._capi import call, hptr
-from .engine import dev, _ptr, _stream
+from ._device import dev, _ptr, _stream
 
 # pyratbay/constants/astrophysical_constants.py:67-131 (scipy.constants, CODATA 2018)
 H = 6.62607015e-27

@@ -28,11 +28,15 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from ._device import dev, profiler_range, side_streams
+from .columns import pack_raypath, transit_path, transit_spectrum
+from .lbl import LBL, LineList, VoigtTable
+from .spectrum import LBLSpectrum
+
 
 def _range(name):
-    """rocTX range around a collective (engine.profiler_range; the import is deferred so that the
-    gloo tests of this module run without the HIP library)."""
-    from .engine import profiler_range
+    """rocTX range around a collective on device tensors (_coll_range: the gloo tests of this
+    module, which run without the HIP library, get _NoRange)."""
     return profiler_range(name)
 
 
@@ -302,15 +306,13 @@ class LayerShardedTransit:
     all-to-all, wavenumber-sharded optical depth + transmission, one all-gather."""
 
     def __init__(self, case, world, rank, group=None, voigt=None, lines=None):
-        from . import engine
-        self.engine = engine
         self.world, self.rank, self.group = world, rank, group
         g, atm, iso = case['grid'], case['atm'], case['iso']
         self.nwave, self.nlayers = g['nwave'], atm['nlayers']
         self.layers = np.arange(rank, self.nlayers, world)
         self.lp = -(-self.nlayers // world)
-        self.model = engine.LBLSpectrum(case, rt_path='transit', voigt=voigt,
-                                        lines=lines)                  # full grid, full plan
+        self.model = LBLSpectrum(case, rt_path='transit', voigt=voigt,
+                                 lines=lines)                  # full grid, full plan
         idx = torch.as_tensor(self.layers, device='cuda')
         self.temp = self.model.temp[idx].contiguous()
         self.dens = self.model.dens[idx].contiguous()
@@ -333,7 +335,7 @@ class LayerShardedTransit:
         self.isoz.copy_(self.model.isoz[:, self._idx])
 
     def step(self):
-        m, e = self.model, self.engine
+        m = self.model
         n = len(self.layers)
         if n:
             if m.resolution:
@@ -342,7 +344,7 @@ class LayerShardedTransit:
         ec_cols, _ = layer_exchange(self.ec.view(self.lp, self.nwave), self.nlayers,
                                     self.nwave, self.world, self.rank, self.group,
                                     self.buffers)
-        spec, self.depth, self.ideep = e.transit_spectrum(
+        spec, self.depth, self.ideep = transit_spectrum(
             ec_cols, m.raypath, m.radius, m.rstar, m.itop, self.nlayers, m.maxdepth)
         return self.gather(spec)
 
@@ -356,7 +358,7 @@ class LayerShardedTransit:
 
     def _consume(self, ec_cols):
         m = self.model
-        spec, self.depth, self.ideep = self.engine.transit_spectrum(
+        spec, self.depth, self.ideep = transit_spectrum(
             ec_cols, m.raypath, m.radius, m.rstar, m.itop, self.nlayers, m.maxdepth)
         return spec
 
@@ -482,8 +484,6 @@ class StackedShard:
     split pinned (PB_STAGE_SPLIT)"""
 
     def __init__(self, case, stack, wbegin=0, wcount=None, itop=0, voigt=None, lines=None):
-        from . import engine
-        self.engine = engine
         g, atm, ln, iso, vg = (case[k] for k in ('grid', 'atm', 'lines', 'iso', 'voigt'))
         assert g.get('resolution') is None and not g.get('interpolate'), \
             'StackedShard: constant-step grids (the interpolating modes plan per layer)'
@@ -492,20 +492,19 @@ class StackedShard:
         self.wbegin = wbegin
         self.wcount = self.nwave - wbegin if wcount is None else wcount
         self.maxdepth, self.rstar = case['maxdepth'], float(atm['rstar'])
-        self.voigt = voigt or engine.VoigtTable.build(vg['lorentz'], vg['doppler'], vg['size'],
-                                                      g['ownstep'], g['wnosamp'])
-        self.lines = lines or engine.LineList(ln['lwn'], ln['elow'], ln['gf'], ln['lid'],
-                                              len(iso['isomass']), g['own'])
+        self.voigt = voigt or VoigtTable.build(vg['lorentz'], vg['doppler'], vg['size'],
+                                               g['ownstep'], g['wnosamp'])
+        self.lines = lines or LineList(ln['lwn'], ln['elow'], ln['gf'], ln['lid'],
+                                       len(iso['isomass']), g['own'])
         K, L = self.stack, self.nlayers
-        self.lbl = engine.LBL(self.voigt, self.lines, g['wn'], g['divisors'], atm['mol_radius'],
-                              atm['mol_mass'], iso['isoimol'], iso['isomass'], iso['isoratio'],
-                              iso['isoiext'], vg['cutoff'], case['ethresh'], max_layers=K * L)
-        dev = engine.dev
+        self.lbl = LBL(self.voigt, self.lines, g['wn'], g['divisors'], atm['mol_radius'],
+                       atm['mol_mass'], iso['isoimol'], iso['isomass'], iso['isoratio'],
+                       iso['isoiext'], vg['cutoff'], case['ethresh'], max_layers=K * L)
         self.temp = dev(np.concatenate([atm['temp']] * K))
         self.dens = dev(np.concatenate([atm['dens']] * K))
         self.isoz = dev(np.concatenate([iso['isoz']] * K, axis=1))
         self.radius = [dev(atm['radius']) for _ in range(K)]
-        path = engine.pack_raypath(engine.transit_path(atm['radius'], itop), itop)
+        path = pack_raypath(transit_path(atm['radius'], itop), itop)
         self.raypath = [dev(path) for _ in range(K)]
         self.ec = torch.empty((K * L, 1, self.wcount), dtype=torch.float64, device='cuda')
         self.spectrum_out = [None] * K      # gather slots ([wcount] tensors) or None
@@ -514,18 +513,18 @@ class StackedShard:
 
     def set_atmosphere(self, k, temp, dens, isoz, radius=None):
         """Atmosphere k of the stack for the next run() (arguments as LBLSpectrum.set_atmosphere)."""
-        e, L = self.engine, self.nlayers
-        self.temp[k * L:(k + 1) * L].copy_(e.dev(temp))
-        self.dens[k * L:(k + 1) * L].copy_(e.dev(dens))
-        self.isoz[:, k * L:(k + 1) * L].copy_(e.dev(isoz))
+        L = self.nlayers
+        self.temp[k * L:(k + 1) * L].copy_(dev(temp))
+        self.dens[k * L:(k + 1) * L].copy_(dev(dens))
+        self.isoz[:, k * L:(k + 1) * L].copy_(dev(isoz))
         if radius is not None:
-            self.radius[k].copy_(e.dev(radius))
-            self.raypath[k].copy_(e.dev(e.pack_raypath(e.transit_path(radius, self.itop),
-                                                       self.itop)))
+            self.radius[k].copy_(dev(radius))
+            self.raypath[k].copy_(dev(pack_raypath(transit_path(radius, self.itop),
+                                                   self.itop)))
 
     def run(self):
         """-> the K spectra (device tensors [wcount]; the gather slots when given)."""
-        e, K, L = self.engine, self.stack, self.nlayers
+        K, L = self.stack, self.nlayers
         if self.kmax_exchange is not None:
             self.lbl.extinction_begin(self.temp, self.dens, self.isoz, add=True, out=self.ec,
                                       wbegin=self.wbegin, wcount=self.wcount)
@@ -535,7 +534,7 @@ class StackedShard:
             self.lbl.extinction(self.temp, self.dens, self.isoz, add=True, out=self.ec,
                                 wbegin=self.wbegin, wcount=self.wcount)
         for k in range(K):
-            self.spectra[k], _, _ = e.transit_spectrum(
+            self.spectra[k], _, _ = transit_spectrum(
                 self.ec[k * L:(k + 1) * L].view(L, self.wcount), self.raypath[k], self.radius[k],
                 self.rstar, self.itop, L, self.maxdepth, out=self.spectrum_out[k])
         return self.spectra
@@ -568,7 +567,6 @@ class ShardPipeline:
 
     def __init__(self, case, world, rank, depth=2, group=None, kmax_exchange=True,
                  voigt=None, lines=None, rt_path='transit', stack=1, **model_kw):
-        from . import engine
         nwave = case['grid']['nwave']
         self.world, self.rank, self.group = world, rank, group
         self.stack = int(stack)
@@ -589,7 +587,7 @@ class ShardPipeline:
                     m.kmax_exchange = kmax_allreduce(group)
                 if world > 1:
                     m.spectrum_out = g.slots
-            self.streams = engine.side_streams(depth)
+            self.streams = side_streams(depth)
             self.done = [None] * depth
             self.count = 0
             self.pending = None
@@ -598,16 +596,16 @@ class ShardPipeline:
                         for _ in range(depth)]
         g0 = self.gathers[0]
         kw = dict(rt_path=rt_path, wbegin=g0.wbegin, wcount=g0.wcount, **model_kw)
-        first = engine.LBLSpectrum(case, voigt=voigt, lines=lines, **kw)
-        self.models = [first] + [engine.LBLSpectrum(case, voigt=first.voigt, lines=first.lines,
-                                                    **kw) for _ in range(depth - 1)]
+        first = LBLSpectrum(case, voigt=voigt, lines=lines, **kw)
+        self.models = [first] + [LBLSpectrum(case, voigt=first.voigt, lines=first.lines,
+                                             **kw) for _ in range(depth - 1)]
         for m, g in zip(self.models, self.gathers):
             m.lbl.set_concurrency(depth)
             if kmax_exchange and world > 1:
                 m.kmax_exchange = kmax_allreduce(group)
             if world > 1 and rt_path == 'transit' and getattr(m, 'materialize_depth', True):
                 m.spectrum_out = g.slot      # the shard goes straight into the gather buffer
-        self.streams = engine.side_streams(depth)
+        self.streams = side_streams(depth)
         self.done = [None] * depth
         self.count = 0
         self.pending = None          # (context, shard) whose all-gather has not been issued yet

@@ -7,7 +7,8 @@ re-upload them."""
 import numpy as np
 import torch
 
-from .. import engine
+from ..columns import interp_ec as _interp_ec
+from ..lbl import LBL, LineList, VoigtTable
 from . import _np
 
 _cache = {}
@@ -130,7 +131,7 @@ def _voigt(profile, psize, pindex, lorentz, doppler, osamp):
         old = _cache.pop('voigt', None)
         if old is not None:
             old.close()
-        _cache['voigt'] = engine.VoigtTable.from_flat(
+        _cache['voigt'] = VoigtTable.from_flat(
             _np.f64(profile), _np.read_int(psize), _np.read_int(pindex), _np.f64(lorentz),
             _np.f64(doppler), osamp, keep_flat=False)
         _cache['voigt_key'] = key
@@ -144,8 +145,8 @@ def _lines(lwn, elow, gf, lID, niso, own):
         old = _cache.pop('lines', None)
         if old is not None:
             old.close()
-        _cache['lines'] = engine.LineList(_np.f64(lwn), _np.f64(elow), _np.f64(gf),
-                                          _np.read_int(lID), niso, _np.f64(own))
+        _cache['lines'] = LineList(_np.f64(lwn), _np.f64(elow), _np.f64(gf),
+                                   _np.read_int(lID), niso, _np.f64(own))
         _cache['lines_key'] = key
         _cache.pop('lbl_key', None)
     return _cache['lines']
@@ -174,10 +175,10 @@ def extinction(ext, profile, psize, pindex, lorentz, doppler, wn, own, divisors,
         old = _cache.pop('lbl', None)
         if old is not None:
             old.close()
-        _cache['lbl'] = engine.LBL(voigt, lines, wn, div, _np.f64(molrad), _np.f64(molmass),
-                                   _np.read_int(isoimol), _np.f64(isomass),
-                                   _np.f64(isoratio), iext, float(cutoff), float(ethresh),
-                                   resolution=bool(resolution), max_layers=1)
+        _cache['lbl'] = LBL(voigt, lines, wn, div, _np.f64(molrad), _np.f64(molmass),
+                            _np.read_int(isoimol), _np.f64(isomass),
+                            _np.f64(isoratio), iext, float(cutoff), float(ethresh),
+                            resolution=bool(resolution), max_layers=1)
         _cache['lbl_key'] = key
         _cache.pop('iext', None)
     lbl = _cache['lbl']
@@ -204,8 +205,8 @@ def extinction(ext, profile, psize, pindex, lorentz, doppler, wn, own, divisors,
 def _interp(extinction_, etable, ttable, temperatures, density, lay1, lay2, per_mol):
     ext_d = _np.dev(_np.f64(extinction_))
     et = _np.dev(_np.f64(etable))
-    engine.interp_ec(ext_d, et, _np.dev(_np.f64(ttable)), _np.dev(_np.f64(temperatures)),
-                     _np.dev(_np.f64(density)), int(lay1), int(lay2), per_mol)
+    _interp_ec(ext_d, et, _np.dev(_np.f64(ttable)), _np.dev(_np.f64(temperatures)),
+               _np.dev(_np.f64(density)), int(lay1), int(lay2), per_mol)
     extinction_[...] = _np.host(ext_d)
     return 1
 

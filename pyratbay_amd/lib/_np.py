@@ -4,12 +4,8 @@ import ctypes
 import numpy as np
 import torch
 
-from .. import engine
 from .._capi import call                      # noqa: F401  (re-export)
-
-dev = engine.dev
-ptr = engine._ptr
-stream = engine._stream
+from .._device import dev, _ptr as ptr, _stream as stream     # noqa: F401  (re-export)
 
 
 def f64(a):

@@ -2,7 +2,7 @@
 import numpy as np
 import torch
 
-from .. import engine
+from ..columns import intensity as _intensity
 from . import _np
 from ._np import call, ptr, stream
 
@@ -77,6 +77,6 @@ def optdepth(data, intervals, taumax, ideep, ilay):
 def intensity(tau, ideep, planck, mu, rtop):
     """intensity(tau, ideep, planck, mu, rtop) -> new [nmu, nwave]
     (src_c/_trapezoid.c:304-341)"""
-    out = engine.intensity(_np.dev(_np.f64(tau)), _np.idev(ideep), _np.dev(_np.f64(planck)),
-                           _np.dev(_np.f64(mu)), int(rtop))
+    out = _intensity(_np.dev(_np.f64(tau)), _np.idev(ideep), _np.dev(_np.f64(planck)),
+                     _np.dev(_np.f64(mu)), int(rtop))
     return _np.host(out)

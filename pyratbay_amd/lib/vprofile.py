@@ -1,7 +1,7 @@
 """pyratbay.lib.vprofile (src_c/vprofile.c:42-114) on the GPU."""
 import numpy as np
 
-from .. import engine
+from ..lbl import VoigtTable
 from . import _np
 
 
@@ -12,8 +12,8 @@ def grid(profile, psize, index, lorentz, doppler, dwn, verb):
     `psize` to the size of the previous Doppler column and writes the start `index` of
     each profile -- all in place, as the reference."""
     size_in = _np.read_int(psize)
-    table = engine.VoigtTable.build(_np.f64(lorentz), _np.f64(doppler), size_in, float(dwn),
-                                    1, keep_flat=True)
+    table = VoigtTable.build(_np.f64(lorentz), _np.f64(doppler), size_in, float(dwn),
+                             1, keep_flat=True)
     if profile.dtype != np.float64:
         raise TypeError('profile must be a float64 array')
     if profile.size < table.nprofile:

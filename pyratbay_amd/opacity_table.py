@@ -12,7 +12,9 @@ units).
 import numpy as np
 import torch
 
-from . import engine
+from ._capi import call
+from ._device import _ptr, _stream, dev, require_gpu
+from .table import TableSpectrum
 from .synth import BAR, K_B
 
 UNITS = {
@@ -25,7 +27,7 @@ UNITS = {
 
 def compute_opacity(lbl, temp_grid, press_bar, vmr, iso_pf, chunk_bytes=8 << 30,
                     out=None):
-    """lbl: engine.LBL plan (built with max_layers >= the chunk size; a plan of the `resolution`
+    """lbl: lbl.LBL plan (built with max_layers >= the chunk size; a plan of the `resolution`
     mode -- the usual grid of such tables -- should have set_gather_mode('dynamic'): the cells of
     a chunk are then walked in runs of equal oversampling factor on the layers' dynamic grids,
     5x the direct gather);
@@ -51,8 +53,8 @@ def compute_opacity(lbl, temp_grid, press_bar, vmr, iso_pf, chunk_bytes=8 << 30,
     flat = out.view(rows, ncell, lbl.nwave)
     for c0 in range(0, ncell, step):
         c1 = min(c0 + step, ncell)
-        ext = lbl.extinction(engine.dev(temps[c0:c1]), engine.dev(dens[c0:c1]),
-                             engine.dev(z[:, c0:c1]), add=False)     # [cells, rows, W]
+        ext = lbl.extinction(dev(temps[c0:c1]), dev(dens[c0:c1]),
+                             dev(z[:, c0:c1]), add=False)     # [cells, rows, W]
         flat[:, c0:c1] = ext.permute(1, 0, 2)
     return out
 
@@ -146,8 +148,8 @@ class CrossSections:
         self.tmin, self.tmax = float(np.amin(temp)), float(np.amax(temp))
 
     def table_spectrum(self, radius, rstar, **kw):
-        """An engine.TableSpectrum on this table (the path of Pyrat.eval())."""
-        return engine.TableSpectrum(self.cs_table, self.temp, self.wn, radius, rstar, **kw)
+        """A table.TableSpectrum on this table (the path of Pyrat.eval())."""
+        return TableSpectrum(self.cs_table, self.temp, self.wn, radius, rstar, **kw)
 
 
 def load_cross_sections(cs_files, temperature=None, pressure=None, min_wn=None, max_wn=None,
@@ -188,7 +190,7 @@ def load_cross_sections(cs_files, temperature=None, pressure=None, min_wn=None, 
         index.append(species.index(sp))
         masks.append(mask)
         grids.append((np.asarray(ttab, float), np.asarray(ptab, float)))
-    engine.require_gpu()
+    require_gpu()
     table = torch.zeros((len(species), len(temp), len(press), len(wn)), dtype=torch.float64,
                         device='cuda')
     for f, idx, mask, (ttab, ptab) in zip(cs_files, index, masks, grids):
@@ -211,13 +213,13 @@ def load_cross_sections(cs_files, temperature=None, pressure=None, min_wn=None, 
             tlo, ta = np.arange(len(temp), dtype=np.int32), np.zeros(len(temp))
         wsel = np.flatnonzero(mask)[::wl_thinning].astype(np.int32)
         # (named, so that every upload outlives the call: a c_void_p does not keep its tensor)
-        cs_d, dst = engine.dev(cs), table[idx]
-        wsel_d, tlo_d, plo_d = (engine.dev(x, torch.int32) for x in (wsel, tlo, plo))
-        ta_d, pa_d = engine.dev(ta), engine.dev(pa)
-        engine.call('pb_resample_cross_section', engine._ptr(dst), engine._ptr(cs_d),
-                    engine._ptr(wsel_d), engine._ptr(tlo_d), engine._ptr(ta_d),
-                    engine._ptr(plo_d), engine._ptr(pa_d), cs.shape[0], cs.shape[1],
-                    cs.shape[2], len(temp), len(press), len(wn), int(resample), 1,
-                    engine._stream())
+        cs_d, dst = dev(cs), table[idx]
+        wsel_d, tlo_d, plo_d = (dev(x, torch.int32) for x in (wsel, tlo, plo))
+        ta_d, pa_d = dev(ta), dev(pa)
+        call('pb_resample_cross_section', _ptr(dst), _ptr(cs_d),
+             _ptr(wsel_d), _ptr(tlo_d), _ptr(ta_d),
+             _ptr(plo_d), _ptr(pa_d), cs.shape[0], cs.shape[1],
+             cs.shape[2], len(temp), len(press), len(wn), int(resample), 1,
+             _stream())
         torch.cuda.synchronize()
     return CrossSections(np.array(species), temp, press, wn, table)

@@ -16,6 +16,9 @@ import collections
 
 import numpy as np
 
+from . import _capi
+from ._device import _ptr, _stream, dev, require_gpu
+
 # the median and the bounds of the central 68.27 % and 95.45 %, in the reference's order
 # (retrieval_tools.py:454)
 QUANTILES = [0.5, 0.15865, 0.84135, 0.02275, 0.97725]
@@ -95,8 +98,6 @@ def weighted_quantiles(values, counts, q, total=None):
     sum of the counts when the caller knows it; None: it is read back from the device (the one
     synchronisation of this function; the ranks are formed on the host, once per call)."""
     import torch
-    from . import _capi
-    from .engine import _ptr, _stream, dev, require_gpu
     require_gpu()
     if not isinstance(values, torch.Tensor) or not values.is_cuda or \
             values.dtype != torch.float64 or values.dim() < 1:
@@ -141,7 +142,6 @@ def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTI
     """TableSpectrum.posterior_summary: see there."""
     import torch
     from .atmosphere import BAR, K_BOLTZ
-    from .engine import dev, require_gpu
     require_gpu()
     quantiles = [float(x) for x in np.atleast_1d(quantiles)]
     quantile_ranks(1, quantiles)                                  # (range check)

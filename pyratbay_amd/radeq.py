@@ -25,7 +25,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import atmosphere as pa
+from . import _capi, atmosphere as pa
+from ._device import _ptr, _stream, dev, require_gpu
+from .batch import interp_ec_batch
+from .columns import internal_flux
 
 SIGMA_SB = 5.6703744191844314e-08 * 1e3     # pc.sigma = sc.sigma * 1e3 (erg s-1 cm-2 K-4)
 MAXF = 1.0e08                               # maximum temperature scale factor
@@ -142,13 +145,12 @@ class RadeqStruct(C.Structure):
 
 def net_parts(nwave):
     """Number of parts pb_two_stream_net_batch writes per (profile, direction, layer)."""
-    from . import _capi
     return int(_capi.lib().pb_two_stream_net_parts(int(nwave)))
 
 
 def two_stream_net_batch(ec, intervals, wn, trapz_weights, temps, f_int=None, flux_top=None,
                          out=None, parts=None, work=None):
-    """engine.two_stream_batch that also integrates every layer's fluxes over wavenumber:
+    """batch.two_stream_batch that also integrates every layer's fluxes over wavenumber:
     ec[nw, L, W] (consumed), intervals[nw, L - 1], wn[W], trapz_weights[W]
     (trapezoid_weights(wn)), temps[nw, L]; f_int / flux_top: [W] shared by the profiles,
     [nw, W] per profile, or None.  Returns (flux_up[0] [nw, W], parts[nw, nparts, 2, L]): summed
@@ -156,8 +158,6 @@ def two_stream_net_batch(ec, intervals, wn, trapz_weights, temps, f_int=None, fl
     (pb_two_stream_net_batch).  Device tensors; out, parts and work (at least
     pb_two_stream_net_work_doubles(L, W, nw) doubles) are allocated here when None."""
     import torch
-    from . import _capi
-    from .engine import _ptr, _stream
     nw, nlayers, nwave = ec.shape
     assert ec.is_contiguous() and temps.shape == (nw, nlayers)
     assert nlayers == 1 or intervals.shape == (nw, nlayers - 1)
@@ -306,8 +306,6 @@ class RadiativeEquilibrium:
         """Everything the loop touches, once per object: device copies of the constants, the
         state, and the buffers of the three launches."""
         import torch
-        from . import _capi
-        from .engine import dev, internal_flux, require_gpu
         require_gpu()
         m, L, W = self.model, self.nlayers, self.nwave
         d = {}
@@ -385,8 +383,6 @@ class RadiativeEquilibrium:
         [nw, nsamples] in .history (device-to-device copies on the stream, still nothing read
         back)."""
         import torch
-        from . import _capi
-        from .engine import _stream, interp_ec_batch
         L = self.nlayers
         nsamples = int(nsamples)
         _check(nsamples >= 0, f'nsamples = {nsamples}')

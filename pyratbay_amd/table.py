@@ -1,0 +1,725 @@
+"""Retrieval inner loop on sampled cross sections: TableSpectrum, and the three steps of its
+batched form eval_bands -- validate (BatchCall), plan (plan_eval_bands -> BatchPlan: which form a
+chunk runs, decided once per call by a pure function) and run (_eval_chunk: one step per stage).
+The batch wrappers are looked up in the module `batch` at call time."""
+import contextlib
+import os
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _capi, batch, posterior
+from ._capi import call
+from ._device import StageTimer, _ptr, _stream, dev, require_gpu, side_streams
+from .bands import HiresData
+from .batch import _check_walker_tensor
+from .columns import (RT_PATHS, default_quadrature, emission_flux, internal_flux, interp_ec,
+                      pack_raypath, plane_parallel_optical_depth, transit_path,
+                      transit_path_device, transit_spectrum, two_stream)
+from .radeq import RadiativeEquilibrium
+
+
+# What the caller of eval_bands gave, validated and filled by name (TableSpectrum._batch_call).
+# radius is [1, L] when shared_radius; out[nw, nbands] receives the result; cloudy: the call takes
+# the cloud form; tmin / tmax: the temperatures outside which a walker is rejected; path1: the ray
+# path of a shared radius in transit geometry (set once the column order is settled).
+BatchCall = namedtuple('BatchCall', (
+    'temps dens bands radius shared_radius f_dilution continuum_density continuum_pars '
+    'alkali_density rv deck_logp f_patchy spectra_out out nw cloudy tmin tmax path1'),
+    defaults=(None,))
+
+# Which kernels the chunks of one eval_bands call run (plan_eval_bands).  form: 'one_pass',
+# 'two_stream', 'emission', 'transit' or 'clouds'; table / wn / column name the attributes of the
+# model a chunk reads (column None: grid order).
+BatchPlan = namedtuple('BatchPlan', 'form ordered limited table wn column may_auto_order')
+
+# The walkers [w0, w1) of a BatchCall: n = w1 - w0 and views, nothing launched (the ray paths and
+# the layer intervals are formed by the radiative-transfer step, after the interpolation).  rad:
+# the chunk's radius rows, or the shared row [1, L]; ckw: the continuum keywords of interp_ec_batch.
+ChunkInputs = namedtuple('ChunkInputs',
+                         'n temps dens rad ckw rv f_dilution deck_logp f_patchy')
+
+
+def ordered_supported(rt_path, nlayers, itop, nwave):
+    """Whether the depth-ordered kernels exist for a shape: the transit form is the matrix-core
+    kernel only (pb_transit_spectrum_ordered: 2 ... 128 impact parameters, i.e.
+    2 <= nlayers - itop <= 128); the emission form has no limit."""
+    if rt_path != 'transit':
+        return True
+    return 2 <= nlayers - itop <= 128 and nwave >= 2
+
+
+def plan_eval_bands(facts, call_facts):
+    """The form of one eval_bands call from plain values -- no device, library or environment
+    access.  facts (the model): rt_path ('transit', 'emission', 'two_stream'), nlayers, itop,
+    nwave, order_set / tile_limit_set (a column order / its layer limits are set), one_pass (the
+    one-pass transit is wanted and the library has it for the shape), continuum (one is
+    attached).  call_facts: cloudy.  (Two-stream with clouds is refused before planning.)"""
+    rt_path = facts['rt_path']
+    # (the one-pass transit takes no continuum: with one attached, the two passes)
+    one_pass = rt_path == 'transit' and facts['one_pass'] and not facts['continuum']
+    form = 'clouds' if call_facts['cloudy'] else 'one_pass' if one_pass else rt_path
+    # (an explicit order on a shape the ordered transit kernel does not take -- more than 128
+    # impact parameters -- is worked in grid order: the spectra do not depend on the order;
+    # two-stream geometry: always grid order -- no stop, nothing to order for)
+    ordered = facts['order_set'] and form not in ('one_pass', 'two_stream') and \
+        ordered_supported(rt_path, facts['nlayers'], facts['itop'], facts['nwave'])
+    # (clouds: the clear column of a patchy walker may run below any limit taken from a
+    # cloud-free base model)
+    limited = ordered and facts['tile_limit_set'] and form != 'clouds'
+    return BatchPlan(form, ordered, limited,
+                     table='etable_ordered' if ordered else 'etable',
+                     wn='wn_ordered' if ordered else 'wn',
+                     column='column_order' if ordered else None,
+                     may_auto_order=facts['nwave'] >= 64 and rt_path != 'two_stream' and
+                     not one_pass)
+
+
+class TableSpectrum:
+    """Retrieval inner loop on sampled cross sections (Line_Sample path,
+    pyratbay/opacity/line_sampling.py:394-463 -> _extcoeff.interp_ec): the table
+    etable[nspec, ntemp, nlayers, nwave] stays resident; each eval() interpolates it to the
+    layer temperatures, weights by the species densities, and runs optical depth + RT.
+
+    column_order='auto' (default) has a ONE-TIME cost in the first eval_bands() call of a model
+    with >= 64 columns: the first walker's temperatures are checked on the host (one stream
+    synchronisation), its spectrum is computed to order the columns by optical depth
+    (order_columns: interpolation + transit/plane-parallel depth + a sort) and a permuted SECOND
+    COPY of the table is made (2 x the table's memory from then on; skipped when
+    1.25 x table + 2 x the batch's ec buffer do not fit in free memory, when the ordered kernels
+    do not support the shape -- transit geometry with more than 128 impact parameters -- or while
+    the stream is being captured into a graph).  Every later call is launch-only.  To keep the first call
+    free of both, call order_columns(temp, dens) yourself during set-up or pass
+    column_order=None (grid order).  In a multi-rank run every rank orders by its own first
+    walker: results do not depend on the order, memory use per rank is the same 2 x table."""
+
+    def __init__(self, etable, ttable, wn, radius, rstar, rt_path='transit', itop=0,
+                 maxdepth=10.0, quadrature_mu=None, quadrature_weights=None, continuum=None,
+                 timestamps=True, column_order='auto', tint=0.0, flux_top=None):
+        require_gpu()
+        # rt_path 'two_stream' / 'emission_two_stream' / 'eclipse_two_stream' (RT_PATHS, as in
+        # LBLSpectrum): the geometry 'two_stream' (pyrat/spectrum.py:454-522) with the internal
+        # flux of tint (K) added at the bottom and flux_top[W], the irradiation
+        # beta_irr * (rstar / smaxis)**2 * starflux the caller forms (host or device; None: none),
+        # at the top.  The optical depth has no maxdepth stop (opacity/optic_depth.py:124-126).
+        self.rt_path_name = rt_path
+        self.observable = None
+        if rt_path in ('two_stream', 'emission_two_stream', 'eclipse_two_stream'):
+            rt_path, self.observable = RT_PATHS[rt_path]
+            if itop != 0:
+                # (layers above itop have dtau0 = 0 and the reference's own statement then gives
+                # 0 * exp1(0) = NaN in every column)
+                raise ValueError(f'rt_path {self.rt_path_name!r}: itop must be 0, got {itop}')
+            maxdepth = float('inf')
+            column_order = None               # (no early exit to order the columns for)
+        elif tint != 0.0 or flux_top is not None:
+            raise ValueError('tint and flux_top belong to the two-stream geometries')
+        self._timer = StageTimer() if timestamps else None
+        # eval_bands: the order the columns are worked in (see order_columns).
+        # 'auto': taken from the first walker of the first batch; None: grid order
+        self.column_order = None
+        self.etable_ordered = None
+        # transit geometry, columns ordered by order_columns(): last row tile a block of 256
+        # ordered columns can need (int32, device) -- see _eval_chunk; None: every layer
+        self.tile_limit = None
+        self.tile_margin = int(os.environ.get('PB_C5_MARGIN', '4'))
+        if isinstance(column_order, str) and column_order == 'auto' and \
+                os.environ.get('PB_COLUMN_ORDER', '1') == '0':
+            column_order = None                       # (A/B switch: grid order)
+        self._auto_order = isinstance(column_order, str) and column_order == 'auto'
+        if isinstance(column_order, str) and not self._auto_order:
+            raise ValueError("column_order: 'auto', None or a permutation of range(nwave)")
+        if column_order is not None and not self._auto_order:
+            self._pending_order = column_order
+        else:
+            self._pending_order = None
+        self.continuum = continuum          # pyratbay_amd.continuum.Continuum or None
+        self._alkali_checked = None         # the Continuum whose alkali models eval_bands has checked
+        # the one-pass transit of eval_bands (_one_pass): True / False, None: PB_TABLE_TRANSIT
+        self.one_pass = None
+        self.etable = etable if isinstance(etable, torch.Tensor) else dev(etable)
+        self.nspec, self.ntemp, self.nlayers, self.nwave = self.etable.shape
+        self.ttable = dev(ttable)
+        self.tmin, self.tmax = float(np.min(ttable)), float(np.max(ttable))
+        self.wn = dev(wn)
+        self.rt_path, self.itop, self.maxdepth = rt_path, itop, maxdepth
+        self.rstar = float(rstar)
+        self.set_radius(radius)
+        if rt_path == 'two_stream':
+            self.f_int = internal_flux(self.wn, tint)
+            self.flux_top = None if flux_top is None else dev(flux_top)
+            if self.flux_top is not None and self.flux_top.shape != (self.nwave,):
+                raise ValueError(f'flux_top must have shape ({self.nwave},), got '
+                                 f'{tuple(self.flux_top.shape)}')
+        elif rt_path != 'transit':
+            if quadrature_mu is None:
+                quadrature_mu, quadrature_weights = default_quadrature()
+            elif quadrature_weights is None:
+                raise ValueError('quadrature_mu needs quadrature_weights')
+            self.mu = dev(quadrature_mu)
+            self.weights = dev(quadrature_weights)
+        self.ec = torch.zeros((self.nlayers, self.nwave), dtype=torch.float64, device='cuda')
+        if self._pending_order is not None:
+            self.set_column_order(self._pending_order)
+
+    def set_column_order(self, order):
+        """Work the columns of eval_bands' batches in the order `order` (a permutation of
+        range(nwave); None: back to grid order).  A second copy of the table is kept with its
+        wavenumber axis in that order, so that every stage still streams contiguous columns."""
+        self.tile_limit = None
+        if order is None:
+            self.column_order = self.etable_ordered = None
+            return
+        order = torch.as_tensor(order, device='cuda').to(torch.int64).contiguous()
+        if order.shape != (self.nwave,) or \
+                not bool(torch.equal(torch.sort(order).values,
+                                     torch.arange(self.nwave, device='cuda'))):
+            raise ValueError('column order: not a permutation of range(nwave)')
+        out = torch.empty_like(self.etable)
+        for s in range(self.nspec):               # (species by species: a bounded temporary)
+            torch.index_select(self.etable[s], -1, order, out=out[s])
+        self.etable_ordered = out
+        self.column_order = order.to(torch.int32)
+        self.wn_ordered = self.wn[order].contiguous()
+
+    def order_columns(self, temp, dens, radius=None):
+        """Order the columns by the layer at which the model (temp[L], dens[L, nspec], radius[L])
+        becomes optically thick (its ideep, _trapezoid.c:259-273).  The reference stops a column
+        there; the matrix-core transit kernel can stop only when all 32 columns of a wavefront
+        have -- which neighbours on the wavenumber grid never do together (a line core next to a
+        window), and columns of similar depth do: at C5's shape 62 % of the products and 76 % of
+        the layer reads remain.  Any model near the ones to come will do (walkers of a retrieval
+        differ by per cent); the spectra do not depend on the order, only the time does."""
+        temp = (temp if isinstance(temp, torch.Tensor) else dev(temp)).reshape(1, -1)
+        dens = (dens if isinstance(dens, torch.Tensor) else dev(dens)).reshape(1, self.nlayers, -1)
+        rad = self.radius if radius is None else \
+            (radius if isinstance(radius, torch.Tensor) else dev(radius))
+        rad = rad.reshape(1, -1).contiguous()
+        ec = batch.interp_ec_batch(self.etable, self.ttable, temp.contiguous(), dens.contiguous())
+        if self.rt_path == 'transit':
+            _, _, ideep = batch.transit_spectrum_batch(
+                ec, transit_path_device(rad, self.itop), rad, self.rstar, self.itop, self.nlayers,
+                self.maxdepth, want_depth=True)
+            ideep = ideep[0]
+        else:
+            # (emission: a wavefront of the fused kernel walks the layers until its last lane has
+            # reached maxdepth -- lanes that stop together waste nothing)
+            _, ideep = plane_parallel_optical_depth(
+                ec[0], (rad[0, :-1] - rad[0, 1:]).contiguous(), self.itop, self.nlayers,
+                self.maxdepth)
+        order = torch.sort(ideep, stable=True).indices
+        self.set_column_order(order)
+        if self.tile_margin >= 0 and self._ordered_supported():
+            # The layers nobody reads: walkers of a retrieval cross maxdepth within a layer or two
+            # of the base model (measured at C5's shape: -1 ... +2 layers), so a block of 256
+            # ordered columns needs the row tiles (transit) / layers (emission) up to the one
+            # holding its deepest base crossing + tile_margin layers -- the interpolation writes
+            # only those (80 % of ec at C5's shape), and a walker that does run past them is
+            # flagged on the device and repaired (see _eval_chunk): the spectra never depend on
+            # the limits.
+            sorted_ideep = ideep[order].to(torch.int64)
+            nblk = -(-self.nwave // 256)
+            pad = nblk * 256 - self.nwave
+            if pad:
+                sorted_ideep = torch.cat([sorted_ideep, sorted_ideep[-1:].expand(pad)])
+            bmax = sorted_ideep.view(nblk, 256).max(dim=1).values
+            ntiles = -(-(self.nlayers - self.itop) // 16)
+            tile = torch.clamp((bmax - self.itop + self.tile_margin) // 16, 0, ntiles - 1)
+            # (worth its two gated repair launches only where it saves something: C5's emission
+            # geometry crosses maxdepth near the bottom and keeps 97 % of the layers)
+            written = torch.clamp(16 * (tile + 1), max=self.nlayers - self.itop).double().mean() / \
+                (self.nlayers - self.itop)
+            if float(written) <= 0.95 or self.tile_margin == 0:
+                self.tile_limit = tile.to(torch.int32).contiguous()
+
+    def set_radius(self, radius):
+        self.radius = dev(radius)
+        if self.rt_path == 'transit':
+            self.raypath = dev(pack_raypath(transit_path(radius, self.itop), self.itop))
+        else:
+            self.intervals = dev(-np.diff(np.asarray(radius, float)))
+
+    def eval(self, temp, dens, continuum_density=None):
+        """temp[L] (K, inside the table's range -- the caller rejects the rest like
+        line_sampling.py:426-427), dens[L, nspec] (molecules cm-3) -> spectrum[W].
+        With a Continuum attached, continuum_density = {species: n[L]} feeds its terms
+        (pyrat/opacity.py:206-257: every model adds to the same ec)."""
+        temp_host = None if isinstance(temp, torch.Tensor) else np.asarray(temp, float)
+        if temp_host is not None and (np.any(temp_host < self.tmin) or
+                                      np.any(temp_host > self.tmax)):
+            raise ValueError(f'temperature outside the {self.tmin:.1f}-{self.tmax:.1f} '
+                             'K range of the table (the reference rejects such a model, '
+                             'line_sampling.py:426-427)')
+        self.temp = temp if isinstance(temp, torch.Tensor) else dev(temp)
+        dens = dens if isinstance(dens, torch.Tensor) else dev(dens)
+        t = self._timer
+        if t is not None:
+            t.start('extinction')
+        interp_ec(self.ec, self.etable, self.ttable, self.temp, dens, 0, self.nlayers,
+                  assign=True)
+        if self.continuum is not None:
+            # the continuum's per-layer factors are prepared on the host: hand it host
+            # temperatures when the caller has them (no device -> host copy in the loop)
+            self.continuum.add(self.ec, temp_host if temp_host is not None
+                               else self.temp.cpu().numpy(), continuum_density)
+        if t is not None:
+            t.mark('extinction', 'odepth')
+        if self.rt_path == 'transit':
+            self.spectrum, self.depth, self.ideep = transit_spectrum(
+                self.ec, self.raypath, self.radius, self.rstar, self.itop, self.nlayers,
+                self.maxdepth)
+        else:
+            self.depth, self.ideep = plane_parallel_optical_depth(
+                self.ec, self.intervals, self.itop, self.nlayers, self.maxdepth)
+            if t is not None:
+                t.mark('odepth', 'spectrum')
+            if self.rt_path == 'two_stream':
+                self.flux_down, self.flux_up = two_stream(self.depth, self.wn, self.temp,
+                                                          self.f_int, self.flux_top, 0)
+                self.spectrum = self.flux_up[0]
+            else:
+                self.spectrum = emission_flux(self.depth, self.ideep, self.wn, self.temp,
+                                              self.mu, self.weights, self.itop)
+        if t is not None:
+            t.mark('spectrum')
+        return self.spectrum
+
+    @property
+    def timestamps(self):
+        """Seconds of the last eval() by stage: 'extinction' (interpolation of the table +
+        continuum terms), 'odepth', 'spectrum' -- the reference's keys (pyrat_obj.py:203-214)."""
+        if self._timer is None:
+            raise _capi.PbError('this model was built with timestamps=False')
+        return self._timer.read()
+
+    def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
+                   f_dilution=None, continuum_density=None, continuum_pars=None, rv=None,
+                   deck_logp=None, f_patchy=None, alkali_density=None, spectra_out=None):
+        """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
+        without the parameter mapping -- eval_params adds it): temps[nw, L], dens[nw, L, nspec] device tensors,
+        optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
+        bands: PassBands on this model's grid -> bandflux[nw, nbands].  Every stage is ONE
+        launch per chunk of walkers -- interp_ec, transit_path, optical depth + transmission,
+        band integration -- with no per-walker Python and no host synchronisation (except the
+        one-time column ordering of the first call with column_order='auto': class docstring).  Walkers
+        whose temperatures leave the table's range get +inf, like eval()'s reject path
+        (pyrat_obj.py:302-320, 378-380).  Emission geometry: f_dilution[nw] = the walkers'
+        dilution factors (pyrat_obj.py:296-297), and bands.set_eclipse(...) for the planet-to-star
+        flux ratios of an eclipse retrieval (pyrat_obj.py:662-665).
+
+        Two-stream geometry (rt_path 'two_stream' / 'emission_two_stream' / 'eclipse_two_stream',
+        pyrat/spectrum.py:454-522): interpolation, then ONE launch for the optical depth without a
+        stop and both sweeps (two_stream_batch), then the bands; f_dilution, set_eclipse, a
+        HiresData with rv, radius[nw, L] and the Continuum's terms and alkali doublets work as in
+        emission geometry.  Always grid order (there is no stop to order the columns for:
+        column_order orders nothing and copies no table); deck_logp, f_patchy and a Continuum with
+        cloud-type models are refused (ValueError: the reference's two-stream ignores the clear
+        column and its deck leaves zero rows below it) -- eval() takes them.
+
+        With a Continuum attached (TableSpectrum(..., continuum=cont)) its terms are added in the
+        store of the interpolation (pb_interp_ec_batch_cont): continuum_density[nw, L, ncs] holds
+        the number densities of cont.species, continuum_pars[nw, npars] the free parameters in
+        cont.free_pars order (None: every walker uses the models' current pars).  A walker outside
+        a CIA table's temperatures is rejected like one outside the table.  Alkali doublets
+        (SodiumVdW, PotassiumVdW) take alkali_density[nw, L, len(cont.alkali)], the number
+        densities of cont.alkali_species in model order (a float64 device tensor): their terms are
+        added in the same store, the Voigt values at the detuning distance formed per walker and
+        layer on the device.  At most 2 alkali models with 4 lines in all; a model whose detuning
+        distance is less than 20 Gaussian widths at the table's lowest temperature (no shipped
+        model: 570 and more) is outside the regime of the device's Faddeeva function.  Both are
+        refused (ValueError), as are alkali models without alkali_density and a Deck without
+        deck_logp; eval() takes them.
+
+        Clouds (pb_clouds.hip; both arguments are device tensors of shape [nw]):
+        deck_logp = log10 of each walker's cloud-deck pressure in bar (needs a Deck in the
+        Continuum; the pressure grid is cont.pressure): the deck's layer, radius and temperature
+        are found on the device (deck_state_batch: clamped at the ends of the grid) and the
+        column ends there.  f_patchy = each walker's cloudy fraction: the spectrum is
+        f cloudy + (1 - f) clear, combined per sample BEFORE the band integration / the
+        instrument profile, where the cloudy column is ec + the terms of the Continuum's
+        cloud_models down to the deck (if any) and the clear column has neither.  f_patchy is
+        CLAMPED to [0, 1] on the device (no host check; NaN gives NaN).  Without f_patchy a deck
+        alone gives the cloudy column; cloud_models without f_patchy likewise.  Both columns come
+        from one kernel on the clear ec (no second ec buffer); it runs in the column order in use
+        but without its layer limits (tile_limit), whatever column_order is: the spectra do not
+        depend on it bit for bit.
+
+        bands may be a HiresData instead (high-resolution spectroscopy, pyrat_obj.py:331-356):
+        the spectra are convolved with the instrument profile, shifted by the walkers' radial
+        velocities rv[nw] (km/s, a device tensor; None: no shift) and sampled at the data in one
+        launch per chunk -> [nw, ndata].  rv with a PassBands is refused (ValueError).
+
+        spectra_out (a contiguous float64 device tensor [nw, nwave]; None: nothing changes)
+        receives every walker's full-resolution spectrum in GRID order, whatever column order is
+        in use: the spectrum a one-walker eval() of this model returns (transit: the modulation
+        spectrum; emission and two-stream: the planet's flux, before f_dilution, the eclipse ratio
+        and the instrument profile, which belong to the bands) -- one copy per chunk on every
+        branch: one-pass, ordered and limited transit, emission, two-stream and clouds.  The rows
+        of rejected walkers hold whatever the kernels made of their inputs."""
+        call_ = self._batch_call(temps, dens, bands, radius, f_dilution, continuum_density,
+                                 continuum_pars, rv, deck_logp, f_patchy, alkali_density,
+                                 spectra_out)
+        nw = call_.nw
+        one_pass = self.rt_path == 'transit' and self._one_pass()
+        plan = plan_eval_bands(self._plan_facts(one_pass), {'cloudy': call_.cloudy})
+        if plan.may_auto_order and self._auto_order and self.column_order is None and nw > 0:
+            self._try_auto_order(call_, chunk)
+            # (the ordering changes column_order and tile_limit: the plan the chunks run is made
+            # after it)
+            plan = plan_eval_bands(self._plan_facts(one_pass), {'cloudy': call_.cloudy})
+        if call_.shared_radius and self.rt_path == 'transit':
+            call_ = call_._replace(
+                path1=transit_path_device(call_.radius[0], self.itop).view(1, -1))
+        # Consecutive chunks are independent: with `streams` > 1 (PB_EVAL_STREAMS) chunk i runs on
+        # side stream i % streams.  Measured at C5's shape and NOT the default: the interpolation
+        # of one chunk beside the optical-depth pass of the previous one gains nothing (two chunks
+        # of 32 on two streams 2.97 ms, one chunk of 64 2.73 ms per 64 walkers): both stages
+        # stream every walker's ec through HBM.
+        nchunks = -(-nw // chunk)
+        if streams is None:
+            streams = int(os.environ.get('PB_EVAL_STREAMS', '1'))
+        streams = max(1, min(streams, nchunks))
+        caller = torch.cuda.current_stream()
+        eval_streams = side_streams(streams) if streams > 1 else []
+        for st in eval_streams:
+            st.wait_stream(caller)
+        for ci, w0 in enumerate(range(0, nw, chunk)):
+            with torch.cuda.stream(eval_streams[ci % streams]) if eval_streams else \
+                    contextlib.nullcontext():
+                self._eval_chunk(plan, call_, w0, min(w0 + chunk, nw))
+        for st in eval_streams:
+            caller.wait_stream(st)
+        # (with CIA tables: the intersection of their temperature ranges and the table's)
+        call('pb_reject_walkers', _ptr(call_.out), _ptr(temps.contiguous()), call_.tmin,
+             call_.tmax, self.nlayers, bands.nbands, nw, _stream())
+        return call_.out
+
+    def _batch_call(self, temps, dens, bands, radius, f_dilution, continuum_density,
+                    continuum_pars, rv, deck_logp, f_patchy, alkali_density, spectra_out):
+        """The arguments of eval_bands, checked and filled -> BatchCall (allocates `out`)."""
+        assert self.rt_path in ('transit', 'emission', 'two_stream'), \
+            'eval_bands: transit, emission or two-stream geometry on sampled cross sections'
+        two_stream_rt = self.rt_path == 'two_stream'
+        if rv is not None:
+            if not isinstance(bands, HiresData):
+                raise ValueError('eval_bands: rv (a radial-velocity shift) needs a HiresData, '
+                                 'pass bands are integrated on the unshifted grid')
+            if tuple(rv.shape) != (temps.shape[0],):
+                raise ValueError(f'eval_bands: rv must have shape {(temps.shape[0],)}, got '
+                                 f'{tuple(rv.shape)}')
+        assert f_dilution is None or self.rt_path in ('emission', 'two_stream'), \
+            'f_dilution: emission geometry'
+        assert f_dilution is None or f_dilution.shape == (temps.shape[0],)
+        nw = temps.shape[0]
+        if spectra_out is not None:
+            _check_walker_tensor('eval_bands: spectra_out', spectra_out, nw,
+                                 shape=(nw, self.nwave))
+            if not spectra_out.is_contiguous():
+                raise ValueError('eval_bands: spectra_out must be contiguous')
+        tmin, tmax = self.tmin, self.tmax
+        cont = self.continuum
+        _check_walker_tensor('eval_bands: deck_logp', deck_logp, nw)
+        _check_walker_tensor('eval_bands: f_patchy', f_patchy, nw)
+        if deck_logp is not None and (cont is None or not cont.deck):
+            raise ValueError('eval_bands: deck_logp needs a Deck among the models of the '
+                             'attached Continuum')
+        if two_stream_rt:
+            # (the reference's two-stream ignores the clear column of a patchy model, and its deck
+            # leaves zero rows below the deck's layer)
+            for name, given in (('deck_logp', deck_logp is not None),
+                                ('f_patchy', f_patchy is not None),
+                                ('a Continuum with cloud-type models',
+                                 cont is not None and bool(cont.cloud))):
+                if given:
+                    raise ValueError(f'eval_bands: {name}: clouds are not supported in batched '
+                                     'form in two-stream geometry; use eval()')
+        # (cloud-type models alone take the cloud path too: the cloudy column is the spectrum)
+        cloudy = deck_logp is not None or f_patchy is not None or \
+            (cont is not None and bool(cont.cloud))
+        if cloudy and radius is not None and (radius.dim() != 2 or
+                                              radius.shape[1] != self.nlayers or
+                                              radius.shape[0] not in (1, nw)):
+            raise ValueError(f'eval_bands: radius must have shape ({nw} or 1, {self.nlayers}), '
+                             f'got {tuple(radius.shape)}')
+        if cont is not None:
+            if alkali_density is not None:
+                if not cont.alkali:
+                    raise ValueError('eval_bands: alkali_density needs an alkali model '
+                                     '(SodiumVdW, PotassiumVdW) among the models of the '
+                                     'attached Continuum')
+                if cont.batch_unsupported(deck=True, alkali=True):
+                    raise ValueError(
+                        f'eval_bands: {len(cont.alkali)} alkali models with '
+                        f'{sum(m.nlines for m in cont.alkali)} lines: the batched form takes at '
+                        'most 2 models with 4 lines in all; use eval()')
+                _check_walker_tensor(f'eval_bands: alkali_density (species '
+                                     f'{cont.alkali_species})', alkali_density, nw,
+                                     shape=(nw, self.nlayers, len(cont.alkali)))
+                if self._alkali_checked is not cont:
+                    cont.check_alkali_batch(self.tmin)       # (once per model: host arithmetic)
+                    self._alkali_checked = cont
+            bad = cont.batch_unsupported(deck=deck_logp is not None,
+                                         alkali=alkali_density is not None)
+            if bad:
+                raise ValueError(f'eval_bands: continuum models {bad} are not supported in '
+                                 'batched form (cloud deck, alkali); use eval()')
+            shape = (nw, self.nlayers, len(cont.species))
+            got = None if continuum_density is None else tuple(continuum_density.shape)
+            if got != shape:
+                raise ValueError(f'eval_bands: continuum_density must be a device tensor of shape '
+                                 f'{shape} (species {cont.species}), got {got}')
+            npars = len(cont.free_pars)
+            if continuum_pars is not None and tuple(continuum_pars.shape) != (nw, npars):
+                raise ValueError(f'eval_bands: continuum_pars must have shape {(nw, npars)} '
+                                 f'({cont.free_pars}), got {tuple(continuum_pars.shape)}')
+            for m in cont.cia:
+                tmin, tmax = max(tmin, float(m.tmin)), min(tmax, float(m.tmax))
+        elif continuum_density is not None or continuum_pars is not None:
+            raise ValueError('eval_bands: continuum arguments without a Continuum')
+        elif alkali_density is not None:
+            raise ValueError('eval_bands: alkali_density without a Continuum that has an alkali '
+                             'model')
+        out = torch.empty((nw, bands.nbands), dtype=torch.float64, device='cuda')
+        if radius is None:
+            radius = self.radius.view(1, -1)
+        return BatchCall(temps, dens, bands, radius, radius.shape[0] == 1, f_dilution,
+                         continuum_density, continuum_pars, alkali_density, rv, deck_logp,
+                         f_patchy, spectra_out, out, nw, cloudy, tmin, tmax)
+
+    def _plan_facts(self, one_pass):
+        """The model's side of plan_eval_bands' inputs; one_pass: wanted and supported."""
+        return dict(rt_path=self.rt_path, nlayers=self.nlayers, itop=self.itop, nwave=self.nwave,
+                    order_set=self.column_order is not None,
+                    tile_limit_set=self.tile_limit is not None, one_pass=one_pass,
+                    continuum=self.continuum is not None)
+
+    def _try_auto_order(self, call_, chunk):
+        """ONE-TIME set-up of the first batch (class docstring): a host read-back, a sort and a
+        permuted second copy of the table.  Skipped -- grid order, nothing else changes --
+        where the ordered kernels do not exist for the shape, while the stream is being
+        captured into a graph, and when the second copy + this batch's ec would not fit."""
+        t0 = call_.temps[0]
+        table_bytes = self.etable.numel() * 8
+        ec_bytes = 8 * min(chunk, call_.nw) * self.nlayers * self.nwave
+        if not self._ordered_supported() or torch.cuda.is_current_stream_capturing():
+            self._auto_order = self._auto_order and self._ordered_supported()
+        elif torch.cuda.mem_get_info()[0] < 1.25 * table_bytes + 2 * ec_bytes:
+            self._auto_order = False      # no room for the second copy of the table: grid order
+        # (a walker outside the table's range would order by garbage: wait for a valid one)
+        elif bool(((t0 >= self.tmin) & (t0 <= self.tmax)).all()):
+            self.order_columns(t0, call_.dens[0], call_.radius[0])
+
+    def eval_params(self, atmosphere, params, bands, **kw):
+        """The batched loop from the walkers' parameter vectors (pyrat_obj.py:225-385 WITH the
+        parameter mapping of :258-275 and Atmosphere.calc_profiles): atmosphere, a bound
+        pyratbay_amd.atmosphere.WalkerAtmosphere, turns params[nw, npar] into temps, dens, radius
+        and the continuum / alkali densities in one launch (WalkerAtmosphere.evaluate), and those
+        tensors go to eval_bands unchanged; kw: everything else eval_bands takes (continuum_pars,
+        rv, deck_logp, f_patchy, f_dilution, chunk, streams).  Walkers the atmosphere rejects
+        (non-positive temperature, trace abundances above qcap, ...: WalkerAtmosphere) come out
+        as +inf like those outside the table's temperatures."""
+        for name in ('temps', 'dens', 'radius', 'continuum_density', 'alkali_density'):
+            if name in kw:
+                raise ValueError(f'eval_params: {name} comes from the atmosphere, not from the '
+                                 'caller')
+        prof = atmosphere.evaluate(params)
+        if prof.continuum_density is not None:
+            kw['continuum_density'] = prof.continuum_density
+        if prof.alkali_density is not None:
+            kw['alkali_density'] = prof.alkali_density
+        return self.eval_bands(prof.temps, prof.dens, bands, radius=prof.radius, **kw)
+
+    def posterior_summary(self, atmosphere, params, counts, bands, quantiles=None, chunk=64,
+                          **kw):
+        """The summary of a posterior (posterior_post_processing, tools/retrieval_tools.py:384-503):
+        params[n, npar] = the chain's UNIQUE samples (device; posterior.unique_samples gives their
+        rows and counts[n], how often the chain visited each) go through the eval_params path in
+        chunks of `chunk`; each chunk's full-resolution spectra, band fluxes, temperatures and mole
+        fractions are written transposed into sample-minor stores ([nwave, n], [nbands, n],
+        [L, n], [L, nspec, n]) and one pb_weighted_quantiles call per store gives the quantiles
+        (default posterior.QUANTILES: the median and the 1- and 2-sigma bounds, the reference's
+        order) of the chain -- each sample counts[i] times, np.percentile's bits, the expansion
+        never formed.  -> posterior.PosteriorSummary of device tensors: spectrum[nq, nwave],
+        bands[nq, nbands], temperature[nq, L], vmr[nq, L, nspec] (nspec: the table's species, the
+        atmosphere's dens output times k T / p), n_rejected, quantiles, stores (None unless
+        keep_stores=True: the four stores and the counts used).
+
+        DEVIATION: samples the batch rejects (+inf band fluxes: outside the table's temperatures,
+        a radial velocity beyond rv_max; or a reject flag of the atmosphere) get count 0 before the
+        reduction and are reported in n_rejected -- the reference would return NaN / inf
+        quantiles.  Every sample rejected: ValueError.  One read-back (n_rejected and the length
+        of the expansion), otherwise launches only.  The spectrum store takes 8 nwave n bytes: a
+        store that does not fit in free device memory is refused (ValueError) before anything is
+        allocated.  kw: what eval_bands takes per walker (continuum_pars, rv, deck_logp, f_patchy,
+        f_dilution) with one row per sample, and streams."""
+        return posterior.posterior_summary(
+            self, atmosphere, params, counts, bands,
+            quantiles=posterior.QUANTILES if quantiles is None else quantiles, chunk=chunk, **kw)
+
+    def radiative_equilibrium(self, pressure, vmr, mol_mass, **kw):
+        """The radiative-equilibrium iteration (runmode = radeq, pyrat_obj.py:559-646) of a batch
+        of profiles on this model's table, grid and Continuum, at fixed volume mixing ratios: a
+        pyratbay_amd.radeq.RadiativeEquilibrium (its docstring has the keywords); .run(temp0,
+        nsamples) iterates on the device.  Two-stream geometry only."""
+        return RadiativeEquilibrium(self, pressure, vmr, mol_mass, **kw)
+
+    def _ordered_supported(self):
+        """Whether the depth-ordered kernels exist for this model's shape (ordered_supported)."""
+        return ordered_supported(self.rt_path, self.nlayers, self.itop, self.nwave)
+
+    def _one_pass(self):
+        """The transit batch through pb_table_transit_batch (interpolation, optical depth and
+        transmission in one pass, ec never stored): opt-in (`one_pass = True` or
+        PB_TABLE_TRANSIT=1).  It saves the ec[walkers, L, W] buffer (4.1 GB per 64 walkers at
+        C5's shape); at that shape it runs 2.54 ms per 64 walkers when the walkers resemble one
+        another (two walkers per wavefront share their table loads; the two passes: 2.42-2.70 box
+        to box), 2.86 when they do not -- which only the device knows, hence not the default."""
+        want = self.one_pass
+        if want is None:
+            want = os.environ.get('PB_TABLE_TRANSIT', '0') == '1'
+        return bool(want) and batch.table_transit_supported(
+            self.nspec, self.ntemp, self.nlayers, self.itop, self.nlayers, self.nwave)
+
+    def _eval_chunk(self, plan, call_, w0, w1):
+        """One chunk of eval_bands: walkers [w0, w1) through every stage, one launch each --
+        interpolation, the radiative transfer of the plan's form, the bands."""
+        table, wn = getattr(self, plan.table), getattr(self, plan.wn)
+        column = getattr(self, plan.column) if plan.column else None
+        ci = self._chunk_inputs(plan, call_, column, w0, w1)
+        keep = None
+        if plan.form == 'one_pass':
+            # interpolation + optical depth + transmission in one pass: ec is never stored
+            rad, path = self._transit_geometry(call_, ci)
+            spectra = batch.table_transit_batch(table, self.ttable, ci.temps, ci.dens, path, rad,
+                                                self.rstar, self.itop, self.nlayers,
+                                                self.maxdepth)
+        else:
+            ec, work = self._interpolate(plan, ci, table)
+            if plan.form == 'clouds':
+                spectra, keep = self._rt_clouds(call_, ci, ec, wn, column)
+            elif plan.form == 'transit':
+                spectra = self._rt_transit(plan, call_, ci, ec, table, column, work)
+            else:
+                spectra = self._rt_emission(plan, ci, ec, table, wn, column, work)
+        if call_.spectra_out is not None:
+            call_.spectra_out[w0:w1].copy_(spectra)
+        # (the walkers' radial velocities: HiresData only -- eval_bands has checked)
+        okw = {} if ci.rv is None else {'rv': ci.rv}
+        call_.bands.integrate_batch(
+            spectra, call_.out[w0:w1],
+            None if ci.f_dilution is None else ci.f_dilution.contiguous(), **okw)
+        del keep
+
+    def _chunk_inputs(self, plan, call_, column, w0, w1):
+        """The walkers [w0, w1) of the call -> ChunkInputs (views only)."""
+        def rows(t):
+            return None if t is None else t[w0:w1]
+        temps = call_.temps[w0:w1]
+        if plan.form == 'clouds':
+            temps = temps.contiguous()
+        # the continuum's operands in the table's column order, this chunk's walkers
+        ckw = {}
+        if self.continuum is not None:
+            ckw = dict(continuum=self.continuum.batch_operands(column),
+                       continuum_density=call_.continuum_density[w0:w1],
+                       continuum_pars=rows(call_.continuum_pars),
+                       alkali_density=rows(call_.alkali_density))
+        return ChunkInputs(w1 - w0, temps, call_.dens[w0:w1],
+                           call_.radius if call_.shared_radius else call_.radius[w0:w1], ckw,
+                           rows(call_.rv), rows(call_.f_dilution), rows(call_.deck_logp),
+                           rows(call_.f_patchy))
+
+    def _interpolate(self, plan, ci, table):
+        """ec[n, L, W] of the chunk -> (ec, work).  Limited: only the layers a block of columns
+        can need are written (ec keeps whatever an earlier batch left in the others: they are
+        read by no one, or the walker is flagged and repaired); work = (flags, iwork, twork), the
+        walkers' flags and the scratch the gated repair reuses."""
+        if not plan.limited:
+            return batch.interp_ec_batch(table, self.ttable, ci.temps, ci.dens, **ci.ckw), None
+        n = ci.n
+        flags = torch.zeros(n + 1, dtype=torch.int32, device=table.device)
+        iwork = torch.empty(n * self.nlayers * 17 + 8 if not ci.ckw else
+                            ci.ckw['continuum'].work_doubles(self.nlayers, self.nwave, n),
+                            dtype=torch.float64, device=table.device)
+        twork = None
+        if self.rt_path == 'transit':
+            twork = torch.empty(_capi.lib().pb_transit_work_doubles(
+                self.nlayers, int(self.itop), int(self.nlayers), self.nwave, n),
+                dtype=torch.float64, device=table.device)
+        ec = batch.interp_ec_batch(table, self.ttable, ci.temps, ci.dens,
+                                   tile_limit=self.tile_limit, row0=self.itop, work=iwork,
+                                   **ci.ckw)
+        return ec, (flags, iwork, twork)
+
+    def _limited_rt(self, rt, args, ci, table, ws, **rt_work):
+        """The limited form of a radiative-transfer wrapper `rt(*args)` (args[0] is ec): first
+        pass under the layer limits, then the repair, gated on the device -- the full
+        interpolation if ANY walker ran past its limit, then `rt` again for the flagged walkers:
+        two launches of workgroups that return at once otherwise, no host round trip."""
+        flags, iwork, _ = ws
+        spectra = rt(*args, tile_limit=self.tile_limit, flags=flags, **rt_work)
+        batch.interp_ec_batch(table, self.ttable, ci.temps, ci.dens, out=args[0],
+                              gate=flags[ci.n:ci.n + 1], work=iwork, **ci.ckw)
+        rt(*args, gate=flags, out=spectra, **rt_work)
+        return spectra
+
+    def _transit_geometry(self, call_, ci):
+        """(radius[n, L], raypath[n, npath]) of the chunk, contiguous."""
+        if call_.shared_radius:
+            return (call_.radius.expand(ci.n, -1).contiguous(),
+                    call_.path1.expand(ci.n, -1).contiguous())
+        rad = ci.rad.contiguous()
+        return rad, transit_path_device(rad, self.itop)
+
+    def _intervals(self, ci):
+        rad = ci.rad.expand(ci.n, -1)
+        return (rad[:, :-1] - rad[:, 1:]).contiguous()                     # -diff(radius)
+
+    def _rt_transit(self, plan, call_, ci, ec, table, column, work):
+        rad, path = self._transit_geometry(call_, ci)
+        if not plan.ordered:
+            return batch.transit_spectrum_batch(ec, path, rad, self.rstar, self.itop,
+                                                self.nlayers, self.maxdepth)
+        # columns in depth order: wavefronts stop at the row tile where theirs have all crossed
+        args = (ec, path, rad, column, self.rstar, self.itop, self.nlayers, self.maxdepth)
+        if plan.limited:
+            return self._limited_rt(batch.transit_spectrum_ordered, args, ci, table, work,
+                                    work=work[2])
+        return batch.transit_spectrum_ordered(*args)
+
+    def _rt_emission(self, plan, ci, ec, table, wn, column, work):
+        """Emission and two-stream geometry."""
+        intervals = self._intervals(ci)
+        if plan.form == 'two_stream':
+            # depth without a stop + both sweeps in one launch; ec is consumed
+            return batch.two_stream_batch(ec, intervals, wn, ci.temps, self.f_int, self.flux_top)
+        args = (ec, intervals, wn, ci.temps, self.mu, self.weights, self.itop, self.nlayers,
+                self.maxdepth, column)
+        if plan.limited:
+            return self._limited_rt(batch.emission_flux_batch, args, ci, table, work)
+        return batch.emission_flux_batch(*args)
+
+    def _rt_clouds(self, call_, ci, ec, wn, column):
+        """A cloud deck and / or patchy clouds on the CLEAR ec: the deck state and the cloud-type
+        models' factors are one small launch each, and one pass over ec gives
+        f cloudy + (1 - f) clear.  -> (spectra, what must outlive the chunk's launches)."""
+        cont = self.continuum
+        deck = None if ci.deck_logp is None else \
+            batch.deck_state_batch(cont.pressure_d, ci.deck_logp, ci.rad, ci.temps)
+        terms = keep = None
+        cops = None if cont is None else cont.cloud_operands(column)
+        if cops is not None:
+            terms, keep = cops.plan(ci.temps, ci.ckw['continuum_pars'])
+        if self.rt_path == 'transit':
+            path = call_.path1 if call_.shared_radius else \
+                transit_path_device(ci.rad.contiguous(), self.itop)
+            spectra = batch.cloudy_transit_batch(ec, path, ci.rad, self.rstar, self.itop,
+                                                 self.maxdepth, deck=deck, f_patchy=ci.f_patchy,
+                                                 column=column, _terms=terms)
+        else:
+            spectra = batch.cloudy_emission_batch(ec, self._intervals(ci), wn, ci.temps, self.mu,
+                                                  self.weights, self.itop, self.maxdepth,
+                                                  deck=deck, f_patchy=ci.f_patchy, column=column,
+                                                  _terms=terms)
+        return spectra, keep

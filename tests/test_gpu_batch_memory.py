@@ -1,6 +1,6 @@
 """TableSpectrum.eval_bands does not depend on what memory held.  The limited path writes only
 the layers a block of columns can need and leaves the rest of ec as allocated ("read by no one,
-or the walker is flagged and repaired", engine._eval_chunk): here every torch.empty /
+or the walker is flagged and repaired", table.TableSpectrum._interpolate): here every torch.empty /
 torch.empty_like returns NaN (floats) or a large negative number (integers), models are reused
 for batches that need different layers, and chunks run on side streams -- the band fluxes must
 have the bits of a fresh grid-order, single-chunk, single-stream evaluation, which is compared
