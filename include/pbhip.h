@@ -949,6 +949,48 @@ int pb_weighted_quantiles(double *out_d, const double *values_d, int64_t ld,
 int64_t pb_weighted_quantiles_work_doubles(int n, int ncol, int nq);
 int pb_weighted_quantiles_resident_rows(void);
 
+/* ---- Band contribution functions per walker (pb_contribution.hip): Pyrat.band_contribution
+ * (pyrat/pyrat_obj.py:671-696 -> spectrum/contribution_funcs.py) without clouds, for a batch.
+ * The bands are the four arrays of pb_band_integrate_batch (the heights cancel and are not taken)
+ * plus max_band_count >= every band_count_d[b]; a band's samples are wn_d[start .. start + count),
+ * clipped to the grid.  out_d[nwalkers,nlayers,nbands] = the band integrals (np.trapezoid of
+ * value x response over the band's samples), each band divided by its maximum over the layers: a
+ * band of one sample (or none) is 0 / 0 = NaN in every layer, like the reference.
+ * work_d: pb_band_contribution_work_doubles(nlayers, nbands, max_band_count, nwalkers) doubles of
+ * device scratch, written before it is read.  FP64, no atomics, fixed summation order: two runs
+ * give the same bits.  Refused before any launch (PB_ERR_ARG): bad sizes, itop outside the
+ * layers, ibottom > nlayers, more than 65535 bands or walkers, more layers than the LDS of a
+ * workgroup holds (1024 emission, 2048 transit), a null pointer; nbands == 0 or nwalkers == 0
+ * succeed and launch nothing.
+ *
+ * Emission and two-stream geometry: contribution_function from ec_d[nwalkers,nlayers,nwave]
+ * directly -- per column the plane-parallel depth with pb_emission_flux_batch's stop rule
+ * (maxdepth = inf in two-stream geometry: no stop; the rows up to itop and below the stop are 0),
+ * detau = diff(exp(-depth)) with the elements > 0.1 set to 0, B = Planck at every layer of
+ * temps_d[nwalkers,nlayers], cf = B detau / dlogp_d[nlayers-1] (= diff(log(pressure)), shared by
+ * the walkers), a zero last row, each column divided by its sum.  Neither depth nor B is stored.
+ * intervals_d[nwalkers,nlayers-1] = -diff(radius).  nlayers >= 2. */
+int pb_band_contribution_emission_batch(double *out_d, const double *ec_d,
+                                        const double *intervals_d, const double *dlogp_d,
+                                        const double *wn_d, const double *temps_d,
+                                        const int32_t *band_start_d, const int32_t *band_count_d,
+                                        const double *response_d,
+                                        const int64_t *response_offset_d, int max_band_count,
+                                        double maxdepth, int itop, int ibottom, int nlayers,
+                                        int nwave, int nbands, int nwalkers, double *work_d,
+                                        void *stream);
+/* Transit geometry: transmittance from depth_d[nwalkers,nlayers,nwave] and ideep_d[nwalkers,nwave]
+ * as pb_transit_spectrum_batch(..., depth_d, ideep_d) leaves them: exp(-depth[r]) for r < ideep,
+ * 0 from row ideep on; the rows above itop are 1 and are not read. */
+int pb_band_transmittance_batch(double *out_d, const double *depth_d, const int32_t *ideep_d,
+                                const double *wn_d, const int32_t *band_start_d,
+                                const int32_t *band_count_d, const double *response_d,
+                                const int64_t *response_offset_d, int max_band_count, int itop,
+                                int nlayers, int nwave, int nbands, int nwalkers, double *work_d,
+                                void *stream);
+int64_t pb_band_contribution_work_doubles(int nlayers, int nbands, int max_band_count,
+                                          int nwalkers);
+
 /* =========================================================================
  * Experiments -- NOT in libpbhip.so.  `make -C pyratbay_amd/csrc EXPERIMENTS=1` builds
  * libpbhip_exp.so (compiled with -DPB_EXPERIMENTS) = the product library + the variants that were

@@ -132,6 +132,11 @@ _PROTOS = {
     'pb_weighted_quantiles': [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp],
     'pb_weighted_quantiles_work_doubles': [i32, i32, i32],
     'pb_weighted_quantiles_resident_rows': [],
+    'pb_band_contribution_emission_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f64, i32,
+                                            i32, i32, i32, i32, i32, vp, vp],
+    'pb_band_transmittance_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
+                                    vp, vp],
+    'pb_band_contribution_work_doubles': [i32, i32, i32, i32],
     'pb_simps2D': [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp],
     'pb_ediff': [vp, vp, i32, vp],
     'pb_band_integrate': [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, vp],
@@ -150,6 +155,7 @@ _RESTYPES = {'pb_transit_work_doubles': C.c_int64, 'pb_two_stream_batch_work_dou
              'pb_two_stream_net_work_doubles': C.c_int64, 'pb_two_stream_net_parts': C.c_int,
              'pb_weighted_quantiles_work_doubles': C.c_int64,
              'pb_weighted_quantiles_resident_rows': C.c_int,
+             'pb_band_contribution_work_doubles': C.c_int64,
              'pb_interp_ec_batch_cont_work_doubles': C.c_int64, 'pb_table_transit_work_doubles': C.c_int64,
              'pb_table_transit_supported': C.c_int, 'pb_voigt_destroy': None, 'pb_lines_destroy': None, 'pb_lbl_destroy': None,
              'pb_voigt_device_bytes': i64, 'pb_timer_destroy': None}

@@ -19,6 +19,7 @@ class PassBands:
         start = np.array([b[0] for b in bands], np.int32)
         count = np.array([len(b[1]) for b in bands], np.int32)
         offset = np.concatenate([[0], np.cumsum(count)[:-1]]).astype(np.int64)
+        self.max_count = int(count.max()) if len(count) else 0     # (the contribution kernels' grid)
         self.start, self.count = dev(start, torch.int32), dev(count, torch.int32)
         self.offset = dev(offset, torch.int64)
         self.response = dev(np.concatenate([np.asarray(b[1], float) for b in bands]))

@@ -188,6 +188,94 @@ def two_stream_batch(ec, intervals, wn, temps, f_int=None, flux_top=None, out=No
 
 
 # --------------------------------------------------------------------------
+# Band contribution functions for a batch (pb_contribution.hip)
+# --------------------------------------------------------------------------
+def _contribution_buffers(name, bands, nw, nlayers, nwave, device, out):
+    """The output [nw, L, nbands] (checked when given), the work buffer and the band arguments of
+    the two contribution entries."""
+    if not hasattr(bands, 'response') or not hasattr(bands, 'offset'):
+        raise ValueError(f'{name}: bands must be a PassBands (high-resolution data have no '
+                         'contribution functions here)')
+    if tuple(bands.wn.shape) != (nwave,):
+        raise ValueError(f'{name}: the bands are on a grid of {tuple(bands.wn.shape)} samples, '
+                         f'the columns on one of {nwave}')
+    shape = (nw, nlayers, bands.nbands)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=device)
+    else:
+        _check_walker_tensor(f'{name}: out', out, nw, shape=shape)
+        if not out.is_contiguous():
+            raise ValueError(f'{name}: out must be contiguous')
+    max_count = bands.max_count if hasattr(bands, 'max_count') else \
+        int(bands.count.max()) if bands.nbands else 0
+    need = _capi.lib().pb_band_contribution_work_doubles(nlayers, bands.nbands, max_count, nw)
+    work = torch.empty(max(need, 1), dtype=torch.float64, device=device)
+    args = (_ptr(bands.start), _ptr(bands.count), _ptr(bands.response), _ptr(bands.offset),
+            max_count)
+    return out, work, args
+
+
+def band_transmittance_batch(depth, ideep, bands, itop, out=None):
+    """Band transmittances of a batch in transit geometry (Pyrat.band_contribution:
+    contribution_funcs.transmittance + band_cf; contribution.band_contribution_host is the NumPy
+    statement): depth[nw, L, W] and ideep[nw, W] (int32) as transit_spectrum_batch(...,
+    want_depth=True) returns them, bands: a PassBands on the same grid -> [nw, L, nbands], every
+    band divided by its maximum over the layers (a band of one sample: NaN)."""
+    nw, nlayers, nwave = depth.shape
+    if depth.dtype != torch.float64 or not depth.is_contiguous() or \
+            ideep.dtype != torch.int32 or tuple(ideep.shape) != (nw, nwave):
+        raise ValueError(f'band_transmittance_batch: contiguous float64 depth[nw, L, W] and int32 '
+                         f'ideep[{nw}, {nwave}] wanted, got {depth.dtype} {tuple(depth.shape)}, '
+                         f'{ideep.dtype} {tuple(ideep.shape)}')
+    out, work, bargs = _contribution_buffers('band_transmittance_batch', bands, nw, nlayers,
+                                             nwave, depth.device, out)
+    call('pb_band_transmittance_batch', _ptr(out), _ptr(depth), _ptr(ideep.contiguous()),
+         _ptr(bands.wn), *bargs, int(itop), nlayers, nwave, bands.nbands, nw, _ptr(work),
+         _stream())
+    return out
+
+
+def band_contribution_emission_batch(ec, intervals, temps, bands, pressure, itop, ibottom,
+                                     maxdepth, out=None, dlogp=None):
+    """Band contribution functions of a batch in emission or two-stream geometry
+    (contribution_funcs.contribution_function + band_cf) from ec[nw, L, W] directly:
+    intervals[nw, L-1] = -diff(radius), temps[nw, L], pressure[L] in any unit (host array or
+    tensor: only diff(log(pressure)), formed on the host with NumPy, enters; or None with dlogp =
+    contribution_dlogp(pressure, L), formed once for several calls), maxdepth (inf in two-stream
+    geometry: no stop) -> [nw, L, nbands].  Neither the depth nor B is stored; ec is
+    only read."""
+    nw, nlayers, nwave = ec.shape
+    if ec.dtype != torch.float64 or not ec.is_contiguous() or \
+            tuple(intervals.shape) != (nw, nlayers - 1) or tuple(temps.shape) != (nw, nlayers):
+        raise ValueError(f'band_contribution_emission_batch: contiguous float64 ec[nw, L, W], '
+                         f'intervals[{nw}, {nlayers - 1}] and temps[{nw}, {nlayers}] wanted, got '
+                         f'{tuple(ec.shape)}, {tuple(intervals.shape)}, {tuple(temps.shape)}')
+    if dlogp is None:
+        dlogp = contribution_dlogp(pressure, nlayers)
+    elif not isinstance(dlogp, torch.Tensor) or not dlogp.is_cuda or \
+            dlogp.dtype != torch.float64 or tuple(dlogp.shape) != (nlayers - 1,):
+        raise ValueError(f'band_contribution_emission_batch: dlogp must be a float64 device '
+                         f'tensor of shape ({nlayers - 1},)')
+    out, work, bargs = _contribution_buffers('band_contribution_emission_batch', bands, nw,
+                                             nlayers, nwave, ec.device, out)
+    call('pb_band_contribution_emission_batch', _ptr(out), _ptr(ec),
+         _ptr(intervals.contiguous()), _ptr(dlogp.contiguous()), _ptr(bands.wn),
+         _ptr(temps.contiguous()), *bargs, float(maxdepth), int(itop), int(ibottom), nlayers, nwave, bands.nbands, nw,
+         _ptr(work), _stream())
+    return out
+
+
+def contribution_dlogp(pressure, nlayers):
+    """diff(log(pressure)) [L-1] on the device, formed with NumPy (the bits of the host form) from
+    pressure[L], a host array or a tensor (read back)."""
+    p = pressure.cpu().numpy() if isinstance(pressure, torch.Tensor) else pressure
+    p = np.asarray(p, float)
+    if p.shape != (nlayers,):
+        raise ValueError(f'contribution pressure must have shape ({nlayers},), got {p.shape}')
+    return dev(np.diff(np.log(p)))
+
+
+# --------------------------------------------------------------------------
 # Cloud deck and patchy clouds for a batch (pb_clouds.hip)
 # --------------------------------------------------------------------------
 def alkali_voigt_det_batch(model, temps, pressure_barye=None):

@@ -13,7 +13,7 @@ ec, depth and B never travel to the host unless asked for.  torch tensors are us
 only as owners of device memory; all arithmetic happens in libpbhip.so.
 
 This module is the front door: the code lives in one module per stage (_device, lbl, columns,
-batch, bands, spectrum, table) and every public name is re-exported here.  The modules of the
+batch, bands, contribution, spectrum, table) and every public name is re-exported here.  The modules of the
 package import from those, not from here.
 """
 from . import _capi                                                     # noqa: F401
@@ -27,8 +27,12 @@ from .columns import (RT_PATHS, _legendre_newton, blackbody_wn_2D,      # noqa: 
                       pack_raypath, patchy_emission_flux, patchy_transit_spectrum,
                       plane_parallel_optical_depth, transit_path, transit_path_device,
                       transit_spectrum, transmission, two_stream)
+from . import contribution                                              # noqa: F401
+from .contribution import (band_cf_host, band_contribution_host,        # noqa: F401
+                           contribution_function_host, transmittance_host)
 from .batch import (_check_walker_tensor, _cloud_call_args,             # noqa: F401
-                    alkali_voigt_det_batch, cloudy_emission_batch, cloudy_transit_batch,
+                    alkali_voigt_det_batch, band_contribution_emission_batch,
+                    band_transmittance_batch, cloudy_emission_batch, cloudy_transit_batch,
                     deck_state_batch, emission_flux_batch, interp_ec_batch, table_transit_batch,
                     table_transit_supported, transit_spectrum_batch, transit_spectrum_ordered,
                     two_stream_batch)

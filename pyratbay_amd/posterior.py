@@ -10,8 +10,10 @@ TableSpectrum.eval_bands in chunks, their results are kept sample-minor on the d
 ([nwave, n], ...) and pb_weighted_quantiles (csrc/pb_quantiles.hip) selects the order statistics
 of the expansion from the samples and their multiplicities, without forming it:
 weighted_quantiles_host is the NumPy statement of that kernel, and both have np.percentile's
-bits.  The reference's fifth product, the median of the band contribution functions, is not
-covered."""
+bits.  The reference's fifth product, the median of the band contribution functions
+(retrieval_tools.py:474-504: np.median(cf[uinv], axis=0)), comes the same way when asked for
+(contribution=True): eval_bands(contribution_out=...) per chunk into a store [L, nbands, n] and
+its 0.5 quantile."""
 import collections
 
 import numpy as np
@@ -131,14 +133,15 @@ def weighted_quantiles(values, counts, q, total=None):
 
 
 PosteriorSummary = collections.namedtuple(
-    'PosteriorSummary', 'spectrum bands temperature vmr n_rejected quantiles stores')
+    'PosteriorSummary', 'spectrum bands temperature vmr n_rejected quantiles stores contribution',
+    defaults=(None,))
 
 # per-walker keywords of eval_bands: posterior_summary hands each chunk its rows
 _PER_SAMPLE = ('continuum_pars', 'rv', 'deck_logp', 'f_patchy', 'f_dilution')
 
 
 def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTILES, chunk=64,
-                      keep_stores=False, **kw):
+                      keep_stores=False, contribution=False, **kw):
     """TableSpectrum.posterior_summary: see there."""
     import torch
     from .atmosphere import BAR, K_BOLTZ
@@ -156,7 +159,8 @@ def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTI
         raise ValueError('posterior_summary: negative counts')
     if int(chunk) < 1:
         raise ValueError('posterior_summary: chunk >= 1')
-    for name in ('temps', 'dens', 'radius', 'continuum_density', 'alkali_density', 'spectra_out'):
+    for name in ('temps', 'dens', 'radius', 'continuum_density', 'alkali_density', 'spectra_out',
+                 'contribution_out', 'contribution_pressure'):
         if name in kw:
             raise ValueError(f'posterior_summary: {name} is not the caller\'s to give')
     for name in _PER_SAMPLE:
@@ -164,11 +168,14 @@ def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTI
             raise ValueError(f'posterior_summary: {name} must have one row per sample ({n})')
     chunk = min(int(chunk), n)
     nwave, L, nbands = model.nwave, model.nlayers, bands.nbands
-    need = 8 * nwave * n
+    need = 8 * nwave * n + (8 * L * nbands * n if contribution else 0)
     free = torch.cuda.mem_get_info()[0]
     if need > free:
         raise ValueError(f'posterior_summary: the spectrum store of {n} samples x {nwave} '
-                         f'wavenumbers needs {need} bytes, {free} bytes of device memory are free')
+                         f'wavenumbers' +
+                         (f' and the contribution store of {L} layers x {nbands} bands need'
+                          if contribution else ' needs') +
+                         f' {need} bytes, {free} bytes of device memory are free')
     device = params.device
     counts_d = counts.to(torch.int64) if counts_host is None else dev(counts_host, torch.int64)
     nspec = None
@@ -176,6 +183,12 @@ def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTI
     stores = dict(spectrum=torch.empty((nwave, n), dtype=torch.float64, device=device),
                   bands=torch.empty((nbands, n), dtype=torch.float64, device=device),
                   temperature=torch.empty((L, n), dtype=torch.float64, device=device))
+    cf = None
+    if contribution:
+        # (the pressure enters as diff(log p) only: the atmosphere's, in its own unit)
+        kw = dict(kw, contribution_pressure=np.asarray(atmosphere.pressure, float))
+        cf = torch.empty((chunk, L, nbands), dtype=torch.float64, device=device)
+        stores['contribution'] = torch.empty((L, nbands, n), dtype=torch.float64, device=device)
     rejected = torch.empty(n, dtype=torch.bool, device=device)
     # (ideal gas: the total number density of a layer is p / (k T); here p / k per layer)
     pressure = dev(np.asarray(atmosphere.pressure, float) * BAR / K_BOLTZ)
@@ -188,8 +201,12 @@ def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTI
             ckw['continuum_density'] = prof.continuum_density
         if prof.alkali_density is not None:
             ckw['alkali_density'] = prof.alkali_density
+        if contribution:
+            ckw['contribution_out'] = cf[:m]
         flux = model.eval_bands(prof.temps, prof.dens, bands, radius=prof.radius, chunk=m,
                                 spectra_out=spectra[:m], **ckw)
+        if contribution:
+            stores['contribution'][:, :, w0:w1] = cf[:m].permute(1, 2, 0)
         if nspec is None:
             nspec = prof.dens.shape[2]
             stores['vmr'] = torch.empty((L, nspec, n), dtype=torch.float64, device=device)
@@ -208,8 +225,11 @@ def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTI
         raise ValueError(f'posterior_summary: no sample is left ({n_rejected} of {n} rejected, '
                          'the others have count 0)')
     out = {name: weighted_quantiles(store, live, quantiles, total=total)
-           for name, store in stores.items()}
+           for name, store in stores.items() if name != 'contribution'}
+    median = None
+    if contribution:
+        median = weighted_quantiles(stores['contribution'], live, [0.5], total=total)[0]
     if keep_stores:
         stores['counts'] = live
     return PosteriorSummary(out['spectrum'], out['bands'], out['temperature'], out['vmr'],
-                            n_rejected, quantiles, stores if keep_stores else None)
+                            n_rejected, quantiles, stores if keep_stores else None, median)

@@ -23,11 +23,14 @@ from .radeq import RadiativeEquilibrium
 # What the caller of eval_bands gave, validated and filled by name (TableSpectrum._batch_call).
 # radius is [1, L] when shared_radius; out[nw, nbands] receives the result; cloudy: the call takes
 # the cloud form; tmin / tmax: the temperatures outside which a walker is rejected; path1: the ray
-# path of a shared radius in transit geometry (set once the column order is settled).
+# path of a shared radius in transit geometry (set once the column order is settled);
+# contribution_out[nw, L, nbands] receives the band contribution functions (None: not asked for),
+# dlogp[L-1] = diff(log(contribution_pressure)) on the device (emission and two-stream geometry).
 BatchCall = namedtuple('BatchCall', (
     'temps dens bands radius shared_radius f_dilution continuum_density continuum_pars '
-    'alkali_density rv deck_logp f_patchy spectra_out out nw cloudy tmin tmax path1'),
-    defaults=(None,))
+    'alkali_density rv deck_logp f_patchy spectra_out out nw cloudy tmin tmax path1 '
+    'contribution_out dlogp'),
+    defaults=(None, None, None))
 
 # Which kernels the chunks of one eval_bands call run (plan_eval_bands).  form: 'one_pass',
 # 'two_stream', 'emission', 'transit' or 'clouds'; table / wn / column name the attributes of the
@@ -55,8 +58,15 @@ def plan_eval_bands(facts, call_facts):
     access.  facts (the model): rt_path ('transit', 'emission', 'two_stream'), nlayers, itop,
     nwave, order_set / tile_limit_set (a column order / its layer limits are set), one_pass (the
     one-pass transit is wanted and the library has it for the shape), continuum (one is
-    attached).  call_facts: cloudy.  (Two-stream with clouds is refused before planning.)"""
+    attached).  call_facts: cloudy; contribution (default False: the band contribution functions
+    are asked for -- grid order, every layer and the two passes whatever the model's column order
+    is: the transit form needs the stored depth, the emission form reads the chunk's ec in grid
+    order; a cloudy call is refused before planning).  (Two-stream with clouds is refused before
+    planning.)"""
     rt_path = facts['rt_path']
+    if call_facts.get('contribution', False):
+        return BatchPlan(rt_path, False, False, table='etable', wn='wn', column=None,
+                         may_auto_order=False)
     # (the one-pass transit takes no continuum: with one attached, the two passes)
     one_pass = rt_path == 'transit' and facts['one_pass'] and not facts['continuum']
     form = 'clouds' if call_facts['cloudy'] else 'one_pass' if one_pass else rt_path
@@ -285,6 +295,33 @@ class TableSpectrum:
             t.mark('spectrum')
         return self.spectrum
 
+    def band_contribution(self, bands, pressure=None):
+        """The band contribution functions of the last eval() (Pyrat.band_contribution,
+        pyrat_obj.py:671-696, without clouds) -> [L, nbands], every band divided by its maximum
+        over the layers: transit geometry: the bands' transmittance per impact parameter;
+        emission and two-stream geometry: the contribution function, with pressure[L] (any unit:
+        only diff(log p) enters).  From the ec (and temperatures) eval() kept, through the kernels
+        of eval_bands(contribution_out=...) with one walker: row 0 of such a batch, bit for bit."""
+        if isinstance(bands, HiresData):
+            raise ValueError('band_contribution: needs a PassBands')
+        if getattr(self, 'spectrum', None) is None or getattr(self, 'depth', None) is None:
+            raise ValueError('band_contribution: call eval() first')
+        if self.rt_path == 'transit':
+            # (eval()'s own depth comes from the one-spectrum kernel and host-made ray paths, which
+            # round differently from the batch's: the depth is formed again from the ec eval()
+            # kept, by the batch's pass, so that the result is row 0 of a batch, bit for bit)
+            rad = self.radius.view(1, -1).contiguous()
+            _, depth, ideep = batch.transit_spectrum_batch(
+                self.ec.unsqueeze(0), transit_path_device(rad, self.itop), rad, self.rstar,
+                self.itop, self.nlayers, self.maxdepth, want_depth=True)
+            return batch.band_transmittance_batch(depth, ideep, bands, self.itop)[0]
+        if pressure is None:
+            raise ValueError(f'band_contribution: pressure[{self.nlayers}] is needed in emission '
+                             'and two-stream geometry')
+        return batch.band_contribution_emission_batch(
+            self.ec.unsqueeze(0), self.intervals.view(1, -1), self.temp.reshape(1, -1), bands,
+            pressure, self.itop, self.nlayers, self.maxdepth)[0]
+
     @property
     def timestamps(self):
         """Seconds of the last eval() by stage: 'extinction' (interpolation of the table +
@@ -295,7 +332,8 @@ class TableSpectrum:
 
     def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
                    f_dilution=None, continuum_density=None, continuum_pars=None, rv=None,
-                   deck_logp=None, f_patchy=None, alkali_density=None, spectra_out=None):
+                   deck_logp=None, f_patchy=None, alkali_density=None, spectra_out=None,
+                   contribution_out=None, contribution_pressure=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
         without the parameter mapping -- eval_params adds it): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
@@ -356,18 +394,37 @@ class TableSpectrum:
         spectrum; emission and two-stream: the planet's flux, before f_dilution, the eclipse ratio
         and the instrument profile, which belong to the bands) -- one copy per chunk on every
         branch: one-pass, ordered and limited transit, emission, two-stream and clouds.  The rows
-        of rejected walkers hold whatever the kernels made of their inputs."""
+        of rejected walkers hold whatever the kernels made of their inputs.
+
+        contribution_out (a contiguous float64 device tensor [nw, L, nbands]; None: nothing
+        changes) receives every walker's band contribution functions (Pyrat.band_contribution,
+        pyrat_obj.py:671-696; contribution.band_contribution_host is the NumPy statement): transit
+        geometry: the bands' transmittance per impact parameter, from the depth a second transit
+        pass stores (transit_spectrum_batch(..., want_depth=True) + band_transmittance_batch);
+        emission and two-stream geometry: the contribution function B d(exp(-tau)) / d(ln p) from
+        the chunk's ec (band_contribution_emission_batch, before two_stream_batch consumes ec),
+        which needs contribution_pressure[L] (any unit: only diff(log p) enters; a host array, or a
+        tensor that is read back once per call).  Every band is divided by its maximum over the
+        layers; a band of one sample is NaN.  Such a call runs in grid order, over every layer and
+        in two passes, whatever column_order is; the band fluxes and spectra_out keep their bits.
+        Refused (ValueError) before any launch: a HiresData as bands, and any cloudy call
+        (deck_logp, f_patchy, cloud-type models: the reference mixes a clear and a cloudy
+        transmittance there).  Rows of rejected walkers hold whatever the kernels made of their
+        inputs."""
         call_ = self._batch_call(temps, dens, bands, radius, f_dilution, continuum_density,
                                  continuum_pars, rv, deck_logp, f_patchy, alkali_density,
-                                 spectra_out)
+                                 spectra_out, contribution_out, contribution_pressure)
         nw = call_.nw
         one_pass = self.rt_path == 'transit' and self._one_pass()
-        plan = plan_eval_bands(self._plan_facts(one_pass), {'cloudy': call_.cloudy})
+        call_facts = {'cloudy': call_.cloudy}
+        if call_.contribution_out is not None:
+            call_facts['contribution'] = True
+        plan = plan_eval_bands(self._plan_facts(one_pass), call_facts)
         if plan.may_auto_order and self._auto_order and self.column_order is None and nw > 0:
             self._try_auto_order(call_, chunk)
             # (the ordering changes column_order and tile_limit: the plan the chunks run is made
             # after it)
-            plan = plan_eval_bands(self._plan_facts(one_pass), {'cloudy': call_.cloudy})
+            plan = plan_eval_bands(self._plan_facts(one_pass), call_facts)
         if call_.shared_radius and self.rt_path == 'transit':
             call_ = call_._replace(
                 path1=transit_path_device(call_.radius[0], self.itop).view(1, -1))
@@ -396,7 +453,8 @@ class TableSpectrum:
         return call_.out
 
     def _batch_call(self, temps, dens, bands, radius, f_dilution, continuum_density,
-                    continuum_pars, rv, deck_logp, f_patchy, alkali_density, spectra_out):
+                    continuum_pars, rv, deck_logp, f_patchy, alkali_density, spectra_out,
+                    contribution_out=None, contribution_pressure=None):
         """The arguments of eval_bands, checked and filled -> BatchCall (allocates `out`)."""
         assert self.rt_path in ('transit', 'emission', 'two_stream'), \
             'eval_bands: transit, emission or two-stream geometry on sampled cross sections'
@@ -480,12 +538,38 @@ class TableSpectrum:
         elif alkali_density is not None:
             raise ValueError('eval_bands: alkali_density without a Continuum that has an alkali '
                              'model')
+        dlogp = None
+        if contribution_out is not None:
+            if isinstance(bands, HiresData):
+                raise ValueError('eval_bands: contribution_out needs a PassBands (band '
+                                 'contribution functions of high-resolution data are not '
+                                 'supported)')
+            if cloudy:
+                raise ValueError('eval_bands: contribution_out with clouds (deck_logp, f_patchy, '
+                                 'cloud-type models) is not supported: the reference mixes a '
+                                 'clear and a cloudy transmittance there')
+            _check_walker_tensor('eval_bands: contribution_out', contribution_out, nw,
+                                 shape=(nw, self.nlayers, bands.nbands))
+            if not contribution_out.is_contiguous():
+                raise ValueError('eval_bands: contribution_out must be contiguous')
+            if self.rt_path != 'transit':
+                if contribution_pressure is None:
+                    raise ValueError('eval_bands: contribution_out needs contribution_pressure'
+                                     f'[{self.nlayers}] in emission and two-stream geometry')
+                if tuple(np.shape(contribution_pressure)) != (self.nlayers,):
+                    raise ValueError(f'eval_bands: contribution_pressure must have shape '
+                                     f'({self.nlayers},), got '
+                                     f'{tuple(np.shape(contribution_pressure))}')
+                dlogp = batch.contribution_dlogp(contribution_pressure, self.nlayers)
+        elif contribution_pressure is not None:
+            raise ValueError('eval_bands: contribution_pressure without contribution_out')
         out = torch.empty((nw, bands.nbands), dtype=torch.float64, device='cuda')
         if radius is None:
             radius = self.radius.view(1, -1)
         return BatchCall(temps, dens, bands, radius, radius.shape[0] == 1, f_dilution,
                          continuum_density, continuum_pars, alkali_density, rv, deck_logp,
-                         f_patchy, spectra_out, out, nw, cloudy, tmin, tmax)
+                         f_patchy, spectra_out, out, nw, cloudy, tmin, tmax,
+                         contribution_out=contribution_out, dlogp=dlogp)
 
     def _plan_facts(self, one_pass):
         """The model's side of plan_eval_bands' inputs; one_pass: wanted and supported."""
@@ -516,7 +600,8 @@ class TableSpectrum:
         pyratbay_amd.atmosphere.WalkerAtmosphere, turns params[nw, npar] into temps, dens, radius
         and the continuum / alkali densities in one launch (WalkerAtmosphere.evaluate), and those
         tensors go to eval_bands unchanged; kw: everything else eval_bands takes (continuum_pars,
-        rv, deck_logp, f_patchy, f_dilution, chunk, streams).  Walkers the atmosphere rejects
+        rv, deck_logp, f_patchy, f_dilution, chunk, streams, spectra_out, contribution_out,
+        contribution_pressure).  Walkers the atmosphere rejects
         (non-positive temperature, trace abundances above qcap, ...: WalkerAtmosphere) come out
         as +inf like those outside the table's temperatures."""
         for name in ('temps', 'dens', 'radius', 'continuum_density', 'alkali_density'):
@@ -552,7 +637,12 @@ class TableSpectrum:
         of the expansion), otherwise launches only.  The spectrum store takes 8 nwave n bytes: a
         store that does not fit in free device memory is refused (ValueError) before anything is
         allocated.  kw: what eval_bands takes per walker (continuum_pars, rv, deck_logp, f_patchy,
-        f_dilution) with one row per sample, and streams."""
+        f_dilution) with one row per sample, and streams.
+
+        contribution=True adds the reference's fifth product, the median over the chain of the
+        band contribution functions (eval_bands' contribution_out, with atmosphere.pressure; no
+        clouds, pass bands only): a fifth store [L, nbands, n], counted in the memory check, and
+        its 0.5 quantile -> PosteriorSummary.contribution[L, nbands] (None when not asked for)."""
         return posterior.posterior_summary(
             self, atmosphere, params, counts, bands,
             quantiles=posterior.QUANTILES if quantiles is None else quantiles, chunk=chunk, **kw)
@@ -598,6 +688,9 @@ class TableSpectrum:
             ec, work = self._interpolate(plan, ci, table)
             if plan.form == 'clouds':
                 spectra, keep = self._rt_clouds(call_, ci, ec, wn, column)
+            elif call_.contribution_out is not None:
+                spectra = self._rt_contribution(plan, call_, ci, ec, wn,
+                                                call_.contribution_out[w0:w1])
             elif plan.form == 'transit':
                 spectra = self._rt_transit(plan, call_, ci, ec, table, column, work)
             else:
@@ -699,6 +792,31 @@ class TableSpectrum:
         if plan.limited:
             return self._limited_rt(batch.emission_flux_batch, args, ci, table, work)
         return batch.emission_flux_batch(*args)
+
+    def _rt_contribution(self, plan, call_, ci, ec, wn, cout):
+        """The radiative transfer of a chunk whose band contribution functions are asked for
+        (grid order, every layer): -> spectra; cout[n, L, nbands] is filled."""
+        if plan.form == 'transit':
+            # The spectra come from the launch a call without contribution_out makes (the
+            # matrix-core kernel stores no depth, and the kernel that does rounds its sums
+            # differently: ~1e-16 relative), so that they keep their bits; a second pass stores
+            # depth and ideep, and the transmittance is read from them.
+            rad, path = self._transit_geometry(call_, ci)
+            spectra = batch.transit_spectrum_batch(ec, path, rad, self.rstar, self.itop,
+                                                   self.nlayers, self.maxdepth)
+            _, depth, ideep = batch.transit_spectrum_batch(
+                ec, path, rad, self.rstar, self.itop, self.nlayers, self.maxdepth, want_depth=True)
+            batch.band_transmittance_batch(depth, ideep, call_.bands, self.itop, out=cout)
+            return spectra
+        # (before the flux: two_stream_batch consumes ec)
+        intervals = self._intervals(ci)
+        batch.band_contribution_emission_batch(ec, intervals, ci.temps, call_.bands, None,
+                                               self.itop, self.nlayers, self.maxdepth, out=cout,
+                                               dlogp=call_.dlogp)
+        if plan.form == 'two_stream':
+            return batch.two_stream_batch(ec, intervals, wn, ci.temps, self.f_int, self.flux_top)
+        return batch.emission_flux_batch(ec, intervals, wn, ci.temps, self.mu, self.weights,
+                                         self.itop, self.nlayers, self.maxdepth, None)
 
     def _rt_clouds(self, call_, ci, ec, wn, column):
         """A cloud deck and / or patchy clouds on the CLEAR ec: the deck state and the cloud-type
