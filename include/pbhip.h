@@ -647,6 +647,44 @@ int pb_band_scale(double *bandflux_d, const double *band_scale_d, const double *
 int pb_reject_walkers(double *bandflux_d, const double *temps_d, double tmin, double tmax,
                       int nlayers, int nbands, int nwalkers, void *stream);
 
+/* ---- The exit towards the sampler (pb_observation.hip).
+ * The eclipse factor of a batch whose walkers have a stellar temperature of their own (eval()'s
+ * tstar branch, pyrat_obj.py:288-294, then Pyrat.band_integrate, pyrat_obj.py:662-665):
+ *   bandflux_d[w,b] *= f_dilution_d[w] (when given), then *= rprs2_w / bandflux_star[w,b]
+ * bandflux_star[w,b] = the band integral (x heights_d[b] when given, like PassBand.integrate) of
+ * star_grid_d[nt,nwave], the SED grid on the model's wavenumbers, interpolated at tstar_d[w]
+ * along sed_temps_d[nt] (strictly ascending, nt >= 2) by interp1d's linear rule:
+ *   i = searchsorted_left(sed_temps, tstar) clipped to [1, nt-1], lo = i-1,
+ *   s = ((y_hi - y_lo) / (x_hi - x_lo)) * (tstar - x_lo) + y_lo   (every operation rounded)
+ * and summed in the order of pb_band_integrate_batch; the interpolated spectra are never stored.
+ * rprs2_w = rprs2 when rplanet_d is NULL, else t * t with t = rplanet_d[w] / rstar.
+ * The bands are the arrays of pb_band_integrate_batch.
+ * DEVIATION: a walker whose tstar is NaN or outside [sed_temps[0], sed_temps[nt-1]] gets +inf in
+ * every band (the reference's interp1d raises there): rejected like a walker outside the table's
+ * temperatures.  nwalkers == 0 or nbands == 0: PB_OK, nothing launched. */
+int pb_star_band_scale_batch(double *bandflux_d, const double *star_grid_d,
+                             const double *sed_temps_d, const double *tstar_d, double rprs2,
+                             const double *rplanet_d, double rstar, const double *f_dilution_d,
+                             const double *wn_d, const int32_t *band_start_d,
+                             const int32_t *band_count_d, const double *response_d,
+                             const int64_t *response_offset_d, const double *heights_d, int nt,
+                             int nbands, int nwave, int nwalkers, void *stream);
+/* pb_loglike with the data and the uncertainties of each walker (Data.offset_data /
+ * Data.scale_errors, tools/data.py:210-270): per band b of walker w
+ *   d = data_d[b] + offset_vals_d[w,g] * offset_unit      g = offset_group_d[b] (-1: none)
+ *   e = pow(10, err_vals_d[w,g])                          g = err_group_d[b]    (-1: none)
+ *   err_mode_d[g] == 0 (scale):      u = uncert_d[b] * e
+ *   err_mode_d[g] == 1 (quadrature): e *= err_unit; u = sqrt(uncert_d[b]^2 + e^2)
+ * and pb_loglike's sums of d, u and bandflux_d[w,b] in its order; not finite: -1e98.
+ * offset_vals_d[nwalkers,noff], err_vals_d[nwalkers,nerr]; with noff == nerr == 0 (their pointers
+ * may then be NULL) the result has the bits of pb_loglike. */
+int pb_loglike_obs(double *loglike_d, const double *bandflux_d, const double *data_d,
+                   const double *uncert_d, const int32_t *offset_group_d,
+                   const double *offset_vals_d, double offset_unit, int noff,
+                   const int32_t *err_group_d, const int32_t *err_mode_d,
+                   const double *err_vals_d, double err_unit, int nerr, int nwalkers, int nbands,
+                   void *stream);
+
 /* High-resolution data (eval()'s second exit, pyrat/pyrat_obj.py:331-356).
  * ps.inst_convolution's last step (spectrum/spec_tools.py:879) for a batch:
  *   out_d[w] = convolve(spectra_d[w] * sample_scale_d, taps_d, mode='same')

@@ -121,6 +121,9 @@ _PROTOS = {
     'pb_alkali_cross_section': [vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, vp, vp, i32, vp, i32, i32, vp],
     'pb_alkali_voigt_det_batch': [vp, vp, vp, f64, f64, f64, vp, i32, i32, i32, vp],
     'pb_loglike': [vp, vp, vp, vp, i32, i32, vp],
+    'pb_star_band_scale_batch': [vp, vp, vp, vp, f64, vp, f64, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                 i32, i32, vp],
+    'pb_loglike_obs': [vp, vp, vp, vp, vp, vp, f64, i32, vp, vp, vp, f64, i32, i32, i32, vp],
     'pb_two_stream': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     'pb_two_stream_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     'pb_two_stream_batch_work_doubles': [i32, i32, i32],

@@ -26,6 +26,7 @@ class PassBands:
         self.heights = dev(np.array([b[2] for b in bands], float))
         self.partial = torch.zeros(self.nbands, dtype=torch.float64, device='cuda')
         self.scale = None               # per-band factor after the heights (set_eclipse)
+        self.star_grid = None           # a StellarGrid: the factor per walker (set_eclipse_grid)
 
     def partial_integrate(self, spectrum_full, wbegin=0, wcount=None):
         """Un-scaled partial sums over the pairs whose left sample is in the shard."""
@@ -54,15 +55,60 @@ class PassBands:
             self.scale = scale
         return out.cpu().numpy()
 
-    def integrate_batch(self, spectra, out=None, f_dilution=None):
+    def set_eclipse_grid(self, rstar, star, rplanet=None):
+        """Eclipse geometry with a stellar temperature per walker (eval()'s tstar branch,
+        pyrat_obj.py:288-294): star, an observation.StellarGrid on these bands' grid;
+        integrate_batch(..., tstar=tstar[nw]) then returns band(fplanet) * rprs**2 /
+        band(star.flux(tstar[w])) per walker, the stellar band fluxes re-integrated on the device
+        (pb_star_band_scale_batch).  rprs = rplanet / rstar with the planet radius given here, or
+        with integrate_batch's rplanet[nw] (a free rplanet changes the factor too:
+        Pyrat.band_integrate, pyrat_obj.py:662-665, reads the current atm.rplanet).
+        DEVIATION: a walker whose tstar is NaN or outside the grid's temperatures gets +inf in
+        every band (the reference's interp1d raises): rejected like a walker outside the table's
+        temperatures.  set_eclipse(), star_bandflux() and a call without tstar are unchanged."""
+        if star.nwave != self.wn.shape[0] or \
+                not np.array_equal(star.wn_host, self.wn.cpu().numpy()):
+            raise ValueError('set_eclipse_grid: the StellarGrid is not on the wavenumbers of '
+                             'these bands')
+        if not float(rstar) > 0.0:
+            raise ValueError(f'set_eclipse_grid: rstar must be positive, got {rstar}')
+        self.star_grid = star
+        self.grid_rstar = float(rstar)
+        self.grid_rplanet = None if rplanet is None else float(rplanet)
+        return self
+
+    def integrate_batch(self, spectra, out=None, f_dilution=None, tstar=None, rplanet=None):
         """Band fluxes (heights applied; then the walkers' dilution factors f_dilution[nw], if
-        given, and the eclipse factor, if set) of full-grid spectra[nw, W] -> [nw, nbands]."""
+        given, and the eclipse factor, if set) of full-grid spectra[nw, W] -> [nw, nbands].
+        tstar[nw] (with rplanet[nw], or the planet radius of set_eclipse_grid): the eclipse factor
+        of each walker's stellar temperature, from the grid of set_eclipse_grid."""
         nw, nwave = spectra.shape
         if out is None:
             out = torch.empty((nw, self.nbands), dtype=torch.float64, device=spectra.device)
         call('pb_band_integrate_batch', _ptr(out), _ptr(spectra), _ptr(self.wn),
              _ptr(self.start), _ptr(self.count), _ptr(self.response), _ptr(self.offset),
              _ptr(self.heights), self.nbands, nwave, nw, _stream())
+        if tstar is not None:
+            star = self.star_grid
+            if star is None:
+                raise ValueError('integrate_batch: tstar needs set_eclipse_grid()')
+            if rplanet is None and self.grid_rplanet is None:
+                raise ValueError('integrate_batch: a planet radius is needed, here (rplanet[nw]) '
+                                 'or in set_eclipse_grid()')
+            assert tstar.shape == (nw,) and (rplanet is None or rplanet.shape == (nw,))
+            assert f_dilution is None or f_dilution.shape == (nw,)
+            assert nwave == star.nwave
+            rprs2 = 0.0 if rplanet is not None else (self.grid_rplanet / self.grid_rstar)**2.0
+            call('pb_star_band_scale_batch', _ptr(out), _ptr(star.fluxes), _ptr(star.sed_temps),
+                 _ptr(tstar.contiguous()), rprs2,
+                 None if rplanet is None else _ptr(rplanet.contiguous()), self.grid_rstar,
+                 _ptr(f_dilution), _ptr(self.wn), _ptr(self.start), _ptr(self.count),
+                 _ptr(self.response), _ptr(self.offset), _ptr(self.heights), star.nt, self.nbands,
+                 nwave, nw, _stream())
+            return out
+        if rplanet is not None:
+            raise ValueError('integrate_batch: rplanet[nw] belongs to tstar[nw] and '
+                             'set_eclipse_grid()')
         if self.scale is not None or f_dilution is not None:
             assert f_dilution is None or f_dilution.shape == (nw,)
             call('pb_band_scale', _ptr(out), _ptr(self.scale), _ptr(f_dilution), self.nbands, nw,

@@ -13,7 +13,7 @@ ec, depth and B never travel to the host unless asked for.  torch tensors are us
 only as owners of device memory; all arithmetic happens in libpbhip.so.
 
 This module is the front door: the code lives in one module per stage (_device, lbl, columns,
-batch, bands, contribution, spectrum, table) and every public name is re-exported here.  The modules of the
+batch, bands, observation, contribution, spectrum, table) and every public name is re-exported here.  The modules of the
 package import from those, not from here.
 """
 from . import _capi                                                     # noqa: F401
@@ -37,5 +37,6 @@ from .batch import (_check_walker_tensor, _cloud_call_args,             # noqa: 
                     table_transit_supported, transit_spectrum_batch, transit_spectrum_ordered,
                     two_stream_batch)
 from .bands import HiresData, PassBands                                 # noqa: F401
+from .observation import Observation, StellarGrid                       # noqa: F401
 from .spectrum import LBLSpectrum, SpectrumPipeline                     # noqa: F401
 from .table import TableSpectrum                                        # noqa: F401

@@ -137,7 +137,8 @@ PosteriorSummary = collections.namedtuple(
     defaults=(None,))
 
 # per-walker keywords of eval_bands: posterior_summary hands each chunk its rows
-_PER_SAMPLE = ('continuum_pars', 'rv', 'deck_logp', 'f_patchy', 'f_dilution')
+_PER_SAMPLE = ('continuum_pars', 'rv', 'deck_logp', 'f_patchy', 'f_dilution', 'tstar',
+               'rplanet')
 
 
 def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTILES, chunk=64,
@@ -163,6 +164,8 @@ def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTI
                  'contribution_out', 'contribution_pressure'):
         if name in kw:
             raise ValueError(f'posterior_summary: {name} is not the caller\'s to give')
+    from .table import free_rplanet
+    kw = free_rplanet(atmosphere, params, bands, kw, 'posterior_summary')
     for name in _PER_SAMPLE:
         if kw.get(name) is not None and tuple(kw[name].shape[:1]) != (n,):
             raise ValueError(f'posterior_summary: {name} must have one row per sample ({n})')

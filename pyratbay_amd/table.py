@@ -25,12 +25,14 @@ from .radeq import RadiativeEquilibrium
 # the cloud form; tmin / tmax: the temperatures outside which a walker is rejected; path1: the ray
 # path of a shared radius in transit geometry (set once the column order is settled);
 # contribution_out[nw, L, nbands] receives the band contribution functions (None: not asked for),
-# dlogp[L-1] = diff(log(contribution_pressure)) on the device (emission and two-stream geometry).
+# dlogp[L-1] = diff(log(contribution_pressure)) on the device (emission and two-stream geometry);
+# tstar[nw] / rplanet[nw]: the walkers' stellar temperatures and planet radii for the eclipse
+# factor of bands.set_eclipse_grid (None: not given).
 BatchCall = namedtuple('BatchCall', (
     'temps dens bands radius shared_radius f_dilution continuum_density continuum_pars '
     'alkali_density rv deck_logp f_patchy spectra_out out nw cloudy tmin tmax path1 '
-    'contribution_out dlogp'),
-    defaults=(None, None, None))
+    'contribution_out dlogp tstar rplanet'),
+    defaults=(None, None, None, None, None))
 
 # Which kernels the chunks of one eval_bands call run (plan_eval_bands).  form: 'one_pass',
 # 'two_stream', 'emission', 'transit' or 'clouds'; table / wn / column name the attributes of the
@@ -41,7 +43,7 @@ BatchPlan = namedtuple('BatchPlan', 'form ordered limited table wn column may_au
 # the layer intervals are formed by the radiative-transfer step, after the interpolation).  rad:
 # the chunk's radius rows, or the shared row [1, L]; ckw: the continuum keywords of interp_ec_batch.
 ChunkInputs = namedtuple('ChunkInputs',
-                         'n temps dens rad ckw rv f_dilution deck_logp f_patchy')
+                         'n temps dens rad ckw rv f_dilution deck_logp f_patchy tstar rplanet')
 
 
 def ordered_supported(rt_path, nlayers, itop, nwave):
@@ -84,6 +86,18 @@ def plan_eval_bands(facts, call_facts):
                      column='column_order' if ordered else None,
                      may_auto_order=facts['nwave'] >= 64 and rt_path != 'two_stream' and
                      not one_pass)
+
+
+def free_rplanet(atmosphere, params, bands, kw, who):
+    """kw with rplanet = the 'rplanet' column of params[nw, npar] (cm) when the atmosphere has
+    it free and the bands carry a stellar SED grid; the caller's own rplanet is then refused."""
+    col = getattr(atmosphere, 'par_scalar', {}).get('rplanet', -1)
+    if col < 0 or getattr(bands, 'star_grid', None) is None:
+        return kw
+    if kw.get('rplanet') is not None:
+        raise ValueError(f"{who}: rplanet comes from the atmosphere's free 'rplanet', not from "
+                         'the caller')
+    return dict(kw, rplanet=params[:, col].contiguous())
 
 
 class TableSpectrum:
@@ -333,7 +347,7 @@ class TableSpectrum:
     def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
                    f_dilution=None, continuum_density=None, continuum_pars=None, rv=None,
                    deck_logp=None, f_patchy=None, alkali_density=None, spectra_out=None,
-                   contribution_out=None, contribution_pressure=None):
+                   contribution_out=None, contribution_pressure=None, tstar=None, rplanet=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
         without the parameter mapping -- eval_params adds it): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
@@ -410,10 +424,23 @@ class TableSpectrum:
         Refused (ValueError) before any launch: a HiresData as bands, and any cloudy call
         (deck_logp, f_patchy, cloud-type models: the reference mixes a clear and a cloudy
         transmittance there).  Rows of rejected walkers hold whatever the kernels made of their
-        inputs."""
+        inputs.
+
+        tstar[nw] (K) and rplanet[nw] (cm), float64 device tensors: an eclipse retrieval with a
+        free stellar temperature (pyrat_obj.py:288-294) on bands that carry a stellar SED grid
+        (PassBands.set_eclipse_grid): each walker's eclipse factor rprs**2 / bandflux_star comes
+        from the grid interpolated at ITS temperature and integrated over the bands on the device
+        (pb_star_band_scale_batch in place of pb_band_scale: still two launches for the bands),
+        with rprs = rplanet[w] / rstar when rplanet is given (a free rplanet enters the factor,
+        pyrat_obj.py:662-665), else the planet radius of set_eclipse_grid.  A walker whose tstar
+        is NaN or outside the grid's temperatures is rejected (+inf; DEVIATION: the reference's
+        interp1d raises).  Refused (ValueError) before any launch: tstar on bands without a grid;
+        bands with a grid and no tstar; rplanet without tstar; either in transit geometry; either
+        with a HiresData (its eclipse factor is applied per sample before the convolution)."""
         call_ = self._batch_call(temps, dens, bands, radius, f_dilution, continuum_density,
                                  continuum_pars, rv, deck_logp, f_patchy, alkali_density,
-                                 spectra_out, contribution_out, contribution_pressure)
+                                 spectra_out, contribution_out, contribution_pressure, tstar,
+                                 rplanet)
         nw = call_.nw
         one_pass = self.rt_path == 'transit' and self._one_pass()
         call_facts = {'cloudy': call_.cloudy}
@@ -454,7 +481,7 @@ class TableSpectrum:
 
     def _batch_call(self, temps, dens, bands, radius, f_dilution, continuum_density,
                     continuum_pars, rv, deck_logp, f_patchy, alkali_density, spectra_out,
-                    contribution_out=None, contribution_pressure=None):
+                    contribution_out=None, contribution_pressure=None, tstar=None, rplanet=None):
         """The arguments of eval_bands, checked and filled -> BatchCall (allocates `out`)."""
         assert self.rt_path in ('transit', 'emission', 'two_stream'), \
             'eval_bands: transit, emission or two-stream geometry on sampled cross sections'
@@ -470,6 +497,31 @@ class TableSpectrum:
             'f_dilution: emission geometry'
         assert f_dilution is None or f_dilution.shape == (temps.shape[0],)
         nw = temps.shape[0]
+        grid = getattr(bands, 'star_grid', None)
+        if tstar is not None or rplanet is not None:
+            if isinstance(bands, HiresData):
+                raise ValueError('eval_bands: tstar / rplanet with a HiresData are not supported '
+                                 '(its eclipse factor is applied per sample before the '
+                                 'convolution); they belong to a PassBands with '
+                                 'set_eclipse_grid()')
+            if self.rt_path == 'transit':
+                raise ValueError('eval_bands: tstar / rplanet (the eclipse factor per walker) '
+                                 'belong to emission and two-stream geometry, not to transit '
+                                 'geometry')
+            if grid is None:
+                raise ValueError('eval_bands: tstar / rplanet need a stellar SED grid on the '
+                                 'bands (PassBands.set_eclipse_grid)')
+            if tstar is None:
+                raise ValueError('eval_bands: rplanet needs tstar (the bands carry a stellar SED '
+                                 'grid: every walker needs its stellar temperature)')
+            if rplanet is None and bands.grid_rplanet is None:
+                raise ValueError('eval_bands: a planet radius is needed, rplanet[nw] or the one '
+                                 'of set_eclipse_grid()')
+            _check_walker_tensor('eval_bands: tstar', tstar, nw)
+            _check_walker_tensor('eval_bands: rplanet', rplanet, nw)
+        elif grid is not None:
+            raise ValueError('eval_bands: the bands carry a stellar SED grid '
+                             '(set_eclipse_grid): tstar[nw] is needed')
         if spectra_out is not None:
             _check_walker_tensor('eval_bands: spectra_out', spectra_out, nw,
                                  shape=(nw, self.nwave))
@@ -569,7 +621,8 @@ class TableSpectrum:
         return BatchCall(temps, dens, bands, radius, radius.shape[0] == 1, f_dilution,
                          continuum_density, continuum_pars, alkali_density, rv, deck_logp,
                          f_patchy, spectra_out, out, nw, cloudy, tmin, tmax,
-                         contribution_out=contribution_out, dlogp=dlogp)
+                         contribution_out=contribution_out, dlogp=dlogp, tstar=tstar,
+                         rplanet=rplanet)
 
     def _plan_facts(self, one_pass):
         """The model's side of plan_eval_bands' inputs; one_pass: wanted and supported."""
@@ -601,19 +654,40 @@ class TableSpectrum:
         and the continuum / alkali densities in one launch (WalkerAtmosphere.evaluate), and those
         tensors go to eval_bands unchanged; kw: everything else eval_bands takes (continuum_pars,
         rv, deck_logp, f_patchy, f_dilution, chunk, streams, spectra_out, contribution_out,
-        contribution_pressure).  Walkers the atmosphere rejects
+        contribution_pressure, tstar).  Walkers the atmosphere rejects
         (non-positive temperature, trace abundances above qcap, ...: WalkerAtmosphere) come out
-        as +inf like those outside the table's temperatures."""
+        as +inf like those outside the table's temperatures.  When the atmosphere has 'rplanet'
+        free and the bands carry a stellar SED grid (PassBands.set_eclipse_grid), that column of
+        params is the rplanet[nw] of eval_bands' eclipse factor (Pyrat.band_integrate reads the
+        current atm.rplanet, pyrat_obj.py:662-665); passing rplanet as well is refused."""
         for name in ('temps', 'dens', 'radius', 'continuum_density', 'alkali_density'):
             if name in kw:
                 raise ValueError(f'eval_params: {name} comes from the atmosphere, not from the '
                                  'caller')
+        kw = free_rplanet(atmosphere, params, bands, kw, 'eval_params')
         prof = atmosphere.evaluate(params)
         if prof.continuum_density is not None:
             kw['continuum_density'] = prof.continuum_density
         if prof.alkali_density is not None:
             kw['alkali_density'] = prof.alkali_density
         return self.eval_bands(prof.temps, prof.dens, bands, radius=prof.radius, **kw)
+
+    def eval_loglike(self, atmosphere, params, bands, observation, offsets=None, err_pars=None,
+                     **kw):
+        """The batched loop from the walkers' parameter vectors to their log-likelihoods
+        (Loglike.__call__, tools/retrieval_tools.py:74-104, around eval()): eval_params, then
+        observation.loglike (an observation.Observation on these bands' data) with the walkers'
+        instrumental offsets offsets[nw, noff] and uncertainty-scaling parameters
+        err_pars[nw, nerr] (pyrat_obj.py:362-372; None: the defaults) -> loglike[nw].  kw:
+        everything eval_params takes, tstar included.  Rejected walkers (+inf band fluxes) come
+        out as -1e98.  Launches only: one pb_loglike_obs after those of eval_params, no
+        read-back.  The likelihood uses the data and uncertainties eval() leaves in obs (see
+        Observation on what the reference's Loglike binds)."""
+        if observation.nbands != bands.nbands:
+            raise ValueError(f'eval_loglike: the observation has {observation.nbands} data '
+                             f'points, the bands give {bands.nbands}')
+        return observation.loglike(self.eval_params(atmosphere, params, bands, **kw),
+                                   offsets=offsets, err_pars=err_pars)
 
     def posterior_summary(self, atmosphere, params, counts, bands, quantiles=None, chunk=64,
                           **kw):
@@ -637,7 +711,8 @@ class TableSpectrum:
         of the expansion), otherwise launches only.  The spectrum store takes 8 nwave n bytes: a
         store that does not fit in free device memory is refused (ValueError) before anything is
         allocated.  kw: what eval_bands takes per walker (continuum_pars, rv, deck_logp, f_patchy,
-        f_dilution) with one row per sample, and streams.
+        f_dilution, tstar, rplanet) with one row per sample, and streams; a free 'rplanet' of the
+        atmosphere enters the eclipse factor of bands with a stellar SED grid as in eval_params.
 
         contribution=True adds the reference's fifth product, the median over the chain of the
         band contribution functions (eval_bands' contribution_out, with atmosphere.pressure; no
@@ -699,6 +774,8 @@ class TableSpectrum:
             call_.spectra_out[w0:w1].copy_(spectra)
         # (the walkers' radial velocities: HiresData only -- eval_bands has checked)
         okw = {} if ci.rv is None else {'rv': ci.rv}
+        if ci.tstar is not None:
+            okw = {'tstar': ci.tstar, 'rplanet': ci.rplanet}
         call_.bands.integrate_batch(
             spectra, call_.out[w0:w1],
             None if ci.f_dilution is None else ci.f_dilution.contiguous(), **okw)
@@ -721,7 +798,7 @@ class TableSpectrum:
         return ChunkInputs(w1 - w0, temps, call_.dens[w0:w1],
                            call_.radius if call_.shared_radius else call_.radius[w0:w1], ckw,
                            rows(call_.rv), rows(call_.f_dilution), rows(call_.deck_logp),
-                           rows(call_.f_patchy))
+                           rows(call_.f_patchy), rows(call_.tstar), rows(call_.rplanet))
 
     def _interpolate(self, plan, ci, table):
         """ec[n, L, W] of the chunk -> (ec, work).  Limited: only the layers a block of columns
