@@ -362,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_transit(CloudArgs a, TransitG
 }
 
 // ---------------------------------------------------------------------------
-// Emission: the pass of k_emission_fused (pb_columns.hip; _trapezoid.c:175-213, 304-341 +
+// Emission: the pass of k_emission_fused (pb_emission.hip; _trapezoid.c:175-213, 304-341 +
 // pyrat/spectrum.py:366-377) for the two columns.  The walker's Planck terms hold the deck's
 // temperature in row deck_itop for BOTH columns (the reference's cloudy pass writes that row of its
 // Planck array in place and the clear pass reads the array afterwards).  The cloudy column's

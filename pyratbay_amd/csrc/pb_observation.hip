@@ -1,6 +1,6 @@
 // Walker-batched retrieval path, the exit towards the sampler: the eclipse factor of a batch whose
 // walkers carry a stellar temperature (and optionally a planet radius) of their own, and the
-// Gaussian log-likelihood with per-walker instrumental offsets and uncertainty scaling.
+// Gaussian log-likelihood, plain and with per-walker instrumental offsets and uncertainty scaling.
 #include "pb_common.h"
 
 namespace {
@@ -80,7 +80,35 @@ __global__ __launch_bounds__(kBlock) void k_star_band_scale_batch(
 }
 
 // ---------------------------------------------------------------------------
-// k_loglike (pb_columns.hip) with the data and the uncertainties of each walker
+// Gaussian log-likelihood of band fluxes (pyratbay/tools/retrieval_tools.py:98-104): one
+// walker per wavefront, -0.5*sum(((data-model)/uncert)^2) - 0.5*sum(log(2*pi*uncert^2)),
+// -inf when not finite.  Sums in lane-strided order, then a fixed butterfly.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_loglike(double *loglike, const double *model,
+                                                const double *data, const double *uncert,
+                                                int nbands)
+{
+    const int w = blockIdx.x;
+    const double *m = model + (int64_t)w * nbands;
+    double chi = 0.0, norm = 0.0;
+    for (int b = threadIdx.x; b < nbands; b += 64) {
+        const double r = (data[b] - m[b]) / uncert[b];
+        chi += r * r;
+        norm += log(2.0 * 3.141592653589793 * (uncert[b] * uncert[b]));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        chi += __shfl_xor(chi, d);
+        norm += __shfl_xor(norm, d);
+    }
+    if (threadIdx.x == 0) {
+        const double ll = -0.5 * chi - 0.5 * norm;
+        loglike[w] = isfinite(ll) ? ll : -1.0e98;     // retrieval_tools.py:101-103
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_loglike with the data and the uncertainties of each walker
 // (Data.offset_data / Data.scale_errors, tools/data.py:210-270, then Loglike.__call__,
 // tools/retrieval_tools.py:98-104): one walker per wavefront, sums in lane-strided order, then the
 // same butterfly.
@@ -155,6 +183,19 @@ int pb_star_band_scale_batch(double *bandflux_d, const double *star_grid_d,
     k_star_band_scale_batch<<<grid, kBlock, 0, pb::as_stream(stream)>>>(
         bandflux_d, star_grid_d, sed_temps_d, tstar_d, rprs2, rplanet_d, rstar, f_dilution_d, wn_d,
         band_start_d, band_count_d, response_d, response_offset_d, heights_d, nt, nbands, nwave);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+int pb_loglike(double *loglike_d, const double *bandflux_d, const double *data_d,
+               const double *uncert_d, int nwalkers, int nbands, void *stream)
+{
+    PB_REQUIRE(nwalkers >= 0 && nbands >= 1, "pb_loglike: bad shape");
+    if (nwalkers == 0)
+        return PB_OK;
+    PB_REQUIRE(loglike_d && bandflux_d && data_d && uncert_d, "pb_loglike: null pointer");
+    k_loglike<<<nwalkers, 64, 0, pb::as_stream(stream)>>>(loglike_d, bandflux_d, data_d, uncert_d,
+                                                         nbands);
     PB_LAUNCH_CHECK();
     return PB_OK;
 }

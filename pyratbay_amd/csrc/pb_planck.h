@@ -1,5 +1,5 @@
-// Planck function of the column kernels (src_c/_blackbody.c:35-130), shared by pb_columns.hip and
-// pb_clouds.hip: every kernel forms B this way (same bits).
+// Planck function of the column kernels (src_c/_blackbody.c:35-130), shared by pb_emission.hip,
+// pb_two_stream.hip and pb_clouds.hip: every kernel forms B this way (same bits).
 #pragma once
 
 #include "pb_common.h"

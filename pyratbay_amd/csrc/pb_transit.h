@@ -37,7 +37,7 @@ struct TransitCall {
     const int32_t *gate = nullptr;
 };
 
-// shared with pb_columns.hip: the single-spectrum entries can use the fused kernel too
+// shared with pb_transit_one.hip: the single-spectrum entries can use the fused kernel too
 int pb_transit_fused_launch(const TransitCall &call, hipStream_t s);
 // the blocked ray-path layout for one spectrum in the stream's persistent scratch (pb_core.hip);
 // PB_ERR_NOMEM when there is none: the caller falls back to the LDS form

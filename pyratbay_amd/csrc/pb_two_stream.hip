@@ -1,3 +1,6 @@
+// Two-stream fluxes (pyratbay/pyrat/spectrum.py:454-522; Heng et al. 2014 Eqs. B5-B6; exp1 and the
+// statements of one layer interval: pb_two_stream.h), for a batch of walkers and for one spectrum.
+//
 // Two-stream emission for a batch of walkers (the retrieval inner loop in the geometry of
 // rt_path emission_two_stream / eclipse_two_stream): per (walker, column) the chain the
 // single-spectrum kernels run as three launches -- k_plane_depth with maxdepth = inf
@@ -20,6 +23,7 @@ namespace {
 
 constexpr int kBlock = 256;
 
+using pb::planck;
 using pb::planck_factor;
 using pb::planck_q;
 using pb::planck_terms;
@@ -91,9 +95,138 @@ __global__ __launch_bounds__(kBlock) void k_two_stream_batch(
     flux[(int64_t)wk * nwave + j] = up;
 }
 
+// ---------------------------------------------------------------------------
+// One spectrum: the chain as separate launches over a depth array that k_plane_depth wrote.
+// ---------------------------------------------------------------------------
+
+// The diffusivity transmission of every (layer interval, sample), trans[i][j] written to
+// flux_up[i][j]: the expensive part of the two-stream solver (exp1: a series or a continued
+// fraction of 20 + 80/x terms, one division each) has no dependence between layers, so it gets a
+// thread per (interval, sample) instead of sitting in the column sweeps (one thread per column =
+// 1.5 wavefronts per SIMD at 1e5 samples).  Same expression as the sweep evaluated before.
+__global__ __launch_bounds__(kBlock) void k_two_stream_trans(double *flux_up, const double *depth,
+                                                            int nlayers, int nwave)
+{
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    const int i = blockIdx.y;
+    if (j >= nwave || i >= nlayers - 1)
+        return;
+    const double dtau0 = depth[(int64_t)(i + 1) * nwave + j] - depth[(int64_t)i * nwave + j];
+    flux_up[(int64_t)i * nwave + j] = two_stream_trans(dtau0);
+}
+
+// One column per thread.  trans[i] comes from k_two_stream_trans (parked in flux_up[i], which
+// the upward sweep then overwrites); Planck values are recomputed in registers.
+__global__ __launch_bounds__(kBlock) void k_two_stream(
+    double *flux_down, double *flux_up, const double *depth, const double *wn,
+    const double *temp, const double *f_int, const double *flux_top, int rtop, int nlayers,
+    int nwave)
+{
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= nwave)
+        return;
+    const double w = wn[j];
+    const double factor = planck_factor(w);
+    // the irradiation is written into row rtop and the sweep overwrites rows 1..L-1
+    // (spectrum.py:498-509): it survives only when rtop == 0
+    double down = (flux_top && rtop == 0) ? flux_top[j] : 0.0;
+    flux_down[j] = down;
+    double dprev = depth[j];
+    double bprev = planck(factor, w, temp[0]);
+    for (int i = 0; i < nlayers - 1; i++) {
+        const double dnext = depth[(int64_t)(i + 1) * nwave + j];
+        const double bnext = planck(factor, w, temp[i + 1]);
+        const double dtau0 = dnext - dprev;
+        const double trans = flux_up[(int64_t)i * nwave + j];
+        down = two_stream_down(down, trans, dtau0, bprev, bnext);
+        flux_down[(int64_t)(i + 1) * nwave + j] = down;
+        dprev = dnext;
+        bprev = bnext;
+    }
+    double up = down + (f_int ? f_int[j] : 0.0);
+    flux_up[(int64_t)(nlayers - 1) * nwave + j] = up;
+    // bprev = B[L-1], dprev = depth[L-1]
+    for (int i = nlayers - 2; i >= 0; i--) {
+        const double dlo = depth[(int64_t)i * nwave + j];
+        const double blo = planck(factor, w, temp[i]);
+        const double dtau0 = dprev - dlo;
+        const double trans = flux_up[(int64_t)i * nwave + j];
+        up = two_stream_up(up, trans, dtau0, blo, bprev);
+        flux_up[(int64_t)i * nwave + j] = up;
+        dprev = dlo;
+        bprev = blo;
+    }
+}
+
+// f_int (spectrum.py:475-478): Planck at tint, scaled so that its trapezoid integral over
+// wn is sigma*tint^4.  One workgroup; fixed-order tree sum.
+__global__ __launch_bounds__(kBlock) void k_internal_flux(double *f_int, const double *wn,
+                                                         double tint, int nwave)
+{
+    __shared__ double s_part[kBlock];
+    const double sigma = 5.6703744191844314e-05;      // constants/astrophysical_constants.py:71
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nwave; i += kBlock) {
+        const double w = wn[i];
+        const double b = planck(planck_factor(w), w, tint);
+        f_int[i] = b;
+        if (i + 1 < nwave) {
+            const double w1 = wn[i + 1];
+            acc += (w1 - w) * (planck(planck_factor(w1), w1, tint) + b) / 2.0;
+        }
+    }
+    s_part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int k = kBlock / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k)
+            s_part[threadIdx.x] += s_part[threadIdx.x + k];
+        __syncthreads();
+    }
+    const double total = s_part[0];
+    if (total > 0) {
+        const double scale = sigma * pow(tint, 4.0) / total;
+        for (int i = threadIdx.x; i < nwave; i += kBlock)
+            f_int[i] *= scale;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int pb_internal_flux(double *f_int_d, const double *wn_d, double tint, int nwave, void *stream)
+{
+    PB_REQUIRE(nwave >= 0, "pb_internal_flux: bad shape");
+    if (nwave == 0)
+        return PB_OK;
+    PB_REQUIRE(f_int_d && wn_d, "pb_internal_flux: null pointer");
+    k_internal_flux<<<1, kBlock, 0, pb::as_stream(stream)>>>(f_int_d, wn_d, tint, nwave);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+int pb_two_stream(double *flux_down_d, double *flux_up_d, const double *depth_d,
+                  const double *wn_d, const double *temp_d, const double *f_int_d,
+                  const double *flux_top_d, int rtop, int nlayers, int nwave, void *stream)
+{
+    PB_REQUIRE(nlayers >= 1 && nwave >= 0, "pb_two_stream: bad shape");
+    PB_REQUIRE(rtop >= 0 && rtop < nlayers, "pb_two_stream: rtop out of range");
+    if (nwave == 0)
+        return PB_OK;
+    PB_REQUIRE(flux_down_d && flux_up_d && depth_d && wn_d && temp_d,
+               "pb_two_stream: null pointer");
+    if (nlayers > 1) {
+        dim3 tgrid((unsigned)pb::div_up(nwave, kBlock), (unsigned)(nlayers - 1));
+        k_two_stream_trans<<<tgrid, kBlock, 0, pb::as_stream(stream)>>>(flux_up_d, depth_d,
+                                                                         nlayers, nwave);
+        PB_LAUNCH_CHECK();
+    }
+    k_two_stream<<<pb::div_up(nwave, kBlock), kBlock, 0, pb::as_stream(stream)>>>(
+        flux_down_d, flux_up_d, depth_d, wn_d, temp_d, f_int_d, flux_top_d, rtop, nlayers,
+        nwave);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
 
 int64_t pb_two_stream_batch_work_doubles(int nlayers, int nwave, int nwalkers)
 {

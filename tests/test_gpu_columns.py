@@ -151,6 +151,49 @@ def test_transit_vs_oracle_shapes(eng, orc, shape):
             rtol=RTOL)
 
 
+@pytest.fixture(scope='module')
+def seam_case(orc):
+    """One 6-layer case of 32769 columns and its oracle results at itop = 1; columns are
+    independent, so its first 32768 columns are the case one column narrower."""
+    c = cases.column_case(seed=6032769, nlayers=6, nwave=32769)
+    want_d, want_i = orc.optical_depth_transit(c['ec'], c['radius'], 1, 6, 0.5)
+    want_s = orc.transmission(want_d, c['radius'], c['rstar'], want_i, 1)
+    assert want_i.min() < want_i.max()          # columns that cross maxdepth and columns that do not
+    return c, want_d, want_i, want_s
+
+
+@pytest.mark.parametrize('scalar', [None, '0'])
+@pytest.mark.parametrize('shape', [(6, 32768), (6, 32769), (2, 257)])
+def test_transit_spectrum_plan_seams(eng, orc, seam_case, monkeypatch, shape, scalar):
+    """The seams of the planned one-spectrum launch: 32768 columns take 4 rows per thread in
+    64-thread workgroups and 32769 take 16 rows in 256; each with the ray paths re-laid for scalar
+    loads and, PB_TRANSIT_SCALAR=0 (read at every call), staged in LDS.  L = 2 with ibottom = 1: a
+    single impact parameter, for which no blocked layout is built."""
+    L, W = shape
+    monkeypatch.delenv('PB_TRANSIT', raising=False)
+    if scalar is None:
+        monkeypatch.delenv('PB_TRANSIT_SCALAR', raising=False)
+    else:
+        monkeypatch.setenv('PB_TRANSIT_SCALAR', scalar)
+    if L == 6:
+        c, want_d, want_i, want_s = seam_case
+        itop, ibottom, maxdepth = 1, 6, 0.5
+        ec, want_d, want_i, want_s = c['ec'][:, :W], want_d[:, :W], want_i[:W], want_s[:W]
+    else:
+        c = cases.column_case(seed=2257, nlayers=L, nwave=W)
+        itop, ibottom, maxdepth = 0, 1, 0.5
+        ec = c['ec']
+        want_d, want_i = orc.optical_depth_transit(ec, c['radius'], itop, ibottom, maxdepth)
+        want_s = orc.transmission(want_d, c['radius'], c['rstar'], want_i, itop)
+    path = eng.dev(eng.pack_raypath(eng.transit_path(c['radius'], itop), itop))
+    spec, depth, ideep = eng.transit_spectrum(eng.dev(np.ascontiguousarray(ec)), path,
+                                              eng.dev(c['radius']), c['rstar'], itop, ibottom,
+                                              maxdepth)
+    assert np.array_equal(host(ideep), want_i)
+    np.testing.assert_allclose(host(depth), want_d, rtol=RTOL)
+    np.testing.assert_allclose(host(spec), want_s, rtol=RTOL)
+
+
 def test_clear_atmosphere_kats(eng):
     """Analytic KATs of the reference's tests (test_transmission.py:43-52,
     test_emission.py:43-52): zero extinction -> (r_bottom/R*)**2 and B(T_bottom)."""
