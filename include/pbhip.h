@@ -400,9 +400,9 @@ int64_t pb_two_stream_batch_work_doubles(int nlayers, int nwave, int nwalkers);
 int pb_internal_flux(double *f_int_d, const double *wn_d, double tint, int nwave, void *stream);
 
 /* ---- Radiative equilibrium (Pyrat.radiative_equilibrium, pyrat/pyrat_obj.py:559-646 ->
- * spectrum/radiative_transfer.py:141-270) for a batch of profiles, at fixed volume mixing ratios
- * and without convection: pb_radeq.hip.  One iteration is pb_interp_ec_batch[_cont],
- * pb_two_stream_net_batch, pb_radeq_update; nothing is read back.
+ * spectrum/radiative_transfer.py:141-272) for a batch of profiles, at fixed volume mixing ratios:
+ * pb_radeq.hip.  One iteration is pb_interp_ec_batch[_cont], pb_two_stream_net_batch and
+ * pb_radeq_update, or with convection pb_radeq_update_convective; nothing is read back.
  *
  * pb_two_stream_net_batch = pb_two_stream_batch (same arguments, same bits in flux_d, ec_d
  * DESTROYED) that also integrates flux_up and flux_down of EVERY layer over wavenumber with the
@@ -475,6 +475,35 @@ typedef struct pb_radeq {
  * init_only != 0: only the atmosphere of temp_d (before the first evaluation).  2 <= nlayers <=
  * PB_ATM_MAX_LAYERS. */
 int pb_radeq_update(const pb_radeq *state, int init_only, void *stream);
+
+/* What pb_radeq_update_convective takes beyond the state; every pointer is device memory. */
+typedef struct pb_radeq_convection {
+    const double *cp_temps_d;      /* [ntemps] ascending temperatures of the heat-capacity table */
+    const double *cp_table_d;      /* [nwalkers or 1, ntemps, nspecies] cp / R of every species of vmr_d */
+    int64_t cp_table_stride;       /* 0 (shared) or ntemps * nspecies */
+    int ntemps;
+    const double *mol_mass_d;      /* [nspecies] g mol-1 */
+    const double *conv_dpress_d;   /* [nlayers] ediff1d(log p), element 0 = 1 (convection.py:49) */
+    double mplanet;                /* g: gravity = pc.G mplanet / radius**2 whatever the radius model */
+    double coeff;                  /* alpha**2 sqrt(beta) of the mixing length */
+    double *conv_flux_d;           /* [nwalkers, nlayers] out: the convective flux (erg s-1 cm-2) */
+    int32_t *convective_d;         /* [nwalkers] out: 1 where the second half ran */
+} pb_radeq_convection;
+
+/* pb_radeq_update(state, 0) with the convective half of the reference's loop
+ * (radiative_transfer.py:239-272, spectrum/convection.py:13-67) behind the same radiative update:
+ * cp = sum(np.interp(T', cp_temps, cp_table) vmr) k / amu at the temperatures T' that update
+ * produced; gravity from radius_d AS IT IS ON ENTRY (the radius the fluxes were computed with;
+ * required whatever rmodel is), rho = sum(n mol_mass) amu over ALL nspecies at temp_d on entry,
+ * the mean mass mm_d (required); conv_flux = coeff cp / mu rho T' sqrt(g H) clip(grad_t -
+ * grad_ad, 0, inf)**1.5.  A profile whose conv_flux is 0 in every layer (a NaN is not 0) keeps the
+ * radiative update, bit for bit that of pb_radeq_update.  Any other: dF = ediff1d(Q_net +
+ * conv_flux), row k % 4 of signs_d holds ITS signs, the wobbling layers are taken against the same
+ * previous rows, the factors 0.5 / 1.15 apply to dt_scale_d as it is on entry, and row k + 1 is
+ * T + dT of that update.  hydro_g needs has_ref (radius 0 at the bottom otherwise).  2 <= nlayers
+ * <= 957 (two more vectors in LDS), nspecies <= 128. */
+int pb_radeq_update_convective(const pb_radeq *state, const pb_radeq_convection *conv,
+                               void *stream);
 
 /* _simpson.simps2D (src_c/_simpson.c:167-203): y_d[ny,nwave] */
 int pb_simps2D(double *out_d, const double *y_d, int ny, int nwave, const double *h_d,

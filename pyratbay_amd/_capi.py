@@ -132,6 +132,7 @@ _PROTOS = {
     'pb_two_stream_net_work_doubles': [i32, i32, i32],
     'pb_two_stream_net_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp],
     'pb_radeq_update': [vp, i32, vp],
+    'pb_radeq_update_convective': [vp, vp, vp],
     'pb_weighted_quantiles': [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp],
     'pb_weighted_quantiles_work_doubles': [i32, i32, i32],
     'pb_weighted_quantiles_resident_rows': [],

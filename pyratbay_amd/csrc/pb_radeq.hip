@@ -1,7 +1,8 @@
 // Radiative equilibrium on the device (Pyrat.radiative_equilibrium, pyrat/pyrat_obj.py:559-646 ->
-// spectrum/radiative_transfer.py:141-270) for a batch of profiles at fixed volume mixing ratios,
-// without convection.  One iteration is three launches and no host work: the interpolation of the
-// table (pb_interp_ec_batch[_cont]), k_two_stream_net_batch and k_radeq_update.
+// spectrum/radiative_transfer.py:141-272) for a batch of profiles at fixed volume mixing ratios,
+// with or without convection.  One iteration is three launches and no host work: the
+// interpolation of the table (pb_interp_ec_batch[_cont]), k_two_stream_net_batch and
+// k_radeq_update.
 //
 // k_two_stream_net_batch is k_two_stream_batch (pb_two_stream.hip: the same statements of
 // pb_two_stream.h in the same order, ec consumed, trans in the work buffer, the profile's
@@ -19,6 +20,14 @@
 // atmosphere of the next iteration (ideal-gas densities and the hydrostatic radius of
 // pb_atm_profile.h) in the same launch.  Its state -- dt_scale, the last four rows of sign(dF), the
 // iteration counter -- lives on the device.
+//
+// k_radeq_update<true> (pb_radeq_update_convective) is the same kernel with the second half of the
+// reference's loop (radiative_transfer.py:239-272) between the update and the atmosphere: the heat
+// capacity of the caller's cp/R table at the temperatures the radiative half produced, the
+// mixing-length flux of spectrum/convection.py:49-65, one workgroup-wide test whether any layer
+// convects, and where one does the update again from Q_net + conv_flux.  Both halves are ONE
+// function (update_from_flux); the first one of the convective kernel leaves the state it reads
+// -- dt_scale, the sign row of this iteration -- unwritten until the outcome is known.
 #include "pb_atm_profile.h"
 #include "pb_common.h"
 #include "pb_planck.h"
@@ -31,6 +40,7 @@ constexpr int kWave = 64;
 constexpr int kUpdate = 256;
 constexpr int kMaxRadius = 8;                        // int(4 * 2.0 + 0.5): sigma is clipped to 2
 constexpr int kRows = 6;                             // profile-length vectors of the update in LDS
+constexpr int kRowsConvection = 8;                   // ... with Q_net kept and the convective flux
 constexpr int kStage = 2 * kUpdate;                  // doubles of LDS for the groups' partial sums
 
 // The order the parts are added in: up to kUpdate / L groups of consecutive parts (one thread per
@@ -249,116 +259,278 @@ __device__ __forceinline__ double np_sign(double x)
     return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : (x == 0.0 ? 0.0 : x));
 }
 
-__global__ __launch_bounds__(kUpdate) void k_radeq_update(pb_radeq a, int init_only)
+// Qup, Qdown of profile w: the parts in the order of part_groups, stored, and Q_net into s_q
+// (every thread its own layers l = tid, tid + kUpdate, ...; no barrier behind them).  s_part: the
+// groups' partial sums.
+__device__ void sum_parts(const pb_radeq &a, int64_t w, double *s_q, double *s_part)
+{
+    const int L = a.nlayers;
+    const int tid = threadIdx.x;
+    const int groups = part_groups(L, a.nparts);
+    const int chunk = (a.nparts + groups - 1) / groups;
+    for (int idx = tid; idx < groups * L; idx += kUpdate) {
+        const int g = idx / L, l = idx - g * L;
+        double qu = 0.0, qd = 0.0;
+        for (int p = g * chunk; p < min((g + 1) * chunk, a.nparts); p++) {
+            const double *q = a.parts_d + ((w * a.nparts + p) * 2) * L;
+            qu += q[l];
+            qd += q[L + l];
+        }
+        s_part[(2 * g) * L + l] = qu;
+        s_part[(2 * g + 1) * L + l] = qd;
+    }
+    __syncthreads();
+    for (int l = tid; l < L; l += kUpdate) {
+        double qu = 0.0, qd = 0.0;
+        for (int g = 0; g < groups; g++) {
+            qu += s_part[(2 * g) * L + l];
+            qd += s_part[(2 * g + 1) * L + l];
+        }
+        a.q_up_d[w * L + l] = qu;
+        a.q_down_d[w * L + l] = qd;
+        s_q[l] = qu - qd;
+    }
+}
+
+// The profile-length vectors of the update in LDS
+struct Rows {
+    double *t;                        // T of this iteration
+    double *q;                        // Q_net; |dT|; the hydrostatic integrand
+    double *df;                       // dF; the cumulative hydrostatic integral
+    double *a;                        // dt_scale_tmp before its filter; T of the next iteration
+    double *b;                        // dt_scale_tmp; the radius
+    double *tn;                       // T + dT
+    double *w;                        // [2 kMaxRadius + 1] filter weights
+    double *qn, *cf;                  // (k_radeq_update<true>) Q_net kept; the convective flux
+    int *radius;                      // the radius of the temperature filter
+};
+
+// The update from a net flux s_f (radiative_transfer.py:211-233, and 254-272 with the convective
+// flux added): s_f may be s.q.  Writes row k + 1 of the history, temp_d and the diagnostics, and
+// leaves the next profile in s.a and the new dt_scale in s.b, behind a barrier; the state the
+// statements read -- row k % 4 of the signs, dt_scale_d -- is written only with commit.
+__device__ void update_from_flux(const pb_radeq &a, int64_t w, int k, const double *s_f,
+                                 const Rows &s, bool commit)
+{
+    const int L = a.nlayers;
+    const int tid = threadIdx.x;
+    if (tid == 0)
+        gauss_weights(1.5, s.w);
+    __syncthreads();
+    // dF, its sign, the wobbling layers, dt_scale_tmp before the filter
+    const int nprev = min(k, 4);
+    for (int l = tid; l < L; l += kUpdate) {
+        const double dF = l == 0 ? 0.0 : s_f[l] - s_f[l - 1];
+        const double sg = np_sign(dF);
+        bool wobble = false;
+        for (int r = 1; r <= nprev; r++)
+            if ((a.signs_d[(w * 4 + ((k - r) & 3)) * L + l] - sg) != 0.0)
+                wobble = true;
+        if (commit)
+            a.signs_d[(w * 4 + (k & 3)) * L + l] = sg;
+        if (a.wobble_d)
+            a.wobble_d[w * L + l] = wobble;
+        double v = a.dt_scale_d[w * L + l] * (wobble ? 0.5 : 1.15);
+        v = v < 1.0 ? 1.0 : v;                   // np.clip = minimum(maximum(x, lo), hi)
+        v = v > 1.0e8 ? 1.0e8 : v;
+        s.df[l] = dF;
+        s.a[l] = v;
+    }
+    __syncthreads();
+    for (int l = tid; l < L; l += kUpdate) {
+        const double dts = correlate_reflect(s.a, l, L, s.w, 6);
+        const double dF = s.df[l], t = s.t[l];
+        const double dT = ((dts * np_sign(dF)) * pow(fabs(dF), 0.1)) /
+                          ((kSigmaSB * pow(t, 3.0)) * a.dpress_d[l]);
+        s.b[l] = dts;
+        s.tn[l] = t + dT;
+        s.q[l] = fabs(dT);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        s.tn[0] = s.tn[1];                       // isothermal top
+        double sigma = (np_sum<4>(s.q, L) / (double)L) / 10.0;
+        sigma = sigma < 0.75 ? 0.75 : sigma;
+        sigma = sigma > 2.0 ? 2.0 : sigma;
+        *s.radius = gauss_weights(sigma, s.w);
+        a.iter_d[w] = k + 1;
+        if (a.sigma_d)
+            a.sigma_d[w] = sigma;
+    }
+    __syncthreads();
+    const int radius = *s.radius;
+    for (int l = tid; l < L; l += kUpdate) {
+        double v = l < L - 1 ? correlate_reflect(s.tn, l, L, s.w, radius) : s.tn[l];
+        v = v < a.tmin ? a.tmin : v;
+        v = v > a.tmax ? a.tmax : v;
+        s.a[l] = v;
+        if (commit)
+            a.dt_scale_d[w * L + l] = s.b[l];
+        a.temps_d[(w * a.nrows + k + 1) * L + l] = v;
+        a.temp_d[w * L + l] = v;
+    }
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------------- the convective half
+
+constexpr double kAmu = 1.66053906892e-27 * 1e3;     // pc.amu = sc 'unified atomic mass unit' * 1e3
+
+// np_sum_block of the n values f(0 .. n - 1), n <= 128
+template <class F>
+__device__ __forceinline__ double np_sum_of(int n, F f)
+{
+    if (n < 8) {
+        double res = 0.0;
+        for (int i = 0; i < n; i++)
+            res += f(i);
+        return res;
+    }
+    double r[8];
+    for (int j = 0; j < 8; j++)
+        r[j] = f(j);
+    int i = 8;
+    for (; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; j++)
+            r[j] += f(i + j);
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++)
+        res += f(i);
+    return res;
+}
+
+// np.interp(x, xp[n], fp[n * stride : stride]): interp_clamped of pb_clouds.hip on one column of a
+// table (the end values outside it, the node's own value on a node)
+__device__ inline double interp_column(const double *xp, const double *fp, int stride, int n,
+                                       double x)
+{
+    if (x > xp[n - 1])
+        return fp[(int64_t)(n - 1) * stride];
+    if (x < xp[0])
+        return fp[0];
+    int lo = 0, hi = n - 1;                    // largest lo with xp[lo] <= x
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (xp[mid] <= x)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    if (xp[hi] <= x)
+        lo = hi;
+    const double f0 = fp[(int64_t)lo * stride];
+    if (lo == n - 1 || xp[lo] == x)
+        return f0;
+    const double slope = (fp[(int64_t)(lo + 1) * stride] - f0) / (xp[lo + 1] - xp[lo]);
+    return slope * (x - xp[lo]) + f0;
+}
+
+// convection.convective_flux (spectrum/convection.py:49-65) at one layer: grad_t = the
+// logarithmic gradient of the temperature over convection.py's own dpress, coeff =
+// alpha**2 sqrt(beta); the product left to right
+__device__ inline double convective_flux(double coeff, double grad_t, double temp, double cp,
+                                         double gravity, double mu, double rho)
+{
+    const double cv = cp - pb::atm::kBoltz / kAmu;
+    const double gamma = cp / cv;
+    const double grad_ad = 1.0 - 1.0 / gamma;
+    double delta = grad_t - grad_ad;
+    delta = delta < 0.0 ? 0.0 : delta;           // np.clip(x, 0, inf): a NaN stays
+    const double H = (pb::atm::kBoltz * temp) / ((mu * kAmu) * gravity);
+    return ((((coeff * cp) / mu) * rho) * temp) * sqrt(gravity * H) * pow(delta, 1.5);
+}
+
+// radiative_transfer.py:239-272 behind update_from_flux(.., commit = false): the heat capacity and
+// the convective flux at the temperatures the radiative half left in s.a, with the gravity,
+// density and mean mass of the evaluated profile (s.t, radius_d as it is on entry); where a layer
+// convects, the update again from Q_net + conv_flux; else the radiative half's state is written.
+__device__ void convective_half(const pb_radeq &a, const pb_radeq_convection &c, int64_t w, int k,
+                                const Rows &s)
+{
+    const int L = a.nlayers, S = a.nspecies;
+    const int tid = threadIdx.x;
+    const double *vmr = a.vmr_d + w * a.vmr_stride;
+    const double *mm = a.mm_d + w * a.mm_stride;
+    const double *cp_table = c.cp_table_d + w * c.cp_table_stride;
+    int nonzero = 0;
+    for (int l = tid; l < L; l += kUpdate) {
+        const double tn = s.a[l], tk = s.t[l], p = a.pressure_d[l];
+        const double *x = vmr + (int64_t)l * S;
+        const double cp = (np_sum_of(S, [&](int j) {
+            return interp_column(c.cp_temps_d, cp_table + j, S, c.ntemps, tn) * x[j];
+        }) * pb::atm::kBoltz) / kAmu;
+        const double r = a.radius_d[w * L + l];
+        const double gravity = (pb::atm::kGrav * c.mplanet) / (r * r);
+        const double rho = np_sum_of(S, [&](int j) {
+            return pb::atm::ideal_gas_density(x[j], p, tk) * c.mol_mass_d[j];
+        }) * kAmu;
+        const double grad_t = (l == 0 ? 0.0 : log(tn) - log(s.a[l - 1])) / c.conv_dpress_d[l];
+        const double f = convective_flux(c.coeff, grad_t, tn, cp, gravity, mm[l], rho);
+        s.cf[l] = f;
+        c.conv_flux_d[w * L + l] = f;
+        nonzero |= !(f == 0.0);                  // (a NaN is not zero)
+    }
+    const int convective = __syncthreads_or(nonzero) != 0;
+    if (tid == 0)
+        c.convective_d[w] = convective;
+    if (!convective) {
+        // np.all(conv_flux == 0): the radiative result stands
+        for (int l = tid; l < L; l += kUpdate) {
+            a.signs_d[(w * 4 + (k & 3)) * L + l] = np_sign(s.df[l]);
+            a.dt_scale_d[w * L + l] = s.b[l];
+        }
+        return;
+    }
+    for (int l = tid; l < L; l += kUpdate)
+        s.qn[l] = s.qn[l] + s.cf[l];
+    update_from_flux(a, w, k, s.qn, s, true);        // (begins with a barrier)
+}
+
+// kConv: pb_radeq_update_convective (two more rows; c is not read otherwise)
+template <bool kConv>
+__global__ __launch_bounds__(kUpdate) void k_radeq_update(pb_radeq a, pb_radeq_convection c,
+                                                          int init_only)
 {
     extern __shared__ double s_row[];
     const int L = a.nlayers;
     const int tid = threadIdx.x;
     const int64_t w = blockIdx.x;
-    double *s_t = s_row;              // T of this iteration
-    double *s_q = s_t + L;            // Q_net; |dT|; the hydrostatic integrand
-    double *s_df = s_q + L;           // dF; the cumulative hydrostatic integral
-    double *s_a = s_df + L;           // dt_scale_tmp before its filter; T of the next iteration
-    double *s_b = s_a + L;            // dt_scale_tmp; the radius
-    double *s_tn = s_b + L;           // T + dT
-    double *s_w = s_tn + L;           // [2 kMaxRadius + 1] filter weights
+    __shared__ int s_radius;
+    Rows s;
+    s.t = s_row;
+    s.q = s.t + L;
+    s.df = s.q + L;
+    s.a = s.df + L;
+    s.b = s.a + L;
+    s.tn = s.b + L;
+    s.qn = s.tn + L;
+    s.cf = s.qn + L;
+    s.w = s.tn + (kConv ? 3 : 1) * L;
+    s.radius = &s_radius;
     // the groups' partial sums [groups][2][L]: groups * L <= kUpdate up to kUpdate layers, i.e. at
     // most kStage doubles behind the weights; above that ONE group, 2 L doubles, which lie over
-    // s_a and s_b (both dead until the sums have been read, a barrier before their first store)
-    double *s_part = L > kUpdate ? s_a : s_w + 2 * kMaxRadius + 1;
-    __shared__ int s_radius;
+    // s.a and s.b (both dead until the sums have been read, a barrier before their first store)
+    double *s_part = L > kUpdate ? s.a : s.w + 2 * kMaxRadius + 1;
     const int k = a.iter_d[w];
     // (a launch beyond the rows of the history does nothing)
     if (!init_only && (k < 0 || k + 1 >= a.nrows))
         return;
     for (int l = tid; l < L; l += kUpdate)
-        s_t[l] = a.temp_d[w * L + l];
-    double *s_next = s_t;
+        s.t[l] = a.temp_d[w * L + l];
+    double *s_next = s.t;
     if (!init_only) {
-        // Qup, Qdown: the parts in the order of part_groups; Q_net
-        const int groups = part_groups(L, a.nparts);
-        const int chunk = (a.nparts + groups - 1) / groups;
-        for (int idx = tid; idx < groups * L; idx += kUpdate) {
-            const int g = idx / L, l = idx - g * L;
-            double qu = 0.0, qd = 0.0;
-            for (int p = g * chunk; p < min((g + 1) * chunk, a.nparts); p++) {
-                const double *q = a.parts_d + ((w * a.nparts + p) * 2) * L;
-                qu += q[l];
-                qd += q[L + l];
-            }
-            s_part[(2 * g) * L + l] = qu;
-            s_part[(2 * g + 1) * L + l] = qd;
-        }
-        __syncthreads();
-        for (int l = tid; l < L; l += kUpdate) {
-            double qu = 0.0, qd = 0.0;
-            for (int g = 0; g < groups; g++) {
-                qu += s_part[(2 * g) * L + l];
-                qd += s_part[(2 * g + 1) * L + l];
-            }
-            a.q_up_d[w * L + l] = qu;
-            a.q_down_d[w * L + l] = qd;
-            s_q[l] = qu - qd;
-        }
-        if (tid == 0)
-            gauss_weights(1.5, s_w);
-        __syncthreads();
-        // dF, its sign, the wobbling layers, dt_scale_tmp before the filter
-        const int nprev = min(k, 4);
-        for (int l = tid; l < L; l += kUpdate) {
-            const double dF = l == 0 ? 0.0 : s_q[l] - s_q[l - 1];
-            const double sg = np_sign(dF);
-            bool wobble = false;
-            for (int r = 1; r <= nprev; r++)
-                if ((a.signs_d[(w * 4 + ((k - r) & 3)) * L + l] - sg) != 0.0)
-                    wobble = true;
-            a.signs_d[(w * 4 + (k & 3)) * L + l] = sg;
-            if (a.wobble_d)
-                a.wobble_d[w * L + l] = wobble;
-            double v = a.dt_scale_d[w * L + l] * (wobble ? 0.5 : 1.15);
-            v = v < 1.0 ? 1.0 : v;                   // np.clip = minimum(maximum(x, lo), hi)
-            v = v > 1.0e8 ? 1.0e8 : v;
-            s_df[l] = dF;
-            s_a[l] = v;
-        }
-        __syncthreads();
-        for (int l = tid; l < L; l += kUpdate) {
-            const double dts = correlate_reflect(s_a, l, L, s_w, 6);
-            const double dF = s_df[l], t = s_t[l];
-            const double dT = ((dts * np_sign(dF)) * pow(fabs(dF), 0.1)) /
-                              ((kSigmaSB * pow(t, 3.0)) * a.dpress_d[l]);
-            s_b[l] = dts;
-            s_tn[l] = t + dT;
-            s_q[l] = fabs(dT);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            s_tn[0] = s_tn[1];                       // isothermal top
-            double sigma = (np_sum<4>(s_q, L) / (double)L) / 10.0;
-            sigma = sigma < 0.75 ? 0.75 : sigma;
-            sigma = sigma > 2.0 ? 2.0 : sigma;
-            s_radius = gauss_weights(sigma, s_w);
-            a.iter_d[w] = k + 1;
-            if (a.sigma_d)
-                a.sigma_d[w] = sigma;
-        }
-        __syncthreads();
-        const int radius = s_radius;
-        for (int l = tid; l < L; l += kUpdate) {
-            double v = l < L - 1 ? correlate_reflect(s_tn, l, L, s_w, radius) : s_tn[l];
-            v = v < a.tmin ? a.tmin : v;
-            v = v > a.tmax ? a.tmax : v;
-            s_a[l] = v;
-            a.dt_scale_d[w * L + l] = s_b[l];
-            a.temps_d[(w * a.nrows + k + 1) * L + l] = v;
-            a.temp_d[w * L + l] = v;
-        }
-        __syncthreads();
-        s_next = s_a;
+        sum_parts(a, w, s.q, s_part);
+        if (kConv)
+            for (int l = tid; l < L; l += kUpdate)
+                s.qn[l] = s.q[l];
+        update_from_flux(a, w, k, s.q, s, !kConv);
+        if (kConv)
+            convective_half(a, c, w, k, s);
+        s_next = s.a;
     } else {
         __syncthreads();
     }
-
+    double *s_q = s.q, *s_df = s.df, *s_b = s.b;
     // ---- the atmosphere of the next evaluation: n = vmr p / (k T) for the table's and the
     // continuum's species, consecutive threads writing consecutive elements
     const double *vmr = a.vmr_d + w * a.vmr_stride;
@@ -406,6 +578,61 @@ __global__ __launch_bounds__(kUpdate) void k_radeq_update(pb_radeq a, int init_o
         if (l < L - 1)
             a.intervals_d[w * (L - 1) + l] = s_b[l] - s_b[l + 1];
     }
+}
+
+// The most layers whose `rows` vectors fit 64 KiB of LDS beside the weights and the partial sums:
+// PB_ATM_MAX_LAYERS with the 6 rows of pb_radeq_update, 957 with the 8 of
+// pb_radeq_update_convective ((8192 - 17 - 512) / 8 doubles)
+constexpr int max_layers_of(int rows)
+{
+    const int fit = (64 * 1024 / (int)sizeof(double) - (2 * kMaxRadius + 1) - kStage) / rows;
+    return fit < PB_ATM_MAX_LAYERS ? fit : PB_ATM_MAX_LAYERS;
+}
+static_assert(max_layers_of(kRowsConvection) == 957, "pbhip.h and radeq.py state this limit");
+
+// The checks both entries of the update make before their launch; *lds_bytes: the dynamic LDS of
+// `rows` profile-length vectors, the filter weights and the groups' partial sums.
+int check_update(const pb_radeq &a, int init_only, const char *name, int rows, size_t *lds_bytes)
+{
+    const int max_layers = max_layers_of(rows);
+    PB_REQUIRE(a.nwalkers >= 0, "%s: %d profiles", name, a.nwalkers);
+    const size_t lds = ((size_t)rows * a.nlayers + 2 * kMaxRadius + 1 + kStage) * sizeof(double);
+    PB_REQUIRE(a.nlayers >= 2 && a.nlayers <= max_layers,
+               "%s: 2-%d layers, not %d (the profile's vectors are kept in LDS)", name,
+               max_layers, a.nlayers);
+    *lds_bytes = lds;
+    if (a.nwalkers == 0)
+        return PB_OK;
+    PB_REQUIRE(a.nrows >= 1 && a.nparts >= 0, "%s: %d history rows, %d parts", name,
+               a.nrows, a.nparts);
+    PB_REQUIRE(a.temp_d && a.iter_d && a.pressure_d && a.vmr_d && a.dens_d && a.tab_map_d,
+               "%s: null pointer", name);
+    PB_REQUIRE(init_only || (a.temps_d && a.dt_scale_d && a.signs_d && a.q_up_d && a.q_down_d &&
+                             a.dpress_d && (a.parts_d || a.nparts == 0)),
+               "%s: null pointer", name);
+    PB_REQUIRE(a.nspecies >= 1 && a.ntab >= 1 && a.ncont >= 0 &&
+                   (a.ncont == 0 || (a.cont_map_d && a.cdens_d)),
+               "%s: %d species, %d table species, %d continuum species", name, a.nspecies,
+               a.ntab, a.ncont);
+    PB_REQUIRE(a.vmr_stride == 0 || a.vmr_stride == (int64_t)a.nlayers * a.nspecies,
+               "%s: the stride of vmr is 0 (shared) or nlayers * nspecies", name);
+    PB_REQUIRE(a.rmodel >= -1 && a.rmodel <= 1,
+               "%s: radius model %d (-1 fixed, 0 hydro_m, 1 hydro_g)", name, a.rmodel);
+    if (a.rmodel >= 0) {
+        PB_REQUIRE(a.lnp_d && a.mm_d && a.radius_d && a.intervals_d,
+                   "%s: null pointer (radius model)", name);
+        PB_REQUIRE(a.mm_stride == 0 || a.mm_stride == a.nlayers,
+                   "%s: the stride of the mean mass is 0 (shared) or nlayers", name);
+        PB_REQUIRE(a.rmodel == 1 || a.has_ref,
+                   "%s: hydro_m needs a reference pressure and radius", name);
+        if (a.has_ref)
+            PB_REQUIRE(a.p0 > 0.0 && a.r0 > 0.0, "%s: p0 %g, r0 %g", name, a.p0, a.r0);
+        if (a.rmodel == 0)
+            PB_REQUIRE(a.mplanet > 0.0, "%s: mplanet %g", name, a.mplanet);
+        else
+            PB_REQUIRE(a.gplanet > 0.0, "%s: gplanet %g", name, a.gplanet);
+    }
+    return PB_OK;
 }
 
 }  // namespace
@@ -460,43 +687,42 @@ int pb_radeq_update(const pb_radeq *state, int init_only, void *stream)
 {
     PB_REQUIRE(state, "pb_radeq_update: null state struct");
     const pb_radeq &a = *state;
-    PB_REQUIRE(a.nwalkers >= 0, "pb_radeq_update: %d profiles", a.nwalkers);
-    const size_t lds = ((size_t)kRows * a.nlayers + 2 * kMaxRadius + 1 + kStage) * sizeof(double);
-    PB_REQUIRE(a.nlayers >= 2 && a.nlayers <= PB_ATM_MAX_LAYERS && lds <= 64 * 1024,
-               "pb_radeq_update: 2-%d layers, not %d (the profile's vectors are kept in LDS)",
-               PB_ATM_MAX_LAYERS, a.nlayers);
-    if (a.nwalkers == 0)
-        return PB_OK;
-    PB_REQUIRE(a.nrows >= 1 && a.nparts >= 0, "pb_radeq_update: %d history rows, %d parts",
-               a.nrows, a.nparts);
-    PB_REQUIRE(a.temp_d && a.iter_d && a.pressure_d && a.vmr_d && a.dens_d && a.tab_map_d,
-               "pb_radeq_update: null pointer");
-    PB_REQUIRE(init_only || (a.temps_d && a.dt_scale_d && a.signs_d && a.q_up_d && a.q_down_d &&
-                             a.dpress_d && (a.parts_d || a.nparts == 0)),
-               "pb_radeq_update: null pointer");
-    PB_REQUIRE(a.nspecies >= 1 && a.ntab >= 1 && a.ncont >= 0 &&
-                   (a.ncont == 0 || (a.cont_map_d && a.cdens_d)),
-               "pb_radeq_update: %d species, %d table species, %d continuum species", a.nspecies,
-               a.ntab, a.ncont);
-    PB_REQUIRE(a.vmr_stride == 0 || a.vmr_stride == (int64_t)a.nlayers * a.nspecies,
-               "pb_radeq_update: the stride of vmr is 0 (shared) or nlayers * nspecies");
-    PB_REQUIRE(a.rmodel >= -1 && a.rmodel <= 1,
-               "pb_radeq_update: radius model %d (-1 fixed, 0 hydro_m, 1 hydro_g)", a.rmodel);
-    if (a.rmodel >= 0) {
-        PB_REQUIRE(a.lnp_d && a.mm_d && a.radius_d && a.intervals_d,
-                   "pb_radeq_update: null pointer (radius model)");
-        PB_REQUIRE(a.mm_stride == 0 || a.mm_stride == a.nlayers,
-                   "pb_radeq_update: the stride of the mean mass is 0 (shared) or nlayers");
-        PB_REQUIRE(a.rmodel == 1 || a.has_ref,
-                   "pb_radeq_update: hydro_m needs a reference pressure and radius");
-        if (a.has_ref)
-            PB_REQUIRE(a.p0 > 0.0 && a.r0 > 0.0, "pb_radeq_update: p0 %g, r0 %g", a.p0, a.r0);
-        if (a.rmodel == 0)
-            PB_REQUIRE(a.mplanet > 0.0, "pb_radeq_update: mplanet %g", a.mplanet);
-        else
-            PB_REQUIRE(a.gplanet > 0.0, "pb_radeq_update: gplanet %g", a.gplanet);
-    }
-    k_radeq_update<<<a.nwalkers, kUpdate, lds, pb::as_stream(stream)>>>(a, init_only);
+    size_t lds = 0;
+    const int rc = check_update(a, init_only, "pb_radeq_update", kRows, &lds);
+    if (rc != PB_OK || a.nwalkers == 0)
+        return rc;
+    k_radeq_update<false><<<a.nwalkers, kUpdate, lds, pb::as_stream(stream)>>>(
+        a, pb_radeq_convection{}, init_only);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+int pb_radeq_update_convective(const pb_radeq *state, const pb_radeq_convection *conv, void *stream)
+{
+    PB_REQUIRE(state && conv, "pb_radeq_update_convective: null state or convection struct");
+    const pb_radeq &a = *state;
+    const pb_radeq_convection &c = *conv;
+    size_t lds = 0;
+    const int rc = check_update(a, 0, "pb_radeq_update_convective", kRowsConvection, &lds);
+    if (rc != PB_OK || a.nwalkers == 0)
+        return rc;
+    PB_REQUIRE(c.cp_temps_d && c.cp_table_d && c.mol_mass_d && c.conv_dpress_d && c.conv_flux_d &&
+                   c.convective_d && a.mm_d && a.radius_d,
+               "pb_radeq_update_convective: null pointer (convection)");
+    PB_REQUIRE(c.ntemps >= 1, "pb_radeq_update_convective: %d temperatures in the heat-capacity "
+               "table", c.ntemps);
+    PB_REQUIRE(c.cp_table_stride == 0 || c.cp_table_stride == (int64_t)c.ntemps * a.nspecies,
+               "pb_radeq_update_convective: the stride of the heat-capacity table is 0 (shared) or "
+               "ntemps * nspecies");
+    PB_REQUIRE(a.nspecies <= 128, "pb_radeq_update_convective: %d species: at most 128 (one block "
+               "of NumPy's pairwise sum)", a.nspecies);
+    PB_REQUIRE(a.mm_stride == 0 || a.mm_stride == a.nlayers,
+               "pb_radeq_update_convective: the stride of the mean mass is 0 (shared) or nlayers");
+    PB_REQUIRE(c.mplanet > 0.0 && c.coeff == c.coeff,
+               "pb_radeq_update_convective: mplanet %g, coeff %g", c.mplanet, c.coeff);
+    PB_REQUIRE(a.rmodel != 1 || a.has_ref, "pb_radeq_update_convective: hydro_g without a "
+               "reference radius has radius 0 at the bottom: no gravity there");
+    k_radeq_update<true><<<a.nwalkers, kUpdate, lds, pb::as_stream(stream)>>>(a, c, 0);
     PB_LAUNCH_CHECK();
     return PB_OK;
 }

@@ -1,6 +1,6 @@
 """Radiative equilibrium on the device: runmode = radeq of the reference
 (Pyrat.radiative_equilibrium, pyrat/pyrat_obj.py:559-646 -> ps.radiative_equilibrium,
-spectrum/radiative_transfer.py:141-270) for a batch of profiles.
+spectrum/radiative_transfer.py:141-272) for a batch of profiles.
 
 One iteration evaluates the two-stream fluxes of every layer, integrates them over wavenumber to
 the bolometric Qup and Qdown, and moves each layer's temperature by an adaptive step along the
@@ -8,18 +8,27 @@ sign of the net-flux divergence.  Here that is three launches per iteration and 
 the interpolation of the table (with the Continuum's terms when one is attached),
 pb_two_stream_net_batch (the two-stream batch kernel that also reduces t_j flux[i][j] over its
 columns) and pb_radeq_update (the update and the atmosphere of the next iteration): csrc/pb_radeq.hip.
+With run(convection=True) the third launch is pb_radeq_update_convective: the same update, the
+mixing-length convective flux (spectrum/convection.py:13-67) at the temperatures it produced and,
+for a profile with a superadiabatic layer, the update again with that flux added to the net flux
+(radiative_transfer.py:239-272).
 
 Deviations from the reference:
   * the volume mixing ratios are FIXED (the reference calls chemcat's thermochemical equilibrium
     every iteration); the mean molecular mass is therefore constant;
-  * no convection (it needs chemcat's heat capacities): the public call does not offer it;
+  * the heat capacities of the convective half are np.interp on the caller's table of cp / R per
+    species (the reference asks chemcat's chem_model.heat_capacity);
+  * in the reference the convective branch's in-place dt_scale[wobble] *= 0.5 followed by the
+    rebinding dt_scale = gaussf(...) leaves atm._dt_scale stale for a later continue_run; here a
+    continued run goes on from the dt_scale the loop itself was using;
   * continue_run starts a fresh sign history (what a second call of the reference's function with
     radeq_temps = atleast_2d(last row) does; with a longer history its df_sign index runs out of
     bounds);
   * the wavenumber integral is sum_j t_j flux_j with the trapezoid weights t_j, summed per
     wavefront of 64 columns and then over the wavefronts in order; np.trapezoid sums pairwise.
 
-step_host is the NumPy form of one update under the reference's names.
+step_host is the NumPy form of one update under the reference's names, step_convective_host that
+of an update with convection; convective_flux_host and heat_capacity_host are its two parts.
 """
 import ctypes as C
 
@@ -35,6 +44,10 @@ MAXF = 1.0e08                               # maximum temperature scale factor
 DT_SCALE0 = 1.0e5                           # dt_scale of a fresh run (pyrat_obj.py:605-606)
 RMODELS = {None: -1, 'hydro_m': 0, 'hydro_g': 1}
 MAX_LAYERS = 744                            # 64 KiB of LDS / (11 doubles per layer): pb_radeq.hip
+# with convection: pb_radeq_update_convective keeps 8 vectors per profile in LDS and takes
+# (8192 - 17 - 512) // 8 = 957 layers; the net-flux kernel of the same iteration still takes 744
+MAX_LAYERS_CONVECTION = min(MAX_LAYERS, 957)
+AMU = 1.66053906892e-27 * 1e3               # pc.amu = sc 'unified atomic mass unit' * 1e3 (g)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -97,6 +110,59 @@ def step_host(temp, dt_scale, df_sign, Qup, Qdown, dpress, tmin=0.0, tmax=6000.0
                 sigma=float(sigma))
 
 
+def convective_flux_host(pressure_barye, temperature, cp, gravity, mu, rho, alpha=1.5, beta=0.5):
+    """convection.convective_flux (spectrum/convection.py:13-67) in its order of operations: the
+    mixing-length flux [L] (erg s-1 cm-2), zero where grad_t <= grad_ad.  Its own dpress keeps
+    element 0 = 1 (unlike log_pressure_steps), so grad_t[0] = 0."""
+    temperature, cp = np.asarray(temperature, float), np.asarray(cp, float)
+    dpress = np.ediff1d(np.log(np.asarray(pressure_barye, float)), to_begin=1.0)
+    grad_t = np.ediff1d(np.log(temperature), to_begin=0.0) / dpress
+    cv = cp - pa.K_BOLTZ / AMU
+    gamma = cp / cv
+    grad_ad = 1.0 - 1.0 / gamma
+    delta_grad = np.clip(grad_t - grad_ad, 0, np.inf)
+    H = pa.K_BOLTZ * temperature / (mu * AMU * gravity)
+    return (alpha**2 * np.sqrt(beta) * cp / mu * rho * temperature * np.sqrt(gravity * H)
+            * delta_grad**1.5)
+
+
+def heat_capacity_host(cp_temps, cp_table, temp):
+    """cp / R [L, S] of the S species at temp[L]: np.interp per column of cp_table[nT, S] on
+    cp_temps[nT], the end values outside the table -- the stand-in for chemcat's
+    chem_model.heat_capacity."""
+    cp_table = np.asarray(cp_table, float)
+    return np.stack([np.interp(temp, cp_temps, cp_table[:, s]) for s in range(cp_table.shape[1])],
+                    axis=1)
+
+
+def step_convective_host(temp, dt_scale, df_sign, Qup, Qdown, dpress, pressure, vmr, mol_mass,
+                         radius, cp_temps, cp_table, mplanet, alpha=1.5, beta=0.5, tmin=0.0,
+                         tmax=6000.0):
+    """step_host followed by radiative_transfer.py:239-272 (convection=True).  Beyond step_host's
+    arguments: pressure[L] (bar), vmr[L, S], mol_mass[S], radius[L] (that of the evaluation the
+    fluxes come from, like temp), the heat-capacity table and mplanet (g).  Returns step_host's
+    dict of the update that stands, plus conv_flux[L], convective (whether the second half ran)
+    and radiative (the radiative half's dict)."""
+    temp, dt_scale = np.asarray(temp, float), np.asarray(dt_scale, float)
+    vmr, mol_mass = np.asarray(vmr, float), np.asarray(mol_mass, float)
+    first = step_host(temp, dt_scale, df_sign, Qup, Qdown, dpress, tmin, tmax)
+    heat_capacity = heat_capacity_host(cp_temps, cp_table, first['temp'])
+    cp = np.sum(heat_capacity * vmr, axis=1) * pa.K_BOLTZ / AMU
+    gplanet = pa.G_GRAV * mplanet / np.asarray(radius, float)**2.0
+    d = pa.ideal_gas_density(vmr, pressure, temp)
+    rho = np.sum(d * mol_mass, axis=1) * AMU
+    mm = pa.mean_weight(vmr, mass=mol_mass)
+    conv_flux = convective_flux_host(np.asarray(pressure, float) * pa.BAR, first['temp'], cp,
+                                     gplanet, mm, rho, alpha, beta)
+    if np.all(conv_flux == 0.0):
+        return dict(first, conv_flux=conv_flux, convective=False, radiative=first)
+    # the update again with the convective flux: the new signs replace this iteration's row, the
+    # factors apply to the dt_scale of the start of the iteration
+    Q_net = np.asarray(Qup, float) - np.asarray(Qdown, float)
+    second = step_host(temp, dt_scale, df_sign, Q_net + conv_flux, 0.0, dpress, tmin, tmax)
+    return dict(second, conv_flux=conv_flux, convective=True, radiative=first)
+
+
 def log_pressure_steps(pressure):
     """dpress of radiative_transfer.py:188-189."""
     dpress = np.ediff1d(np.log(np.asarray(pressure, float)), to_begin=1.0)
@@ -140,6 +206,16 @@ class RadeqStruct(C.Structure):
         ('rmodel', C.c_int), ('has_ref', C.c_int),
         ('mplanet', C.c_double), ('gplanet', C.c_double), ('p0', C.c_double), ('r0', C.c_double),
         ('radius_d', C.c_void_p), ('intervals_d', C.c_void_p),
+    ]
+
+
+class ConvectionStruct(C.Structure):
+    """pb_radeq_convection of include/pbhip.h."""
+    _fields_ = [
+        ('cp_temps_d', C.c_void_p), ('cp_table_d', C.c_void_p), ('cp_table_stride', C.c_int64),
+        ('ntemps', C.c_int), ('mol_mass_d', C.c_void_p), ('conv_dpress_d', C.c_void_p),
+        ('mplanet', C.c_double), ('coeff', C.c_double),
+        ('conv_flux_d', C.c_void_p), ('convective_d', C.c_void_p),
     ]
 
 
@@ -210,6 +286,10 @@ class RadiativeEquilibrium:
     tint: internal temperature (K), a scalar or [nw]; flux_top: the irradiation at the top, [W],
     [nw, W] or None.  tmin / tmax: the bounds the new temperatures are clipped to; default the
     intersection of the table's and the CIA tables' ranges.
+    heat_capacity: (cp_temps[nT] ascending, cp_over_R[nT, S] or [nw, nT, S]), cp / R > 1 of every
+    column of vmr, read by np.interp (the end values outside the table); mixing_length: (alpha,
+    beta) of convection.convective_flux.  Both are read only by run(convection=True), which also
+    needs mplanet (the gravity is G mplanet / radius**2 whatever the radius model).
 
     For tests and diagnosis, beyond what the reference's loop leaves behind: run(...,
     diagnostics=True) keeps every iteration's q_up, q_down, dt_scale, wobbling layers and filter
@@ -217,11 +297,13 @@ class RadiativeEquilibrium:
 
     Refused with ValueError before any launch: a spectrum that is not two-stream, alkali models,
     a Deck or cloud-type models in its Continuum, fewer than 2 layers, shapes that do not match,
-    and (in run) a starting temperature outside [tmin, tmax]."""
+    a heat-capacity table that is not finite, not ascending or has cp / R <= 1, and (in run) a
+    starting temperature outside [tmin, tmax], or convection=True without heat_capacity, without
+    mplanet > 0, or with a radius that is 0 at the bottom (hydro_g without p0, r0)."""
 
     def __init__(self, spectrum, pressure, vmr, mol_mass, radius_model=None, gravity=None,
                  mplanet=None, p0=None, r0=None, tint=0.0, flux_top=None, tmin=None, tmax=None,
-                 species=None, table_species=None):
+                 species=None, table_species=None, heat_capacity=None, mixing_length=(1.5, 0.5)):
         self.model = spectrum
         _check(getattr(spectrum, 'rt_path', None) == 'two_stream',
                f"rt_path {getattr(spectrum, 'rt_path_name', getattr(spectrum, 'rt_path', None))!r}: "
@@ -236,8 +318,10 @@ class RadiativeEquilibrium:
         L, W, S = spectrum.nlayers, spectrum.nwave, spectrum.nspec
         self.nlayers, self.nwave = L, W
         _check(L >= 2, f'{L} layer: the update differences neighbouring layers, at least 2')
-        _check(L <= MAX_LAYERS, f'{L} layers: at most {MAX_LAYERS} (the net-flux kernel keeps the '
-               "profile and its workgroup's flux sums in LDS)")
+        most = MAX_LAYERS if heat_capacity is None else MAX_LAYERS_CONVECTION
+        _check(L <= most, f'{L} layers: at most {most} (the net-flux kernel keeps the profile and '
+               "its workgroup's flux sums in LDS" +
+               ('' if heat_capacity is None else ', the convective update eight vectors of it') + ')')
         self.pressure = np.asarray(pressure, float)
         _check(self.pressure.shape == (L,), f'pressure must have shape ({L},), got '
                f'{self.pressure.shape}')
@@ -286,9 +370,25 @@ class RadiativeEquilibrium:
         ftshape = None if flux_top is None else tuple(flux_top.shape)
         _check(ftshape is None or (len(ftshape) in (1, 2) and ftshape[-1] == W),
                f'flux_top must have shape ({W},) or (nw, {W}), got {ftshape}')
+        self.heat_capacity = None
+        if heat_capacity is not None:
+            _check(len(heat_capacity) == 2, 'heat_capacity = (cp_temps[nT], cp_over_R[nT, S])')
+            cp_temps = np.asarray(heat_capacity[0], float)
+            cp_table = np.asarray(heat_capacity[1], float)
+            _check(cp_temps.ndim == 1 and len(cp_temps) >= 1 and cp_table.ndim in (2, 3) and
+                   cp_table.shape[-2:] == (len(cp_temps), nsp),
+                   f'heat_capacity = (cp_temps[nT], cp_over_R[nT, {nsp}] or [nw, nT, {nsp}]), got '
+                   f'shapes {cp_temps.shape} and {cp_table.shape}')
+            _check(np.all(np.isfinite(cp_temps)) and np.all(np.isfinite(cp_table)),
+                   'heat_capacity: a value that is not finite')
+            _check(np.all(np.diff(cp_temps) > 0), 'heat_capacity: cp_temps must be ascending')
+            _check(np.all(cp_table > 1.0), 'heat_capacity: cp_over_R <= 1 (cv = cp - R <= 0)')
+            self.heat_capacity = (cp_temps, cp_table)
         counts = {'vmr': self.vmr.shape[0] if self.vmr.ndim == 3 else None,
                   'tint': self.tint.shape[0] if self.tint.ndim == 1 else None,
-                  'flux_top': ftshape[0] if ftshape is not None and len(ftshape) == 2 else None}
+                  'flux_top': ftshape[0] if ftshape is not None and len(ftshape) == 2 else None,
+                  'heat_capacity': self.heat_capacity[1].shape[0] if self.heat_capacity is not None
+                  and self.heat_capacity[1].ndim == 3 else None}
         given = {k: v for k, v in counts.items() if v is not None}
         _check(len(set(given.values())) <= 1, f'different numbers of profiles: {given}')
         self.nprofiles = next(iter(given.values())) if given else None     # None: temp0 decides
@@ -298,7 +398,11 @@ class RadiativeEquilibrium:
         self.tmin = lo if tmin is None else float(tmin)
         self.tmax = hi if tmax is None else float(tmax)
         _check(self.tmin < self.tmax, f'tmin = {self.tmin} >= tmax = {self.tmax}')
+        _check(len(mixing_length) == 2 and all(np.isfinite(v) and v >= 0 for v in mixing_length),
+               f'mixing_length = (alpha, beta), both finite and >= 0, got {mixing_length}')
+        self.mixing_length = (float(mixing_length[0]), float(mixing_length[1]))
         self.temps = self.dt_scale = self.q_up = self.q_down = self.spectrum = None
+        self.conv_flux = self.convective = None
         self._state = None
 
     # ------------------------------------------------------------------------------ set-up
@@ -369,10 +473,28 @@ class RadiativeEquilibrium:
         st.p0, st.r0 = float(self.p0 or 0.0), float(self.r0 or 0.0)
         st.radius_d, st.intervals_d = d['radius'].data_ptr(), d['intervals'].data_ptr()
         d['struct'] = st
+        if self.heat_capacity is not None:
+            cp_temps, cp_table = self.heat_capacity
+            alpha, beta = self.mixing_length
+            d['cp_temps'], d['cp_table'] = dev(cp_temps), dev(cp_table)
+            d['mol_mass'] = dev(self.mol_mass)
+            d['conv_dpress'] = dev(np.ediff1d(np.log(self.pressure * pa.BAR), to_begin=1.0))
+            d['conv_flux'] = new(nw, L, fill=0.0)
+            d['convective'] = new(nw, dtype=torch.int32, fill=0)
+            cv = ConvectionStruct()
+            cv.cp_temps_d, cv.cp_table_d = d['cp_temps'].data_ptr(), d['cp_table'].data_ptr()
+            cv.cp_table_stride = cp_table.shape[1] * cp_table.shape[2] if cp_table.ndim == 3 else 0
+            cv.ntemps = len(cp_temps)
+            cv.mol_mass_d, cv.conv_dpress_d = d['mol_mass'].data_ptr(), d['conv_dpress'].data_ptr()
+            cv.mplanet = float(self.mplanet or 0.0)
+            cv.coeff = float(alpha**2 * np.sqrt(beta))
+            cv.conv_flux_d, cv.convective_d = d['conv_flux'].data_ptr(), d['convective'].data_ptr()
+            d['convection'] = cv
         self._state = d
 
     # --------------------------------------------------------------------------------- run
-    def run(self, temp0=None, nsamples=100, continue_run=False, diagnostics=False):
+    def run(self, temp0=None, nsamples=100, continue_run=False, diagnostics=False,
+            convection=False):
         """nsamples iterations from temp0 ([L] for every profile, or [nw, L]; host array or device
         tensor) -> the history temps[nw, 1 + nsamples, L] (device tensor; row 0 is temp0).
         continue_run=True: from the last row of the previous run with its dt_scale and a fresh
@@ -381,11 +503,26 @@ class RadiativeEquilibrium:
         evaluated profile, temps[:, -2].  diagnostics=True also keeps every iteration's q_up,
         q_down, dt_scale [nw, nsamples, L], wobble (int32, the wobbling layers) and sigma
         [nw, nsamples] in .history (device-to-device copies on the stream, still nothing read
-        back)."""
+        back).
+        convection=True (the reference's flag; needs heat_capacity= and mplanet=): every
+        iteration's update is pb_radeq_update_convective, which adds the mixing-length convective
+        flux to the net flux of a profile with a superadiabatic layer and redoes its update.
+        Leaves .conv_flux [nw, L] and .convective [nw] (int32: whether the second half ran) of the
+        last iteration; with diagnostics, history['conv_flux'] [nw, nsamples, L] and
+        history['convective'] [nw, nsamples]."""
         import torch
         L = self.nlayers
         nsamples = int(nsamples)
         _check(nsamples >= 0, f'nsamples = {nsamples}')
+        if convection:
+            _check(self.heat_capacity is not None, 'convection=True needs the heat capacities: '
+                   'heat_capacity=(cp_temps[nT], cp_over_R[nT, S])')
+            _check(self.mplanet is not None and self.mplanet > 0,
+                   f'convection=True needs mplanet > 0 (gravity = G mplanet / radius**2), got '
+                   f'{self.mplanet}')
+            _check(not (self.radius_model == 'hydro_g' and self.p0 is None),
+                   'convection=True with hydro_g needs p0 and r0: the radius is 0 at the bottom '
+                   'without them')
         if continue_run:
             _check(self.temps is not None, 'continue_run without an earlier run')
             _check(temp0 is None, 'continue_run starts from the last row, not from a temp0')
@@ -429,6 +566,10 @@ class RadiativeEquilibrium:
                     for k in ('q_up', 'q_down', 'dt_scale')}
             hist['wobble'] = torch.empty((nw, nsamples, L), dtype=torch.int32, device='cuda')
             hist['sigma'] = torch.empty((nw, nsamples), dtype=torch.float64, device='cuda')
+            if convection:
+                hist['conv_flux'] = torch.empty((nw, nsamples, L), dtype=torch.float64,
+                                                device='cuda')
+                hist['convective'] = torch.empty((nw, nsamples), dtype=torch.int32, device='cuda')
             d['wobble'] = torch.empty((nw, L), dtype=torch.int32, device='cuda')
             d['sigma'] = torch.empty(nw, dtype=torch.float64, device='cuda')
             st.wobble_d, st.sigma_d = d['wobble'].data_ptr(), d['sigma'].data_ptr()
@@ -443,7 +584,11 @@ class RadiativeEquilibrium:
                             **ckw)
             two_stream_net_batch(d['ec'], d['intervals'], m.wn, d['tw'], d['temp'], d['f_int'],
                                  d['flux_top'], out=d['flux'], parts=d['parts'], work=d['work'])
-            _capi.call('pb_radeq_update', C.byref(st), 0, stream)
+            if convection:
+                _capi.call('pb_radeq_update_convective', C.byref(st), C.byref(d['convection']),
+                           stream)
+            else:
+                _capi.call('pb_radeq_update', C.byref(st), 0, stream)
             if hist is not None:
                 for k in hist:
                     hist[k][:, i].copy_(d[k])
@@ -452,4 +597,6 @@ class RadiativeEquilibrium:
         self.dt_scale, self.q_up, self.q_down = d['dt_scale'], d['q_up'], d['q_down']
         self.spectrum = d['flux']
         self.radius = d['radius']
+        if convection:
+            self.conv_flux, self.convective = d['conv_flux'], d['convective']
         return temps

@@ -7,13 +7,17 @@ Legs, each in ms per iteration (the whole batch of nw profiles):
   loop         RadiativeEquilibrium.run: interpolation, pb_two_stream_net_batch, pb_radeq_update
   interp / net / update   each of its three launches alone, on the state the loop left
   two_stream   pb_two_stream_batch alone at the same shape (what the net-flux kernel adds to)
+  conv_loop / conv_update   (--convection) the loop with run(convection=True) and its third
+               launch, pb_radeq_update_convective, alone, with a cp / R table of 12 temperatures and
+               a start that is superadiabatic in the bottom third (conv_profiles_convecting:
+               the profiles whose last iteration ran the second half)
   host_route   (nw = 1) what a checkout without this loop can do: TableSpectrum.eval() in
                two-stream geometry (three launches, two [L, W] arrays), torch.trapezoid of both,
                the read-back, radeq.step_host in NumPy, the new densities and radius on the host
 Prints one JSON line.  Kernel times are device-side (events around `--steps` back-to-back
 launches); loop and host_route are wall clock with a synchronisation at both ends.
 
-    python tools/bench_radeq.py [--steps K] [--warmup W] [--profiles 1,64]
+    python tools/bench_radeq.py [--steps K] [--warmup W] [--profiles 1,64] [--convection]
 """
 import argparse
 import json
@@ -58,7 +62,7 @@ def wall_ms(fn, steps, warmup):
     return 1e3 * (time.perf_counter() - t0) / steps
 
 
-def run(inp, nw, steps, warmup):
+def run(inp, nw, steps, warmup, convection=False):
     import torch
     from pyratbay_amd import engine, radeq
     g, atm = inp['grid'], inp['atm']
@@ -70,6 +74,12 @@ def run(inp, nw, steps, warmup):
                                  timestamps=False)
     kw = dict(radius_model='hydro_m', mplanet=0.6 * MJUP, p0=0.1, r0=1.0 * RJUP, tint=TINT,
               flux_top=flux_top, species=atm['species'], table_species=atm['species'][2:6])
+    if convection:
+        cp_temps = np.array([100.0, 200.0, 300.0, 450.0, 600.0, 800.0, 1000.0, 1300.0, 1700.0,
+                             2200.0, 3000.0, 4000.0])
+        rise = cp_temps / (cp_temps + 1500.0)
+        kw['heat_capacity'] = (cp_temps, 3.5 + np.outer(rise, np.linspace(0.5, 2.5,
+                                                                        len(atm['species']))))
     re = model.radiative_equilibrium(atm['press'], atm['vmr'], atm['mol_mass'], **kw)
     rng = np.random.default_rng(5)
     temp0 = atm['temp'][None, :] * (1.0 + 0.05 * rng.uniform(-1, 1, (nw, 1)))
@@ -103,6 +113,22 @@ def run(inp, nw, steps, warmup):
         _capi.call('pb_radeq_update', C.byref(st), 0, engine._stream())
     res['update_ms'] = device_ms(update, steps, warmup)
     res['finite'] = bool(torch.isfinite(re.temps).all())
+    if convection:
+        # T ~ p**0.35 below the top two thirds of the layers, kept within the table's range
+        knee = atm['press'][2 * L // 3]
+        start = np.clip(temp0 * np.maximum(atm['press'] / knee, 1.0)**0.35, 1.02 * re.tmin,
+                        0.98 * re.tmax)
+        res['conv_loop_ms'] = wall_ms(lambda: re.run(start, 32, convection=True),
+                                      max(steps // 8, 1), 1) / 32
+        res['conv_profiles_convecting'] = int(re.convective.sum())
+        res['conv_loop_minus_loop_ms'] = res['conv_loop_ms'] - res['loop_ms']
+        cv = d['convection']
+
+        def conv_update():
+            d['iter'].zero_()
+            _capi.call('pb_radeq_update_convective', C.byref(st), C.byref(cv), engine._stream())
+        res['conv_update_ms'] = device_ms(conv_update, steps, warmup)
+        res['finite'] = res['finite'] and bool(torch.isfinite(re.temps).all())
     if nw == 1:
         itab = [atm['species'].index(s) for s in atm['species'][2:6]]
         dpress = radeq.log_pressure_steps(atm['press'])
@@ -132,6 +158,8 @@ def main():
     ap.add_argument('--steps', type=int, default=16)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--profiles', default='1,64')
+    ap.add_argument('--convection', action='store_true',
+                    help='also time the loop and its update with convection=True')
     args = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
@@ -139,7 +167,7 @@ def main():
     res = {'workload': 'c5-radeq', 'steps': args.steps,
            'shape': [bench_c5.NLAYERS, bench_c5.NWAVE, bench_c5.NSPEC]}
     for nw in (int(v) for v in args.profiles.split(',')):
-        res[f'nw{nw}'] = run(inp, nw, args.steps, args.warmup)
+        res[f'nw{nw}'] = run(inp, nw, args.steps, args.warmup, args.convection)
     print(json.dumps(res))
 
 
