@@ -1020,7 +1020,9 @@ int pb_weighted_quantiles_resident_rows(void);
  * (pyrat/pyrat_obj.py:671-696 -> spectrum/contribution_funcs.py) without clouds, for a batch.
  * The bands are the four arrays of pb_band_integrate_batch (the heights cancel and are not taken)
  * plus max_band_count >= every band_count_d[b]; a band's samples are wn_d[start .. start + count),
- * clipped to the grid.  out_d[nwalkers,nlayers,nbands] = the band integrals (np.trapezoid of
+ * clipped to the grid.  At a clip the band's end weight is one-sided (the trapezoid of the retained
+ * samples; response_d stays indexed by the unclipped position) and wn_d is never read outside
+ * [0, nwave); a clipped band has the bits of the in-grid band of its retained samples.  out_d[nwalkers,nlayers,nbands] = the band integrals (np.trapezoid of
  * value x response over the band's samples), each band divided by its maximum over the layers: a
  * band of one sample (or none) is 0 / 0 = NaN in every layer, like the reference.
  * work_d: pb_band_contribution_work_doubles(nlayers, nbands, max_band_count, nwalkers) doubles of
@@ -1048,7 +1050,8 @@ int pb_band_contribution_emission_batch(double *out_d, const double *ec_d,
                                         void *stream);
 /* Transit geometry: transmittance from depth_d[nwalkers,nlayers,nwave] and ideep_d[nwalkers,nwave]
  * as pb_transit_spectrum_batch(..., depth_d, ideep_d) leaves them: exp(-depth[r]) for r < ideep,
- * 0 from row ideep on; the rows above itop are 1 and are not read. */
+ * 0 from row ideep on; the rows above itop are 1 and are not read.  ideep_d values outside
+ * [0, nlayers] are taken as the nearer end. */
 int pb_band_transmittance_batch(double *out_d, const double *depth_d, const int32_t *ideep_d,
                                 const double *wn_d, const int32_t *band_start_d,
                                 const int32_t *band_count_d, const double *response_d,

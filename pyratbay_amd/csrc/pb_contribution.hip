@@ -33,23 +33,35 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-// np.trapezoid as a weight per sample: half of each neighbouring gap INSIDE the band (one-sided at
-// the band's ends, 0 for a band of one sample); wn is read at g - 1 / g + 1 only inside the band
-__device__ __forceinline__ double band_weight(const double *wn, int64_t g, int i, int count)
+// np.trapezoid as a weight per sample: half of each neighbouring gap INSIDE the band and the grid
+// (one-sided at the band's ends and where the grid clips the band, 0 for one retained sample); wn
+// is read at g - 1 / g + 1 only inside both, so never outside [0, nwave)
+__device__ __forceinline__ double band_weight(const double *wn, int64_t g, int i, int count,
+                                              int nwave)
 {
     const double x = wn[g];
     double wgt = 0.0;
-    if (i > 0)
+    if (i > 0 && g > 0)
         wgt += 0.5 * (x - wn[g - 1]);
-    if (i + 1 < count)
+    if (i + 1 < count && g + 1 < nwave)
         wgt += 0.5 * (wn[g + 1] - x);
     return wgt;
 }
 
-// What the two kernels share: the workgroup's band and chunk, the lane's sample.
+// the samples of a band that lie on the grid: [start, start + count) clipped to [0, nwave)
+__device__ __forceinline__ int band_retained(int start, int count, int nwave)
+{
+    const int64_t lo = max(start, 0), hi = min((int64_t)start + count, (int64_t)nwave);
+    return (int)max(hi - lo, (int64_t)0);
+}
+
+// What the two kernels share: the workgroup's band and chunk, the lane's sample.  The chunks
+// count from the band's first sample ON THE GRID, so a clipped band takes the lanes (and with
+// them the summation order and the bits) of the in-grid band of its retained samples.
 struct Sample {
     int count;        // samples of the band
-    int i;            // this lane's sample within the band
+    int retained;     // those on the grid
+    int i;            // this lane's sample within the (unclipped) band
     int64_t g;        // its column on the grid
     bool live;        // inside the band and the grid
 };
@@ -58,10 +70,13 @@ __device__ __forceinline__ Sample band_sample(const int32_t *band_start, const i
 {
     Sample s;
     const int b = blockIdx.y;
+    const int start = pb::uniform_i32(band_start + b);
     s.count = pb::uniform_i32(band_count + b);
-    s.i = blockIdx.x * kBlock + threadIdx.x;
-    s.g = (int64_t)pb::uniform_i32(band_start + b) + s.i;
-    s.live = s.i < s.count && s.g >= 0 && s.g < nwave;
+    s.retained = band_retained(start, s.count, nwave);
+    const int64_t at = (int64_t)blockIdx.x * kBlock + threadIdx.x;      // among the retained
+    s.live = at < s.retained;
+    s.g = max(start, 0) + at;
+    s.i = s.live ? (int)(s.g - start) : 0;
     return s;
 }
 
@@ -134,8 +149,8 @@ __global__ __launch_bounds__(kBlock) void k_band_cf_emission(
 {
     extern __shared__ double s_kt[];                    // [2][L]: kT of this walker, its reciprocal
     const Sample s = band_sample(band_start, band_count, nwave);
-    if (blockIdx.x * kBlock >= s.count)
-        return;                                         // (past the end of this band: uniform)
+    if (blockIdx.x * kBlock >= s.retained)
+        return;                                         // (past its last grid sample: uniform)
     double *s_h = s_kt + 2 * nlayers;                   // [L-1]
     double *s_dlp = s_h + (nlayers - 1);                // [L-1]
     double *s_red = s_dlp + (nlayers - 1);              // [kWaves][L]
@@ -167,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void k_band_cf_emission(
     }
     // second walk: every lane of the wavefront takes every layer (the sums are wave-wide)
     const double scale = s.live ? response[response_offset[blockIdx.y] + s.i] *
-                                      band_weight(wn, s.g, s.i, s.count)
+                                      band_weight(wn, s.g, s.i, s.count, nwave)
                                 : 0.0;
     if (s.live)
         c.start(itop);
@@ -197,7 +212,7 @@ __global__ __launch_bounds__(kBlock) void k_band_transmittance(
 {
     extern __shared__ double s_red[];                   // [kWaves][L]
     const Sample s = band_sample(band_start, band_count, nwave);
-    if (blockIdx.x * kBlock >= s.count)
+    if (blockIdx.x * kBlock >= s.retained)
         return;
     const int wk = blockIdx.z;
     const double *col = depth + (int64_t)wk * nlayers * nwave + (s.live ? s.g : 0);
@@ -205,7 +220,8 @@ __global__ __launch_bounds__(kBlock) void k_band_transmittance(
     double scale = 0.0;
     if (s.live) {
         deep = min(max(ideep[(int64_t)wk * nwave + s.g], 0), nlayers);
-        scale = response[response_offset[blockIdx.y] + s.i] * band_weight(wn, s.g, s.i, s.count);
+        scale = response[response_offset[blockIdx.y] + s.i] * band_weight(wn, s.g, s.i, s.count,
+                                                                         nwave);
     }
     double *red = s_red + (threadIdx.x / kWave) * nlayers;
     const int lane = threadIdx.x & (kWave - 1);
@@ -234,14 +250,17 @@ __device__ __forceinline__ double nan_max(double a, double b)
 
 __global__ __launch_bounds__(kBlock) void k_band_cf_finish(double *__restrict__ out,
                                                            const double *__restrict__ parts,
+                                                           const int32_t *__restrict__ band_start,
                                                            const int32_t *__restrict__ band_count,
-                                                           int nbands, int nchunks, int nlayers)
+                                                           int nbands, int nchunks, int nlayers,
+                                                           int nwave)
 {
     __shared__ double s_max[kBlock];
     const int b = blockIdx.x, wk = blockIdx.y;
-    const int count = pb::uniform_i32(band_count + b);
-    // (the chunks past the end of the band were never written)
-    const int used = min(max((count + kBlock - 1) / kBlock, 0), nchunks);
+    const int retained = band_retained(pb::uniform_i32(band_start + b),
+                                       pb::uniform_i32(band_count + b), nwave);
+    // (the chunks past the band's last sample on the grid were never written)
+    const int used = (int)min(((int64_t)retained + kBlock - 1) / kBlock, (int64_t)nchunks);
     parts += ((int64_t)wk * nbands + b) * nchunks * nlayers;
     double m = -INFINITY;
     for (int k = threadIdx.x; k < nlayers; k += kBlock) {
@@ -266,11 +285,12 @@ __global__ __launch_bounds__(kBlock) void k_band_cf_finish(double *__restrict__ 
     }
 }
 
-int finish(double *out_d, const double *work_d, const int32_t *band_count_d, int nbands,
-           int nchunks, int nlayers, int nwalkers, void *stream)
+int finish(double *out_d, const double *work_d, const int32_t *band_start_d,
+           const int32_t *band_count_d, int nbands, int nchunks, int nlayers, int nwave,
+           int nwalkers, void *stream)
 {
     k_band_cf_finish<<<dim3(nbands, nwalkers), kBlock, 0, pb::as_stream(stream)>>>(
-        out_d, work_d, band_count_d, nbands, nchunks, nlayers);
+        out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave);
     PB_LAUNCH_CHECK();
     return PB_OK;
 }
@@ -320,7 +340,8 @@ int pb_band_contribution_emission_batch(double *out_d, const double *ec_d,
             response_d, response_offset_d, maxdepth, itop, ibottom, nlayers, nwave);
         PB_LAUNCH_CHECK();
     }
-    return finish(out_d, work_d, band_count_d, nbands, nchunks, nlayers, nwalkers, stream);
+    return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,
+                  nwalkers, stream);
 }
 
 int pb_band_transmittance_batch(double *out_d, const double *depth_d, const int32_t *ideep_d,
@@ -353,7 +374,8 @@ int pb_band_transmittance_batch(double *out_d, const double *depth_d, const int3
             response_offset_d, itop, nlayers, nwave);
         PB_LAUNCH_CHECK();
     }
-    return finish(out_d, work_d, band_count_d, nbands, nchunks, nlayers, nwalkers, stream);
+    return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,
+                  nwalkers, stream);
 }
 
 }  // extern "C"
