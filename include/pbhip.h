@@ -1017,7 +1017,8 @@ int64_t pb_weighted_quantiles_work_doubles(int n, int ncol, int nq);
 int pb_weighted_quantiles_resident_rows(void);
 
 /* ---- Band contribution functions per walker (pb_contribution.hip): Pyrat.band_contribution
- * (pyrat/pyrat_obj.py:671-696 -> spectrum/contribution_funcs.py) without clouds, for a batch.
+ * (pyrat/pyrat_obj.py:671-696 -> spectrum/contribution_funcs.py) for a batch: first without
+ * clouds, then -- the two *_cloudy_batch entries at the end -- with them.
  * The bands are the four arrays of pb_band_integrate_batch (the heights cancel and are not taken)
  * plus max_band_count >= every band_count_d[b]; a band's samples are wn_d[start .. start + count),
  * clipped to the grid.  At a clip the band's end weight is one-sided (the trapezoid of the retained
@@ -1060,6 +1061,54 @@ int pb_band_transmittance_batch(double *out_d, const double *depth_d, const int3
                                 void *stream);
 int64_t pb_band_contribution_work_doubles(int nlayers, int nbands, int max_band_count,
                                           int nwalkers);
+/* The same with clouds (pyrat_obj.py:129-164, 671-696; opacity/optic_depth.py:91-136): per walker
+ * an opaque deck at layer deck_itop_d[w] (pb_deck_state_batch; NULL: no deck), cloud-type opacity
+ * ec_cloud from `cloud` (pb_cloud_terms in ec_d's column order, i.e. grid order; NULL or nr = 0:
+ * none), which is added to ec_d as a column is walked and never stored, and in transit geometry a
+ * patchy fraction.  Bands, out_d, work_d (the same pb_band_contribution_work_doubles), the
+ * summation order and the refusals are those of the two entries above; also refused: more than
+ * PB_CLOUD_MAX cloud terms, null cloud factors.  Neither entry stores a depth.
+ *
+ * Emission: pb_band_contribution_emission_batch on the CLOUDY column only, as the reference --
+ * the clear column of a patchy model is not mixed in and a patchy fraction does not enter:
+ *   the column is ec + ec_cloud; with a deck the stop rule's ibottom is deck_itop_d[w] + 1 (the
+ *   ibottom argument otherwise), so the depth runs through the row past the deck, as the
+ *   reference's loop stores row ibottom before it stops; row deck_itop_d[w] of B is the Planck
+ *   function at deck_tsurf_d[w] (spectrum/radiative_transfer.py:125-127 writes it in place).
+ * deck_itop_d and deck_tsurf_d go together; deck_itop_d values outside [0, nlayers) are taken as
+ * the nearer end. */
+int pb_band_contribution_emission_cloudy_batch(
+    double *out_d, const double *ec_d, const double *intervals_d, const double *dlogp_d,
+    const double *wn_d, const double *temps_d, const int32_t *band_start_d,
+    const int32_t *band_count_d, const double *response_d, const int64_t *response_offset_d,
+    int max_band_count, double maxdepth, int itop, int ibottom, int nlayers, int nwave, int nbands,
+    int nwalkers, const int32_t *deck_itop_d, const double *deck_tsurf_d,
+    const pb_cloud_terms *cloud, double *work_d, void *stream);
+/* Transit: from ec_d[nwalkers,nlayers,nwave] and the ray paths of pb_cloudy_transit_batch
+ * (raypath_d[w * path_stride + .] = pb_transit_path's packed triangle from itop; stride 0:
+ * shared), with that entry's walk.  Two columns per walker:
+ *   clear : ec over the rows itop .. nlayers-1
+ *   cloudy: ec + ec_cloud over the rows itop .. deck_itop (no deck: nlayers-1)
+ * In each, ideep = the first row whose depth exceeds maxdepth, else the column's last row
+ * (deck_itop <= itop: itop, the cloudy column has no row), and the transmittance is 1 above itop,
+ * exp(-depth[r]) for itop <= r < ideep and 0 from row ideep on.  A layer's value is
+ * f T_cloudy + (1 - f) T_clear, f = f_patchy_d[w] clamped to [0, 1] (NaN stays NaN), formed per
+ * sample BEFORE the band integral; f_patchy_d NULL: T_cloudy, and the clear column is not walked.
+ * The deck's radius does not enter.  With cloud == NULL (or nr = 0) one running sum serves both
+ * columns.  A sum of two layers' opacities is capped at the largest finite double, as in
+ * pb_cloudy_transit_batch.
+ * LDS of a workgroup: 4 nlayers doubles of wavefront sums + 16 (nlayers - itop) doubles of staged
+ * ray-path segments; 64 KiB hold that for nlayers <= PB_BAND_CLOUDY_MAX_LAYERS, more is refused. */
+#define PB_BAND_CLOUDY_MAX_LAYERS 400
+int pb_band_transmittance_cloudy_batch(double *out_d, const double *ec_d, const double *raypath_d,
+                                       int64_t path_stride, const double *wn_d,
+                                       const int32_t *band_start_d, const int32_t *band_count_d,
+                                       const double *response_d,
+                                       const int64_t *response_offset_d, int max_band_count,
+                                       int itop, double maxdepth, int nlayers, int nwave,
+                                       int nbands, int nwalkers, const int32_t *deck_itop_d,
+                                       const pb_cloud_terms *cloud, const double *f_patchy_d,
+                                       double *work_d, void *stream);
 
 /* =========================================================================
  * Experiments -- NOT in libpbhip.so.  `make -C pyratbay_amd/csrc EXPERIMENTS=1` builds

@@ -141,6 +141,11 @@ _PROTOS = {
     'pb_band_transmittance_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
                                     vp, vp],
     'pb_band_contribution_work_doubles': [i32, i32, i32, i32],
+    'pb_band_contribution_emission_cloudy_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f64,
+                                                   i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,
+                                                   vp],
+    'pb_band_transmittance_cloudy_batch': [vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, f64, i32,
+                                           i32, i32, i32, vp, vp, vp, vp, vp],
     'pb_simps2D': [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp],
     'pb_ediff': [vp, vp, i32, vp],
     'pb_band_integrate': [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, vp],

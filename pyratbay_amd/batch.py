@@ -418,3 +418,97 @@ def cloudy_emission_batch(ec, intervals, wn, temps, mu, weights, itop, maxdepth,
          _ptr(column), len(mu), float(maxdepth), int(itop), nlayers, nwave, nw, *tail)
     del keep
     return (flux, clear, cloudy) if want_parts else flux
+
+
+# --------------------------------------------------------------------------
+# Band contribution functions for a batch with clouds (pb_contribution.hip)
+# --------------------------------------------------------------------------
+def _contribution_cloud_args(name, nw, deck, surf, cloud_cs, cloud_f, f_patchy, terms):
+    """The deck's tensors, the pb_cloud_terms struct and f_patchy of the two cloudy contribution
+    entries -> (deck itop, deck surface or None, terms or None, f_patchy, keep-alive)."""
+    for what, t, dtype in ((f'{name}: f_patchy', f_patchy, torch.float64),) + \
+            (() if deck is None else ((f'{name}: deck itop', deck[0], torch.int32),
+                                      (f'{name}: deck surface', deck[surf], torch.float64))):
+        _check_walker_tensor(what, t, nw, dtype)
+    keep = []
+    if terms is None and cloud_cs is not None:
+        if cloud_f is None or cloud_f.dim() != 3 or cloud_f.shape[0] != nw:
+            raise ValueError(f'{name}: cloud_cs needs cloud_f[nw, L, nr]')
+        terms, keep = ct.cloud_terms(cloud_cs, cloud_f)
+    ditop = None if deck is None else deck[0].contiguous()
+    dsurf = None if deck is None else deck[surf].contiguous()
+    fp = None if f_patchy is None else f_patchy.contiguous()
+    return ditop, dsurf, None if terms is None else C.byref(terms), fp, (keep, terms)
+
+
+def band_transmittance_cloudy_batch(ec, raypath, bands, itop, maxdepth, deck=None, cloud_cs=None,
+                                    cloud_f=None, f_patchy=None, out=None, _terms=None):
+    """Band transmittances of a batch in transit geometry WITH clouds (Pyrat.band_contribution,
+    pyrat_obj.py:671-696, on the two optical depths of opacity/optic_depth.py:94-121;
+    contribution.band_contribution_cloudy_host is the NumPy statement), from ec[nw, L, W] in ONE
+    pass -- neither column's depth is stored -- with the walk and the arguments of
+    cloudy_transit_batch:
+      clear   ec over the rows itop .. L-1
+      cloudy  ec + ec_cloud over the rows itop .. deck itop: deck = deck_state_batch()'s (itop[nw],
+              rsurf[nw], tsurf[nw]; only itop enters); None: down to the last row
+      transmittance  exp(-depth) above the row where a column exceeded maxdepth, or its last row;
+              0 from there on; 1 above itop
+      value   f_patchy[w] cloudy + (1 - f_patchy[w]) clear per sample, before the band integral;
+              f_patchy None: the cloudy column alone.  f_patchy is CLAMPED to [0, 1] on the device
+              (NaN gives NaN).
+    ec_cloud = sum_m cloud_cs[m] x cloud_f[:, :, m] as in cloudy_transit_batch (None: none, one
+    running sum serves both columns).  raypath[nw, npath] or [1, npath] / [npath] (shared).
+    -> [nw, L, nbands], every band divided by its maximum over the layers (one sample: NaN)."""
+    name = 'band_transmittance_cloudy_batch'
+    nw, nlayers, nwave = ec.shape
+    path = raypath if raypath.dim() == 2 else raypath.view(1, -1)
+    nrow = nlayers - int(itop)
+    if ec.dtype != torch.float64 or not ec.is_contiguous() or path.shape[0] not in (1, nw) or \
+            path.shape[1] != (nrow * (nrow - 1)) // 2:
+        raise ValueError(f'{name}: contiguous float64 ec[nw, L, W] and raypath[{nw} or 1, '
+                         f'{(nrow * (nrow - 1)) // 2}] wanted, got {ec.dtype} {tuple(ec.shape)}, '
+                         f'{tuple(raypath.shape)}')
+    ditop, _, terms, fp, keep = _contribution_cloud_args(name, nw, deck, 1, cloud_cs, cloud_f,
+                                                         f_patchy, _terms)
+    out, work, bargs = _contribution_buffers(name, bands, nw, nlayers, nwave, ec.device, out)
+    path = path.contiguous()
+    call('pb_band_transmittance_cloudy_batch', _ptr(out), _ptr(ec),
+         _ptr(path) if path.numel() else None, 0 if path.shape[0] == 1 else path.shape[1],
+         _ptr(bands.wn), *bargs, int(itop), float(maxdepth), nlayers, nwave, bands.nbands, nw,
+         _ptr(ditop), terms, _ptr(fp), _ptr(work), _stream())
+    del keep
+    return out
+
+
+def band_contribution_emission_cloudy_batch(ec, intervals, temps, bands, pressure, itop, ibottom,
+                                            maxdepth, deck=None, cloud_cs=None, cloud_f=None,
+                                            out=None, dlogp=None, _terms=None):
+    """band_contribution_emission_batch WITH clouds: the contribution function of the CLOUDY
+    column only, as the reference (pyrat_obj.py:691-693 reads od.depth and od.B: the clear column
+    of a patchy model is not mixed in, and a patchy fraction does not enter).  The column is
+    ec + ec_cloud (cloud_cs / cloud_f as in cloudy_emission_batch; None: none); with deck =
+    deck_state_batch()'s (itop[nw], rsurf[nw], tsurf[nw]) the depth runs through the row past
+    the deck's layer and is 0 below (ibottom = deck itop + 1 per walker; else `ibottom`), and
+    that layer radiates at the deck's tsurf.  -> [nw, L, nbands]."""
+    name = 'band_contribution_emission_cloudy_batch'
+    nw, nlayers, nwave = ec.shape
+    if ec.dtype != torch.float64 or not ec.is_contiguous() or \
+            tuple(intervals.shape) != (nw, nlayers - 1) or tuple(temps.shape) != (nw, nlayers):
+        raise ValueError(f'{name}: contiguous float64 ec[nw, L, W], intervals[{nw}, '
+                         f'{nlayers - 1}] and temps[{nw}, {nlayers}] wanted, got '
+                         f'{tuple(ec.shape)}, {tuple(intervals.shape)}, {tuple(temps.shape)}')
+    if dlogp is None:
+        dlogp = contribution_dlogp(pressure, nlayers)
+    elif not isinstance(dlogp, torch.Tensor) or not dlogp.is_cuda or \
+            dlogp.dtype != torch.float64 or tuple(dlogp.shape) != (nlayers - 1,):
+        raise ValueError(f'{name}: dlogp must be a float64 device tensor of shape '
+                         f'({nlayers - 1},)')
+    ditop, dsurf, terms, _, keep = _contribution_cloud_args(name, nw, deck, 2, cloud_cs, cloud_f,
+                                                            None, _terms)
+    out, work, bargs = _contribution_buffers(name, bands, nw, nlayers, nwave, ec.device, out)
+    call('pb_band_contribution_emission_cloudy_batch', _ptr(out), _ptr(ec),
+         _ptr(intervals.contiguous()), _ptr(dlogp.contiguous()), _ptr(bands.wn),
+         _ptr(temps.contiguous()), *bargs, float(maxdepth), int(itop), int(ibottom), nlayers,
+         nwave, bands.nbands, nw, _ptr(ditop), _ptr(dsurf), terms, _ptr(work), _stream())
+    del keep
+    return out

@@ -1,11 +1,18 @@
 // Walker-batched retrieval path: band contribution functions (Pyrat.band_contribution,
-// pyrat/pyrat_obj.py:671-696 -> spectrum/contribution_funcs.py) per walker, without clouds.
+// pyrat/pyrat_obj.py:671-696 -> spectrum/contribution_funcs.py) per walker, clear and with clouds
+// (an opaque deck, cloud-type opacity ec_cloud, a patchy fraction).
 //   k_band_cf_emission     contribution_function + band_cf's integral from ec: the plane-parallel
 //                          depth, exp(-depth), B and the per-column normalisation stay in registers
 //   k_band_transmittance   transmittance + band_cf's integral from the depth / ideep that
 //                          pb_transit_spectrum_batch stores
 //   k_band_cf_finish       the bands' parts added in chunk order, divided by their maximum over
 //                          the layers
+// With clouds (the reference's rules are written out at the kernels):
+//   k_band_cf_emission<true>      the same two walks on ec + ec_cloud down to the walker's deck,
+//                                 whose temperature takes the deck layer's place in B
+//   k_band_transmittance_cloudy   transmittance of the clear and the cloudy column + band_cf's
+//                                 integral FROM ec: k_cloudy_transit's walk (pb_clouds.hip), no
+//                                 depth stored for either column
 // FP64, no atomics, every sum in a fixed order: two runs give the same bits.
 #include "pb_common.h"
 #include "pb_planck.h"
@@ -20,10 +27,56 @@ constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxLayersEmission = 1024;
 // k_band_transmittance keeps only the wavefronts' sums: 4 L doubles
 constexpr int kMaxLayersTransit = 2048;
+// k_band_transmittance_cloudy: the wavefronts' sums and the ray-path segments of a block of
+// kCloudyRows impact parameters, (4 L + kCloudyRows (L - itop)) doubles
+constexpr int kCloudyRows = 16;
+constexpr int kMaxLayersCloudyTransit = PB_BAND_CLOUDY_MAX_LAYERS;
+static_assert((size_t)(kWaves + kCloudyRows) * kMaxLayersCloudyTransit * sizeof(double) <=
+                  64 * 1024, "the cloudy transmittance kernel's LDS");
+constexpr int kMaxCloud = PB_CLOUD_MAX;
 
 using pb::planck_factor;
 using pb::planck_q;
 using pb::planck_terms;
+
+typedef const double __attribute__((address_space(4))) *cdbl_t;
+
+__device__ __forceinline__ double uniform_f64(const double *p)
+{
+    return *((cdbl_t)(unsigned long long)p);
+}
+
+// ec_cloud = sum_m cs_m[sample] f_m[walker, layer] at this thread's sample (pb_cloud_terms): the
+// cross sections in registers, the factors wave-uniform scalar loads, the models' terms added in
+// their order -- pb_clouds.hip's cloud_init / cloud_at, so that the column is the one the flux
+// kernels walk
+struct CloudWalk {
+    double cs[kMaxCloud];
+    const double *f;            // this walker's factors [L][nr]
+    int nr;
+
+    __device__ __forceinline__ void init(const pb_cloud_terms &cl, int w, int64_t col, int nlayers)
+    {
+        nr = cl.nr;
+        f = cl.f_d + (int64_t)w * nlayers * cl.nr;
+#pragma unroll
+        for (int m = 0; m < kMaxCloud; m++) {
+            cs[m] = 0.0;
+            if (m < cl.nr)
+                cs[m] = cl.cs_d[m] ? cl.cs_d[m][(int64_t)w * cl.cs_stride[m] + col] : 1.0;
+        }
+    }
+    __device__ __forceinline__ double at(int layer) const
+    {
+        const cdbl_t fl = (cdbl_t)(unsigned long long)(f + (int64_t)layer * nr);
+        double sum = 0.0;
+#pragma unroll
+        for (int m = 0; m < kMaxCloud; m++)
+            if (m < nr)
+                sum += cs[m] * fl[m];
+        return sum;
+    }
+};
 
 // the sum over the wavefront, the same bits in every lane (pb_radeq.hip's)
 __device__ __forceinline__ double wave_sum(double v)
@@ -101,20 +154,34 @@ __device__ __forceinline__ void store_parts(double *parts, const double *s_red, 
 //   cf[k] = B[k] detau[k] / dlnp[k] (k < L - 1), cf[L-1] = 0;  cf /= sum_k cf
 // The first walk gives the column's sum, the second the same values again, divided by it and
 // weighted by response x trapezoid weight, summed over the wavefront layer by layer.
+// kCloudy (pyrat_obj.py:135-139, 691-693; spectrum/radiative_transfer.py:125-127): the column is
+// ec + ec_cloud, ibottom = deck_itop[walker] + 1 -- the reference's loop stores row ibottom before
+// it stops, so the depth runs through the row past the deck -- and the deck's temperature takes
+// the place of the layer's in row deck_itop of B.  The cloudy column ONLY, patchy or not: the
+// reference does not mix the clear column into the emission contribution function.
 // ---------------------------------------------------------------------------
+template <bool kCloudy>
 struct EmissionColumn {
     const double *ec;       // this column of the walker's ec: stride nwave
     int64_t nwave;
     double w, factor;
     double acc, prev, eprev;
     bool stopped;
+    CloudWalk cloud;        // (kCloudy)
 
+    __device__ __forceinline__ double at(int k) const
+    {
+        if constexpr (kCloudy)
+            return ec[(int64_t)k * nwave] + cloud.at(k);
+        else
+            return ec[(int64_t)k * nwave];
+    }
     __device__ __forceinline__ void start(int itop)
     {
         acc = 0.0;
         eprev = 1.0;                                    // exp(-0): rows up to itop
         stopped = false;
-        prev = ec[(int64_t)itop * nwave];
+        prev = at(itop);
     }
     // cf[k] before the normalisation, k = 0 .. L-2 in order
     __device__ __forceinline__ double step(int k, const double *s_kt, const double *s_h,
@@ -123,7 +190,7 @@ struct EmissionColumn {
     {
         double enext = 1.0;                             // rows up to itop and below the stop: depth 0
         if (k + 1 > itop && !stopped) {
-            const double cur = ec[(int64_t)(k + 1) * nwave];
+            const double cur = at(k + 1);
             acc += 0.5 * s_h[k] * (cur + prev);
             prev = cur;
             enext = pb::exp_s(-acc);
@@ -139,13 +206,21 @@ struct EmissionColumn {
     }
 };
 
+// the clouds of the kCloudy instantiation: deck_itop / deck_tsurf [nwalkers] or null (no deck)
+struct EmissionClouds {
+    const int32_t *deck_itop;
+    const double *deck_tsurf;
+    pb_cloud_terms cl;
+};
+
+template <bool kCloudy>
 __global__ __launch_bounds__(kBlock) void k_band_cf_emission(
     double *__restrict__ parts, const double *__restrict__ ec, const double *__restrict__ intervals,
     const double *__restrict__ dlogp, const double *__restrict__ wn,
     const double *__restrict__ temps, const int32_t *__restrict__ band_start,
     const int32_t *__restrict__ band_count, const double *__restrict__ response,
     const int64_t *__restrict__ response_offset, double maxdepth, int itop, int ibottom,
-    int nlayers, int nwave)
+    int nlayers, int nwave, EmissionClouds clouds)
 {
     extern __shared__ double s_kt[];                    // [2][L]: kT of this walker, its reciprocal
     const Sample s = band_sample(band_start, band_count, nwave);
@@ -161,7 +236,18 @@ __global__ __launch_bounds__(kBlock) void k_band_cf_emission(
     }
     planck_terms(s_kt, temps + (int64_t)wk * nlayers, nlayers);       // (ends with the barrier)
 
-    EmissionColumn c;
+    EmissionColumn<kCloudy> c;
+    if constexpr (kCloudy) {
+        if (clouds.deck_itop) {                         // (wave-uniform: the walker's deck)
+            const int dk = min(max(pb::uniform_i32(clouds.deck_itop + wk), 0), nlayers - 1);
+            ibottom = dk + 1;
+            if (threadIdx.x == 0)
+                pb::sane_divisor(pb::kKB * uniform_f64(clouds.deck_tsurf + wk), s_kt[dk],
+                                 s_kt[nlayers + dk]);
+            __syncthreads();
+        }
+        c.cloud.init(clouds.cl, wk, s.live ? s.g : 0, nlayers);
+    }
     c.nwave = nwave;
     c.ec = ec + (int64_t)wk * nlayers * nwave + (s.live ? s.g : 0);
     c.w = s.live ? wn[s.g] : 1.0;
@@ -239,6 +325,173 @@ __global__ __launch_bounds__(kBlock) void k_band_transmittance(
 }
 
 // ---------------------------------------------------------------------------
+// Transit geometry with clouds, FROM ec (pyrat_obj.py:135-139, 683-689; optic_depth.py:94-121 with
+// the early exit of _trapezoid.c:259-273): per walker a clear column, ec over the rows itop .. L-1,
+// and a cloudy one, ec + ec_cloud over the rows itop .. deck_itop (no deck: L-1).  In each,
+//   ideep = the first row whose depth exceeds maxdepth, else the column's last row
+//           (deck_itop <= itop: itop -- no cloudy row at all)
+//   T[r]  = 1 above itop, exp(-depth[r]) for itop <= r < ideep, 0 from ideep on
+// and the layer's value is f T_cloudy + (1 - f) T_clear (f_patchy NULL: T_cloudy, and the clear
+// column is not walked), times response x trapezoid weight.  The deck's radius does not enter.
+// The walk is k_cloudy_transit's (pb_clouds.hip): a thread owns a column, the impact parameters are
+// taken kCloudyRows at a time with the block's ray-path segments staged in LDS ([segment][row],
+// zero where segment >= row), the sums capped at the largest finite double (finite_sum there);
+// kTwo: ec_cloud != 0, else one running sum serves both columns.  Row by row the wavefront's sum
+// goes into the LDS row store_parts reads; the rows after every column of the workgroup has closed
+// are written too (a closed row is f 0 + (1 - f) 0: 0, or NaN with f).  (Reducing the 16 rows of
+// a block together -- 17 shuffles instead of 96 -- was measured SLOWER, 6.9 against 5.0 ms at
+// C5's shape: profiles/contribution.md.)
+// ---------------------------------------------------------------------------
+struct CloudyBandArgs {
+    double *parts;
+    const double *ec, *wn, *raypath;
+    int64_t path_stride;
+    const int32_t *band_start, *band_count;
+    const double *response;
+    const int64_t *response_offset;
+    const int32_t *deck_itop;                  // [nwalkers] or null: no deck
+    const double *f_patchy;                    // [nwalkers] or null: the cloudy column alone
+    double maxdepth;
+    int itop, nlayers, nwave;
+    pb_cloud_terms cl;
+};
+
+__device__ __forceinline__ double finite_sum(double s)
+{
+    return s > 0x1.fffffffffffffp+1023 ? 0x1.fffffffffffffp+1023 : s;
+}
+
+template <bool kTwo>
+__global__ __launch_bounds__(kBlock) void k_band_transmittance_cloudy(CloudyBandArgs a)
+{
+    constexpr int kRows = kCloudyRows;
+    extern __shared__ __align__(16) double s_lds[];     // [kWaves][L] sums, [segment][kRows] paths
+    const Sample s = band_sample(a.band_start, a.band_count, a.nwave);
+    if (blockIdx.x * kBlock >= s.retained)
+        return;
+    const int nlayers = a.nlayers, nwave = a.nwave, itop = a.itop;
+    double *s_path = s_lds + kWaves * nlayers;
+    const int wk = blockIdx.z;
+    const double *path = a.raypath + (int64_t)wk * a.path_stride;
+    const bool need_clear = a.f_patchy != nullptr;
+    // wave-uniform: the walker's deck and cloudy fraction
+    const int dk = a.deck_itop ? min(max(pb::uniform_i32(a.deck_itop + wk), 0), nlayers - 1)
+                               : nlayers - 1;
+    const int nrow = nlayers - itop;
+    const int nimp_c = dk + 1 - itop;                   // rows of the cloudy column (<= 0: none)
+    const int nimp_l = need_clear ? nrow : 0;
+    const int nimp = max(max(nimp_c, nimp_l), 0);
+    double f = 0.0;
+    if (need_clear) {
+        f = uniform_f64(a.f_patchy + wk);
+        f = f < 0.0 ? 0.0 : (f > 1.0 ? 1.0 : f);        // (cloud_store's clamp: NaN stays NaN)
+    }
+    const auto mix = [&](double cloudy, double clear) {
+        return need_clear ? f * cloudy + (1.0 - f) * clear : cloudy;
+    };
+    const double scale = s.live ? a.response[a.response_offset[blockIdx.y] + s.i] *
+                                      band_weight(a.wn, s.g, s.i, s.count, nwave)
+                                : 0.0;
+    const double *src = a.ec + ((int64_t)wk * nlayers + itop) * nwave + (s.live ? s.g : 0);
+    CloudWalk cloud;
+    if constexpr (kTwo)
+        cloud.init(a.cl, wk, s.live ? s.g : 0, nlayers);
+    double *red = s_lds + (threadIdx.x / kWave) * nlayers;
+    const int lane = threadIdx.x & (kWave - 1);
+
+    // the rows above itop: depth 0 in both columns
+    {
+        const double v = wave_sum(s.live ? mix(1.0, 1.0) * scale : 0.0);
+        if (lane == 0)
+            for (int r = 0; r < itop; r++)
+                red[r] = v;
+    }
+    bool open_l = s.live && nimp_l > 0, open_c = s.live && nimp_c > 0;
+    int rb = 0;
+    for (; rb < nimp; rb += kRows) {
+        // every column of the workgroup has closed both of its integrals: nothing left to compute
+        if (__syncthreads_count(open_l || open_c) == 0)
+            break;
+        const int rlast = min(rb + kRows, nimp) - 1;
+        const int nseg = rlast;
+        for (int e = threadIdx.x; e < nseg * kRows; e += kBlock) {
+            const int i = e / kRows, k = e % kRows;
+            const int r = rb + k;
+            s_path[e] = (r <= rlast && i < r) ? path[((int64_t)r * (r - 1)) / 2 + i] : 0.0;
+        }
+        __syncthreads();
+        double tau[kRows], tau_c[kTwo ? kRows : 1];
+#pragma unroll
+        for (int k = 0; k < kRows; k++)
+            tau[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < (kTwo ? kRows : 1); k++)
+            tau_c[k] = 0.0;
+        if ((open_l || open_c) && nseg > 0) {
+            double prev = src[0];
+            double prev_c = kTwo ? prev + cloud.at(itop) : 0.0;
+#pragma unroll 2
+            for (int i = 0; i < nseg; i++) {
+                const double next = src[(int64_t)(i + 1) * nwave];
+                const double sm = finite_sum(next + prev);
+                prev = next;
+                const double *pk = s_path + i * kRows;      // LDS broadcast reads
+                if constexpr (kTwo) {
+                    const double next_c = next + cloud.at(itop + i + 1);
+                    const double sm_c = finite_sum(next_c + prev_c);
+                    prev_c = next_c;
+#pragma unroll
+                    for (int k = 0; k < kRows; k++) {
+                        tau[k] = fma(pk[k], sm, tau[k]);
+                        tau_c[k] = fma(pk[k], sm_c, tau_c[k]);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < kRows; k++)
+                        tau[k] = fma(pk[k], sm, tau[k]);
+                }
+            }
+        }
+        // (every lane of the wavefront takes every row: the sums are wave-wide)
+#pragma unroll
+        for (int k = 0; k < kRows; k++) {
+            const int r = rb + k;
+            if (r > rlast)
+                continue;
+            const double t = tau[k];
+            const double t_c = kTwo ? tau_c[k] : t;
+            const bool do_l = open_l && r < nimp_l, do_c = open_c && r < nimp_c;
+            double e = 0.0, t_clear = 0.0, t_cloudy = 0.0;
+            if (do_l || (!kTwo && do_c))
+                e = pb::exp_s(-t);
+            if (do_l) {
+                if (t > a.maxdepth || r == nimp_l - 1)
+                    open_l = false;                         // this row is the column's ideep
+                else
+                    t_clear = e;
+            }
+            if (do_c) {
+                if (t_c > a.maxdepth || r == nimp_c - 1)
+                    open_c = false;
+                else
+                    t_cloudy = kTwo ? pb::exp_s(-t_c) : e;
+            }
+            const double v = wave_sum(s.live ? mix(t_cloudy, t_clear) * scale : 0.0);
+            if (lane == 0)
+                red[itop + r] = v;
+        }
+    }
+    // the rows no column of the workgroup reached
+    {
+        const double v = wave_sum(s.live ? mix(0.0, 0.0) * scale : 0.0);
+        if (lane == 0)
+            for (int r = min(rb, nimp); r < nrow; r++)
+                red[itop + r] = v;
+    }
+    store_parts(a.parts, s_lds, nlayers);
+}
+
+// ---------------------------------------------------------------------------
 // band_cf's normalisation: grid (bands, walkers).  The band's chunks are added in chunk order, the
 // maximum over the layers is np.amax's (a NaN anywhere gives NaN), and every layer is divided by
 // it: a band of one sample (or none) is 0 / 0 = NaN in every layer, as in the reference.
@@ -295,6 +548,19 @@ int finish(double *out_d, const double *work_d, const int32_t *band_start_d,
     return PB_OK;
 }
 
+// pb_clouds.hip's check of a pb_cloud_terms
+int check_cloud(const pb_cloud_terms *cloud, const char *who)
+{
+    if (!cloud)
+        return PB_OK;
+    PB_REQUIRE(cloud->nr >= 0 && cloud->nr <= kMaxCloud, "%s: 0 ... %d cloud terms (got %d)", who,
+               kMaxCloud, cloud->nr);
+    PB_REQUIRE(cloud->nr == 0 || cloud->f_d, "%s: null cloud factors", who);
+    for (int m = 0; m < cloud->nr; m++)
+        PB_REQUIRE(cloud->cs_stride[m] >= 0, "%s: negative cross-section stride", who);
+    return PB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -335,9 +601,11 @@ int pb_band_contribution_emission_batch(double *out_d, const double *ec_d,
     PB_REQUIRE(nchunks == 0 || work_d, "pb_band_contribution_emission_batch: null work buffer");
     if (nchunks > 0) {
         const size_t lds = ((size_t)(4 + kWaves) * nlayers - 2) * sizeof(double);
-        k_band_cf_emission<<<dim3(nchunks, nbands, nwalkers), kBlock, lds, pb::as_stream(stream)>>>(
-            work_d, ec_d, intervals_d, dlogp_d, wn_d, temps_d, band_start_d, band_count_d,
-            response_d, response_offset_d, maxdepth, itop, ibottom, nlayers, nwave);
+        k_band_cf_emission<false>
+            <<<dim3(nchunks, nbands, nwalkers), kBlock, lds, pb::as_stream(stream)>>>(
+                work_d, ec_d, intervals_d, dlogp_d, wn_d, temps_d, band_start_d, band_count_d,
+                response_d, response_offset_d, maxdepth, itop, ibottom, nlayers, nwave,
+                EmissionClouds{});
         PB_LAUNCH_CHECK();
     }
     return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,
@@ -372,6 +640,106 @@ int pb_band_transmittance_batch(double *out_d, const double *depth_d, const int3
                                pb::as_stream(stream)>>>(
             work_d, depth_d, ideep_d, wn_d, band_start_d, band_count_d, response_d,
             response_offset_d, itop, nlayers, nwave);
+        PB_LAUNCH_CHECK();
+    }
+    return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,
+                  nwalkers, stream);
+}
+
+int pb_band_contribution_emission_cloudy_batch(
+    double *out_d, const double *ec_d, const double *intervals_d, const double *dlogp_d,
+    const double *wn_d, const double *temps_d, const int32_t *band_start_d,
+    const int32_t *band_count_d, const double *response_d, const int64_t *response_offset_d,
+    int max_band_count, double maxdepth, int itop, int ibottom, int nlayers, int nwave, int nbands,
+    int nwalkers, const int32_t *deck_itop_d, const double *deck_tsurf_d,
+    const pb_cloud_terms *cloud, double *work_d, void *stream)
+{
+    PB_REQUIRE(nlayers >= 2 && nwave >= 1 && nbands >= 0 && nwalkers >= 0 && max_band_count >= 0,
+               "pb_band_contribution_emission_cloudy_batch: bad sizes (nlayers >= 2, nwave >= 1)");
+    PB_REQUIRE(nlayers <= kMaxLayersEmission,
+               "pb_band_contribution_emission_cloudy_batch: %d layers, at most %d fit in the LDS "
+               "of a workgroup", nlayers, kMaxLayersEmission);
+    PB_REQUIRE(itop >= 0 && itop < nlayers,
+               "pb_band_contribution_emission_cloudy_batch: itop out of range");
+    PB_REQUIRE(ibottom <= nlayers, "pb_band_contribution_emission_cloudy_batch: ibottom > nlayers");
+    PB_REQUIRE(nbands <= 65535 && nwalkers <= 65535,
+               "pb_band_contribution_emission_cloudy_batch: at most 65535 bands and walkers per "
+               "call");
+    PB_REQUIRE(!deck_itop_d == !deck_tsurf_d,
+               "pb_band_contribution_emission_cloudy_batch: deck_itop_d and deck_tsurf_d go "
+               "together");
+    if (int rc = check_cloud(cloud, "pb_band_contribution_emission_cloudy_batch"))
+        return rc;
+    if (nbands == 0 || nwalkers == 0)
+        return PB_OK;
+    PB_REQUIRE(out_d && ec_d && intervals_d && dlogp_d && wn_d && temps_d && band_start_d &&
+                   band_count_d && response_d && response_offset_d,
+               "pb_band_contribution_emission_cloudy_batch: null pointer");
+    const int nchunks = pb::div_up(max_band_count, kBlock);
+    PB_REQUIRE(nchunks == 0 || work_d,
+               "pb_band_contribution_emission_cloudy_batch: null work buffer");
+    if (nchunks > 0) {
+        EmissionClouds clouds{deck_itop_d, deck_tsurf_d, {}};
+        if (cloud && cloud->nr > 0)
+            clouds.cl = *cloud;
+        const size_t lds = ((size_t)(4 + kWaves) * nlayers - 2) * sizeof(double);
+        k_band_cf_emission<true>
+            <<<dim3(nchunks, nbands, nwalkers), kBlock, lds, pb::as_stream(stream)>>>(
+                work_d, ec_d, intervals_d, dlogp_d, wn_d, temps_d, band_start_d, band_count_d,
+                response_d, response_offset_d, maxdepth, itop, ibottom, nlayers, nwave, clouds);
+        PB_LAUNCH_CHECK();
+    }
+    return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,
+                  nwalkers, stream);
+}
+
+int pb_band_transmittance_cloudy_batch(double *out_d, const double *ec_d, const double *raypath_d,
+                                       int64_t path_stride, const double *wn_d,
+                                       const int32_t *band_start_d, const int32_t *band_count_d,
+                                       const double *response_d,
+                                       const int64_t *response_offset_d, int max_band_count,
+                                       int itop, double maxdepth, int nlayers, int nwave,
+                                       int nbands, int nwalkers, const int32_t *deck_itop_d,
+                                       const pb_cloud_terms *cloud, const double *f_patchy_d,
+                                       double *work_d, void *stream)
+{
+    PB_REQUIRE(nlayers >= 1 && nwave >= 1 && nbands >= 0 && nwalkers >= 0 && max_band_count >= 0,
+               "pb_band_transmittance_cloudy_batch: bad sizes");
+    PB_REQUIRE(nlayers <= kMaxLayersCloudyTransit,
+               "pb_band_transmittance_cloudy_batch: %d layers, at most %d fit in the LDS of a "
+               "workgroup", nlayers, kMaxLayersCloudyTransit);
+    PB_REQUIRE(itop >= 0 && itop < nlayers,
+               "pb_band_transmittance_cloudy_batch: itop out of range");
+    PB_REQUIRE(nbands <= 65535 && nwalkers <= 65535,
+               "pb_band_transmittance_cloudy_batch: at most 65535 bands and walkers per call");
+    const int nrow = nlayers - itop;
+    const int64_t npath = ((int64_t)nrow * (nrow - 1)) / 2;
+    PB_REQUIRE(path_stride == 0 || path_stride >= npath,
+               "pb_band_transmittance_cloudy_batch: path_stride must be 0 or at least a walker's "
+               "length");
+    if (int rc = check_cloud(cloud, "pb_band_transmittance_cloudy_batch"))
+        return rc;
+    if (nbands == 0 || nwalkers == 0)
+        return PB_OK;
+    PB_REQUIRE(out_d && ec_d && (raypath_d || npath == 0) && wn_d && band_start_d &&
+                   band_count_d && response_d && response_offset_d,
+               "pb_band_transmittance_cloudy_batch: null pointer");
+    const int nchunks = pb::div_up(max_band_count, kBlock);
+    PB_REQUIRE(nchunks == 0 || work_d, "pb_band_transmittance_cloudy_batch: null work buffer");
+    if (nchunks > 0) {
+        // (no ray path at one impact parameter: the kernel then reads none)
+        CloudyBandArgs a{work_d, ec_d, wn_d, raypath_d ? raypath_d : ec_d, path_stride,
+                         band_start_d, band_count_d, response_d, response_offset_d, deck_itop_d,
+                         f_patchy_d, maxdepth, itop, nlayers, nwave, {}};
+        const bool two = cloud && cloud->nr > 0;
+        if (two)
+            a.cl = *cloud;
+        const dim3 grid(nchunks, nbands, nwalkers);
+        const size_t lds = ((size_t)kWaves * nlayers + (size_t)kCloudyRows * nrow) * sizeof(double);
+        if (two)
+            k_band_transmittance_cloudy<true><<<grid, kBlock, lds, pb::as_stream(stream)>>>(a);
+        else
+            k_band_transmittance_cloudy<false><<<grid, kBlock, lds, pb::as_stream(stream)>>>(a);
         PB_LAUNCH_CHECK();
     }
     return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,

@@ -28,11 +28,13 @@ from .columns import (RT_PATHS, _legendre_newton, blackbody_wn_2D,      # noqa: 
                       plane_parallel_optical_depth, transit_path, transit_path_device,
                       transit_spectrum, transmission, two_stream)
 from . import contribution                                              # noqa: F401
-from .contribution import (band_cf_host, band_contribution_host,        # noqa: F401
-                           contribution_function_host, transmittance_host)
+from .contribution import (band_cf_host, band_contribution_cloudy_host,  # noqa: F401
+                           band_contribution_host, contribution_function_host,
+                           transmittance_host, transmittance_patchy_host)
 from .batch import (_check_walker_tensor, _cloud_call_args,             # noqa: F401
                     alkali_voigt_det_batch, band_contribution_emission_batch,
-                    band_transmittance_batch, cloudy_emission_batch, cloudy_transit_batch,
+                    band_contribution_emission_cloudy_batch, band_transmittance_batch,
+                    band_transmittance_cloudy_batch, cloudy_emission_batch, cloudy_transit_batch,
                     deck_state_batch, emission_flux_batch, interp_ec_batch, table_transit_batch,
                     table_transit_supported, transit_spectrum_batch, transit_spectrum_ordered,
                     two_stream_batch)

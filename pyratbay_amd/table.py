@@ -63,12 +63,12 @@ def plan_eval_bands(facts, call_facts):
     attached).  call_facts: cloudy; contribution (default False: the band contribution functions
     are asked for -- grid order, every layer and the two passes whatever the model's column order
     is: the transit form needs the stored depth, the emission form reads the chunk's ec in grid
-    order; a cloudy call is refused before planning).  (Two-stream with clouds is refused before
-    planning.)"""
+    order; a cloudy call takes the form 'clouds' in the same grid order: its contribution kernels
+    walk the chunk's clear ec themselves).  (Two-stream with clouds is refused before planning.)"""
     rt_path = facts['rt_path']
     if call_facts.get('contribution', False):
-        return BatchPlan(rt_path, False, False, table='etable', wn='wn', column=None,
-                         may_auto_order=False)
+        return BatchPlan('clouds' if call_facts['cloudy'] else rt_path, False, False,
+                         table='etable', wn='wn', column=None, may_auto_order=False)
     # (the one-pass transit takes no continuum: with one attached, the two passes)
     one_pass = rt_path == 'transit' and facts['one_pass'] and not facts['continuum']
     form = 'clouds' if call_facts['cloudy'] else 'one_pass' if one_pass else rt_path
@@ -421,10 +421,22 @@ class TableSpectrum:
         tensor that is read back once per call).  Every band is divided by its maximum over the
         layers; a band of one sample is NaN.  Such a call runs in grid order, over every layer and
         in two passes, whatever column_order is; the band fluxes and spectra_out keep their bits.
-        Refused (ValueError) before any launch: a HiresData as bands, and any cloudy call
-        (deck_logp, f_patchy, cloud-type models: the reference mixes a clear and a cloudy
-        transmittance there).  Rows of rejected walkers hold whatever the kernels made of their
-        inputs.
+        With clouds (deck_logp, or a Continuum with cloud-type models; with or without f_patchy)
+        one more pass over the chunk's clear ec takes the deck state and the cloud factors the
+        flux kernel is given (no depth and no second ec is stored for either column): transit
+        geometry: f transmittance(cloudy) + (1 - f) transmittance(clear) per sample before the
+        band integral, the cloudy column ending at the deck's layer (the deck's radius does not
+        enter), or the cloudy column alone without f_patchy (band_transmittance_cloudy_batch);
+        emission geometry: the contribution function of the cloudy column only, as the reference
+        -- the clear column is not mixed in and f_patchy does not enter -- with the depth through
+        the row past the deck and the deck's temperature in its layer's row of B
+        (band_contribution_emission_cloudy_batch); contribution.band_contribution_cloudy_host is
+        the NumPy statement.  The band fluxes and spectra_out of such a call have the bits of the
+        same call without contribution_out.
+        Refused (ValueError) before any launch: a HiresData as bands; f_patchy ALONE (no
+        deck_logp and no cloud-type model: there is nothing cloudy to mix, the clear call gives
+        the result); clouds in two-stream geometry.  Rows of rejected walkers hold whatever the
+        kernels made of their inputs.
 
         tstar[nw] (K) and rplanet[nw] (cm), float64 device tensors: an eclipse retrieval with a
         free stellar temperature (pyrat_obj.py:288-294) on bands that carry a stellar SED grid
@@ -596,7 +608,9 @@ class TableSpectrum:
                 raise ValueError('eval_bands: contribution_out needs a PassBands (band '
                                  'contribution functions of high-resolution data are not '
                                  'supported)')
-            if cloudy:
+            if cloudy and deck_logp is None and not (cont is not None and bool(cont.cloud)):
+                # (f_patchy alone: nothing cloudy to mix -- the two columns are the same numbers,
+                # and the clear call gives them in half the work)
                 raise ValueError('eval_bands: contribution_out with clouds (deck_logp, f_patchy, '
                                  'cloud-type models) is not supported: the reference mixes a '
                                  'clear and a cloudy transmittance there')
@@ -715,8 +729,10 @@ class TableSpectrum:
         atmosphere enters the eclipse factor of bands with a stellar SED grid as in eval_params.
 
         contribution=True adds the reference's fifth product, the median over the chain of the
-        band contribution functions (eval_bands' contribution_out, with atmosphere.pressure; no
-        clouds, pass bands only): a fifth store [L, nbands, n], counted in the memory check, and
+        band contribution functions (eval_bands' contribution_out, with atmosphere.pressure; pass
+        bands only; with deck_logp / f_patchy / cloud-type models the cloudy forms described
+        there -- in emission geometry the cloudy column only, as the reference): a fifth store
+        [L, nbands, n], counted in the memory check, and
         its 0.5 quantile -> PosteriorSummary.contribution[L, nbands] (None when not asked for)."""
         return posterior.posterior_summary(
             self, atmosphere, params, counts, bands,
@@ -762,7 +778,9 @@ class TableSpectrum:
         else:
             ec, work = self._interpolate(plan, ci, table)
             if plan.form == 'clouds':
-                spectra, keep = self._rt_clouds(call_, ci, ec, wn, column)
+                spectra, keep = self._rt_clouds(call_, ci, ec, wn, column,
+                                                None if call_.contribution_out is None else
+                                                call_.contribution_out[w0:w1])
             elif call_.contribution_out is not None:
                 spectra = self._rt_contribution(plan, call_, ci, ec, wn,
                                                 call_.contribution_out[w0:w1])
@@ -895,10 +913,12 @@ class TableSpectrum:
         return batch.emission_flux_batch(ec, intervals, wn, ci.temps, self.mu, self.weights,
                                          self.itop, self.nlayers, self.maxdepth, None)
 
-    def _rt_clouds(self, call_, ci, ec, wn, column):
+    def _rt_clouds(self, call_, ci, ec, wn, column, cout=None):
         """A cloud deck and / or patchy clouds on the CLEAR ec: the deck state and the cloud-type
         models' factors are one small launch each, and one pass over ec gives
-        f cloudy + (1 - f) clear.  -> (spectra, what must outlive the chunk's launches)."""
+        f cloudy + (1 - f) clear.  cout[n, L, nbands] (or None): the chunk's band contribution
+        functions, from the same deck state and factors in one more pass over ec (grid order:
+        column is None).  -> (spectra, what must outlive the chunk's launches)."""
         cont = self.continuum
         deck = None if ci.deck_logp is None else \
             batch.deck_state_batch(cont.pressure_d, ci.deck_logp, ci.rad, ci.temps)
@@ -912,7 +932,17 @@ class TableSpectrum:
             spectra = batch.cloudy_transit_batch(ec, path, ci.rad, self.rstar, self.itop,
                                                  self.maxdepth, deck=deck, f_patchy=ci.f_patchy,
                                                  column=column, _terms=terms)
+            if cout is not None:
+                batch.band_transmittance_cloudy_batch(ec, path, call_.bands, self.itop,
+                                                      self.maxdepth, deck=deck,
+                                                      f_patchy=ci.f_patchy, out=cout,
+                                                      _terms=terms)
         else:
+            if cout is not None:
+                batch.band_contribution_emission_cloudy_batch(
+                    ec, self._intervals(ci), ci.temps, call_.bands, None, self.itop,
+                    self.nlayers, self.maxdepth, deck=deck, out=cout, dlogp=call_.dlogp,
+                    _terms=terms)
             spectra = batch.cloudy_emission_batch(ec, self._intervals(ci), wn, ci.temps, self.mu,
                                                   self.weights, self.itop, self.maxdepth,
                                                   deck=deck, f_patchy=ci.f_patchy, column=column,
