@@ -396,6 +396,24 @@ int pb_two_stream_batch(double *flux_d, double *ec_d, const double *intervals_d,
                         const double *flux_top_d, double *work_d, int nlayers, int nwave,
                         int nwalkers, void *stream);
 int64_t pb_two_stream_batch_work_doubles(int nlayers, int nwave, int nwalkers);
+/* pb_two_stream_batch with the irradiation of every walker's own stellar temperature (a retrieval
+ * with a free T_eff: pyrat_obj.py:288-290 updates spec.starflux, the top boundary of the downward
+ * sweep, pyrat/spectrum.py:498-500): in place of flux_top_d, star_grid_d[nt,nwave] (the SED grid on
+ * the model's wavenumbers), sed_temps_d[nt] (strictly ascending, nt >= 2), tstar_d[nwalkers] and
+ * factor = beta_irr*(rstar/smaxis)^2.  The bracket of tstar is found once per walker and per
+ * column
+ *   down = factor * (slope * (t - x_lo) + y_lo),   slope = (y_hi - y_lo) / (x_hi - x_lo)
+ * -- interp1d's linear rule as SciPy states it, then the multiply, every operation rounded on its
+ * own -- is formed in registers: no flux_top[nwalkers,nwave] exists.  Everything else is
+ * pb_two_stream_batch's kernel (one template): the bits of that entry run one walker at a time with
+ * the host-formed flux_top.  DEVIATION: a walker whose tstar is NaN or outside the grid reads no
+ * grid row and gets +inf in its whole flux row (the reference's interp1d raises there); its ec and
+ * work rows are left untouched.  At most 65535 walkers per call. */
+int pb_two_stream_batch_star(double *flux_d, double *ec_d, const double *intervals_d,
+                             const double *wn_d, const double *temps_d, const double *f_int_d,
+                             const double *star_grid_d, const double *sed_temps_d,
+                             const double *tstar_d, double factor, int nt, double *work_d,
+                             int nlayers, int nwave, int nwalkers, void *stream);
 /* f_int of spectrum.py:475-478: Planck at tint scaled to a bolometric sigma*tint^4. */
 int pb_internal_flux(double *f_int_d, const double *wn_d, double tint, int nwave, void *stream);
 
@@ -713,6 +731,50 @@ int pb_loglike_obs(double *loglike_d, const double *bandflux_d, const double *da
                    const int32_t *err_group_d, const int32_t *err_mode_d,
                    const double *err_vals_d, double err_unit, int nerr, int nwalkers, int nbands,
                    void *stream);
+
+/* ---- The front end towards the sampler (pb_retrieval.hip): theta_d[nwalkers,nfree], the free
+ * parameters a sampler holds, -> every per-walker tensor of the batched loop, the log-prior and the
+ * bounds flag, in one launch.  The map is nmap entries (device arrays, built once per retrieval);
+ * entry e writes ONE element of one destination:
+ *   v = src_d[e] >= 0 ? theta[w, src_d[e]] : const_d[e];   if (factor_d[e] != 1) v = v * factor_d[e]
+ *   dest_ptrs[dest_d[e]][w * dest_ncols[dest_d[e]] + col_d[e]] = v
+ * (a fixed parameter is a constant; a shared one has the src of the parameter it follows: Loglike's
+ * rule, tools/retrieval_tools.py:91-93; values are copies and at most one multiply).  dest_ptrs /
+ * dest_ncols: HOST arrays of ndest device pointers [nwalkers,ncols] and their column counts,
+ * passed to the kernel by value.  Per free parameter f: pmin_d, pmax_d, prior_d, priorlow_d,
+ * priorup_d and value_d [nfree].  The bounds test comes first:
+ *   inside_d[w] = every theta[w,f] is finite and pmin[f] <= theta[w,f] <= pmax[f]
+ * and a walker that fails it is mapped from value_d instead of its own row (DEVIATION: so that no
+ * later kernel sees NaN or out-of-range input); its log_prior_d[w] is -inf.  Otherwise
+ *   log_prior_d[w] = sum_f (priorlow[f] == 0 && priorup[f] == 0 ? 0
+ *                           : -0.5 ((p - prior[f]) / s)^2,  s = p < prior[f] ? priorlow[f] : priorup[f])
+ * without a normalisation term, summed in a fixed order (two terms per lane, then a butterfly):
+ * the same bits in every run.  One wavefront per walker.  An entry whose dest, col or src is out
+ * of range writes nothing.  More than PB_RETRIEVAL_MAX_PARAMS entries or free parameters, or
+ * more than PB_RETRIEVAL_MAX_DESTS destinations: PB_ERR_ARG.  nwalkers == 0: nothing launched. */
+#define PB_RETRIEVAL_MAX_PARAMS 128
+#define PB_RETRIEVAL_MAX_DESTS 16
+int pb_retrieval_map(double *const *dest_ptrs, const int32_t *dest_ncols, int ndest,
+                     double *log_prior_d, int32_t *inside_d, const double *theta_d,
+                     const int32_t *src_d, const double *const_d, const double *factor_d,
+                     const int32_t *dest_d, const int32_t *col_d, const double *value_d,
+                     const double *pmin_d, const double *pmax_d, const double *prior_d,
+                     const double *priorlow_d, const double *priorup_d, int nmap, int nfree,
+                     int nwalkers, void *stream);
+/* The prior transform of a nested sampler: cube_d[nwalkers,nfree] in (0, 1) -> theta_d, per free
+ * parameter: uniform (priorlow == priorup == 0): pmin + u (pmax - pmin); two-sided Gaussian, with
+ * lo = priorlow and up = priorup:
+ *   u <  lo / (lo + up):  prior + lo * ndtri(0.5 u (lo + up) / lo)
+ *   otherwise:            prior + up * ndtri(1 - 0.5 (1 - u) (1 + lo / up))
+ * with the device library's inverse normal CDF; not truncated to [pmin, pmax]. */
+int pb_prior_transform(double *theta_d, const double *cube_d, const double *pmin_d,
+                       const double *pmax_d, const double *prior_d, const double *priorlow_d,
+                       const double *priorup_d, int nfree, int nwalkers, void *stream);
+/* out_d[w] = inside_d[w] ? (add_prior ? loglike_d[w] + log_prior_d[w] : loglike_d[w])
+ *                        : outside_value     (log_prior_d may be NULL when add_prior == 0). */
+int pb_log_posterior(double *out_d, const double *loglike_d, const double *log_prior_d,
+                     const int32_t *inside_d, double outside_value, int add_prior, int nwalkers,
+                     void *stream);
 
 /* High-resolution data (eval()'s second exit, pyrat/pyrat_obj.py:331-356).
  * ps.inst_convolution's last step (spectrum/spec_tools.py:879) for a batch:

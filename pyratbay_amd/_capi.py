@@ -127,6 +127,11 @@ _PROTOS = {
     'pb_two_stream': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     'pb_two_stream_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     'pb_two_stream_batch_work_doubles': [i32, i32, i32],
+    'pb_two_stream_batch_star': [vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, vp, i32, i32, i32, vp],
+    'pb_retrieval_map': [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32,
+                         i32, i32, vp],
+    'pb_prior_transform': [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
+    'pb_log_posterior': [vp, vp, vp, vp, f64, i32, i32, vp],
     'pb_internal_flux': [vp, vp, f64, i32, vp],
     'pb_two_stream_net_parts': [i32],
     'pb_two_stream_net_work_doubles': [i32, i32, i32],

@@ -553,6 +553,9 @@ class WalkerAtmosphere:
         self._maps = None
         self._dev = None
         self._struct = None
+        # (kept for the retrieval front end: the value of a column no retrieval parameter names)
+        self.base_params = None if base_params is None else \
+            np.array(base_params, dtype=np.float64)
         if base_radius is None:
             if base_params is None:
                 raise ValueError('give base_radius[L], or base_params (the parameter vector of '

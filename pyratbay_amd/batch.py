@@ -187,6 +187,34 @@ def two_stream_batch(ec, intervals, wn, temps, f_int=None, flux_top=None, out=No
     return flux
 
 
+def two_stream_batch_star(ec, intervals, wn, temps, f_int, star_grid, factor, tstar, out=None,
+                          work=None):
+    """two_stream_batch with every walker's own irradiation (pb_two_stream_batch_star): the top
+    boundary of walker w is factor * star_grid.flux_host(tstar[w]) -- star_grid: an
+    observation.StellarGrid on wn, factor = beta_irr * (rstar / smaxis)**2, tstar[nw] a float64
+    device tensor -- formed per column inside the sweep, no flux_top[nw, W] is stored.  The bits
+    of two_stream_batch run one walker at a time with that flux_top.  A walker whose tstar is NaN
+    or outside the grid's temperatures gets a row of +inf."""
+    nw, nlayers, nwave = ec.shape
+    assert ec.is_contiguous() and ec.dtype == torch.float64
+    if star_grid.nwave != nwave:
+        raise ValueError(f'two_stream_batch_star: the stellar grid has {star_grid.nwave} samples, '
+                         f'the columns {nwave}')
+    _check_walker_tensor('two_stream_batch_star: tstar', tstar, nw)
+    flux = out if out is not None else torch.empty((nw, nwave), dtype=torch.float64,
+                                                   device=ec.device)
+    need = _capi.lib().pb_two_stream_batch_work_doubles(nlayers, nwave, nw)
+    if work is None:
+        work = torch.empty(need, dtype=torch.float64, device=ec.device) if need else None
+    elif work.numel() < need or work.dtype != torch.float64 or not work.is_contiguous():
+        raise ValueError(f'two_stream_batch_star: work must hold {need} contiguous doubles')
+    call('pb_two_stream_batch_star', _ptr(flux), _ptr(ec), _ptr(intervals.contiguous()), _ptr(wn),
+         _ptr(temps.contiguous()), _ptr(f_int), _ptr(star_grid.fluxes), _ptr(star_grid.sed_temps),
+         _ptr(tstar.contiguous()), float(factor), star_grid.nt, _ptr(work), nlayers, nwave, nw,
+         _stream())
+    return flux
+
+
 # --------------------------------------------------------------------------
 # Band contribution functions for a batch (pb_contribution.hip)
 # --------------------------------------------------------------------------

@@ -31,18 +31,49 @@ using pb::two_stream_down;
 using pb::two_stream_trans;
 using pb::two_stream_up;
 
+// The irradiation of a walker with a stellar temperature of its own (pb_two_stream_batch_star):
+// the bracket of tstar[walker] in sed_temps[nt], found once per walker (block-uniform).
+struct StarTop {
+    const double *star_grid;   // [nt][W]; null: the shared flux_top[W] (or none)
+    const double *sed_temps;   // [nt]
+    const double *tstar;       // [nw]
+    double factor;
+    int nt;
+};
+
 // grid (blocks of 256 columns, walkers): every global access of a wavefront is a contiguous row
-// segment.  ec[nw][L][W] is consumed; intervals[nw][L-1], temp[nw][L] -> flux[nw][W].
+// segment.  ec[nw][L][W] is consumed; intervals[nw][L-1], temp[nw][L] -> flux[nw][W].  kStar: the
+// top boundary is factor * (the SED grid interpolated at the walker's tstar), interp1d's linear
+// rule as SciPy states it (StellarGrid.flux_host) then the multiply, per column in registers; a
+// walker whose tstar is NaN or outside the grid reads no grid row and gets a +inf flux row.
+template <bool kStar>
 __global__ __launch_bounds__(kBlock) void k_two_stream_batch(
     double *__restrict__ flux, double *__restrict__ ec, const double *__restrict__ intervals,
     const double *__restrict__ wn, const double *__restrict__ temp,
-    const double *__restrict__ f_int, const double *__restrict__ flux_top,
+    const double *__restrict__ f_int, const double *__restrict__ flux_top, StarTop star,
     double *__restrict__ work, int nlayers, int nwave)
 {
     // this walker's kKB T [L], its reciprocal [L] and layer intervals [L-1]: wave-uniform reads
     extern __shared__ double s_kt[];
     double *s_h = s_kt + 2 * nlayers;
     const int wk = blockIdx.y;
+    int hi = 1;
+    double tstar = 0.0;
+    if (kStar) {
+        tstar = star.tstar[wk];
+        // (block-uniform: every thread of the block leaves here, before any barrier)
+        if (!(tstar >= star.sed_temps[0] && tstar <= star.sed_temps[star.nt - 1])) {
+            const int j = blockIdx.x * kBlock + threadIdx.x;
+            if (j < nwave)
+                flux[(int64_t)wk * nwave + j] = INFINITY;
+            return;
+        }
+        // searchsorted(sed_temps, tstar, side='left') clipped to [1, nt - 1]
+        hi = 0;
+        while (hi < star.nt && star.sed_temps[hi] < tstar)
+            hi++;
+        hi = min(max(hi, 1), star.nt - 1);
+    }
     for (int k = threadIdx.x; k < nlayers - 1; k += kBlock)
         s_h[k] = intervals[(int64_t)wk * (nlayers - 1) + k];
     planck_terms(s_kt, temp + (int64_t)wk * nlayers, nlayers);        // (ends with the barrier)
@@ -54,7 +85,16 @@ __global__ __launch_bounds__(kBlock) void k_two_stream_batch(
     const double w = wn[j];
     const double factor = planck_factor(w);
     // downward sweep from the irradiation at the top (itop = 0: spectrum.py:498-509)
-    double down = flux_top ? flux_top[j] : 0.0;
+    double down;
+    if (kStar) {
+        const double x_lo = star.sed_temps[hi - 1];
+        const double y_lo = star.star_grid[(int64_t)(hi - 1) * nwave + j];
+        const double y_hi = star.star_grid[(int64_t)hi * nwave + j];
+        const double slope = (y_hi - y_lo) / (star.sed_temps[hi] - x_lo);
+        down = star.factor * (slope * (tstar - x_lo) + y_lo);
+    } else {
+        down = flux_top ? flux_top[j] : 0.0;
+    }
     double depth = 0.0;
     double prev = ec[0];
     double cur = nlayers > 1 ? ec[nwave] : 0.0;
@@ -252,8 +292,38 @@ int pb_two_stream_batch(double *flux_d, double *ec_d, const double *intervals_d,
     PB_REQUIRE(lds <= 64 * 1024, "pb_two_stream_batch: %d layers: at most %d (the walker's "
                "temperatures and intervals are kept in LDS)", nlayers, 64 * 1024 / 24);
     dim3 grid(pb::div_up(nwave, kBlock), nwalkers);
-    k_two_stream_batch<<<grid, kBlock, lds, pb::as_stream(stream)>>>(
-        flux_d, ec_d, intervals_d, wn_d, temps_d, f_int_d, flux_top_d, work_d, nlayers, nwave);
+    k_two_stream_batch<false><<<grid, kBlock, lds, pb::as_stream(stream)>>>(
+        flux_d, ec_d, intervals_d, wn_d, temps_d, f_int_d, flux_top_d, StarTop{}, work_d, nlayers,
+        nwave);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+int pb_two_stream_batch_star(double *flux_d, double *ec_d, const double *intervals_d,
+                             const double *wn_d, const double *temps_d, const double *f_int_d,
+                             const double *star_grid_d, const double *sed_temps_d,
+                             const double *tstar_d, double factor, int nt, double *work_d,
+                             int nlayers, int nwave, int nwalkers, void *stream)
+{
+    PB_REQUIRE(nlayers >= 1 && nwave >= 0 && nwalkers >= 0,
+               "pb_two_stream_batch_star: bad shape");
+    PB_REQUIRE(nt >= 2, "pb_two_stream_batch_star: the grid needs at least 2 temperatures");
+    if (nwave == 0 || nwalkers == 0)
+        return PB_OK;
+    PB_REQUIRE(flux_d && ec_d && wn_d && temps_d && (nlayers == 1 || intervals_d) &&
+                   star_grid_d && sed_temps_d && tstar_d,
+               "pb_two_stream_batch_star: null pointer");
+    PB_REQUIRE(work_d || pb_two_stream_batch_work_doubles(nlayers, nwave, nwalkers) == 0,
+               "pb_two_stream_batch_star: null work (pb_two_stream_batch_work_doubles doubles of "
+               "device scratch)");
+    PB_REQUIRE(nwalkers <= 65535, "pb_two_stream_batch_star: at most 65535 walkers per call");
+    const size_t lds = ((size_t)3 * nlayers) * sizeof(double);
+    PB_REQUIRE(lds <= 64 * 1024, "pb_two_stream_batch_star: %d layers: at most %d (the walker's "
+               "temperatures and intervals are kept in LDS)", nlayers, 64 * 1024 / 24);
+    dim3 grid(pb::div_up(nwave, kBlock), nwalkers);
+    k_two_stream_batch<true><<<grid, kBlock, lds, pb::as_stream(stream)>>>(
+        flux_d, ec_d, intervals_d, wn_d, temps_d, f_int_d, nullptr,
+        StarTop{star_grid_d, sed_temps_d, tstar_d, factor, nt}, work_d, nlayers, nwave);
     PB_LAUNCH_CHECK();
     return PB_OK;
 }

@@ -13,7 +13,7 @@ ec, depth and B never travel to the host unless asked for.  torch tensors are us
 only as owners of device memory; all arithmetic happens in libpbhip.so.
 
 This module is the front door: the code lives in one module per stage (_device, lbl, columns,
-batch, bands, observation, contribution, spectrum, table) and every public name is re-exported here.  The modules of the
+batch, bands, observation, contribution, spectrum, table, retrieval) and every public name is re-exported here.  The modules of the
 package import from those, not from here.
 """
 from . import _capi                                                     # noqa: F401
@@ -37,8 +37,9 @@ from .batch import (_check_walker_tensor, _cloud_call_args,             # noqa: 
                     band_transmittance_cloudy_batch, cloudy_emission_batch, cloudy_transit_batch,
                     deck_state_batch, emission_flux_batch, interp_ec_batch, table_transit_batch,
                     table_transit_supported, transit_spectrum_batch, transit_spectrum_ordered,
-                    two_stream_batch)
+                    two_stream_batch, two_stream_batch_star)
 from .bands import HiresData, PassBands                                 # noqa: F401
 from .observation import Observation, StellarGrid                       # noqa: F401
 from .spectrum import LBLSpectrum, SpectrumPipeline                     # noqa: F401
 from .table import TableSpectrum                                        # noqa: F401
+from .retrieval import Retrieval, parse_retrieval_params                # noqa: F401

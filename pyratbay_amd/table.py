@@ -17,6 +17,7 @@ from .batch import _check_walker_tensor
 from .columns import (RT_PATHS, default_quadrature, emission_flux, internal_flux, interp_ec,
                       pack_raypath, plane_parallel_optical_depth, transit_path,
                       transit_path_device, transit_spectrum, two_stream)
+from .observation import StellarGrid
 from .radeq import RadiativeEquilibrium
 
 
@@ -44,6 +45,24 @@ BatchPlan = namedtuple('BatchPlan', 'form ordered limited table wn column may_au
 # the chunk's radius rows, or the shared row [1, L]; ckw: the continuum keywords of interp_ec_batch.
 ChunkInputs = namedtuple('ChunkInputs',
                          'n temps dens rad ckw rv f_dilution deck_logp f_patchy tstar rplanet')
+
+
+# refusals of eval_bands that the retrieval front end (retrieval.Retrieval) repeats at construction
+MSG_RV_NEEDS_HIRES = ('eval_bands: rv (a radial-velocity shift) needs a HiresData, pass bands are '
+                      'integrated on the unshifted grid')
+MSG_STAR_HIRES = ('eval_bands: tstar / rplanet with a HiresData are not supported (its eclipse '
+                  'factor is applied per sample before the convolution); they belong to a '
+                  'PassBands with set_eclipse_grid()')
+MSG_STAR_TRANSIT = ('eval_bands: tstar / rplanet (the eclipse factor per walker) belong to '
+                    'emission and two-stream geometry, not to transit geometry')
+MSG_STAR_NEEDS_GRID = ('eval_bands: tstar / rplanet need a stellar SED grid on the bands '
+                       '(PassBands.set_eclipse_grid)')
+MSG_GRID_NEEDS_TSTAR = ('eval_bands: the bands carry a stellar SED grid (set_eclipse_grid): '
+                        'tstar[nw] is needed')
+MSG_IRRADIATION_NEEDS_TSTAR = ('eval_bands: the model carries a stellar SED grid for its '
+                               'irradiation (irradiation=): tstar[nw] is needed')
+MSG_DECK_NEEDS_DECK = ('eval_bands: deck_logp needs a Deck among the models of the attached '
+                       'Continuum')
 
 
 def ordered_supported(rt_path, nlayers, itop, nwave):
@@ -120,13 +139,19 @@ class TableSpectrum:
 
     def __init__(self, etable, ttable, wn, radius, rstar, rt_path='transit', itop=0,
                  maxdepth=10.0, quadrature_mu=None, quadrature_weights=None, continuum=None,
-                 timestamps=True, column_order='auto', tint=0.0, flux_top=None):
+                 timestamps=True, column_order='auto', tint=0.0, flux_top=None,
+                 irradiation=None):
         require_gpu()
         # rt_path 'two_stream' / 'emission_two_stream' / 'eclipse_two_stream' (RT_PATHS, as in
         # LBLSpectrum): the geometry 'two_stream' (pyrat/spectrum.py:454-522) with the internal
         # flux of tint (K) added at the bottom and flux_top[W], the irradiation
         # beta_irr * (rstar / smaxis)**2 * starflux the caller forms (host or device; None: none),
         # at the top.  The optical depth has no maxdepth stop (opacity/optic_depth.py:124-126).
+        # irradiation=(StellarGrid, factor), exclusive with flux_top: a retrieval with a free
+        # stellar temperature (pyrat_obj.py:288-290 updates spec.starflux, which two_stream() puts
+        # at the top, pyrat/spectrum.py:498-500): eval_bands(..., tstar=) takes every walker's top
+        # boundary factor * grid(tstar[w]) from the grid (an observation.StellarGrid on wn);
+        # factor = beta_irr * (rstar / smaxis)**2, formed by the caller like flux_top's.
         self.rt_path_name = rt_path
         self.observable = None
         if rt_path in ('two_stream', 'emission_two_stream', 'eclipse_two_stream'):
@@ -137,8 +162,12 @@ class TableSpectrum:
                 raise ValueError(f'rt_path {self.rt_path_name!r}: itop must be 0, got {itop}')
             maxdepth = float('inf')
             column_order = None               # (no early exit to order the columns for)
-        elif tint != 0.0 or flux_top is not None:
-            raise ValueError('tint and flux_top belong to the two-stream geometries')
+        elif tint != 0.0 or flux_top is not None or irradiation is not None:
+            raise ValueError('tint, flux_top and irradiation belong to the two-stream geometries')
+        if irradiation is not None and flux_top is not None:
+            raise ValueError('irradiation (a stellar SED grid, one top boundary per walker) and '
+                             'flux_top (one shared top boundary) are exclusive')
+        self.irradiation = None
         self._timer = StageTimer() if timestamps else None
         # eval_bands: the order the columns are worked in (see order_columns).
         # 'auto': taken from the first walker of the first batch; None: grid order
@@ -176,6 +205,12 @@ class TableSpectrum:
             if self.flux_top is not None and self.flux_top.shape != (self.nwave,):
                 raise ValueError(f'flux_top must have shape ({self.nwave},), got '
                                  f'{tuple(self.flux_top.shape)}')
+            if irradiation is not None:
+                grid, factor = irradiation
+                if not isinstance(grid, StellarGrid) or grid.nwave != self.nwave:
+                    raise ValueError('irradiation: (StellarGrid, factor) with the grid on the '
+                                     f"model's {self.nwave} wavenumbers")
+                self.irradiation = (grid, float(factor))
         elif rt_path != 'transit':
             if quadrature_mu is None:
                 quadrature_mu, quadrature_weights = default_quadrature()
@@ -275,6 +310,9 @@ class TableSpectrum:
             raise ValueError(f'temperature outside the {self.tmin:.1f}-{self.tmax:.1f} '
                              'K range of the table (the reference rejects such a model, '
                              'line_sampling.py:426-427)')
+        if getattr(self, 'irradiation', None) is not None:
+            raise ValueError('eval: a model with irradiation= has one top boundary per walker: '
+                             'use eval_bands(..., tstar=)')
         self.temp = temp if isinstance(temp, torch.Tensor) else dev(temp)
         dens = dens if isinstance(dens, torch.Tensor) else dev(dens)
         t = self._timer
@@ -448,7 +486,15 @@ class TableSpectrum:
         is NaN or outside the grid's temperatures is rejected (+inf; DEVIATION: the reference's
         interp1d raises).  Refused (ValueError) before any launch: tstar on bands without a grid;
         bands with a grid and no tstar; rplanet without tstar; either in transit geometry; either
-        with a HiresData (its eclipse factor is applied per sample before the convolution)."""
+        with a HiresData (its eclipse factor is applied per sample before the convolution).
+
+        Two-stream geometry and the star's temperature: on a model built with
+        irradiation=(StellarGrid, factor) tstar also sets every walker's top boundary,
+        factor * grid(tstar[w]), inside the sweep (two_stream_batch_star: one launch, as before);
+        bands without a grid are then allowed (tstar moves the irradiation only), and such a model
+        without tstar is refused.  On a model built with a shared flux_top the irradiation is
+        FROZEN at the temperature flux_top was formed with, whatever tstar is: tstar then moves
+        the eclipse factor only."""
         call_ = self._batch_call(temps, dens, bands, radius, f_dilution, continuum_density,
                                  continuum_pars, rv, deck_logp, f_patchy, alkali_density,
                                  spectra_out, contribution_out, contribution_pressure, tstar,
@@ -500,8 +546,7 @@ class TableSpectrum:
         two_stream_rt = self.rt_path == 'two_stream'
         if rv is not None:
             if not isinstance(bands, HiresData):
-                raise ValueError('eval_bands: rv (a radial-velocity shift) needs a HiresData, '
-                                 'pass bands are integrated on the unshifted grid')
+                raise ValueError(MSG_RV_NEEDS_HIRES)
             if tuple(rv.shape) != (temps.shape[0],):
                 raise ValueError(f'eval_bands: rv must have shape {(temps.shape[0],)}, got '
                                  f'{tuple(rv.shape)}')
@@ -510,30 +555,27 @@ class TableSpectrum:
         assert f_dilution is None or f_dilution.shape == (temps.shape[0],)
         nw = temps.shape[0]
         grid = getattr(bands, 'star_grid', None)
+        irradiation = getattr(self, 'irradiation', None)
         if tstar is not None or rplanet is not None:
             if isinstance(bands, HiresData):
-                raise ValueError('eval_bands: tstar / rplanet with a HiresData are not supported '
-                                 '(its eclipse factor is applied per sample before the '
-                                 'convolution); they belong to a PassBands with '
-                                 'set_eclipse_grid()')
+                raise ValueError(MSG_STAR_HIRES)
             if self.rt_path == 'transit':
-                raise ValueError('eval_bands: tstar / rplanet (the eclipse factor per walker) '
-                                 'belong to emission and two-stream geometry, not to transit '
-                                 'geometry')
-            if grid is None:
-                raise ValueError('eval_bands: tstar / rplanet need a stellar SED grid on the '
-                                 'bands (PassBands.set_eclipse_grid)')
+                raise ValueError(MSG_STAR_TRANSIT)
+            # (tstar alone on bands without a grid: the irradiation of a model that carries one)
+            if grid is None and (irradiation is None or rplanet is not None):
+                raise ValueError(MSG_STAR_NEEDS_GRID)
             if tstar is None:
                 raise ValueError('eval_bands: rplanet needs tstar (the bands carry a stellar SED '
                                  'grid: every walker needs its stellar temperature)')
-            if rplanet is None and bands.grid_rplanet is None:
+            if grid is not None and rplanet is None and bands.grid_rplanet is None:
                 raise ValueError('eval_bands: a planet radius is needed, rplanet[nw] or the one '
                                  'of set_eclipse_grid()')
             _check_walker_tensor('eval_bands: tstar', tstar, nw)
             _check_walker_tensor('eval_bands: rplanet', rplanet, nw)
         elif grid is not None:
-            raise ValueError('eval_bands: the bands carry a stellar SED grid '
-                             '(set_eclipse_grid): tstar[nw] is needed')
+            raise ValueError(MSG_GRID_NEEDS_TSTAR)
+        if irradiation is not None and tstar is None:
+            raise ValueError(MSG_IRRADIATION_NEEDS_TSTAR)
         if spectra_out is not None:
             _check_walker_tensor('eval_bands: spectra_out', spectra_out, nw,
                                  shape=(nw, self.nwave))
@@ -544,8 +586,7 @@ class TableSpectrum:
         _check_walker_tensor('eval_bands: deck_logp', deck_logp, nw)
         _check_walker_tensor('eval_bands: f_patchy', f_patchy, nw)
         if deck_logp is not None and (cont is None or not cont.deck):
-            raise ValueError('eval_bands: deck_logp needs a Deck among the models of the '
-                             'attached Continuum')
+            raise ValueError(MSG_DECK_NEEDS_DECK)
         if two_stream_rt:
             # (the reference's two-stream ignores the clear column of a patchy model, and its deck
             # leaves zero rows below the deck's layer)
@@ -792,7 +833,7 @@ class TableSpectrum:
             call_.spectra_out[w0:w1].copy_(spectra)
         # (the walkers' radial velocities: HiresData only -- eval_bands has checked)
         okw = {} if ci.rv is None else {'rv': ci.rv}
-        if ci.tstar is not None:
+        if ci.tstar is not None and getattr(call_.bands, 'star_grid', None) is not None:
             okw = {'tstar': ci.tstar, 'rplanet': ci.rplanet}
         call_.bands.integrate_batch(
             spectra, call_.out[w0:w1],
@@ -881,7 +922,7 @@ class TableSpectrum:
         intervals = self._intervals(ci)
         if plan.form == 'two_stream':
             # depth without a stop + both sweeps in one launch; ec is consumed
-            return batch.two_stream_batch(ec, intervals, wn, ci.temps, self.f_int, self.flux_top)
+            return self._two_stream(ci, ec, intervals, wn)
         args = (ec, intervals, wn, ci.temps, self.mu, self.weights, self.itop, self.nlayers,
                 self.maxdepth, column)
         if plan.limited:
@@ -909,9 +950,18 @@ class TableSpectrum:
                                                self.itop, self.nlayers, self.maxdepth, out=cout,
                                                dlogp=call_.dlogp)
         if plan.form == 'two_stream':
-            return batch.two_stream_batch(ec, intervals, wn, ci.temps, self.f_int, self.flux_top)
+            return self._two_stream(ci, ec, intervals, wn)
         return batch.emission_flux_batch(ec, intervals, wn, ci.temps, self.mu, self.weights,
                                          self.itop, self.nlayers, self.maxdepth, None)
+
+    def _two_stream(self, ci, ec, intervals, wn):
+        """Depth without a stop + both sweeps in one launch (ec is consumed): the shared flux_top,
+        or with irradiation= every walker's own top boundary from the stellar grid at its tstar."""
+        if getattr(self, 'irradiation', None) is None:
+            return batch.two_stream_batch(ec, intervals, wn, ci.temps, self.f_int, self.flux_top)
+        grid, factor = self.irradiation
+        return batch.two_stream_batch_star(ec, intervals, wn, ci.temps, self.f_int, grid, factor,
+                                           ci.tstar)
 
     def _rt_clouds(self, call_, ci, ec, wn, column, cout=None):
         """A cloud deck and / or patchy clouds on the CLEAR ec: the deck state and the cloud-type

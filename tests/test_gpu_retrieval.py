@@ -1,0 +1,599 @@
+"""The retrieval front end on the device (csrc/pb_retrieval.hip, pyratbay_amd/retrieval.py) and
+the per-walker irradiation of the two-stream batch (pb_two_stream_batch_star):
+
+  * pb_retrieval_map against the host statements of Retrieval (expand_host / split_host /
+    log_prior_host / inside_host) at the C ABI, on NaN-filled outputs;
+  * pb_prior_transform against prior_transform_host (scipy.special.ndtri);
+  * pb_log_posterior;
+  * Retrieval.log_likelihood / log_posterior / bandflux end to end on test_gpu_observation's small
+    model, emission (tstar, offsets, error scaling) and transit (deck, f_patchy);
+  * pb_two_stream_batch_star against pb_two_stream_batch one walker at a time with the host-formed
+    flux_top (bits) and against the oracle; eval_bands on a model built with irradiation=."""
+import ctypes as C
+import types
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+EPS = np.finfo(float).eps
+
+
+@pytest.fixture(scope='module')
+def eng():
+    from pyratbay_amd import engine
+    engine.require_gpu()
+    return engine
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+# -------------------------------------------------------------------------------------------------
+# pb_retrieval_map
+# -------------------------------------------------------------------------------------------------
+def map_case(npar, nfree, seed):
+    """A Retrieval of npar lines, nfree of them free, on stand-in objects (Retrieval reads only
+    attributes): the lines name, in shuffled order, R_planet and M_planet (unit factors),
+    f_dilution (a destination of one column), columns of the atmosphere's params and offsets (a
+    destination of several columns); what is not free is fixed or shared, alternately.  Below 128
+    lines two columns of params are named by nobody (constants from base_params), one comes from
+    fixed=, and f_patchy is a destination fed only by a constant.  Free parameter 0 has finite
+    bounds; priors alternate between uniform and two-sided Gaussian with lo != up."""
+    from pyratbay_amd import retrieval as pr
+    rng = np.random.default_rng(seed)
+    solo = ['R_planet', 'M_planet', 'f_dilution'][:max(0, min(3, npar - 1))]
+    rest = npar - len(solo)
+    n_atm = (rest + 1) // 2
+    n_off = rest - n_atm
+    extra = 0 if npar == 128 else 3
+    model_names = [f'a{k}' for k in range(n_atm + extra)]
+    scalars = [s for s, n in (('rplanet', 'R_planet'), ('mplanet', 'M_planet')) if n in solo]
+    free_names = model_names + scalars
+    atm = types.SimpleNamespace(
+        free=free_names, npar=len(free_names),
+        par_scalar={s: (free_names.index(s) if s in scalars else -1)
+                    for s in ('rplanet', 'log_refpressure', 'mplanet')},
+        base_params=rng.uniform(1.0, 2.0, len(free_names)))
+    offs = [f'offset_i{k}' for k in range(n_off)]
+    obs = types.SimpleNamespace(offset_models=offs, err_models=[], noff=n_off, nerr=0,
+                                err_defaults=np.zeros(0), nbands=1)
+    model = types.SimpleNamespace(rt_path='emission', continuum=None, irradiation=None)
+    bands = types.SimpleNamespace(star_grid=None, nbands=1)
+    names = solo + model_names[:n_atm] + offs
+    names = [names[i] for i in rng.permutation(npar)]
+    value = rng.uniform(0.5, 1.5, npar)
+    pmin, pmax = value - rng.uniform(0.5, 1.0, npar), value + rng.uniform(0.5, 1.0, npar)
+    pstep = np.zeros(npar)
+    free = np.sort(rng.permutation(npar)[:nfree])
+    pstep[free] = 0.1
+    others = [i for i in range(npar) if i not in set(free)]
+    targets = sorted(set(free) | set(others[::2]))          # (never shared themselves)
+    for i in others[1::2]:
+        pstep[i] = -(int(rng.choice(targets)) + 1)
+    open_ended = rng.uniform(0, 1, npar) < 0.3
+    open_ended[free[0]] = False
+    pmin[open_ended], pmax[open_ended] = -np.inf, np.inf
+    gauss = np.arange(npar) % 2 == 0
+    prior = np.where(gauss, value + rng.uniform(-0.2, 0.2, npar), 0.0)
+    lo = np.where(gauss, rng.uniform(0.05, 0.5, npar), 0.0)
+    up = np.where(gauss, rng.uniform(0.05, 0.5, npar), 0.0)
+    fixed = {} if npar == 128 else {model_names[-1]: 0.125, 'f_patchy': 0.3}
+    ret = pr.Retrieval(model, atm, bands, obs, (names, value, pmin, pmax, pstep, prior, lo, up),
+                       fixed=fixed)
+    return ret
+
+
+def map_theta(ret, nw, seed):
+    """theta[nw, nfree] inside the bounds, then -- as far as nw allows -- rows with a value
+    exactly at pmin and at pmax (inside), one ulp below pmin and above pmax, NaN, +inf, -inf."""
+    rng = np.random.default_rng(seed)
+    f = ret.ifree
+    lo = np.where(np.isfinite(ret.pmin[f]), ret.pmin[f], ret.params[f] - 1.0)
+    hi = np.where(np.isfinite(ret.pmax[f]), ret.pmax[f], ret.params[f] + 1.0)
+    theta = rng.uniform(lo, hi, (nw, ret.nfree))
+    special = [lo[0], hi[0], np.nextafter(lo[0], -np.inf), np.nextafter(hi[0], np.inf), np.nan,
+               np.inf, -np.inf]
+    expect = [True, True, False, False, False, False, False]
+    if nw >= len(special):
+        rows, picks = range(nw - len(special), nw), range(len(special))
+    elif nw > 1:
+        # (row 0 stays an ordinary walker; which special values the others take goes by the seed)
+        rows, picks = range(1, nw), [(seed + i) % len(special) for i in range(nw - 1)]
+    else:
+        rows, picks = [0], [seed % len(special)]
+    want = np.ones(nw, bool)
+    for r, k in zip(rows, picks):
+        # (a later free parameter carries NaN / inf where there is one: not only lane 0)
+        col = 0 if k < 4 else (ret.nfree - 1)
+        theta[r, col] = special[k]
+        want[r] = expect[k]
+    return theta, want
+
+
+def run_map(eng, ret, theta):
+    """pb_retrieval_map at the C ABI on NaN-filled outputs (inside: a poison value) ->
+    ({destination: array}, log_prior, inside)."""
+    import torch
+    from pyratbay_amd import _capi
+    from pyratbay_amd._device import _ptr, _stream
+    nw = theta.shape[0]
+    d = ret._resident()
+    outs = [torch.full((nw, n), float('nan'), dtype=torch.float64, device='cuda')
+            for n in ret.dest_ncols]
+    log_prior = torch.full((nw,), float('nan'), dtype=torch.float64, device='cuda')
+    inside = torch.full((nw,), -77, dtype=torch.int32, device='cuda')
+    ptrs = (C.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
+    ncols = (C.c_int32 * len(outs))(*ret.dest_ncols)
+    theta_d = eng.dev(theta)
+    _capi.call('pb_retrieval_map', ptrs, ncols, len(outs), _ptr(log_prior), _ptr(inside),
+               _ptr(theta_d), _ptr(d['src']), _ptr(d['const']), _ptr(d['factor']),
+               _ptr(d['dest']), _ptr(d['col']), _ptr(d['value']), _ptr(d['pmin']),
+               _ptr(d['pmax']), _ptr(d['prior']), _ptr(d['priorlow']), _ptr(d['priorup']),
+               ret.nmap, ret.nfree, nw, _stream())
+    torch.cuda.synchronize()
+    return {n: host(t) for n, t in zip(ret.dest_names, outs)}, host(log_prior), host(inside)
+
+
+@pytest.mark.parametrize('nw', [1, 5, 65])
+@pytest.mark.parametrize('npar', [1, 9, 64, 65, 128])
+def test_retrieval_map_against_the_host_statements(eng, npar, nw):
+    from pyratbay_amd import retrieval as pr
+    for nfree in sorted({1, 2, (npar + 1) // 2, npar - 1, npar} & set(range(1, npar + 1))):
+        seed = 1000 * npar + 10 * nfree + nw
+        ret = map_case(npar, nfree, seed)
+        assert ret.npar == npar and ret.nfree == nfree and ret.nmap <= 128
+        if npar < 128:
+            assert ret.nmap == npar + 4 and 'f_patchy' in ret.dest_names
+        if npar >= 4:
+            assert set(ret.map_factor) == {1.0, 7.1492e9, 1.8982e30}
+            assert len(ret.ishare) > 0 or nfree >= npar - 1
+        theta, expect = map_theta(ret, nw, seed)
+        got, log_prior, inside = run_map(eng, ret, theta)
+        assert np.array_equal(ret.inside_host(theta), expect)
+        assert np.array_equal(inside, expect.astype(np.int32))
+        want = ret.split_host(theta)
+        assert set(want) == set(got)
+        for name, a in want.items():
+            g = got[name][:, 0] if a.ndim == 1 else got[name]
+            assert not np.any(np.isnan(a))
+            assert np.array_equal(g.view(np.int64), a.view(np.int64)), (name, nfree)
+        # the log-prior: -inf outside; inside within (n + 2) eps sum|terms| of NumPy's sum
+        f = ret.ifree
+        terms = pr.log_prior_terms(theta, ret.prior[f], ret.priorlow[f], ret.priorup[f])
+        ngauss = int(np.sum((ret.priorlow[f] != 0) | (ret.priorup[f] != 0)))
+        ref = ret.log_prior_host(theta)
+        assert np.all(log_prior[~expect] == -np.inf) and np.all(ref[~expect] == -np.inf)
+        bound = (ngauss + 2) * EPS * np.sum(np.abs(terms[expect]), axis=1)
+        assert np.all(np.abs(log_prior[expect] - ref[expect]) <= bound)
+        # two runs: identical bits; and Retrieval.arguments is this launch
+        again = run_map(eng, ret, theta)
+        assert np.array_equal(again[1].view(np.int64), log_prior.view(np.int64))
+        args = ret.arguments(eng.dev(theta))
+        assert np.array_equal(host(args.log_prior).view(np.int64), log_prior.view(np.int64))
+        assert np.array_equal(host(args.inside), inside)
+        assert np.array_equal(host(args.params), got['params'])
+        if 'offsets' in got:
+            assert np.array_equal(host(args.offsets), got['offsets'])
+        for name in ('f_dilution', 'f_patchy'):
+            if name in got:
+                assert args.kw[name].shape == (nw,)
+                assert np.array_equal(host(args.kw[name]), got[name][:, 0])
+
+
+def test_retrieval_map_limits(eng):
+    import torch
+    from pyratbay_amd import _capi
+    ret = map_case(9, 5, 1)
+    empty = ret.arguments(torch.empty((0, 5), dtype=torch.float64, device='cuda'))
+    assert empty.params.shape == (0, ret.atmosphere.npar) and empty.inside.shape == (0,)
+    with pytest.raises(ValueError, match=r'theta must be a float64 device tensor of shape '
+                                         r'\(nw, 5\)'):
+        ret.arguments(torch.zeros((3, 4), dtype=torch.float64, device='cuda'))
+    null = C.c_void_p(None)
+    with pytest.raises(_capi.PbError, match='129 mapped and 5 free parameters: at most 128'):
+        _capi.call('pb_retrieval_map', null, null, 0, *([null] * 14), 129, 5, 3, null)
+    with pytest.raises(_capi.PbError, match='17 destinations: at most 16'):
+        _capi.call('pb_retrieval_map', null, null, 17, *([null] * 14), 9, 5, 3, null)
+
+
+# -------------------------------------------------------------------------------------------------
+# pb_prior_transform
+# -------------------------------------------------------------------------------------------------
+# The largest error measured on the device, in units of eps (|prior| + s (1 + |z|)), is 1.110
+# (profiles/retrieval.md): the bound is the next power of two above four times that.  Above 256
+# the wrong function is being called; that is not a tolerance to widen.
+TRANSFORM_UNITS = 8.0
+
+
+def test_prior_transform_against_the_host_statement(eng):
+    from scipy.special import ndtri
+    from pyratbay_amd import retrieval as pr
+    ratios = [1.0, 0.1, 10.0]                                    # lo / up
+    names = [f'a{k}' for k in range(6)]
+    atm = types.SimpleNamespace(free=names, npar=6, base_params=None,
+                                par_scalar={'rplanet': -1, 'log_refpressure': -1, 'mplanet': -1})
+    obs = types.SimpleNamespace(offset_models=[], err_models=[], noff=0, nerr=0,
+                                err_defaults=np.zeros(0), nbands=1)
+    model = types.SimpleNamespace(rt_path='emission', continuum=None, irradiation=None)
+    bands = types.SimpleNamespace(star_grid=None, nbands=1)
+    up = np.array([0.5, 0.0, 2.0, 0.3, 0.0, 0.05])
+    lo = np.array([0.5 * ratios[0], 0.0, 2.0 * ratios[1], 0.3 * ratios[2], 0.0, 0.05 * ratios[2]])
+    prior = np.array([3.0, 0.0, -1400.0, 0.25, 0.0, 1.0e-3])
+    pmin = np.array([-np.inf, -2.0, -np.inf, -9.0, 1.0e3, -np.inf])
+    pmax = np.array([np.inf, 7.0, np.inf, 9.0, 1.0e4, np.inf])
+    ret = pr.Retrieval(model, atm, bands, obs,
+                       (names, prior + 0.1, pmin, pmax, np.ones(6), prior, lo, up))
+    gauss = up != 0
+    split = np.where(gauss, lo / np.where(gauss, lo + up, 1.0), 0.5)
+    rows = [np.full(6, u) for u in (1e-300, 1e-16, 0.02275, 0.5, 0.97725, 1 - 1e-16)]
+    rows += [split, np.nextafter(split, 0.0), np.nextafter(split, 1.0)]
+    cube = np.array(rows)
+    want = ret.prior_transform_host(cube)
+    got = host(ret.prior_transform(eng.dev(cube)))
+    # uniform parameters: the same two operations
+    assert np.array_equal(got[:, ~gauss], want[:, ~gauss])
+    assert np.array_equal(want[:, 1], -2.0 + cube[:, 1] * 9.0)
+    # Gaussian parameters, in units of eps (|prior| + s (1 + |z|))
+    below = cube < split
+    s = np.where(below, lo, up)
+    z = (want - prior) / np.where(gauss, s, 1.0)
+    assert np.all(np.isfinite(want[:, gauss])) and np.all(np.isfinite(got[:, gauss]))
+    assert np.min(z[:, gauss]) < -37.0 and np.max(z[:, gauss]) > 8.0
+    np.testing.assert_allclose(z[2, 0], ndtri(0.02275), rtol=1e-14)
+    with np.errstate(all='ignore'):
+        units = np.abs(got - want) / (EPS * (np.abs(prior) + s * (1 + np.abs(z))))
+    worst = np.max(units[:, gauss])
+    print(f'prior transform: largest error {worst:.3f} units of eps (|prior| + s (1 + |z|))')
+    assert worst <= 256.0, 'not the inverse normal CDF'
+    assert worst <= TRANSFORM_UNITS
+
+
+# -------------------------------------------------------------------------------------------------
+# pb_log_posterior
+# -------------------------------------------------------------------------------------------------
+def test_log_posterior_combine(eng):
+    import torch
+    from pyratbay_amd import _capi
+    from pyratbay_amd._device import _ptr, _stream
+    nw = 300
+    rng = np.random.default_rng(4)
+    ll = rng.uniform(-500.0, 10.0, nw)
+    ll[7] = ll[100] = -1.0e98                                    # rejected by the model
+    lp = -rng.uniform(0.0, 30.0, nw)
+    lp[::3] = 0.0
+    inside = (rng.uniform(0, 1, nw) < 0.8).astype(np.int32)
+    inside[7], inside[100], inside[8] = 1, 0, 0
+    lp[inside == 0] = -np.inf
+    lp[7] = -12.5
+    ll_d, lp_d, in_d = eng.dev(ll), eng.dev(lp), eng.dev(inside, torch.int32)
+
+    def run(outside, add, prior=lp_d):
+        out = torch.full((nw + 1,), float('nan'), dtype=torch.float64, device='cuda')
+        _capi.call('pb_log_posterior', _ptr(out), _ptr(ll_d), _ptr(prior), _ptr(in_d), outside,
+                   add, nw, _stream())
+        assert bool(torch.isnan(out[nw]))
+        return host(out[:nw])
+    post = run(-np.inf, 1)
+    like = run(-1.0e98, 0)
+    assert np.array_equal(like, run(-1.0e98, 0, None))
+    out = inside == 0
+    assert np.all(post[out] == -np.inf) and np.all(like[out] == -1.0e98)
+    assert np.array_equal(post[~out], (ll + lp)[~out])
+    assert np.array_equal(like[~out].view(np.int64), ll[~out].view(np.int64))
+    assert np.isfinite(post[7]) and post[7] < -9e97              # -1e98 + prior stays finite
+    zero = (lp == 0.0) & ~out
+    assert np.any(zero)
+    assert np.array_equal(post[zero].view(np.int64), ll[zero].view(np.int64))
+    with pytest.raises(_capi.PbError, match='null'):
+        _capi.call('pb_log_posterior', _ptr(ll_d), _ptr(ll_d), None, _ptr(in_d), 0.0, 1, nw,
+                   _stream())
+
+
+# -------------------------------------------------------------------------------------------------
+# end to end
+# -------------------------------------------------------------------------------------------------
+NW = 5
+OUTSIDE, REJECTED = 3, 1
+EMISSION_BLOCK = """
+    log_kappa'    -1.5    -3.0     1.0    0.1
+    log_gamma1    -0.8    -3.0     1.0    0.1
+    log_gamma2     0.2    -2.0     2.0    0.0
+    alpha          0.4
+    T_irr       1400.0     0.0  3000.0   50.0  1450.0   100.0   200.0
+    T_int        150.0     0.0   500.0   10.0
+    log_H2O       -3.4    -9.0    -1.0    0.2
+    log_CO        -3.3    -9.0    -1.0   -7
+    log_Na         0.0    -2.0     2.0    0.1
+    R_planet      1.05     0.5     2.0    0.02
+    T_eff       5200.0  4000.0  6500.0   50.0  5300.0   200.0
+    offset_nrs1    0.0  {omin}  {omax}    1.0
+    offset_miri    0.0  {omin}  {omax}    1.0
+    err_scale_nrs2 0.0    -1.0     1.0    0.1
+    err_quad_miri  {q}    {qmin}  {qmax}  0.1
+"""
+TRANSIT_BLOCK = """
+    log_kappa'    -1.5    -3.0     1.0    0.1
+    log_gamma1    -0.8    -3.0     1.0    0.1
+    log_gamma2     0.2    -2.0     2.0    0.0
+    alpha          0.4
+    T_irr       1400.0     0.0  3000.0   50.0  1450.0   100.0   200.0
+    T_int        150.0     0.0   500.0   10.0
+    log_H2O       -3.4    -9.0    -1.0    0.2
+    log_CO        -3.3    -9.0    -1.0   -7
+    log_Na         0.0    -2.0     2.0    0.1
+    R_planet      1.05     0.5     2.0    0.02    1.0     0.1
+    log_p_cl      -1.0    -3.0     0.5    0.3
+    f_patchy       0.5     0.0     1.0    0.1
+"""
+
+
+def walkers(ret, seed):
+    """theta[5, nfree] around the block's values; walker 1 has T_irr = T_int = 0 (inside the
+    bounds, rejected by the table's temperatures), walker 3 has log_H2O below pmin."""
+    rng = np.random.default_rng(seed)
+    f = ret.ifree
+    theta = ret.params[f] + 0.5 * ret.pstep[f] * rng.uniform(-1, 1, (NW, ret.nfree))
+    free_names = [ret.pnames[i] for i in f]
+    theta[REJECTED, free_names.index('T_irr')] = 0.0
+    theta[REJECTED, free_names.index('T_int')] = 0.0
+    theta[OUTSIDE, free_names.index('log_H2O')] = -9.5
+    assert list(ret.inside_host(theta)) == [w != OUTSIDE for w in range(NW)]
+    return theta
+
+
+def e2e_case(eng, golden, rt_path):
+    import test_gpu_atmosphere as atm_setup
+    import test_gpu_batch_continuum as base
+    from pyratbay_amd import atmosphere as pa
+    transit = rt_path == 'transit'
+    s = atm_setup.spectrum_case(eng, pa, golden('g7_continuum'), NW, 77, transit, transit)
+    wn, atm = s['wn'], s['atm']
+    model = eng.TableSpectrum(s['etable'], s['ttable'], wn, s['base_radius'], 8.8e10,
+                              rt_path=rt_path, column_order=None, continuum=s['cont'])
+    bands, _ = base.make_bands(eng, wn)
+    pb = eng.PassBands(wn, bands)
+    kw = {}
+    if not transit:
+        sed_temps = np.array([4000.0, 5000.0, 6500.0])
+        x = np.linspace(0.0, 1.0, len(wn))
+        fluxes = 2.0e5 * (sed_temps[:, None] / 5000.0)**3 * (1 + 0.2 * np.sin(7 * x)[None, :])
+        pb.set_eclipse_grid(8.8e10, eng.StellarGrid(wn, sed_temps, fluxes))
+        kw['tstar'] = eng.dev(np.full(1, 5200.0))
+    else:
+        kw['deck_logp'] = eng.dev(np.full(1, -1.0))
+        kw['f_patchy'] = eng.dev(np.full(1, 0.5))
+    flux = host(model.eval_params(atm, eng.dev(atm.base_params[None, :]), pb, **kw))[0]
+    assert np.all(np.isfinite(flux)) and np.all(flux > 0)
+    rng = np.random.default_rng(11)
+    data = flux * (1 + rng.normal(0, 0.02, 3))
+    if transit:
+        obs = eng.Observation(data, 0.03 * flux)
+        block = TRANSIT_BLOCK
+    else:
+        obs = eng.Observation(data, 0.03 * flux, ['nrs1', 'nrs2', 'miri'],
+                              ['offset_nrs1', 'offset_miri'], ['err_scale_nrs2', 'err_quad_miri'],
+                              units='ppm')
+        top = np.max(flux) * 1e4
+        q = np.log10(np.max(flux) * 1e6 * 0.03)
+        block = EMISSION_BLOCK.format(omin=-top, omax=top, q=q, qmin=q - 1, qmax=q + 1)
+    ret = eng.Retrieval(model, atm, pb, obs, block, chunk=2)
+    return dict(ret=ret, model=model, atm=atm, pb=pb, obs=obs, theta=walkers(ret, 5))
+
+
+@pytest.mark.parametrize('rt_path', ['emission', 'transit'])
+def test_end_to_end(eng, golden, rt_path):
+    """5 walkers in chunks of 2, walker 3 outside the bounds, walker 1 rejected by the table's
+    temperatures: log_likelihood has the bits of eval_loglike on the tensors of split_host;
+    log_posterior is that plus log_prior_host within one rounding of the sum; bandflux has the
+    bits of eval_params."""
+    import torch
+    c = e2e_case(eng, golden, rt_path)
+    ret, model, atm, pb, obs, theta = (c[k] for k in ('ret', 'model', 'atm', 'pb', 'obs', 'theta'))
+    if rt_path == 'emission':
+        assert ret.dest_names == ['params', 'tstar', 'offsets', 'err_pars']
+    else:
+        assert ret.dest_names == ['params', 'deck_logp', 'f_patchy']
+    split = ret.split_host(theta)
+    tensors = {k: eng.dev(v) for k, v in split.items()}
+    params = tensors.pop('params')
+    offsets, err_pars = tensors.pop('offsets', None), tensors.pop('err_pars', None)
+    want = model.eval_loglike(atm, params, pb, obs, offsets=offsets, err_pars=err_pars, chunk=2,
+                              **tensors)
+    theta_d = eng.dev(theta)
+    got = ret.log_likelihood(theta_d)
+    torch.cuda.synchronize()
+    want, got = host(want), host(got)
+    live = [w for w in range(NW) if w != OUTSIDE]
+    assert np.array_equal(got[live].view(np.int64), want[live].view(np.int64))
+    assert got[OUTSIDE] == -1.0e98 and got[REJECTED] == -1.0e98
+    fine = [w for w in live if w != REJECTED]
+    assert np.all(got[fine] > -1e6), got
+    prior = ret.log_prior_host(theta)
+    assert np.all(prior[live] < 0) and prior[OUTSIDE] == -np.inf
+    post = host(ret.log_posterior(theta_d))
+    total = got[live] + prior[live]
+    assert np.all(np.abs(post[live] - total) <= EPS * np.abs(total))
+    assert post[OUTSIDE] == -np.inf
+    assert np.isfinite(post[REJECTED]) and post[REJECTED] < -9e97
+    flux = ret.bandflux(theta_d)
+    want_flux = model.eval_params(atm, params, pb, chunk=2, **tensors)
+    assert torch.equal(flux, want_flux)
+    assert bool(torch.isposinf(flux[REJECTED]).all()) and bool(torch.isfinite(flux[fine]).all())
+    # nothing is read back between theta and the result
+    reads = []
+    real = torch.Tensor.cpu
+
+    def spy(self, *a, **k):
+        reads.append(1)
+        return real(self, *a, **k)
+    torch.Tensor.cpu = spy
+    try:
+        again = ret.log_posterior(theta_d)
+    finally:
+        torch.Tensor.cpu = real
+    assert reads == [] and torch.equal(again.cpu(), torch.as_tensor(post))
+
+
+# -------------------------------------------------------------------------------------------------
+# pb_two_stream_batch_star
+# -------------------------------------------------------------------------------------------------
+FACTOR = 0.37
+
+
+def star_grid(eng, wn, nt, seed):
+    rng = np.random.default_rng(seed)
+    sed_temps = np.sort(rng.uniform(3500.0, 7000.0, nt))
+    x = np.linspace(0.0, 1.0, len(wn))
+    fluxes = (3.0e3 * (sed_temps[:, None] / 5000.0)**3.5 * (1 + 0.3 * x[None, :]) *
+              (1 + 0.05 * np.sin(9.0 * x[None, :] + sed_temps[:, None] / 900.0)))
+    return eng.StellarGrid(wn, sed_temps, fluxes)
+
+
+def star_temperatures(grid, nw, pick):
+    """At a node, between nodes and at both ends; one walker: the case `pick` selects."""
+    x = grid.sed_temps_host
+    choices = [x[0], x[-1], x[len(x) // 2], 0.5 * (x[0] + x[1]), 0.3 * x[-2] + 0.7 * x[-1]]
+    if nw == 1:
+        return np.array([choices[pick % len(choices)]])
+    return np.array((choices * nw)[:nw])
+
+
+def run_star(eng, ecs, intervals, temps, wn, f_int, grid, tstar):
+    """two_stream_batch_star with a NaN row behind ec, NaN-filled work and output."""
+    import torch
+    nw, L, W = ecs.shape
+    ec = torch.full((nw + 1, L, W), float('nan'), dtype=torch.float64, device='cuda')
+    ec[:nw] = eng.dev(ecs)
+    work = torch.full((max(nw * (L - 1) * W, 1) + 64,), float('nan'), dtype=torch.float64,
+                      device='cuda')
+    out = torch.full((nw + 1, W), float('nan'), dtype=torch.float64, device='cuda')
+    eng.two_stream_batch_star(ec[:nw], eng.dev(intervals), eng.dev(wn), eng.dev(temps),
+                              eng.dev(f_int), grid, FACTOR, eng.dev(tstar), out=out[:nw],
+                              work=work)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out[nw]).all()) and bool(torch.isnan(ec[nw]).all())
+    assert bool(torch.isnan(work[nw * (L - 1) * W:]).all())
+    return host(out[:nw])
+
+
+@pytest.mark.parametrize('W', [1, 255, 256, 257, 700])
+@pytest.mark.parametrize('L', [1, 2, 5])
+def test_two_stream_batch_star(eng, orc, L, W):
+    """Bits of pb_two_stream_batch per walker with flux_top = factor * grid.flux_host(tstar[w]);
+    the oracle's two-stream on that flux_top within test_gpu_batch_two_stream's tolerance."""
+    import test_gpu_two_stream_batch as tsb
+    for nw in (1, 5):
+        ecs, intervals, temps, wn, f_int, _ = tsb.case(L, W, nw)
+        depths = [tsb.oracle_depth(orc, ecs[w], intervals[w]) for w in range(nw)]
+        for nt in (2, 3, 5):
+            grid = star_grid(eng, wn, nt, 100 * L + nt)
+            tstar = star_temperatures(grid, nw, nt + L)
+            got = run_star(eng, ecs, intervals, temps, wn, f_int, grid, tstar)
+            for w in range(nw):
+                top = FACTOR * grid.flux_host(tstar[w])
+                one = host(tsb.run_batch(eng, ecs[w:w + 1], intervals[w:w + 1], temps[w:w + 1],
+                                         wn, f_int, top))[0]
+                assert np.array_equal(got[w].view(np.int64), one.view(np.int64)), (nw, nt, w)
+                ups = orc.two_stream(depths[w], wn, temps[w], f_int, top, 0)[1]
+                tsb.close_by_column(got[w], ups[0], tsb.RTOL, np.max(np.abs(ups), axis=0))
+
+
+def test_two_stream_batch_star_rejects(eng):
+    """tstar NaN, below and above the grid: a row of +inf; the other walkers keep their bits."""
+    import test_gpu_two_stream_batch as tsb
+    L, W, nw = 5, 257, 5
+    ecs, intervals, temps, wn, f_int, _ = tsb.case(L, W, nw)
+    grid = star_grid(eng, wn, 3, 9)
+    good = star_temperatures(grid, nw, 0)
+    want = run_star(eng, ecs, intervals, temps, wn, f_int, grid, good)
+    assert np.all(np.isfinite(want))
+    bad = good.copy()
+    bad[0], bad[2], bad[4] = np.nan, grid.tmin - 1e-9, np.nextafter(grid.tmax, np.inf)
+    got = run_star(eng, ecs, intervals, temps, wn, f_int, grid, bad)
+    assert np.all(np.isposinf(got[[0, 2, 4]]))
+    assert np.array_equal(got[[1, 3]], want[[1, 3]])
+    with pytest.raises(ValueError, match='the stellar grid has 257 samples, the columns 256'):
+        e, h, t, w256, fi, _ = tsb.case(L, 256, nw)
+        run_star(eng, e, h, t, w256, fi, grid, good)
+    with pytest.raises(ValueError, match='tstar must be a float64 device tensor'):
+        eng.two_stream_batch_star(eng.dev(ecs), eng.dev(intervals), eng.dev(wn), eng.dev(temps),
+                                  None, grid, FACTOR, good)
+
+
+# -------------------------------------------------------------------------------------------------
+# eval_bands on a model with irradiation=
+# -------------------------------------------------------------------------------------------------
+def test_eval_bands_with_irradiation(eng, monkeypatch):
+    """Row w has the bits of a one-walker call on a model built with flux_top = factor *
+    grid.flux_host(tstar[w]); a flux_top model keeps its launches and bits with or without tstar;
+    the refusals."""
+    import torch
+    import test_gpu_batch_two_stream as bts
+    from test_gpu_observation import recorded
+    c = bts.case()
+    wn = c['wn']
+    grid = star_grid(eng, wn, 4, 21)
+    td, dd, rd = bts.device_walkers(eng)
+    tstar = star_temperatures(grid, bts.NW, 0)
+    tstar_d = eng.dev(tstar)
+    pb = eng.PassBands(wn, c['bands'])
+    model = bts.make_model(eng, flux_top=None, irradiation=(grid, FACTOR))
+    log, got, again = recorded(
+        monkeypatch, lambda: model.eval_bands(td, dd, pb, radius=rd, tstar=tstar_d,
+                                              chunk=bts.CHUNK, streams=1))
+    assert torch.equal(got, again)
+    chunk = ['pb_interp_ec_batch', 'pb_two_stream_batch_star', 'pb_band_integrate_batch']
+    assert log == 3 * chunk + ['pb_reject_walkers'], log
+    for w in range(bts.NW):
+        frozen = bts.make_model(eng, flux_top=FACTOR * grid.flux_host(tstar[w]))
+        one = frozen.eval_bands(td[w:w + 1], dd[w:w + 1], pb, radius=rd[w:w + 1])
+        assert torch.equal(got[w], one[0]), w
+    # with a grid on the bands too: the eclipse factor and the irradiation move together
+    eclipse = eng.PassBands(wn, c['bands']).set_eclipse_grid(bts.RSTAR, grid, bts.RPLANET)
+    both = model.eval_bands(td, dd, eclipse, radius=rd, tstar=tstar_d, chunk=bts.CHUNK)
+    w = 4
+    frozen = bts.make_model(eng, flux_top=FACTOR * grid.flux_host(tstar[w]))
+    one = frozen.eval_bands(td[w:w + 1], dd[w:w + 1], eclipse, radius=rd[w:w + 1],
+                            tstar=tstar_d[w:w + 1])
+    assert torch.equal(both[w], one[0])
+    # a model with a shared flux_top: today's launches and bits, the irradiation frozen
+    shared = bts.make_model(eng)
+    log, plain, _ = recorded(
+        monkeypatch, lambda: shared.eval_bands(td, dd, pb, radius=rd, chunk=bts.CHUNK, streams=1))
+    assert log == 3 * ['pb_interp_ec_batch', 'pb_two_stream_batch',
+                       'pb_band_integrate_batch'] + ['pb_reject_walkers'], log
+    log, with_t, _ = recorded(
+        monkeypatch, lambda: shared.eval_bands(td, dd, eclipse, radius=rd, tstar=tstar_d,
+                                               chunk=bts.CHUNK, streams=1))
+    assert 'pb_two_stream_batch_star' not in log and log.count('pb_two_stream_batch') == 3
+    # (its rows are still one-walker calls of the same model: the frozen irradiation)
+    for w in (0, bts.NW - 1):
+        assert torch.equal(plain[w], shared.eval_bands(td[w:w + 1], dd[w:w + 1], pb,
+                                                       radius=rd[w:w + 1])[0])
+        assert torch.equal(with_t[w], shared.eval_bands(td[w:w + 1], dd[w:w + 1], eclipse,
+                                                        radius=rd[w:w + 1],
+                                                        tstar=tstar_d[w:w + 1])[0])
+    # a rejected stellar temperature: that walker alone
+    hot = tstar.copy()
+    hot[2] = 9000.0
+    rej = model.eval_bands(td, dd, pb, radius=rd, tstar=eng.dev(hot), chunk=bts.CHUNK)
+    assert bool(torch.isposinf(rej[2]).all())
+    keep = [w for w in range(bts.NW) if w != 2]
+    assert torch.equal(rej[keep], got[keep])
+    # the refusals
+    with pytest.raises(ValueError, match='are exclusive'):
+        bts.make_model(eng, irradiation=(grid, FACTOR))
+    with pytest.raises(ValueError, match=r'irradiation \(irradiation=\): tstar\[nw\] is needed'):
+        model.eval_bands(td, dd, pb, radius=rd)
+    with pytest.raises(ValueError, match='two-stream geometries'):
+        bts.make_model(eng, 'emission', tint=0.0, flux_top=None, irradiation=(grid, FACTOR))
+    with pytest.raises(ValueError, match=r"grid on the model's 300 wavenumbers"):
+        bts.make_model(eng, flux_top=None,
+                       irradiation=(star_grid(eng, wn[:-1], 3, 1), FACTOR))
+    with pytest.raises(ValueError, match=r'use eval_bands\(\.\.\., tstar=\)'):
+        model.eval(c['temps'][0], c['dens'][0])
+    with pytest.raises(ValueError, match='need a stellar SED grid'):
+        shared.eval_bands(td, dd, pb, radius=rd, tstar=tstar_d)
