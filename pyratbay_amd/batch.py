@@ -263,6 +263,24 @@ def band_transmittance_batch(depth, ideep, bands, itop, out=None):
     return out
 
 
+def _emission_contribution_args(name, ec, intervals, temps, pressure, dlogp):
+    """What the two emission contribution wrappers check alike: ec[nw, L, W], intervals[nw, L-1]
+    and temps[nw, L]; dlogp[L-1] (formed from pressure when None) -> dlogp."""
+    nw, nlayers, _ = ec.shape
+    if ec.dtype != torch.float64 or not ec.is_contiguous() or \
+            tuple(intervals.shape) != (nw, nlayers - 1) or tuple(temps.shape) != (nw, nlayers):
+        raise ValueError(f'{name}: contiguous float64 ec[nw, L, W], intervals[{nw}, '
+                         f'{nlayers - 1}] and temps[{nw}, {nlayers}] wanted, got '
+                         f'{tuple(ec.shape)}, {tuple(intervals.shape)}, {tuple(temps.shape)}')
+    if dlogp is None:
+        return contribution_dlogp(pressure, nlayers)
+    if not isinstance(dlogp, torch.Tensor) or not dlogp.is_cuda or \
+            dlogp.dtype != torch.float64 or tuple(dlogp.shape) != (nlayers - 1,):
+        raise ValueError(f'{name}: dlogp must be a float64 device tensor of shape '
+                         f'({nlayers - 1},)')
+    return dlogp
+
+
 def band_contribution_emission_batch(ec, intervals, temps, bands, pressure, itop, ibottom,
                                      maxdepth, out=None, dlogp=None):
     """Band contribution functions of a batch in emission or two-stream geometry
@@ -272,24 +290,14 @@ def band_contribution_emission_batch(ec, intervals, temps, bands, pressure, itop
     contribution_dlogp(pressure, L), formed once for several calls), maxdepth (inf in two-stream
     geometry: no stop) -> [nw, L, nbands].  Neither the depth nor B is stored; ec is
     only read."""
+    name = 'band_contribution_emission_batch'
     nw, nlayers, nwave = ec.shape
-    if ec.dtype != torch.float64 or not ec.is_contiguous() or \
-            tuple(intervals.shape) != (nw, nlayers - 1) or tuple(temps.shape) != (nw, nlayers):
-        raise ValueError(f'band_contribution_emission_batch: contiguous float64 ec[nw, L, W], '
-                         f'intervals[{nw}, {nlayers - 1}] and temps[{nw}, {nlayers}] wanted, got '
-                         f'{tuple(ec.shape)}, {tuple(intervals.shape)}, {tuple(temps.shape)}')
-    if dlogp is None:
-        dlogp = contribution_dlogp(pressure, nlayers)
-    elif not isinstance(dlogp, torch.Tensor) or not dlogp.is_cuda or \
-            dlogp.dtype != torch.float64 or tuple(dlogp.shape) != (nlayers - 1,):
-        raise ValueError(f'band_contribution_emission_batch: dlogp must be a float64 device '
-                         f'tensor of shape ({nlayers - 1},)')
-    out, work, bargs = _contribution_buffers('band_contribution_emission_batch', bands, nw,
-                                             nlayers, nwave, ec.device, out)
+    dlogp = _emission_contribution_args(name, ec, intervals, temps, pressure, dlogp)
+    out, work, bargs = _contribution_buffers(name, bands, nw, nlayers, nwave, ec.device, out)
     call('pb_band_contribution_emission_batch', _ptr(out), _ptr(ec),
          _ptr(intervals.contiguous()), _ptr(dlogp.contiguous()), _ptr(bands.wn),
-         _ptr(temps.contiguous()), *bargs, float(maxdepth), int(itop), int(ibottom), nlayers, nwave, bands.nbands, nw,
-         _ptr(work), _stream())
+         _ptr(temps.contiguous()), *bargs, float(maxdepth), int(itop), int(ibottom), nlayers,
+         nwave, bands.nbands, nw, _ptr(work), _stream())
     return out
 
 
@@ -362,29 +370,45 @@ def _check_walker_tensor(name, t, nw, dtype=torch.float64, shape=None):
                          f'{tuple(getattr(t, "shape", ()))} on {getattr(t, "device", "the host")}')
 
 
-def _cloud_call_args(nw, nwave, device, deck, surf, cloud_cs, cloud_f, f_patchy, want_parts,
-                     terms, out):
-    """What cloudy_transit_batch and cloudy_emission_batch share: outputs, the deck's tensors, the
-    pb_cloud_terms struct and the tensors that must outlive the launch."""
+def _cloud_args(prefix, nw, deck, surf, cloud_cs, cloud_f, f_patchy, terms, flux=None):
+    """What the cloudy flux and contribution wrappers share: the deck's tensors (deck[0] and
+    deck[surf]), the pb_cloud_terms struct, f_patchy and the tensors that must outlive the
+    launch; `prefix` opens the names in the error messages.  flux = (nwave, device, want_parts,
+    out): the outputs (spectrum, clear, cloudy) too, else None.
+    -> (deck itop, deck surface, terms by reference or None, f_patchy, outputs, keep-alive)."""
     for name, t, dtype in (('f_patchy', f_patchy, torch.float64),) + \
             (() if deck is None else (('deck itop', deck[0], torch.int32),
                                       ('deck surface', deck[surf], torch.float64))):
-        _check_walker_tensor(name, t, nw, dtype)
+        _check_walker_tensor(prefix + name, t, nw, dtype)
     keep = []
     if terms is None and cloud_cs is not None:
         if cloud_f is None or cloud_f.dim() != 3 or cloud_f.shape[0] != nw:
-            raise ValueError('cloud_cs needs cloud_f[nw, L, nr]')
+            raise ValueError(f'{prefix}cloud_cs needs cloud_f[nw, L, nr]')
         terms, keep = ct.cloud_terms(cloud_cs, cloud_f)
-    spectrum = out if out is not None else torch.empty((nw, nwave), dtype=torch.float64,
-                                                       device=device)
-    clear = torch.empty_like(spectrum) if want_parts else None
-    cloudy = torch.empty_like(spectrum) if want_parts else None
+    outs = None
+    if flux is not None:
+        nwave, device, want_parts, out = flux
+        spectrum = out if out is not None else torch.empty((nw, nwave), dtype=torch.float64,
+                                                           device=device)
+        outs = (spectrum, torch.empty_like(spectrum) if want_parts else None,
+                torch.empty_like(spectrum) if want_parts else None)
     ditop = None if deck is None else deck[0].contiguous()
     dsurf = None if deck is None else deck[surf].contiguous()
     fp = None if f_patchy is None else f_patchy.contiguous()
-    tail = (_ptr(ditop), _ptr(dsurf), None if terms is None else C.byref(terms), _ptr(fp),
-            _stream())
-    return spectrum, clear, cloudy, tail, (keep, ditop, dsurf, fp)
+    return (ditop, dsurf, None if terms is None else C.byref(terms), fp, outs,
+            (keep, terms, ditop, dsurf, fp))
+
+
+def _ray_path_args(raypath, nw, nrow):
+    """The ray paths of the two cloudy transit wrappers: raypath[nw, npath] or [1, npath] /
+    [npath] (shared), npath = nrow (nrow - 1) / 2 the packed triangle of nrow impact parameters
+    -> (whether the shape fits, npath, the C arguments (pointer or None, walker stride), the
+    tensor they point into)."""
+    path = (raypath if raypath.dim() == 2 else raypath.view(1, -1)).contiguous()
+    npath = (nrow * (nrow - 1)) // 2
+    fits = path.shape[0] in (1, nw) and path.shape[1] == npath
+    return fits, npath, (_ptr(path) if path.numel() else None,
+                         0 if path.shape[0] == 1 else path.shape[1]), path
 
 
 def cloudy_transit_batch(ec, raypath, radius, rstar, itop, maxdepth, deck=None, cloud_cs=None,
@@ -405,22 +429,21 @@ def cloudy_transit_batch(ec, raypath, radius, rstar, itop, maxdepth, deck=None, 
     columns are in that order, the spectra come in grid order (same bits).
     -> spectrum[nw, W], or (spectrum, clear, cloudy) with want_parts."""
     nw, nlayers, nwave = ec.shape
-    path = raypath if raypath.dim() == 2 else raypath.view(1, -1)
     rad = radius if radius.dim() == 2 else radius.view(1, -1)
-    nrow = nlayers - int(itop)
-    if rad.shape[1] != nlayers or rad.shape[0] not in (1, nw) or path.shape[0] not in (1, nw) or \
-            path.shape[1] != (nrow * (nrow - 1)) // 2:
+    fits, npath, pargs, path = _ray_path_args(raypath, nw, nlayers - int(itop))
+    if rad.shape[1] != nlayers or rad.shape[0] not in (1, nw) or not fits:
         raise ValueError(f'cloudy_transit_batch: radius[{nw} or 1, {nlayers}] and raypath[{nw} or '
-                         f'1, {(nrow * (nrow - 1)) // 2}] wanted, got {tuple(radius.shape)}, '
+                         f'1, {npath}] wanted, got {tuple(radius.shape)}, '
                          f'{tuple(raypath.shape)}')
-    spectrum, clear, cloudy, tail, keep = _cloud_call_args(
-        nw, nwave, ec.device, deck, 1, cloud_cs, cloud_f, f_patchy, want_parts, _terms, out)
-    path, rad = path.contiguous(), rad.contiguous()
-    call('pb_cloudy_transit_batch', _ptr(spectrum), _ptr(clear), _ptr(cloudy), _ptr(ec),
-         _ptr(path) if path.numel() else None, 0 if path.shape[0] == 1 else path.shape[1],
+    ditop, dsurf, terms, fp, (spectrum, clear, cloudy), keep = _cloud_args(
+        '', nw, deck, 1, cloud_cs, cloud_f, f_patchy, _terms,
+        flux=(nwave, ec.device, want_parts, out))
+    rad = rad.contiguous()
+    call('pb_cloudy_transit_batch', _ptr(spectrum), _ptr(clear), _ptr(cloudy), _ptr(ec), *pargs,
          _ptr(rad), 0 if rad.shape[0] == 1 else nlayers, _ptr(column), float(rstar), int(itop),
-         float(maxdepth), nlayers, nwave, nw, *tail)
-    del keep
+         float(maxdepth), nlayers, nwave, nw, _ptr(ditop), _ptr(dsurf), terms, _ptr(fp),
+         _stream())
+    del keep, path
     return (spectrum, clear, cloudy) if want_parts else spectrum
 
 
@@ -439,11 +462,13 @@ def cloudy_emission_batch(ec, intervals, wn, temps, mu, weights, itop, maxdepth,
         raise ValueError(f'cloudy_emission_batch: intervals[{nw}, {nlayers - 1}], temps[{nw}, '
                          f'{nlayers}], wn[{nwave}] wanted, got {tuple(intervals.shape)}, '
                          f'{tuple(temps.shape)}, {tuple(wn.shape)}')
-    flux, clear, cloudy, tail, keep = _cloud_call_args(
-        nw, nwave, ec.device, deck, 2, cloud_cs, cloud_f, f_patchy, want_parts, _terms, out)
+    ditop, dsurf, terms, fp, (flux, clear, cloudy), keep = _cloud_args(
+        '', nw, deck, 2, cloud_cs, cloud_f, f_patchy, _terms,
+        flux=(nwave, ec.device, want_parts, out))
     call('pb_cloudy_emission_batch', _ptr(flux), _ptr(clear), _ptr(cloudy), _ptr(ec),
          _ptr(intervals.contiguous()), _ptr(wn), _ptr(temps.contiguous()), _ptr(mu), _ptr(weights),
-         _ptr(column), len(mu), float(maxdepth), int(itop), nlayers, nwave, nw, *tail)
+         _ptr(column), len(mu), float(maxdepth), int(itop), nlayers, nwave, nw, _ptr(ditop),
+         _ptr(dsurf), terms, _ptr(fp), _stream())
     del keep
     return (flux, clear, cloudy) if want_parts else flux
 
@@ -451,24 +476,6 @@ def cloudy_emission_batch(ec, intervals, wn, temps, mu, weights, itop, maxdepth,
 # --------------------------------------------------------------------------
 # Band contribution functions for a batch with clouds (pb_contribution.hip)
 # --------------------------------------------------------------------------
-def _contribution_cloud_args(name, nw, deck, surf, cloud_cs, cloud_f, f_patchy, terms):
-    """The deck's tensors, the pb_cloud_terms struct and f_patchy of the two cloudy contribution
-    entries -> (deck itop, deck surface or None, terms or None, f_patchy, keep-alive)."""
-    for what, t, dtype in ((f'{name}: f_patchy', f_patchy, torch.float64),) + \
-            (() if deck is None else ((f'{name}: deck itop', deck[0], torch.int32),
-                                      (f'{name}: deck surface', deck[surf], torch.float64))):
-        _check_walker_tensor(what, t, nw, dtype)
-    keep = []
-    if terms is None and cloud_cs is not None:
-        if cloud_f is None or cloud_f.dim() != 3 or cloud_f.shape[0] != nw:
-            raise ValueError(f'{name}: cloud_cs needs cloud_f[nw, L, nr]')
-        terms, keep = ct.cloud_terms(cloud_cs, cloud_f)
-    ditop = None if deck is None else deck[0].contiguous()
-    dsurf = None if deck is None else deck[surf].contiguous()
-    fp = None if f_patchy is None else f_patchy.contiguous()
-    return ditop, dsurf, None if terms is None else C.byref(terms), fp, (keep, terms)
-
-
 def band_transmittance_cloudy_batch(ec, raypath, bands, itop, maxdepth, deck=None, cloud_cs=None,
                                     cloud_f=None, f_patchy=None, out=None, _terms=None):
     """Band transmittances of a batch in transit geometry WITH clouds (Pyrat.band_contribution,
@@ -489,22 +496,18 @@ def band_transmittance_cloudy_batch(ec, raypath, bands, itop, maxdepth, deck=Non
     -> [nw, L, nbands], every band divided by its maximum over the layers (one sample: NaN)."""
     name = 'band_transmittance_cloudy_batch'
     nw, nlayers, nwave = ec.shape
-    path = raypath if raypath.dim() == 2 else raypath.view(1, -1)
-    nrow = nlayers - int(itop)
-    if ec.dtype != torch.float64 or not ec.is_contiguous() or path.shape[0] not in (1, nw) or \
-            path.shape[1] != (nrow * (nrow - 1)) // 2:
+    fits, npath, pargs, path = _ray_path_args(raypath, nw, nlayers - int(itop))
+    if ec.dtype != torch.float64 or not ec.is_contiguous() or not fits:
         raise ValueError(f'{name}: contiguous float64 ec[nw, L, W] and raypath[{nw} or 1, '
-                         f'{(nrow * (nrow - 1)) // 2}] wanted, got {ec.dtype} {tuple(ec.shape)}, '
+                         f'{npath}] wanted, got {ec.dtype} {tuple(ec.shape)}, '
                          f'{tuple(raypath.shape)}')
-    ditop, _, terms, fp, keep = _contribution_cloud_args(name, nw, deck, 1, cloud_cs, cloud_f,
-                                                         f_patchy, _terms)
+    ditop, _, terms, fp, _, keep = _cloud_args(f'{name}: ', nw, deck, 1, cloud_cs, cloud_f,
+                                               f_patchy, _terms)
     out, work, bargs = _contribution_buffers(name, bands, nw, nlayers, nwave, ec.device, out)
-    path = path.contiguous()
-    call('pb_band_transmittance_cloudy_batch', _ptr(out), _ptr(ec),
-         _ptr(path) if path.numel() else None, 0 if path.shape[0] == 1 else path.shape[1],
-         _ptr(bands.wn), *bargs, int(itop), float(maxdepth), nlayers, nwave, bands.nbands, nw,
-         _ptr(ditop), terms, _ptr(fp), _ptr(work), _stream())
-    del keep
+    call('pb_band_transmittance_cloudy_batch', _ptr(out), _ptr(ec), *pargs, _ptr(bands.wn),
+         *bargs, int(itop), float(maxdepth), nlayers, nwave, bands.nbands, nw, _ptr(ditop), terms,
+         _ptr(fp), _ptr(work), _stream())
+    del keep, path
     return out
 
 
@@ -520,19 +523,9 @@ def band_contribution_emission_cloudy_batch(ec, intervals, temps, bands, pressur
     that layer radiates at the deck's tsurf.  -> [nw, L, nbands]."""
     name = 'band_contribution_emission_cloudy_batch'
     nw, nlayers, nwave = ec.shape
-    if ec.dtype != torch.float64 or not ec.is_contiguous() or \
-            tuple(intervals.shape) != (nw, nlayers - 1) or tuple(temps.shape) != (nw, nlayers):
-        raise ValueError(f'{name}: contiguous float64 ec[nw, L, W], intervals[{nw}, '
-                         f'{nlayers - 1}] and temps[{nw}, {nlayers}] wanted, got '
-                         f'{tuple(ec.shape)}, {tuple(intervals.shape)}, {tuple(temps.shape)}')
-    if dlogp is None:
-        dlogp = contribution_dlogp(pressure, nlayers)
-    elif not isinstance(dlogp, torch.Tensor) or not dlogp.is_cuda or \
-            dlogp.dtype != torch.float64 or tuple(dlogp.shape) != (nlayers - 1,):
-        raise ValueError(f'{name}: dlogp must be a float64 device tensor of shape '
-                         f'({nlayers - 1},)')
-    ditop, dsurf, terms, _, keep = _contribution_cloud_args(name, nw, deck, 2, cloud_cs, cloud_f,
-                                                            None, _terms)
+    dlogp = _emission_contribution_args(name, ec, intervals, temps, pressure, dlogp)
+    ditop, dsurf, terms, _, _, keep = _cloud_args(f'{name}: ', nw, deck, 2, cloud_cs, cloud_f,
+                                                  None, _terms)
     out, work, bargs = _contribution_buffers(name, bands, nw, nlayers, nwave, ec.device, out)
     call('pb_band_contribution_emission_cloudy_batch', _ptr(out), _ptr(ec),
          _ptr(intervals.contiguous()), _ptr(dlogp.contiguous()), _ptr(bands.wn),

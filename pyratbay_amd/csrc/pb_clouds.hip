@@ -10,14 +10,16 @@
 // its ec, and ec + ec_cloud is never stored (a second ec[nw, L, W] is 4.1 GB per 64 walkers at
 // C5's shape):
 //   * ec_cloud is a sum of rank-1 terms cs_m[sample] f_m[walker, layer] (Lecavelier, CCSgray): a
-//     thread keeps the cs_m of its sample in registers and adds sum_m cs_m f_m as it walks, the
-//     f_m being wave-uniform scalar loads (kTwo: two running sums side by side);
+//     thread keeps the cs_m of its sample in registers and adds sum_m cs_m f_m as it walks
+//     (pb::CloudWalk; kTwo: two running sums side by side);
 //   * with the deck as the only cloud-type model ec_cloud is zero: the optical depths of the two
 //     columns are equal row for row down to the deck, so one running sum serves both and the
 //     cloudy column is closed on the way (at its crossing of maxdepth if that comes first, else at
 //     the deck).
 // Per column the arithmetic does not depend on where the column sits: grid order and any column
-// order give the same bits.
+// order give the same bits.  The walk itself -- the cloudy column, the patchy mix, the transit
+// blocks of impact parameters -- is stated in pb_cloud_walk.h, for these kernels and for the band
+// contribution kernels (pb_contribution.hip).
 //
 //   k_deck_state       (deck_itop, rsurf, tsurf) of every walker from its log10 pressure
 //   k_cloud_plan/rows  the rank-1 factors of the cloud-type models from the walkers' parameters
@@ -25,6 +27,7 @@
 //   k_cloudy_emission  ec -> emission flux     f cloudy + (1 - f) clear
 #include <algorithm>
 
+#include "pb_cloud_walk.h"
 #include "pb_common.h"
 #include "pb_planck.h"
 
@@ -32,20 +35,15 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kMaxMu = 16;
-constexpr int kMaxCloud = PB_CLOUD_MAX;
+constexpr int kMaxCloud = PB_CLOUD_MAX;          // (the plan's; the terms' cap: pb_cloud_walk.h)
 constexpr double kBar = 1e6, kBoltz = 1.380649e-16;   // the continuum models' units (lecavelier.py)
 
-typedef const double __attribute__((address_space(4))) *cdbl_t;
-
-using pb::uniform_i32;
+using pb::cdbl_t;
+using pb::CloudWalk;
+using pb::uniform_f64;
 using pb::planck_factor;
 using pb::planck_q;
 using pb::planck_terms;
-
-__device__ __forceinline__ double uniform_f64(const double *p)
-{
-    return *((cdbl_t)(unsigned long long)p);
-}
 
 // ---------------------------------------------------------------------------
 // Deck.calc_extinction_coefficient per walker (gray.py:129-150): itop by the reference's rule,
@@ -172,42 +170,13 @@ struct CloudArgs {
     pb_cloud_terms cl;
 };
 
-// this thread's cloud cross sections (a gray model: 1)
-__device__ __forceinline__ void cloud_init(double (&cs)[kMaxCloud], const CloudArgs &a, int w,
-                                           int col)
-{
-#pragma unroll
-    for (int m = 0; m < kMaxCloud; m++) {
-        cs[m] = 0.0;
-        if (m < a.cl.nr)
-            cs[m] = a.cl.cs_d[m] ? a.cl.cs_d[m][(int64_t)w * a.cl.cs_stride[m] + col] : 1.0;
-    }
-}
-
-// ec_cloud of (walker, layer) at this thread's sample: the models' terms added in their order
-__device__ __forceinline__ double cloud_at(const double (&cs)[kMaxCloud], const CloudArgs &a,
-                                           int w, int layer)
-{
-    const cdbl_t f =
-        (cdbl_t)(unsigned long long)(a.cl.f_d + ((int64_t)w * a.nlayers + layer) * a.cl.nr);
-    double sum = 0.0;
-#pragma unroll
-    for (int m = 0; m < kMaxCloud; m++)
-        if (m < a.cl.nr)
-            sum += cs[m] * f[m];
-    return sum;
-}
-
 // spectrum = f cloudy + (1 - f) clear (pyrat/spectrum.py:362, 384), scattered to grid order
 __device__ __forceinline__ void cloud_store(const CloudArgs &a, int w, int col, double clear,
                                             double cloudy)
 {
     double out = cloudy;
-    if (a.f_patchy) {
-        double f = uniform_f64(a.f_patchy + w);
-        f = f < 0.0 ? 0.0 : (f > 1.0 ? 1.0 : f);          // (NaN stays NaN)
-        out = f * cloudy + (1.0 - f) * clear;
-    }
+    if (a.f_patchy)
+        out = pb::patchy_mix(pb::patchy_fraction(a.f_patchy, w), cloudy, clear);
     const int dst = a.column ? a.column[col] : col;
     if (dst < 0 || dst >= a.nwave)
         return;
@@ -226,13 +195,8 @@ __device__ __forceinline__ void cloud_store(const CloudArgs &a, int w, int col, 
 // block staged in LDS ([segment][row], zero where segment >= row).  kTwo: ec_cloud != 0, the
 // cloudy column has optical depths of its own; else the rows of one sum serve both columns.
 // Row r of the cloudy column exists for r < deck_itop + 1 - itop; its last interval ends at the
-// deck's radius (deck_integrand, as in k_transit_fused).
-// Infinite opacity: the fma over the rows of a block is predicate-free, and the staged zeros of
-// the rows ABOVE a layer would meet an infinite sum of that layer as 0 * inf = NaN, where the
-// reference never touches the layer for those rows.  The sum of a segment's two layers is
-// therefore capped at the largest finite double (finite_sum): 0 * it = 0 for the rows above, and
-// the rows that do include the layer still get an optical depth beyond any maxdepth whose
-// exp(-depth) is 0, as with +inf.  Every finite sum keeps its bits; NaN stays NaN.
+// deck's radius (deck_integrand, as in k_transit_fused).  The staging and the rows' optical
+// depths are pb::stage_path_block / pb::depth_block.
 // ---------------------------------------------------------------------------
 struct TransitGeom {
     const double *raypath, *radius;
@@ -241,11 +205,6 @@ struct TransitGeom {
 };
 
 using pb::deck_integrand;         // (pb_common.h)
-
-__device__ __forceinline__ double finite_sum(double s)
-{
-    return s > 0x1.fffffffffffffp+1023 ? 0x1.fffffffffffffp+1023 : s;
-}
 
 template <int kRows, bool kTwo>
 __global__ __launch_bounds__(kBlock) void k_cloudy_transit(CloudArgs a, TransitGeom g)
@@ -260,16 +219,16 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_transit(CloudArgs a, TransitG
     const bool deck = a.deck_itop != nullptr;
     const bool need_clear = a.f_patchy || a.clear;
     // wave-uniform: the walker's deck
-    const int dk = deck ? min(max(uniform_i32(a.deck_itop + w), 0), nlayers - 1) : -1;
+    const int dk = deck ? pb::deck_layer(a.deck_itop, w, nlayers) : -1;
     const double rsurf = deck ? uniform_f64(a.deck_surf + w) : 0.0;
     const int nimp_c = (deck ? dk + 1 : nlayers) - itop;  // rows of the cloudy column (<= 0: none)
     const int nimp_l = need_clear ? nlayers - itop : 0;
     const int nimp = max(nimp_c, nimp_l);
     const int deck_row = deck ? dk - itop : -1;
     const double *src = a.ec + ((int64_t)w * nlayers + itop) * nwave + (active ? col : 0);
-    double cs[kMaxCloud];
+    CloudWalk cloud;
     if (kTwo)
-        cloud_init(cs, a, w, active ? col : 0);
+        cloud.init(a.cl, w, active ? col : 0, nlayers);
 
     bool open_l = nimp_l > 0, open_c = nimp_c > 0;
     double acc_l = 0.0, acc_c = 0.0, fprev_l = 0.0, fprev_c = 0.0;
@@ -278,47 +237,12 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_transit(CloudArgs a, TransitG
         if (__syncthreads_count(active && (open_l || open_c)) == 0)
             break;
         const int rlast = min(rb + kRows, nimp) - 1;
-        const int nseg = max(rlast, 0);
-        for (int e = threadIdx.x; e < nseg * kRows; e += kBlock) {
-            const int i = e / kRows, k = e % kRows;
-            const int r = rb + k;
-            s_path[e] = (r <= rlast && i < r) ? path[((int64_t)r * (r - 1)) / 2 + i] : 0.0;
-        }
+        pb::stage_path_block<kRows, kBlock>(s_path, path, rb, rlast);
         __syncthreads();
         if (!active || !(open_l || open_c))
             continue;
         double tau[kRows], tau_c[kTwo ? kRows : 1];
-#pragma unroll
-        for (int k = 0; k < kRows; k++)
-            tau[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < (kTwo ? kRows : 1); k++)
-            tau_c[k] = 0.0;
-        if (nseg > 0) {
-            double prev = src[0];
-            double prev_c = kTwo ? prev + cloud_at(cs, a, w, itop) : 0.0;
-#pragma unroll 2
-            for (int i = 0; i < nseg; i++) {
-                const double next = src[(int64_t)(i + 1) * nwave];
-                const double s = finite_sum(next + prev);
-                prev = next;
-                const double *pk = s_path + i * kRows;      // LDS broadcast reads
-                if constexpr (kTwo) {
-                    const double next_c = next + cloud_at(cs, a, w, itop + i + 1);
-                    const double s_c = finite_sum(next_c + prev_c);
-                    prev_c = next_c;
-#pragma unroll
-                    for (int k = 0; k < kRows; k++) {
-                        tau[k] = fma(pk[k], s, tau[k]);
-                        tau_c[k] = fma(pk[k], s_c, tau_c[k]);
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < kRows; k++)
-                        tau[k] = fma(pk[k], s, tau[k]);
-                }
-            }
-        }
+        pb::depth_block<kRows, kTwo>(tau, tau_c, src, nwave, rlast, s_path, cloud, itop);
 #pragma unroll
         for (int k = 0; k < kRows; k++) {
             const int r = rb + k;
@@ -402,7 +326,7 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_emission(CloudArgs a, Emissio
     const int nlayers = a.nlayers, nwave = a.nwave, rtop = a.itop;
     const bool deck = a.deck_itop != nullptr;
     const bool need_clear = a.f_patchy || a.clear;
-    const int dk = deck ? min(max(uniform_i32(a.deck_itop + w), 0), nlayers - 1) : -1;
+    const int dk = deck ? pb::deck_layer(a.deck_itop, w, nlayers) : -1;
     planck_terms(s_kt, g.temp + (int64_t)w * nlayers, nlayers, g.mu, g.nmu);
     if (deck) {
         if (threadIdx.x == 0)
@@ -417,9 +341,9 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_emission(CloudArgs a, Emissio
     const double *h = g.intervals + (int64_t)w * (nlayers - 1);
     const double wn = g.wn[j];
     const double factor = planck_factor(wn);
-    double cs[kMaxCloud];
+    CloudWalk cloud;
     if (kTwo)
-        cloud_init(cs, a, w, j);
+        cloud.init(a.cl, w, j, nlayers);
     // the sums of the clear column (kTwo) or of both (one optical depth down to the deck)
     double acc[MU], eprev[MU], acc_c[kTwo ? MU : 1], eprev_c[kTwo ? MU : 1];
 #pragma unroll
@@ -434,7 +358,7 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_emission(CloudArgs a, Emissio
     double bprev = planck_q(factor, wn, s_kt[rtop], s_kt[nlayers + rtop]);
     double depth = 0.0, depth_c = 0.0;
     double prev = ec[(int64_t)rtop * nwave];
-    double prev_c = kTwo ? prev + cloud_at(cs, a, w, rtop) : 0.0;
+    double prev_c = kTwo ? prev + cloud.at(rtop) : 0.0;
     const int kend = deck ? dk : nlayers - 1;                 // the cloudy column's deepest layer
     bool open_l = need_clear, open_c = true;
     double total_l = 0.0, total_c = 0.0;
@@ -449,7 +373,7 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_emission(CloudArgs a, Emissio
         const double bnext = planck_q(factor, wn, s_kt[k], s_kt[nlayers + k]);
         const double bsum = bnext + bprev;
         if constexpr (kTwo) {
-            const double cur_c = cur + cloud_at(cs, a, w, k);
+            const double cur_c = cur + cloud.at(k);
             if (open_c) {
                 depth_c += 0.5 * h[k - 1] * (cur_c + prev_c);
                 const double dq = pb::clamp_depth(depth_c);
@@ -508,17 +432,7 @@ __global__ __launch_bounds__(kBlock) void k_cloudy_emission(CloudArgs a, Emissio
     cloud_store(a, w, j, total_l, total_c);
 }
 
-int check_cloud(const pb_cloud_terms *cloud, const char *who)
-{
-    if (!cloud)
-        return PB_OK;
-    PB_REQUIRE(cloud->nr >= 0 && cloud->nr <= kMaxCloud, "%s: 0 ... %d cloud terms (got %d)", who,
-               kMaxCloud, cloud->nr);
-    PB_REQUIRE(cloud->nr == 0 || cloud->f_d, "%s: null cloud factors", who);
-    for (int m = 0; m < cloud->nr; m++)
-        PB_REQUIRE(cloud->cs_stride[m] >= 0, "%s: negative cross-section stride", who);
-    return PB_OK;
-}
+using pb::check_cloud;
 
 }  // namespace
 

@@ -213,6 +213,20 @@ __device__ __forceinline__ int uniform_i32(const int32_t *p)
     typedef const int32_t __attribute__((address_space(4))) *cptr;
     return *((cptr)(unsigned long long)p);
 }
+typedef const double __attribute__((address_space(4))) *cdbl_t;
+__device__ __forceinline__ double uniform_f64(const double *p)
+{
+    return *((cdbl_t)(unsigned long long)p);
+}
+
+// the sum over the wavefront, the same bits in every lane
+template <int kWave = 64>
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int off = kWave / 2; off > 0; off >>= 1)
+        v += __shfl_xor(v, off, kWave);
+    return v;
+}
 
 // is layer k of the samples [s0, s1) wanted?  (wave-uniform)
 __device__ __forceinline__ bool layer_wanted(const TileLimit &lim, int k, int s0, int s1, int nwave)

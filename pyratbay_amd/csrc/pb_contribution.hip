@@ -11,9 +11,11 @@
 //   k_band_cf_emission<true>      the same two walks on ec + ec_cloud down to the walker's deck,
 //                                 whose temperature takes the deck layer's place in B
 //   k_band_transmittance_cloudy   transmittance of the clear and the cloudy column + band_cf's
-//                                 integral FROM ec: k_cloudy_transit's walk (pb_clouds.hip), no
-//                                 depth stored for either column
+//                                 integral FROM ec, no depth stored for either column
+// The cloudy column, the patchy mix and the transit walk over blocks of impact parameters are the
+// flux kernels' (pb_clouds.hip): both take them from pb_cloud_walk.h.
 // FP64, no atomics, every sum in a fixed order: two runs give the same bits.
+#include "pb_cloud_walk.h"
 #include "pb_common.h"
 #include "pb_planck.h"
 
@@ -33,58 +35,14 @@ constexpr int kCloudyRows = 16;
 constexpr int kMaxLayersCloudyTransit = PB_BAND_CLOUDY_MAX_LAYERS;
 static_assert((size_t)(kWaves + kCloudyRows) * kMaxLayersCloudyTransit * sizeof(double) <=
                   64 * 1024, "the cloudy transmittance kernel's LDS");
-constexpr int kMaxCloud = PB_CLOUD_MAX;
 
 using pb::planck_factor;
 using pb::planck_q;
 using pb::planck_terms;
 
-typedef const double __attribute__((address_space(4))) *cdbl_t;
-
-__device__ __forceinline__ double uniform_f64(const double *p)
-{
-    return *((cdbl_t)(unsigned long long)p);
-}
-
-// ec_cloud = sum_m cs_m[sample] f_m[walker, layer] at this thread's sample (pb_cloud_terms): the
-// cross sections in registers, the factors wave-uniform scalar loads, the models' terms added in
-// their order -- pb_clouds.hip's cloud_init / cloud_at, so that the column is the one the flux
-// kernels walk
-struct CloudWalk {
-    double cs[kMaxCloud];
-    const double *f;            // this walker's factors [L][nr]
-    int nr;
-
-    __device__ __forceinline__ void init(const pb_cloud_terms &cl, int w, int64_t col, int nlayers)
-    {
-        nr = cl.nr;
-        f = cl.f_d + (int64_t)w * nlayers * cl.nr;
-#pragma unroll
-        for (int m = 0; m < kMaxCloud; m++) {
-            cs[m] = 0.0;
-            if (m < cl.nr)
-                cs[m] = cl.cs_d[m] ? cl.cs_d[m][(int64_t)w * cl.cs_stride[m] + col] : 1.0;
-        }
-    }
-    __device__ __forceinline__ double at(int layer) const
-    {
-        const cdbl_t fl = (cdbl_t)(unsigned long long)(f + (int64_t)layer * nr);
-        double sum = 0.0;
-#pragma unroll
-        for (int m = 0; m < kMaxCloud; m++)
-            if (m < nr)
-                sum += cs[m] * fl[m];
-        return sum;
-    }
-};
-
-// the sum over the wavefront, the same bits in every lane (pb_radeq.hip's)
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int off = kWave / 2; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, kWave);
-    return v;
-}
+using pb::CloudWalk;
+using pb::uniform_f64;
+using pb::wave_sum;
 
 // np.trapezoid as a weight per sample: half of each neighbouring gap INSIDE the band and the grid
 // (one-sided at the band's ends and where the grid clips the band, 0 for one retained sample); wn
@@ -239,7 +197,7 @@ __global__ __launch_bounds__(kBlock) void k_band_cf_emission(
     EmissionColumn<kCloudy> c;
     if constexpr (kCloudy) {
         if (clouds.deck_itop) {                         // (wave-uniform: the walker's deck)
-            const int dk = min(max(pb::uniform_i32(clouds.deck_itop + wk), 0), nlayers - 1);
+            const int dk = pb::deck_layer(clouds.deck_itop, wk, nlayers);
             ibottom = dk + 1;
             if (threadIdx.x == 0)
                 pb::sane_divisor(pb::kKB * uniform_f64(clouds.deck_tsurf + wk), s_kt[dk],
@@ -333,10 +291,10 @@ __global__ __launch_bounds__(kBlock) void k_band_transmittance(
 //   T[r]  = 1 above itop, exp(-depth[r]) for itop <= r < ideep, 0 from ideep on
 // and the layer's value is f T_cloudy + (1 - f) T_clear (f_patchy NULL: T_cloudy, and the clear
 // column is not walked), times response x trapezoid weight.  The deck's radius does not enter.
-// The walk is k_cloudy_transit's (pb_clouds.hip): a thread owns a column, the impact parameters are
-// taken kCloudyRows at a time with the block's ray-path segments staged in LDS ([segment][row],
-// zero where segment >= row), the sums capped at the largest finite double (finite_sum there);
-// kTwo: ec_cloud != 0, else one running sum serves both columns.  Row by row the wavefront's sum
+// The walk is pb_cloud_walk.h's: a thread owns a column, the impact parameters are taken
+// kCloudyRows at a time with the block's ray-path segments staged in LDS (stage_path_block), the
+// rows' optical depths formed by depth_block; kTwo: ec_cloud != 0, else one running sum serves
+// both columns.  Row by row the wavefront's sum
 // goes into the LDS row store_parts reads; the rows after every column of the workgroup has closed
 // are written too (a closed row is f 0 + (1 - f) 0: 0, or NaN with f).  (Reducing the 16 rows of
 // a block together -- 17 shuffles instead of 96 -- was measured SLOWER, 6.9 against 5.0 ms at
@@ -356,11 +314,6 @@ struct CloudyBandArgs {
     pb_cloud_terms cl;
 };
 
-__device__ __forceinline__ double finite_sum(double s)
-{
-    return s > 0x1.fffffffffffffp+1023 ? 0x1.fffffffffffffp+1023 : s;
-}
-
 template <bool kTwo>
 __global__ __launch_bounds__(kBlock) void k_band_transmittance_cloudy(CloudyBandArgs a)
 {
@@ -375,19 +328,14 @@ __global__ __launch_bounds__(kBlock) void k_band_transmittance_cloudy(CloudyBand
     const double *path = a.raypath + (int64_t)wk * a.path_stride;
     const bool need_clear = a.f_patchy != nullptr;
     // wave-uniform: the walker's deck and cloudy fraction
-    const int dk = a.deck_itop ? min(max(pb::uniform_i32(a.deck_itop + wk), 0), nlayers - 1)
-                               : nlayers - 1;
+    const int dk = a.deck_itop ? pb::deck_layer(a.deck_itop, wk, nlayers) : nlayers - 1;
     const int nrow = nlayers - itop;
     const int nimp_c = dk + 1 - itop;                   // rows of the cloudy column (<= 0: none)
     const int nimp_l = need_clear ? nrow : 0;
     const int nimp = max(max(nimp_c, nimp_l), 0);
-    double f = 0.0;
-    if (need_clear) {
-        f = uniform_f64(a.f_patchy + wk);
-        f = f < 0.0 ? 0.0 : (f > 1.0 ? 1.0 : f);        // (cloud_store's clamp: NaN stays NaN)
-    }
+    const double f = need_clear ? pb::patchy_fraction(a.f_patchy, wk) : 0.0;
     const auto mix = [&](double cloudy, double clear) {
-        return need_clear ? f * cloudy + (1.0 - f) * clear : cloudy;
+        return need_clear ? pb::patchy_mix(f, cloudy, clear) : cloudy;
     };
     const double scale = s.live ? a.response[a.response_offset[blockIdx.y] + s.i] *
                                       band_weight(a.wn, s.g, s.i, s.count, nwave)
@@ -413,45 +361,11 @@ __global__ __launch_bounds__(kBlock) void k_band_transmittance_cloudy(CloudyBand
         if (__syncthreads_count(open_l || open_c) == 0)
             break;
         const int rlast = min(rb + kRows, nimp) - 1;
-        const int nseg = rlast;
-        for (int e = threadIdx.x; e < nseg * kRows; e += kBlock) {
-            const int i = e / kRows, k = e % kRows;
-            const int r = rb + k;
-            s_path[e] = (r <= rlast && i < r) ? path[((int64_t)r * (r - 1)) / 2 + i] : 0.0;
-        }
+        pb::stage_path_block<kRows, kBlock>(s_path, path, rb, rlast);
         __syncthreads();
-        double tau[kRows], tau_c[kTwo ? kRows : 1];
-#pragma unroll
-        for (int k = 0; k < kRows; k++)
-            tau[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < (kTwo ? kRows : 1); k++)
-            tau_c[k] = 0.0;
-        if ((open_l || open_c) && nseg > 0) {
-            double prev = src[0];
-            double prev_c = kTwo ? prev + cloud.at(itop) : 0.0;
-#pragma unroll 2
-            for (int i = 0; i < nseg; i++) {
-                const double next = src[(int64_t)(i + 1) * nwave];
-                const double sm = finite_sum(next + prev);
-                prev = next;
-                const double *pk = s_path + i * kRows;      // LDS broadcast reads
-                if constexpr (kTwo) {
-                    const double next_c = next + cloud.at(itop + i + 1);
-                    const double sm_c = finite_sum(next_c + prev_c);
-                    prev_c = next_c;
-#pragma unroll
-                    for (int k = 0; k < kRows; k++) {
-                        tau[k] = fma(pk[k], sm, tau[k]);
-                        tau_c[k] = fma(pk[k], sm_c, tau_c[k]);
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < kRows; k++)
-                        tau[k] = fma(pk[k], sm, tau[k]);
-                }
-            }
-        }
+        double tau[kRows] = {}, tau_c[kTwo ? kRows : 1] = {};   // (both columns closed: no walk)
+        if (open_l || open_c)
+            pb::depth_block<kRows, kTwo>(tau, tau_c, src, nwave, rlast, s_path, cloud, itop);
         // (every lane of the wavefront takes every row: the sums are wave-wide)
 #pragma unroll
         for (int k = 0; k < kRows; k++) {
@@ -538,6 +452,35 @@ __global__ __launch_bounds__(kBlock) void k_band_cf_finish(double *__restrict__ 
     }
 }
 
+// What the four entry points refuse alike, in the order they refuse it: the sizes, the layer cap,
+// itop, ibottom (an entry without one passes 0), 65535 bands / walkers; then what the entry checks
+// on its own (`own`); then -- unless there is nothing to do: *nchunks = -1 -- the null pointers
+// (`pointers`: the entry's list) and the work buffer.
+template <class Own>
+int check_band_call(const char *who, int min_layers, int max_layers, int itop, int ibottom,
+                    int nlayers, int nwave, int nbands, int nwalkers, int max_band_count,
+                    bool pointers, const double *work_d, int *nchunks, Own own)
+{
+    *nchunks = -1;
+    PB_REQUIRE(nlayers >= min_layers && nwave >= 1 && nbands >= 0 && nwalkers >= 0 &&
+                   max_band_count >= 0,
+               "%s: bad sizes%s", who, min_layers == 2 ? " (nlayers >= 2, nwave >= 1)" : "");
+    PB_REQUIRE(nlayers <= max_layers, "%s: %d layers, at most %d fit in the LDS of a workgroup",
+               who, nlayers, max_layers);
+    PB_REQUIRE(itop >= 0 && itop < nlayers, "%s: itop out of range", who);
+    PB_REQUIRE(ibottom <= nlayers, "%s: ibottom > nlayers", who);
+    PB_REQUIRE(nbands <= 65535 && nwalkers <= 65535,
+               "%s: at most 65535 bands and walkers per call", who);
+    if (int rc = own())
+        return rc;
+    if (nbands == 0 || nwalkers == 0)
+        return PB_OK;
+    PB_REQUIRE(pointers, "%s: null pointer", who);
+    *nchunks = pb::div_up(max_band_count, kBlock);
+    PB_REQUIRE(*nchunks == 0 || work_d, "%s: null work buffer", who);
+    return PB_OK;
+}
+
 int finish(double *out_d, const double *work_d, const int32_t *band_start_d,
            const int32_t *band_count_d, int nbands, int nchunks, int nlayers, int nwave,
            int nwalkers, void *stream)
@@ -548,17 +491,46 @@ int finish(double *out_d, const double *work_d, const int32_t *band_start_d,
     return PB_OK;
 }
 
-// pb_clouds.hip's check of a pb_cloud_terms
-int check_cloud(const pb_cloud_terms *cloud, const char *who)
+// The two emission entries: kCloudy takes the deck's pointers (both or neither) and the cloud
+// terms (or null).  Two instantiations, since the clear one needs 45 VGPRs against 67.
+template <bool kCloudy>
+int band_cf_emission(const char *who, double *out_d, const double *ec_d, const double *intervals_d,
+                     const double *dlogp_d, const double *wn_d, const double *temps_d,
+                     const int32_t *band_start_d, const int32_t *band_count_d,
+                     const double *response_d, const int64_t *response_offset_d,
+                     int max_band_count, double maxdepth, int itop, int ibottom, int nlayers,
+                     int nwave, int nbands, int nwalkers, const int32_t *deck_itop_d,
+                     const double *deck_tsurf_d, const pb_cloud_terms *cloud, double *work_d,
+                     void *stream)
 {
-    if (!cloud)
-        return PB_OK;
-    PB_REQUIRE(cloud->nr >= 0 && cloud->nr <= kMaxCloud, "%s: 0 ... %d cloud terms (got %d)", who,
-               kMaxCloud, cloud->nr);
-    PB_REQUIRE(cloud->nr == 0 || cloud->f_d, "%s: null cloud factors", who);
-    for (int m = 0; m < cloud->nr; m++)
-        PB_REQUIRE(cloud->cs_stride[m] >= 0, "%s: negative cross-section stride", who);
-    return PB_OK;
+    int nchunks;
+    const int rc = check_band_call(
+        who, 2, kMaxLayersEmission, itop, ibottom, nlayers, nwave, nbands, nwalkers,
+        max_band_count,
+        out_d && ec_d && intervals_d && dlogp_d && wn_d && temps_d && band_start_d &&
+            band_count_d && response_d && response_offset_d,
+        work_d, &nchunks, [&]() -> int {
+            if (!kCloudy)
+                return PB_OK;
+            PB_REQUIRE(!deck_itop_d == !deck_tsurf_d,
+                       "%s: deck_itop_d and deck_tsurf_d go together", who);
+            return pb::check_cloud(cloud, who);
+        });
+    if (rc || nchunks < 0)
+        return rc;
+    if (nchunks > 0) {
+        EmissionClouds clouds{deck_itop_d, deck_tsurf_d, {}};
+        if (cloud && cloud->nr > 0)
+            clouds.cl = *cloud;
+        const size_t lds = ((size_t)(4 + kWaves) * nlayers - 2) * sizeof(double);
+        k_band_cf_emission<kCloudy>
+            <<<dim3(nchunks, nbands, nwalkers), kBlock, lds, pb::as_stream(stream)>>>(
+                work_d, ec_d, intervals_d, dlogp_d, wn_d, temps_d, band_start_d, band_count_d,
+                response_d, response_offset_d, maxdepth, itop, ibottom, nlayers, nwave, clouds);
+        PB_LAUNCH_CHECK();
+    }
+    return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,
+                  nwalkers, stream);
 }
 
 }  // namespace
@@ -583,33 +555,11 @@ int pb_band_contribution_emission_batch(double *out_d, const double *ec_d,
                                         int nwave, int nbands, int nwalkers, double *work_d,
                                         void *stream)
 {
-    PB_REQUIRE(nlayers >= 2 && nwave >= 1 && nbands >= 0 && nwalkers >= 0 && max_band_count >= 0,
-               "pb_band_contribution_emission_batch: bad sizes (nlayers >= 2, nwave >= 1)");
-    PB_REQUIRE(nlayers <= kMaxLayersEmission,
-               "pb_band_contribution_emission_batch: %d layers, at most %d fit in the LDS of a "
-               "workgroup", nlayers, kMaxLayersEmission);
-    PB_REQUIRE(itop >= 0 && itop < nlayers, "pb_band_contribution_emission_batch: itop out of range");
-    PB_REQUIRE(ibottom <= nlayers, "pb_band_contribution_emission_batch: ibottom > nlayers");
-    PB_REQUIRE(nbands <= 65535 && nwalkers <= 65535,
-               "pb_band_contribution_emission_batch: at most 65535 bands and walkers per call");
-    if (nbands == 0 || nwalkers == 0)
-        return PB_OK;
-    PB_REQUIRE(out_d && ec_d && intervals_d && dlogp_d && wn_d && temps_d && band_start_d &&
-                   band_count_d && response_d && response_offset_d,
-               "pb_band_contribution_emission_batch: null pointer");
-    const int nchunks = pb::div_up(max_band_count, kBlock);
-    PB_REQUIRE(nchunks == 0 || work_d, "pb_band_contribution_emission_batch: null work buffer");
-    if (nchunks > 0) {
-        const size_t lds = ((size_t)(4 + kWaves) * nlayers - 2) * sizeof(double);
-        k_band_cf_emission<false>
-            <<<dim3(nchunks, nbands, nwalkers), kBlock, lds, pb::as_stream(stream)>>>(
-                work_d, ec_d, intervals_d, dlogp_d, wn_d, temps_d, band_start_d, band_count_d,
-                response_d, response_offset_d, maxdepth, itop, ibottom, nlayers, nwave,
-                EmissionClouds{});
-        PB_LAUNCH_CHECK();
-    }
-    return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,
-                  nwalkers, stream);
+    return band_cf_emission<false>("pb_band_contribution_emission_batch", out_d, ec_d, intervals_d,
+                                   dlogp_d, wn_d, temps_d, band_start_d, band_count_d, response_d,
+                                   response_offset_d, max_band_count, maxdepth, itop, ibottom,
+                                   nlayers, nwave, nbands, nwalkers, nullptr, nullptr, nullptr,
+                                   work_d, stream);
 }
 
 int pb_band_transmittance_batch(double *out_d, const double *depth_d, const int32_t *ideep_d,
@@ -619,21 +569,15 @@ int pb_band_transmittance_batch(double *out_d, const double *depth_d, const int3
                                 int nlayers, int nwave, int nbands, int nwalkers, double *work_d,
                                 void *stream)
 {
-    PB_REQUIRE(nlayers >= 1 && nwave >= 1 && nbands >= 0 && nwalkers >= 0 && max_band_count >= 0,
-               "pb_band_transmittance_batch: bad sizes");
-    PB_REQUIRE(nlayers <= kMaxLayersTransit,
-               "pb_band_transmittance_batch: %d layers, at most %d fit in the LDS of a workgroup",
-               nlayers, kMaxLayersTransit);
-    PB_REQUIRE(itop >= 0 && itop < nlayers, "pb_band_transmittance_batch: itop out of range");
-    PB_REQUIRE(nbands <= 65535 && nwalkers <= 65535,
-               "pb_band_transmittance_batch: at most 65535 bands and walkers per call");
-    if (nbands == 0 || nwalkers == 0)
-        return PB_OK;
-    PB_REQUIRE(out_d && depth_d && ideep_d && wn_d && band_start_d && band_count_d && response_d &&
-                   response_offset_d,
-               "pb_band_transmittance_batch: null pointer");
-    const int nchunks = pb::div_up(max_band_count, kBlock);
-    PB_REQUIRE(nchunks == 0 || work_d, "pb_band_transmittance_batch: null work buffer");
+    const char *who = "pb_band_transmittance_batch";
+    int nchunks;
+    const int rc = check_band_call(
+        who, 1, kMaxLayersTransit, itop, 0, nlayers, nwave, nbands, nwalkers, max_band_count,
+        out_d && depth_d && ideep_d && wn_d && band_start_d && band_count_d && response_d &&
+            response_offset_d,
+        work_d, &nchunks, []() -> int { return PB_OK; });
+    if (rc || nchunks < 0)
+        return rc;
     if (nchunks > 0) {
         const size_t lds = (size_t)kWaves * nlayers * sizeof(double);
         k_band_transmittance<<<dim3(nchunks, nbands, nwalkers), kBlock, lds,
@@ -654,43 +598,11 @@ int pb_band_contribution_emission_cloudy_batch(
     int nwalkers, const int32_t *deck_itop_d, const double *deck_tsurf_d,
     const pb_cloud_terms *cloud, double *work_d, void *stream)
 {
-    PB_REQUIRE(nlayers >= 2 && nwave >= 1 && nbands >= 0 && nwalkers >= 0 && max_band_count >= 0,
-               "pb_band_contribution_emission_cloudy_batch: bad sizes (nlayers >= 2, nwave >= 1)");
-    PB_REQUIRE(nlayers <= kMaxLayersEmission,
-               "pb_band_contribution_emission_cloudy_batch: %d layers, at most %d fit in the LDS "
-               "of a workgroup", nlayers, kMaxLayersEmission);
-    PB_REQUIRE(itop >= 0 && itop < nlayers,
-               "pb_band_contribution_emission_cloudy_batch: itop out of range");
-    PB_REQUIRE(ibottom <= nlayers, "pb_band_contribution_emission_cloudy_batch: ibottom > nlayers");
-    PB_REQUIRE(nbands <= 65535 && nwalkers <= 65535,
-               "pb_band_contribution_emission_cloudy_batch: at most 65535 bands and walkers per "
-               "call");
-    PB_REQUIRE(!deck_itop_d == !deck_tsurf_d,
-               "pb_band_contribution_emission_cloudy_batch: deck_itop_d and deck_tsurf_d go "
-               "together");
-    if (int rc = check_cloud(cloud, "pb_band_contribution_emission_cloudy_batch"))
-        return rc;
-    if (nbands == 0 || nwalkers == 0)
-        return PB_OK;
-    PB_REQUIRE(out_d && ec_d && intervals_d && dlogp_d && wn_d && temps_d && band_start_d &&
-                   band_count_d && response_d && response_offset_d,
-               "pb_band_contribution_emission_cloudy_batch: null pointer");
-    const int nchunks = pb::div_up(max_band_count, kBlock);
-    PB_REQUIRE(nchunks == 0 || work_d,
-               "pb_band_contribution_emission_cloudy_batch: null work buffer");
-    if (nchunks > 0) {
-        EmissionClouds clouds{deck_itop_d, deck_tsurf_d, {}};
-        if (cloud && cloud->nr > 0)
-            clouds.cl = *cloud;
-        const size_t lds = ((size_t)(4 + kWaves) * nlayers - 2) * sizeof(double);
-        k_band_cf_emission<true>
-            <<<dim3(nchunks, nbands, nwalkers), kBlock, lds, pb::as_stream(stream)>>>(
-                work_d, ec_d, intervals_d, dlogp_d, wn_d, temps_d, band_start_d, band_count_d,
-                response_d, response_offset_d, maxdepth, itop, ibottom, nlayers, nwave, clouds);
-        PB_LAUNCH_CHECK();
-    }
-    return finish(out_d, work_d, band_start_d, band_count_d, nbands, nchunks, nlayers, nwave,
-                  nwalkers, stream);
+    return band_cf_emission<true>("pb_band_contribution_emission_cloudy_batch", out_d, ec_d,
+                                  intervals_d, dlogp_d, wn_d, temps_d, band_start_d, band_count_d,
+                                  response_d, response_offset_d, max_band_count, maxdepth, itop,
+                                  ibottom, nlayers, nwave, nbands, nwalkers, deck_itop_d,
+                                  deck_tsurf_d, cloud, work_d, stream);
 }
 
 int pb_band_transmittance_cloudy_batch(double *out_d, const double *ec_d, const double *raypath_d,
@@ -703,29 +615,21 @@ int pb_band_transmittance_cloudy_batch(double *out_d, const double *ec_d, const 
                                        const pb_cloud_terms *cloud, const double *f_patchy_d,
                                        double *work_d, void *stream)
 {
-    PB_REQUIRE(nlayers >= 1 && nwave >= 1 && nbands >= 0 && nwalkers >= 0 && max_band_count >= 0,
-               "pb_band_transmittance_cloudy_batch: bad sizes");
-    PB_REQUIRE(nlayers <= kMaxLayersCloudyTransit,
-               "pb_band_transmittance_cloudy_batch: %d layers, at most %d fit in the LDS of a "
-               "workgroup", nlayers, kMaxLayersCloudyTransit);
-    PB_REQUIRE(itop >= 0 && itop < nlayers,
-               "pb_band_transmittance_cloudy_batch: itop out of range");
-    PB_REQUIRE(nbands <= 65535 && nwalkers <= 65535,
-               "pb_band_transmittance_cloudy_batch: at most 65535 bands and walkers per call");
-    const int nrow = nlayers - itop;
-    const int64_t npath = ((int64_t)nrow * (nrow - 1)) / 2;
-    PB_REQUIRE(path_stride == 0 || path_stride >= npath,
-               "pb_band_transmittance_cloudy_batch: path_stride must be 0 or at least a walker's "
-               "length");
-    if (int rc = check_cloud(cloud, "pb_band_transmittance_cloudy_batch"))
+    const char *who = "pb_band_transmittance_cloudy_batch";
+    const int64_t nrow = (int64_t)nlayers - itop, npath = (nrow * (nrow - 1)) / 2;
+    int nchunks;
+    const int rc = check_band_call(
+        who, 1, kMaxLayersCloudyTransit, itop, 0, nlayers, nwave, nbands, nwalkers,
+        max_band_count,
+        out_d && ec_d && (raypath_d || npath == 0) && wn_d && band_start_d && band_count_d &&
+            response_d && response_offset_d,
+        work_d, &nchunks, [&]() -> int {
+            PB_REQUIRE(path_stride == 0 || path_stride >= npath,
+                       "%s: path_stride must be 0 or at least a walker's length", who);
+            return pb::check_cloud(cloud, who);
+        });
+    if (rc || nchunks < 0)
         return rc;
-    if (nbands == 0 || nwalkers == 0)
-        return PB_OK;
-    PB_REQUIRE(out_d && ec_d && (raypath_d || npath == 0) && wn_d && band_start_d &&
-                   band_count_d && response_d && response_offset_d,
-               "pb_band_transmittance_cloudy_batch: null pointer");
-    const int nchunks = pb::div_up(max_band_count, kBlock);
-    PB_REQUIRE(nchunks == 0 || work_d, "pb_band_transmittance_cloudy_batch: null work buffer");
     if (nchunks > 0) {
         // (no ray path at one impact parameter: the kernel then reads none)
         CloudyBandArgs a{work_d, ec_d, wn_d, raypath_d ? raypath_d : ec_d, path_stride,

@@ -21,11 +21,7 @@ constexpr int kMaxTaps = kOut + 1;     // halo (T - 1) / 2 <= kOut / 2 on each s
 constexpr double kKm = 1.0e5;          // the reference's pc.km
 constexpr double kC = 29979245800.0;   // the reference's pc.c (scipy.constants, CODATA 2018)
 
-__device__ __forceinline__ double uniform_f64(const double *p)
-{
-    typedef const double __attribute__((address_space(4))) *cptr;
-    return *((cptr)(unsigned long long)p);
-}
+using pb::uniform_f64;
 
 // s_l[m] = sample first + m of the walker's row (m < count), scaled; 0 outside [0, W)
 __device__ __forceinline__ void stage_samples(double *s_l, const double *row, const double *scale,

@@ -61,14 +61,7 @@ using pb::planck_terms;
 using pb::two_stream_down;
 using pb::two_stream_trans;
 using pb::two_stream_up;
-
-// the sum over the wavefront, the same bits in every lane
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int off = kWave / 2; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, kWave);
-    return v;
-}
+using pb::wave_sum;
 
 // grid (blocks of 256 columns, walkers) as k_two_stream_batch.  Lanes past nwave of the last live
 // wavefront take part in the sums with 0 and touch no global memory; a wavefront wholly past nwave

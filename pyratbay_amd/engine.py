@@ -31,7 +31,7 @@ from . import contribution                                              # noqa: 
 from .contribution import (band_cf_host, band_contribution_cloudy_host,  # noqa: F401
                            band_contribution_host, contribution_function_host,
                            transmittance_host, transmittance_patchy_host)
-from .batch import (_check_walker_tensor, _cloud_call_args,             # noqa: F401
+from .batch import (_check_walker_tensor, _cloud_args,                  # noqa: F401
                     alkali_voigt_det_batch, band_contribution_emission_batch,
                     band_contribution_emission_cloudy_batch, band_transmittance_batch,
                     band_transmittance_cloudy_batch, cloudy_emission_batch, cloudy_transit_batch,
