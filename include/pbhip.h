@@ -776,6 +776,58 @@ int pb_log_posterior(double *out_d, const double *loglike_d, const double *log_p
                      const int32_t *inside_d, double outside_value, int add_prior, int nwalkers,
                      void *stream);
 
+/* ---- The sampler (pb_sampler.hip): DEMC-zs (ter Braak & Vrugt 2008, Stat. Comput. 18, 435).  A
+ * generation is pb_demc_propose -> the caller's log-posterior of prop_d -> pb_demc_accept, with
+ * nothing read back; pyratbay_amd/sampler.py states every kernel in NumPy (the specification).
+ * Random numbers: Philox4x32-10 (pb_philox.h), key = seed (low word, high word), counter =
+ * (block, chain w, generation g, tag), tags 0 propose, 1 accept, 2 initial draw; a block's words
+ * (0, 1) and (2, 3) give two uniforms u = (n + 0.5) 2^-52, n = ((x_a >> 6) << 26) + (x_b >> 6), in
+ * [2^-53, 1 - 2^-53], and two normals sqrt(-2 ln u_a) cos(2 pi u_b), ... sin(2 pi u_b); an index
+ * into n rows is idx(u, n) = min(floor(u n), n - 1).  One wavefront per chain, two parameters per
+ * lane, nfree <= PB_RETRIEVAL_MAX_PARAMS; sums in a fixed order (the lane's two terms, then a
+ * butterfly).  0 <= g < 2^32, else PB_ERR_ARG.  nwalkers == 0: nothing launched.
+ *
+ * pb_demc_propose: theta_d[nwalkers,nfree], the history z_d[., nfree] whose first M >= 3 rows exist
+ * (fewer: PB_ERR_ARG), pstep_d[nfree] -> prop_d[nwalkers,nfree], log_jac_d[nwalkers],
+ * kind_d[nwalkers] (0 parallel, 1 snooker).  Block 0: r1 = idx(u, M), r2 = idx(u', M - 1),
+ * r2 += (r2 >= r1); block 1: u_s, rz = idx(u', M); block 2: u_g; block 3 + f / 2: the normals n_f
+ * (even f the cosine, odd f the sine).
+ *   u_s >= p_snooker:  prop = (theta + gamma (Z[r1] - Z[r2])) + (fepsilon pstep) n,
+ *                      gamma = fgamma 2.38 / sqrt(2 nfree); log_jac = 0
+ *   otherwise:         d = theta - Z[rz], D2 = d.d,
+ *                      prop = theta + ((1.2 + u_g) ((Z[r1] - Z[r2]).d / D2)) d,
+ *                      log_jac = 0.5 (nfree - 1) (ln |prop - Z[rz]|^2 - ln D2);
+ *                      D2 not > 0 or log_jac not finite: prop = theta, log_jac = 0. */
+int pb_demc_propose(double *prop_d, double *log_jac_d, int32_t *kind_d, const double *theta_d,
+                    const double *z_d, const double *pstep_d, int64_t g, uint64_t seed, int64_t M,
+                    double fgamma, double fepsilon, double p_snooker, int nfree, int nwalkers,
+                    void *stream);
+/* The rest of a generation.  With u the first uniform of block 0, tag 1, chain w accepts iff
+ *   ln u < (logp_prop_d[w] - logp_d[w]) + log_jac_d[w]
+ * (a NaN on either side rejects; so does a proposal at -inf).  On accept theta_d[w] and logp_d[w]
+ * are overwritten in place and row nrows_d[w] of the chain store is opened: rows_d[w,.,nfree],
+ * row_logp_d[w,.], row_gen_d[w,.] = g, counts_d[w,.] = 1 (cap rows per chain), nrows_d[w] += 1; on
+ * reject counts_d[w, nrows_d[w] - 1] += 1.  An accept at nrows_d[w] == cap sets overflow_d[w]
+ * instead; from then on (and while nrows_d[w] is outside 1 .. cap) the chain records nothing but
+ * goes on sampling.  Per chain and parameter Welford's running mean and M2 of the state after the
+ * decision: nstat_d[w] += 1, delta = x - mean, mean += delta / nstat, M2 += delta (x - mean).
+ * append != 0: the state after the decision is written to z_d[M + w] (M + nwalkers <= Mcap, else
+ * PB_ERR_ARG; g must also fit row_gen_d).  accepted_d[w] = 1 or 0. */
+int pb_demc_accept(double *theta_d, double *logp_d, const double *prop_d,
+                   const double *logp_prop_d, const double *log_jac_d, double *rows_d,
+                   double *row_logp_d, int32_t *row_gen_d, int64_t *counts_d, int32_t *nrows_d,
+                   int32_t *overflow_d, double *mean_d, double *m2_d, int64_t *nstat_d,
+                   double *z_d, int32_t *accepted_d, int64_t g, uint64_t seed, int64_t M,
+                   int64_t Mcap, int append, int cap, int nfree, int nwalkers, void *stream);
+/* rhat_d[nfree] of nwalkers chains of n states each from their Welford sums: W = the mean over
+ * chains of M2 / (n - 1), B / n = the ddof = 1 variance of the chain means,
+ * R = sqrt(((n - 1) / n W + B / n) / W); NaN where W == 0, n < 2 or nwalkers < 2. */
+int pb_gelman_rubin(double *rhat_d, const double *mean_d, const double *m2_d, int64_t n,
+                    int nfree, int nwalkers, void *stream);
+/* out_d[n,ncol]: the uniforms of tag 2 -- row = chain slot, g = 0, block col / 2, even columns
+ * from words (0, 1), odd ones from words (2, 3).  For the initial draw. */
+int pb_philox_uniform(double *out_d, uint64_t seed, int64_t n, int ncol, void *stream);
+
 /* High-resolution data (eval()'s second exit, pyrat/pyrat_obj.py:331-356).
  * ps.inst_convolution's last step (spectrum/spec_tools.py:879) for a batch:
  *   out_d[w] = convolve(spectra_d[w] * sample_scale_d, taps_d, mode='same')

@@ -23,7 +23,7 @@ class PbError(RuntimeError):
 _lib = None
 
 vp = C.c_void_p
-i32, i64, f64 = C.c_int, C.c_int64, C.c_double
+i32, i64, u64, f64 = C.c_int, C.c_int64, C.c_uint64, C.c_double
 
 # name: argtypes (all functions return int unless listed in _RESTYPES)
 _PROTOS = {
@@ -132,6 +132,11 @@ _PROTOS = {
                          i32, i32, vp],
     'pb_prior_transform': [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
     'pb_log_posterior': [vp, vp, vp, vp, f64, i32, i32, vp],
+    'pb_demc_propose': [vp, vp, vp, vp, vp, vp, i64, u64, i64, f64, f64, f64, i32, i32, vp],
+    'pb_demc_accept': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, u64,
+                       i64, i64, i32, i32, i32, i32, vp],
+    'pb_gelman_rubin': [vp, vp, vp, i64, i32, i32, vp],
+    'pb_philox_uniform': [vp, u64, i64, i32, vp],
     'pb_internal_flux': [vp, vp, f64, i32, vp],
     'pb_two_stream_net_parts': [i32],
     'pb_two_stream_net_work_doubles': [i32, i32, i32],

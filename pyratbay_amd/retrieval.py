@@ -7,7 +7,10 @@ the index maps of pyrat/retrieval.py:77-121, 167-284; their use in every eval()
 (pyrat_obj.py:258-297); Loglike's free / fixed / shared rule by pstep and the priors
 (tools/retrieval_tools.py:45-46, 91-93).  mc3 is not part of this package: the NumPy statements
 here (expand_host, split_host, log_prior_host, inside_host, prior_transform_host) are the
-specification of the kernels in csrc/pb_retrieval.hip.
+specification of the kernels in csrc/pb_retrieval.hip.  The sampler that drives the loop is this
+package's own (sampler.py: DEMC-zs on the device, csrc/pb_sampler.hip): draw_initial draws from the
+priors, sample builds and runs a sampler.DEMC over log_posterior, summary reduces its chain with
+model.posterior_summary.
 
 DEVIATIONS from the reference:
   * a shared parameter (pstep < 0) whose target is itself shared is refused; the reference copies
@@ -544,3 +547,40 @@ class Retrieval:
              _ptr(d['prior']), _ptr(d['priorlow']), _ptr(d['priorup']), self.nfree,
              cube.shape[0], _stream())
         return theta
+
+    # ------------------------------------------------------------------ the sampler
+    def draw_initial(self, n, seed=0):
+        """[n, nfree]: n draws from the priors: pb_philox_uniform (sampler.uniforms_host) ->
+        prior_transform, with the refusals prior_transform has."""
+        self._check_transform()
+        cube = torch.empty((int(n), self.nfree), dtype=torch.float64, device='cuda')
+        call('pb_philox_uniform', _ptr(cube), int(seed) % 2**64, int(n), self.nfree, _stream())
+        return self.prior_transform(cube)
+
+    def sample(self, nchains, ngen, seed=0, z0=None, capacity=None, **kw):
+        """A sampler.DEMC over log_posterior, started and run for ngen generations: pstep from the
+        block's free lines; z0[M0, nfree], the initial history, defaults to
+        draw_initial(10 nchains, seed), and its last nchains rows are the starting states (one
+        outside the bounds is refused before the loop); capacity, the rows per chain of the store,
+        defaults to ngen + 1; kw: fgamma, fepsilon, p_snooker, thin_z.  -> the DEMC: run(more)
+        continues it, summary(it) reduces it."""
+        from .sampler import DEMC
+        nchains = int(nchains)
+        z0 = self.draw_initial(10 * nchains, seed) if z0 is None else \
+            self._theta_device('z0', dev(z0))
+        if z0.shape[0] < max(nchains, 3) or nchains < 1:
+            raise ValueError(f'z0 has {z0.shape[0]} rows: at least {max(nchains, 3)} for '
+                             f'{nchains} chains')
+        demc = DEMC(self.log_posterior, self.nfree, self.pstep[self.ifree], seed=seed, **kw)
+        demc.start(z0[z0.shape[0] - nchains:], z0, int(ngen) + 1 if capacity is None else capacity)
+        return demc.run(ngen)
+
+    def summary(self, sampler, burn=0, **kw):
+        """The posterior summary of a sampler's chain: sampler.unique(burn) -> arguments ->
+        model.posterior_summary(atmosphere, params, counts, bands, ...); kw: what
+        posterior_summary takes besides the per-sample tensors (quantiles, chunk,
+        contribution, ...)."""
+        theta, counts = sampler.unique(burn)
+        args = self.arguments(theta)
+        return self.model.posterior_summary(self.atmosphere, args.params, counts, self.bands,
+                                            **args.kw, **kw)
