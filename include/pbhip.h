@@ -828,6 +828,77 @@ int pb_gelman_rubin(double *rhat_d, const double *mean_d, const double *m2_d, in
  * from words (0, 1), odd ones from words (2, 3).  For the initial draw. */
 int pb_philox_uniform(double *out_d, uint64_t seed, int64_t n, int ncol, void *stream);
 
+/* ---- Nested sampling (pb_nested.hip; Skilling 2006, Bayesian Anal. 1, 833): the evidence ln Z and
+ * the weighted dead points, in the unit cube, on nlive <= PB_NESTED_MAX_LIVE live points
+ * live_u_d[nlive,nfree], live_logl_d[nlive].  An iteration `it` (from 1) is pb_nested_select ->
+ * nsteps x (pb_nested_propose -> the caller's prior transform and log-likelihood of point_d ->
+ * pb_nested_accept), with nothing read back; pyratbay_amd/nested.py states every kernel in NumPy
+ * (the specification).  Random numbers, idx(u, n) and the conventions are the sampler's above,
+ * with the tags 3 (start), 4 (walk step), 5 (resample); the walk's kernels run one wavefront per
+ * slot, two parameters per lane, nfree <= PB_RETRIEVAL_MAX_PARAMS.  state_d[4]: ln X (starts at
+ * 0), ln Z (starts at -inf), Lstar, remain.  Refused with PB_ERR_ARG and a message: a null pointer,
+ * a batch K outside 1 .. nlive - 2, nlive > PB_NESTED_MAX_LIVE, nfree too large, `it` or `q`
+ * outside 0 .. 2^32 - 1.
+ *
+ * pb_nested_select: the live points ranked by logl ascending -- ties to the lower index, NaN the
+ * lowest -- by counting over the values held in LDS (one thread per point; the result depends on
+ * the values alone).  The K lowest die in rank order: dead_idx_d[K]; the others are
+ * surv_idx_d[nlive - K] in rank order.  Dead point j, n = nlive - j, one after the other:
+ *   ln w = (logl + ln X) + ln(-expm1(-1 / n))   (-inf for a NaN logl)
+ *   ln X = ln X - 1 / n;   ln Z = logaddexp(ln Z, ln w)         (NumPy's logaddexp)
+ * Its cube row, logl and ln w go to row dead_base + j of dead_u_d[dead_cap,nfree], dead_logl_d,
+ * dead_logw_d (dead_base + K > dead_cap: PB_ERR_ARG).  Lstar = logl of the last dead point;
+ * remain = logaddexp(ln Z, Ltop + ln X) - ln Z with Ltop the logl of the last survivor. */
+#define PB_NESTED_MAX_LIVE 4096
+int pb_nested_select(int32_t *dead_idx_d, int32_t *surv_idx_d, double *dead_u_d,
+                     double *dead_logl_d, double *dead_logw_d, double *state_d,
+                     const double *live_u_d, const double *live_logl_d, int64_t dead_base,
+                     int64_t dead_cap, int K, int nlive, int nfree, void *stream);
+/* One walk step of the K slots, nsurv = nlive - K.  start != 0 (the first step of an iteration):
+ * slot k first takes cur_d[k] = live_u[pick], cur_logl_d[k] = live_logl[pick], pick =
+ * surv_idx[idx(u, nsurv)], u the first uniform of block 0 at (0, k, it, tag 3), and acc_it_d[k] = 0.
+ * Then, at (block, k, q, tag 4): block 0: a = idx(u, nsurv), b = idx(u', nsurv - 1), b += (b >= a);
+ * block 1: gamma = u_m < p_unit ? 1 : fgamma 2.38 / sqrt(2 nfree);
+ *   prop = cur + gamma (U[surv a] - U[surv b])     (product and sum rounded separately)
+ *   inside_d[k] = every 0 < prop_f < 1;   point_d[k] = inside ? prop : cur
+ * a_d, b_d, gamma_d [K]: the draw.  An entry of surv_idx_d outside the live set is clamped into
+ * it.  K == 0: nothing launched. */
+int pb_nested_propose(double *point_d, int32_t *inside_d, int32_t *a_d, int32_t *b_d,
+                      double *gamma_d, double *cur_d, double *cur_logl_d, int32_t *acc_it_d,
+                      const double *live_u_d, const double *live_logl_d,
+                      const int32_t *surv_idx_d, int64_t it, int64_t q, uint64_t seed,
+                      double fgamma, double p_unit, int start, int nlive, int nfree, int K,
+                      void *stream);
+/* The rest of a walk step.  Slot k accepts iff inside_d[k] != 0 and logl_prop_d[k] > Lstar
+ * (state_d[2]; strict, and a NaN on either side rejects): cur_d[k], cur_logl_d[k] overwritten in
+ * place, naccept_d[k] (int64) and acc_it_d[k] raised; accepted_d[k] = 1 or 0.  last != 0 (the last
+ * step of an iteration): live_u[dead_idx_d[k]] = cur[k], live_logl[dead_idx_d[k]] = cur_logl[k]
+ * (an index outside the live set writes nothing), and stuck_d[k] += 1 where acc_it_d[k] == 0: the
+ * replacement duplicates a survivor.  K == 0: nothing launched. */
+int pb_nested_accept(double *cur_d, double *cur_logl_d, const double *point_d,
+                     const double *logl_prop_d, const int32_t *inside_d, const double *state_d,
+                     int64_t *naccept_d, int32_t *acc_it_d, int64_t *stuck_d, int32_t *accepted_d,
+                     double *live_u_d, double *live_logl_d, const int32_t *dead_idx_d, int last,
+                     int nlive, int nfree, int K, void *stream);
+/* The result so far; changes nothing of the run.  n = ndead + nlive rows: the dead points, then
+ * the live ones at ln w = (logl + ln X) - ln(nlive) (-inf for a NaN logl) -> logl_d[n], logw_d[n].
+ * m = max ln w, e = exp(ln w - m) (0 where ln w = -inf), S = sum e:
+ *   out_d[0] = ln Z = m + ln S;   out_d[2] = H = (sum of e ln L over e > 0) / S - ln Z;
+ *   out_d[1] = ln Z_err = sqrt(max(H, 0) / nlive);   cdf_d[i] = (e_0 + ... + e_i) / S
+ * The sums run over 256 chunks of ceil(n / 256) consecutive rows: each chunk from 0 in index
+ * order, the chunk sums in chunk order, the running sum of a chunk from the sum of the chunks
+ * before it.  One block. */
+int pb_nested_finish(double *out_d, double *logw_d, double *logl_d, double *cdf_d,
+                     const double *dead_logl_d, const double *dead_logw_d,
+                     const double *live_logl_d, const double *state_d, int64_t ndead, int nlive,
+                     void *stream);
+/* The equal-weight posterior as a histogram: counts_d[n] (int64, zeroed here, integer atomics) of
+ * nsamples <= 2^32 draws; sample s takes uniform s % 2 of block 0 at (0, s / 2, 0, tag 5) and
+ * falls on the first row i with cdf_d[i] > u (bisection; cdf_d must not decrease), clipped to
+ * n - 1. */
+int pb_nested_resample(int64_t *counts_d, const double *cdf_d, int64_t n, int64_t nsamples,
+                       uint64_t seed, void *stream);
+
 /* High-resolution data (eval()'s second exit, pyrat/pyrat_obj.py:331-356).
  * ps.inst_convolution's last step (spectrum/spec_tools.py:879) for a batch:
  *   out_d[w] = convolve(spectra_d[w] * sample_scale_d, taps_d, mode='same')

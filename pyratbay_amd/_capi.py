@@ -137,6 +137,13 @@ _PROTOS = {
                        i64, i64, i32, i32, i32, i32, vp],
     'pb_gelman_rubin': [vp, vp, vp, i64, i32, i32, vp],
     'pb_philox_uniform': [vp, u64, i64, i32, vp],
+    'pb_nested_select': [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp],
+    'pb_nested_propose': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, u64, f64, f64,
+                          i32, i32, i32, i32, vp],
+    'pb_nested_accept': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32,
+                         vp],
+    'pb_nested_finish': [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp],
+    'pb_nested_resample': [vp, vp, i64, i64, u64, vp],
     'pb_internal_flux': [vp, vp, f64, i32, vp],
     'pb_two_stream_net_parts': [i32],
     'pb_two_stream_net_work_doubles': [i32, i32, i32],

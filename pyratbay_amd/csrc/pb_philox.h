@@ -1,7 +1,8 @@
 // Philox4x32-10 (Salmon, Moraes, Dror & Shaw 2011, "Parallel random numbers: as easy as 1, 2,
-// 3"), the counter-based generator of the sampler (pb_sampler.hip; sampler.philox_host is the same
-// statement in NumPy): a pure function of (counter, key), so that host and device draw the same
-// random words bit for bit and nothing has to be kept between launches.
+// 3"), the counter-based generator of the samplers (pb_sampler.hip, pb_nested.hip;
+// sampler.philox_host is the same statement in NumPy): a pure function of (counter, key), so that
+// host and device draw the same random words bit for bit and nothing has to be kept between
+// launches.
 //
 // Addressing: key = the 64-bit seed (low word, high word); counter = (block, chain, generation,
 // tag).  One block of four words gives two uniforms (words 0, 1 and words 2, 3) and, by Box-Muller
@@ -16,8 +17,9 @@ namespace pb {
 
 constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
 constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-// what a block is drawn for (counter word 3)
+// what a block is drawn for (counter word 3): the sampler's three, then nested sampling's
 constexpr uint32_t kTagPropose = 0, kTagAccept = 1, kTagInitial = 2;
+constexpr uint32_t kTagNestedStart = 3, kTagNestedStep = 4, kTagNestedResample = 5;
 
 struct PhiloxWords {
     uint32_t x[4];
@@ -53,6 +55,16 @@ __host__ __device__ inline double philox_u01(uint32_t hi, uint32_t lo)
 {
     const uint64_t n = ((uint64_t)(hi >> 6) << 26) + (uint64_t)(lo >> 6);
     return ((double)n + 0.5) * 0x1p-52;
+}
+
+// the two uniforms of a block
+__host__ __device__ inline void philox_block_uniforms(uint64_t seed, uint32_t block,
+                                                      uint32_t chain, uint32_t generation,
+                                                      uint32_t tag, double &ua, double &ub)
+{
+    const PhiloxWords r = philox_block(seed, block, chain, generation, tag);
+    ua = philox_u01(r.x[0], r.x[1]);
+    ub = philox_u01(r.x[2], r.x[3]);
 }
 
 // an index into n rows

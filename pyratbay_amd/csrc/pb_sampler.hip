@@ -18,20 +18,11 @@ constexpr int kWavesPerBlock = 4;
 constexpr int kMaxPar = PB_RETRIEVAL_MAX_PARAMS;
 static_assert(kMaxPar == 2 * kWave, "the sampler's kernels give every lane two parameters");
 
-// the two uniforms of a block
-__device__ __forceinline__ void block_uniforms(uint64_t seed, uint32_t block, uint32_t w,
-                                               uint32_t g, uint32_t tag, double &ua, double &ub)
-{
-    const pb::PhiloxWords r = pb::philox_block(seed, block, w, g, tag);
-    ua = pb::philox_u01(r.x[0], r.x[1]);
-    ub = pb::philox_u01(r.x[2], r.x[3]);
-}
-
 // the normal of parameter f: Box-Muller on block 3 + f / 2, cosine for even f, sine for odd f
 __device__ __forceinline__ double normal_of(uint64_t seed, uint32_t w, uint32_t g, int f)
 {
     double ua, ub;
-    block_uniforms(seed, 3u + (uint32_t)(f >> 1), w, g, pb::kTagPropose, ua, ub);
+    pb::philox_block_uniforms(seed, 3u + (uint32_t)(f >> 1), w, g, pb::kTagPropose, ua, ub);
     const double r = sqrt(-2.0 * log(ua));
     const double angle = (2.0 * pb::kPi) * ub;
     return r * ((f & 1) ? sin(angle) : cos(angle));
@@ -48,13 +39,13 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void k_demc_propose(
     if (w >= nw)                                        // (wave-uniform)
         return;
     double ua, ub, us, ug;
-    block_uniforms(seed, 0u, (uint32_t)w, g, pb::kTagPropose, ua, ub);
+    pb::philox_block_uniforms(seed, 0u, (uint32_t)w, g, pb::kTagPropose, ua, ub);
     const int64_t r1 = pb::philox_index(ua, M);
     int64_t r2 = pb::philox_index(ub, M - 1);
     r2 += (r2 >= r1) ? 1 : 0;
-    block_uniforms(seed, 1u, (uint32_t)w, g, pb::kTagPropose, us, ub);
+    pb::philox_block_uniforms(seed, 1u, (uint32_t)w, g, pb::kTagPropose, us, ub);
     const int64_t rz = pb::philox_index(ub, M);
-    block_uniforms(seed, 2u, (uint32_t)w, g, pb::kTagPropose, ug, ub);
+    pb::philox_block_uniforms(seed, 2u, (uint32_t)w, g, pb::kTagPropose, ug, ub);
     const bool snooker = us < p_snooker;                // (wave-uniform)
 
     const double *row = theta + (int64_t)w * nfree;
@@ -140,7 +131,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void k_demc_accept(AcceptAr
     if (w >= a.nw)                                      // (wave-uniform)
         return;
     double u, unused;
-    block_uniforms(a.seed, 0u, (uint32_t)w, a.g, pb::kTagAccept, u, unused);
+    pb::philox_block_uniforms(a.seed, 0u, (uint32_t)w, a.g, pb::kTagAccept, u, unused);
     const double lp = a.logp[w], lpp = a.logp_prop[w], lj = a.log_jac[w];
     // (a NaN on either side compares false; -inf - logp is -inf or NaN)
     const bool acc = log(u) < (lpp - lp) + lj;          // (wave-uniform)

@@ -575,6 +575,20 @@ class Retrieval:
         demc.start(z0[z0.shape[0] - nchains:], z0, int(ngen) + 1 if capacity is None else capacity)
         return demc.run(ngen)
 
+    def nested(self, nlive=1000, seed=0, dlogz=0.5, **kw):
+        """A nested.NestedSampler over log_likelihood and prior_transform (the reference's
+        `sampler = multinest` with `nlive` live points), started and run until the evidence still
+        to come is below dlogz (dlogz=None: started only; run(niter) or run_until() continue it).
+        kw: batch, nsteps, fgamma, p_unit of the sampler, check_every and max_iter of run_until.
+        A uniform parameter with an infinite bound is refused before anything is launched.
+        -> the sampler: logz() is (ln Z, ln Z_err, H), summary(it) reduces its posterior."""
+        from .nested import NestedSampler
+        self._check_transform()
+        until = {k: kw.pop(k) for k in ('check_every', 'max_iter') if k in kw}
+        ns = NestedSampler(self.log_likelihood, self.prior_transform, self.nfree, nlive,
+                           seed=seed, **kw).start()
+        return ns if dlogz is None else ns.run_until(dlogz, **until)
+
     def summary(self, sampler, burn=0, **kw):
         """The posterior summary of a sampler's chain: sampler.unique(burn) -> arguments ->
         model.posterior_summary(atmosphere, params, counts, bands, ...); kw: what
