@@ -91,9 +91,28 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void k_retrieval_map(
     }
 }
 
+// u (lo + up) < lo, the side of prior an element of the unit cube falls on, decided exactly: the
+// sum lo + up with its rounding error (two-sum), u times that sum with its rounding error (one
+// fma), and a difference p - lo that is exact near the split.  fl(lo / (lo + up)) lies an ulp or
+// two off the split, and a u between the two is computed by the other side's statement: right to
+// first order, but with the rounding of the OTHER side's width, a thousand units of
+// eps (|prior| + s (1 + |z|)) where lo = 1000 up.  (The build's -ffp-contract=off keeps these
+// operations apart.)  u = 0: below; u = 1 and NaN: not below.
+__device__ __forceinline__ bool below_split(double u, double lo, double up)
+{
+    const double s = lo + up;
+    const double t = s - lo;
+    const double es = (lo - (s - t)) + (up - t);
+    const double p = u * s;
+    const double ep = fma(u, s, -p);
+    return (p - lo) + (ep + u * es) < 0.0;
+}
+
 // theta[w, f] from the unit cube: uniform: pmin + u (pmax - pmin); two-sided Gaussian: the inverse
 // CDF of the density exp(-0.5 ((p - prior) / s)^2), s = lo below prior and up above it, whose mass
-// below prior is lo / (lo + up).  Not truncated to [pmin, pmax].
+// below prior is lo / (lo + up).  Either branch hands normcdfinv the tail mass itself: above prior
+// -normcdfinv(x), not normcdfinv(1 - x), which loses the tail from three sigma upward.  u = 0
+// gives -inf, u = 1 +inf.  Not truncated to [pmin, pmax].
 __global__ __launch_bounds__(256) void k_prior_transform(
     double *__restrict__ theta, const double *__restrict__ cube, const double *__restrict__ pmin,
     const double *__restrict__ pmax, const double *__restrict__ prior,
@@ -109,10 +128,10 @@ __global__ __launch_bounds__(256) void k_prior_transform(
     double v;
     if (lo == 0.0 && up == 0.0) {
         v = pmin[f] + u * (pmax[f] - pmin[f]);
-    } else if (u < lo / (lo + up)) {
+    } else if (below_split(u, lo, up)) {
         v = prior[f] + lo * normcdfinv(0.5 * u * (lo + up) / lo);
     } else {
-        v = prior[f] + up * normcdfinv(1.0 - 0.5 * (1.0 - u) * (1.0 + lo / up));
+        v = prior[f] - up * normcdfinv(0.5 * (1.0 - u) * (1.0 + lo / up));
     }
     theta[i] = v;
 }

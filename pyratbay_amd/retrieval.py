@@ -108,6 +108,29 @@ def log_prior_terms(p, prior, priorlow, priorup):
     return np.where(uniform, 0.0, terms)
 
 
+def below_split(u, lo, up):
+    """u (lo + up) < lo, the side of prior an element of the unit cube falls on, decided exactly:
+    the sum lo + up with its rounding error (two-sum), u times that sum with its rounding error
+    (Dekker's product: NumPy has no fma), and a difference p - lo that is exact near the split.
+    fl(lo / (lo + up)) lies an ulp or two off the split, and a u between the two would be computed
+    by the other side's statement: right to first order, but with the rounding of the OTHER
+    side's width, a thousand units of eps (|prior| + s (1 + |z|)) where lo = 1000 up.
+    u = 0: below; u = 1 and NaN: not below."""
+    def halves(a):
+        c = 134217729.0 * a                                  # 2^27 + 1: Veltkamp's split
+        high = c - (c - a)
+        return high, a - high
+    with np.errstate(all='ignore'):
+        s = lo + up
+        t = s - lo
+        es = (lo - (s - t)) + (up - t)
+        p = u * s
+        uh, ul = halves(u)
+        sh, sl = halves(s)
+        ep = ((uh * sh - p) + uh * sl + ul * sh) + ul * sl
+        return (p - lo) + (ep + u * es) < 0.0
+
+
 class Retrieval:
     """Retrieval(model, atmosphere, bands, observation, retrieval_params, runits='rjup',
     mass_units='mjup', fixed=None, **eval_kw): model, a TableSpectrum; atmosphere, a bound
@@ -134,8 +157,10 @@ class Retrieval:
 
     Priors: a free parameter with priorlow == priorup == 0 is uniform and contributes 0; otherwise
     -0.5 ((p - prior) / s)**2, s = priorlow for p < prior, else priorup -- WITHOUT a normalisation
-    term.  inside: every free value is finite and pmin <= p <= pmax; the log-prior of a walker
-    that is not inside is -inf, and it is evaluated at the `value` column (DEVIATION).
+    term.  A free parameter with a negative or non-finite priorlow or priorup, or with exactly one
+    of the two zero, is refused.  inside: every free value is finite and pmin <= p <= pmax; the
+    log-prior of a walker that is not inside is -inf, and it is evaluated at the `value` column
+    (DEVIATION).
 
     The *_host methods are NumPy and carry the specification; arguments, log_likelihood,
     log_posterior, prior_transform and bandflux take float64 device tensors, read nothing back and
@@ -183,6 +208,7 @@ class Retrieval:
         for i, j in self.share_target.items():
             self.constant[i] = self.params[j]
         self.value_free = self.params[self.ifree].copy()
+        self._check_prior_widths()
 
         self._resolve(dict(fixed or {}))
         self._device = None
@@ -435,9 +461,11 @@ class Retrieval:
 
     def prior_transform_host(self, cube):
         """cube[nw, nfree] in (0, 1) -> theta: uniform: pmin + u (pmax - pmin); two-sided Gaussian
-        (lo = priorlow, up = priorup): u < lo / (lo + up): prior + lo ndtri(0.5 u (lo + up) / lo),
-        otherwise prior + up ndtri(1 - 0.5 (1 - u) (1 + lo / up)).  Not truncated to
-        [pmin, pmax]: inside catches what falls out."""
+        (lo = priorlow, up = priorup): where u (lo + up) < lo, decided exactly (below_split),
+        prior + lo ndtri(0.5 u (lo + up) / lo), otherwise prior - up ndtri(0.5 (1 - u) (1 + lo /
+        up)): either branch hands ndtri the tail mass itself (1 minus it would lose the tail from
+        three sigma upward).  u = 0 gives -inf, u = 1 +inf.  Not truncated to [pmin, pmax]:
+        inside catches what falls out."""
         from scipy.special import ndtri
         u = self._theta_host(cube)
         self._check_transform()
@@ -449,9 +477,29 @@ class Retrieval:
         with np.errstate(all='ignore'):
             flat = np.where(uniform, pmin, 0.0) + u * np.where(uniform, pmax - pmin, 0.0)
             low = prior + lo1 * ndtri(0.5 * u * (lo1 + up1) / lo1)
-            high = prior + up1 * ndtri(1.0 - 0.5 * (1.0 - u) * (1.0 + lo1 / up1))
-            gauss = np.where(u < lo1 / (lo1 + up1), low, high)
+            high = prior - up1 * ndtri(0.5 * (1.0 - u) * (1.0 + lo1 / up1))
+            gauss = np.where(below_split(u, lo1, up1), low, high)
         return np.where(uniform, flat, gauss)
+
+    def _check_prior_widths(self):
+        """A free parameter's priorlow and priorup are finite and not negative, and both zero
+        (uniform) or neither: with one of them zero the prior term is 0 / 0 at p == prior and the
+        transform is infinite (the reference gives that case no meaning: it tests only
+        priorlow == 0 and priorup == 0, pyrat/retrieval.py:362)."""
+        f = self.ifree
+        lo, up = self.priorlow[f], self.priorup[f]
+        with np.errstate(invalid='ignore'):
+            bad = ~(np.isfinite(lo) & np.isfinite(up) & (lo >= 0) & (up >= 0))
+        if np.any(bad):
+            names = [self.pnames[i] for i in f[bad]]
+            raise ValueError(f'retrieval_params: free parameters {names} have a negative or '
+                             'non-finite priorlow or priorup')
+        half = (lo == 0) != (up == 0)
+        if np.any(half):
+            names = [self.pnames[i] for i in f[half]]
+            raise ValueError(f'retrieval_params: free parameters {names} have exactly one of '
+                             'priorlow and priorup equal to zero: a half-open prior is not '
+                             'defined (both zero: uniform)')
 
     def _check_transform(self):
         f = self.ifree
