@@ -1172,6 +1172,45 @@ int pb_walker_atmosphere(const pb_atm_model *model, const double *params_d, int 
                          double *temps_d, double *dens_d, double *radius_d, double *mm_d,
                          double *cont_dens_d, double *alk_dens_d, int32_t *reject_d, void *stream);
 
+/* ---- Isotope ratios of the table's slots (pb_isotopes.hip): Line_Sample's isotope_ratios
+ * (pyratbay/opacity/line_sampling.py:282-298, 451-456: density * iso_ratios before interp_ec) for
+ * a batch, in ONE launch with no host read-back and no allocation (graph-capturable).  The table
+ * has nspec slots; nlabelled <= PB_ISO_MAX_SLOTS of them carry an isotope label, the others have
+ * the ratio 1.0.  Labelled slot i is table slot slot[i] and has
+ *   kind PB_ISO_CONST  ratio = constant[i]
+ *   kind PB_ISO_FREE   ratio = pow(10.0, pars_d[w][par[i]])
+ *   kind PB_ISO_FILL   ratio = 1 - (r_a + r_b + ...), the ratios of the labelled slots
+ *                      fill[i][0 .. nfill[i]-1] (1 ... PB_ISO_MAX_FILLERS of them, none a fill slot
+ *                      itself), summed left to right, every operation rounded on its own
+ * dens_out_d[nw][L][nspec] = dens_in_d * ratio (one multiply), temps_out_d[nw][L] = temps_in_d,
+ * ratios_out_d[nw][nspec] (or NULL), reject_out_d[nw].  A walker with a ratio that is negative or
+ * not finite gets 0 in every element of dens_out_d and temps_out_d (pb_walker_atmosphere's reject
+ * contract: pb_reject_walkers turns it into +inf band fluxes) and reject PB_ISO_REJECT, else 0;
+ * its ratios_out row holds the ratios as formed.  pars_d[nw][npars] may be NULL when no slot is
+ * PB_ISO_FREE.  Limits (PB_ERR_ARG beyond them): nspec <= 4096 (a walker's ratios are held in LDS),
+ * nlayers * nspec <= INT32_MAX (a walker's slab is indexed in 32 bits).  The outputs may not
+ * overlap the inputs.  The model struct (a host struct) is
+ * checked before any HIP call.  nwalkers == 0: nothing launched. */
+#define PB_ISO_MAX_SLOTS 32
+#define PB_ISO_MAX_FILLERS 7
+#define PB_ISO_CONST 0
+#define PB_ISO_FREE 1
+#define PB_ISO_FILL 2
+#define PB_ISO_REJECT 32            /* continues the PB_ATM_REJECT_* bits */
+typedef struct pb_iso_model {
+    int nspec, npars, nlabelled;
+    int slot[PB_ISO_MAX_SLOTS];
+    int kind[PB_ISO_MAX_SLOTS];
+    int par[PB_ISO_MAX_SLOTS];
+    int nfill[PB_ISO_MAX_SLOTS];
+    int fill[PB_ISO_MAX_SLOTS][PB_ISO_MAX_FILLERS];
+    double constant[PB_ISO_MAX_SLOTS];
+} pb_iso_model;
+int pb_iso_density(double *dens_out_d, double *temps_out_d, double *ratios_out_d,
+                   int32_t *reject_out_d, const double *dens_in_d, const double *temps_in_d,
+                   const double *pars_d, const pb_iso_model *model, int nlayers, int nwalkers,
+                   void *stream);
+
 /* ---- Posterior summary: weighted column quantiles (pb_quantiles.hip).  The reduction of
  * posterior_post_processing (pyratbay/tools/retrieval_tools.py:384-503: np.percentile of
  * models[uinv] along the samples, per wavenumber / band / layer) on the UNIQUE samples and their

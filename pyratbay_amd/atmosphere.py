@@ -30,11 +30,15 @@ EULER = 0.57721566490153286061
 E2_CUTOFF = 88.029691931113054296     # log(2**127): the reference's E2 returns 0 above it
 
 MAX_SPECIES, MAX_VMR, MAX_BULK, MAX_LAYERS = 32, 16, 4, 1024
+# isotope ratios of the table's slots (isotopes.py): labelled slots, fillers of one fill slot
+MAX_ISO_SLOTS, MAX_ISO_FILLERS = 32, 7
 REJECT_TEMP, REJECT_MADHU, REJECT_QCAP, REJECT_REFPRESSURE, REJECT_DIVERGENT = 1, 2, 4, 8, 16
+REJECT_ISOTOPE = 32                    # a non-finite or negative isotope ratio (isotopes.py)
 REJECT_NAMES = {REJECT_TEMP: 'temperature <= 0 or not finite', REJECT_MADHU: 'madhu log_p1 > log_p3',
                 REJECT_QCAP: 'trace abundances above qcap',
                 REJECT_REFPRESSURE: 'reference pressure outside the grid',
-                REJECT_DIVERGENT: 'divergent hydro_m profile, or a radius <= 0 or not finite'}
+                REJECT_DIVERGENT: 'divergent hydro_m profile, or a radius <= 0 or not finite',
+                REJECT_ISOTOPE: 'a negative or non-finite isotope ratio'}
 
 
 # ---------------------------------------------------------------------------------------------

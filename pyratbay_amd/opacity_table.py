@@ -12,6 +12,7 @@ units).
 import numpy as np
 import torch
 
+from . import isotopes as iso
 from ._capi import call
 from ._device import _ptr, _stream, dev, require_gpu
 from .table import TableSpectrum
@@ -139,27 +140,37 @@ def _brackets(x_table, x_new):
 class CrossSections:
     """species[nspec], temp[ntemp] (K), press[nlayers] (bar), wn[nwave] (cm-1) and
     cs_table[nspec, ntemp, nlayers, nwave] (cm2 molecule-1, device tensor): the attributes of
-    the reference's Line_Sample that the retrieval path reads."""
+    the reference's Line_Sample that the retrieval path reads.  isotopes: the
+    isotopes.IsotopeRatios of a table loaded with an isotope_ratios block (species then repeats
+    a molecule's name once per labelled slot, as in the reference), else None."""
 
-    def __init__(self, species, temp, press, wn, cs_table):
+    def __init__(self, species, temp, press, wn, cs_table, isotopes=None):
         self.species, self.temp, self.press, self.wn = species, temp, press, wn
         self.cs_table = cs_table
+        self.isotopes = isotopes
         self.nspec, self.ntemp, self.nlayers, self.nwave = cs_table.shape
         self.tmin, self.tmax = float(np.amin(temp)), float(np.amax(temp))
 
     def table_spectrum(self, radius, rstar, **kw):
         """A table.TableSpectrum on this table (the path of Pyrat.eval())."""
+        if self.isotopes is not None:
+            kw.setdefault('isotopes', self.isotopes)
         return TableSpectrum(self.cs_table, self.temp, self.wn, radius, rstar, **kw)
 
 
 def load_cross_sections(cs_files, temperature=None, pressure=None, min_wn=None, max_wn=None,
-                        min_wl=None, max_wl=None, wl_thinning=1):
-    """Line_Sample.__init__ without its isotope-ratio parameters: read the opacity files, keep
-    the wavenumber window [min_wn, max_wn] (or wavelengths in microns) thinned by wl_thinning,
+                        min_wl=None, max_wl=None, wl_thinning=1, isotope_ratios=None):
+    """Line_Sample.__init__: read the opacity files, keep the wavenumber window [min_wn, max_wn]
+    (or wavelengths in microns) thinned by wl_thinning,
     bring every file onto (temperature, pressure) -- default: the first file's -- with
     tools.interpolate_opacity's rule, ADD the files of a species.  Same errors as the reference
     for mismatching wavenumber grids and for a pressure profile beyond a table.  The table is
-    assembled on the device (pb_resample_cross_section): files are uploaded one at a time."""
+    assembled on the device (pb_resample_cross_section): files are uploaded one at a time.
+    isotope_ratios: the reference's block, one line `key label ratio` per isotopologue
+    (isotopes.parse): a file whose path contains `key` goes to the table slot of (its species,
+    label) -- slots in first-seen order, files of one slot are added -- and the result carries
+    .isotopes, an isotopes.IsotopeRatios.  Same errors as the reference for two keys matching
+    one file and for an unknown filler.  None: one slot per species, as before."""
     if isinstance(cs_files, str):
         cs_files = [cs_files]
     if min_wn is not None and max_wl is not None:
@@ -175,7 +186,8 @@ def load_cross_sections(cs_files, temperature=None, pressure=None, min_wn=None, 
     temp = np.asarray(temp0 if temperature is None else temperature, float)
     press = np.asarray(press0 if pressure is None else pressure, float)
     wn = np.asarray(wn0)[_wn_mask(wn0, min_wn, max_wn)][::wl_thinning]
-    species, index, masks, grids = [], [], [], []
+    species, index, masks, grids, file_species = [], [], [], [], []
+    entries = None if isotope_ratios is None else iso.parse(isotope_ratios)
     for f in cs_files:
         sp, ttab, ptab, wtab = read_opacity(f, extract='arrays')
         mask = _wn_mask(wtab, min_wn, max_wn)
@@ -188,8 +200,13 @@ def load_cross_sections(cs_files, temperature=None, pressure=None, min_wn=None, 
         if sp not in species:
             species.append(sp)
         index.append(species.index(sp))
+        file_species.append(sp)
         masks.append(mask)
         grids.append((np.asarray(ttab, float), np.asarray(ptab, float)))
+    isotopes = None
+    if entries is not None:
+        species, labels, index = iso.assign(entries, cs_files, file_species)
+        isotopes = iso.IsotopeRatios(species, labels, entries)
     require_gpu()
     table = torch.zeros((len(species), len(temp), len(press), len(wn)), dtype=torch.float64,
                         device='cuda')
@@ -222,4 +239,4 @@ def load_cross_sections(cs_files, temperature=None, pressure=None, min_wn=None, 
              cs.shape[2], len(temp), len(press), len(wn), int(resample), 1,
              _stream())
         torch.cuda.synchronize()
-    return CrossSections(np.array(species), temp, press, wn, table)
+    return CrossSections(np.array(species), temp, press, wn, table, isotopes=isotopes)

@@ -138,7 +138,7 @@ PosteriorSummary = collections.namedtuple(
 
 # per-walker keywords of eval_bands: posterior_summary hands each chunk its rows
 _PER_SAMPLE = ('continuum_pars', 'rv', 'deck_logp', 'f_patchy', 'f_dilution', 'tstar',
-               'rplanet')
+               'rplanet', 'iso_pars')
 
 
 def posterior_summary(model, atmosphere, params, counts, bands, quantiles=QUANTILES, chunk=64,

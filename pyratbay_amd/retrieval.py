@@ -145,12 +145,15 @@ class Retrieval:
         log_p_ref    the atmosphere's free 'log_refpressure'
         log_k_ray, alpha_ray                  the Lecavelier columns of continuum_pars
         log_k_gray, log_p_top, log_p_bot      the CCSgray columns of continuum_pars
+        iso_<label> (model.isotopes.pnames)   that column of iso_pars (log10 of the isotope ratio
+                                              of a table slot, line_sampling.py:282-298)
         log_p_cl -> deck_logp    f_patchy -> f_patchy    rv_shift -> rv
         T_eff -> tstar           f_dilution -> f_dilution
         observation.offset_models -> offsets         observation.err_models -> err_pars
     Every column of a destination that no line names is a constant of the map: fixed[name] (in
     the units of a retrieval_params line), else the objects' current value (the atmosphere's
-    base_params, cont.current_pars(), no offset, the error models' defaults); neither: ValueError.
+    base_params, cont.current_pars(), the isotope model's default pars, no offset, the error
+    models' defaults); neither: ValueError.
 
     pstep (tools/retrieval_tools.py:45-46, 91-93): > 0 free; == 0 fixed at `value`; < 0 shared with
     parameter -int(pstep) - 1, which must not be shared itself (DEVIATION, module docstring).
@@ -256,6 +259,12 @@ class Retrieval:
         two_stream = rt_path == 'two_stream'
         cloudy_two_stream = ('eval_bands: {}: clouds are not supported in batched form in '
                              'two-stream geometry; use eval()')
+        # the isotope ratios of the sampled cross sections ('line sampling' in the reference)
+        iso = getattr(model, 'isotopes', None)
+        self.iso_pnames = [] if iso is None else list(iso.pnames)
+        for col, name in enumerate(self.iso_pnames):
+            self.opacity_pnames.append(name)
+            slots.setdefault(name, ('iso_pars', col, 1.0))
         ndeck = 0 if cont is None else len(cont.deck)
         if ndeck:
             self.opacity_pnames.append('log_p_cl')
@@ -318,14 +327,14 @@ class Retrieval:
         # the destination tensors of this retrieval, in a fixed order, with their column counts
         ncols = {'params': atm.npar,
                  'continuum_pars': 0 if cont is None else len(cont.free_pars),
-                 'offsets': obs.noff, 'err_pars': obs.nerr}
+                 'iso_pars': len(self.iso_pnames), 'offsets': obs.noff, 'err_pars': obs.nerr}
         wanted = {'params'} | {d for d, _, _ in dest_of} | {d for d, _, _ in fixed_of.values()}
         if 'tstar' not in wanted:
             if getattr(self.bands, 'star_grid', None) is not None:
                 raise ValueError(_table.MSG_GRID_NEEDS_TSTAR)
             if getattr(model, 'irradiation', None) is not None:
                 raise ValueError(_table.MSG_IRRADIATION_NEEDS_TSTAR)
-        order = ('params', 'continuum_pars') + _SCALAR_DESTS + ('offsets', 'err_pars')
+        order = ('params', 'continuum_pars', 'iso_pars') + _SCALAR_DESTS + ('offsets', 'err_pars')
         self.dest_names = [d for d in order if d in wanted]
         self.dest_ncols = [ncols.get(d, 1) for d in self.dest_names]
         if len(self.dest_names) > MAX_DESTS:
@@ -334,8 +343,11 @@ class Retrieval:
         # what the objects hold now, for the columns nobody names
         current = {'params': getattr(atm, 'base_params', None),
                    'continuum_pars': None if cont is None else cont.current_pars(),
+                   'iso_pars': None if not self.iso_pnames else
+                   np.array(model.isotopes.pars, float),
                    'offsets': np.zeros(obs.noff), 'err_pars': np.array(obs.err_defaults, float)}
         column_names = {'params': list(atm.free), 'continuum_pars': self.cont_pnames,
+                        'iso_pars': self.iso_pnames,
                         'offsets': list(obs.offset_models), 'err_pars': list(obs.err_models)}
         src, cons, factor, dest, col = [], [], [], [], []
 
@@ -396,6 +408,9 @@ class Retrieval:
                 mname, idx = cont.free_pars[k]
                 self.iopacity.setdefault(mname, []).append(i)
                 self.map_pars['opacity'].setdefault(mname, []).append(idx)
+            elif d == 'iso_pars':
+                self.iopacity.setdefault('line sampling', []).append(i)
+                self.map_pars['opacity'].setdefault('line sampling', []).append(k)
             elif d == 'deck_logp':
                 self.iopacity.setdefault('deck', []).append(i)
                 self.map_pars['opacity'].setdefault('deck', []).append(0)
@@ -442,7 +457,8 @@ class Retrieval:
 
     def split_host(self, theta, substitute=True):
         """theta[nw, nfree] -> {destination: array}: 'params'[nw, npar of the atmosphere] and, as
-        far as this retrieval has them, 'continuum_pars'[nw, ncont], 'deck_logp', 'f_patchy',
+        far as this retrieval has them, 'continuum_pars'[nw, ncont], 'iso_pars'[nw, niso],
+        'deck_logp', 'f_patchy',
         'rv', 'tstar', 'f_dilution' [nw], 'offsets'[nw, noff], 'err_pars'[nw, nerr]: copies, and
         one multiply where the unit factor is not 1.  substitute: a walker that is not inside is
         mapped from the `value` column, as the device does."""
@@ -549,7 +565,7 @@ class Retrieval:
              _ptr(d['value']), _ptr(d['pmin']), _ptr(d['pmax']), _ptr(d['prior']),
              _ptr(d['priorlow']), _ptr(d['priorup']), self.nmap, self.nfree, nw, _stream())
         named = dict(zip(self.dest_names, outs))
-        kw = {k: named[k] for k in ('continuum_pars',) + _SCALAR_DESTS if k in named}
+        kw = {k: named[k] for k in ('continuum_pars', 'iso_pars') + _SCALAR_DESTS if k in named}
         return RetrievalArguments(named['params'], kw, named.get('offsets'),
                                   named.get('err_pars'), log_prior, inside)
 

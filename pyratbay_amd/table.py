@@ -28,7 +28,8 @@ from .radeq import RadiativeEquilibrium
 # contribution_out[nw, L, nbands] receives the band contribution functions (None: not asked for),
 # dlogp[L-1] = diff(log(contribution_pressure)) on the device (emission and two-stream geometry);
 # tstar[nw] / rplanet[nw]: the walkers' stellar temperatures and planet radii for the eclipse
-# factor of bands.set_eclipse_grid (None: not given).
+# factor of bands.set_eclipse_grid (None: not given).  On a model with isotope ratios temps and
+# dens are the SCALED tensors (isotopes.IsotopeRatios.scale): zeros for a walker it rejects.
 BatchCall = namedtuple('BatchCall', (
     'temps dens bands radius shared_radius f_dilution continuum_density continuum_pars '
     'alkali_density rv deck_logp f_patchy spectra_out out nw cloudy tmin tmax path1 '
@@ -140,7 +141,7 @@ class TableSpectrum:
     def __init__(self, etable, ttable, wn, radius, rstar, rt_path='transit', itop=0,
                  maxdepth=10.0, quadrature_mu=None, quadrature_weights=None, continuum=None,
                  timestamps=True, column_order='auto', tint=0.0, flux_top=None,
-                 irradiation=None):
+                 irradiation=None, isotopes=None):
         require_gpu()
         # rt_path 'two_stream' / 'emission_two_stream' / 'eclipse_two_stream' (RT_PATHS, as in
         # LBLSpectrum): the geometry 'two_stream' (pyrat/spectrum.py:454-522) with the internal
@@ -193,6 +194,14 @@ class TableSpectrum:
         self.one_pass = None
         self.etable = etable if isinstance(etable, torch.Tensor) else dev(etable)
         self.nspec, self.ntemp, self.nlayers, self.nwave = self.etable.shape
+        # isotopes (an isotopes.IsotopeRatios: opacity_table.load_cross_sections(...,
+        # isotope_ratios=) makes it; None: none): every table slot's density is multiplied by its
+        # isotope ratio (line_sampling.py:451-456) before the table is interpolated -- eval() and
+        # eval_bands take the walkers' log10 ratios as iso_pars, None: the block's defaults
+        if isotopes is not None and isotopes.nspec != self.nspec:
+            raise ValueError(f'isotopes: the model has {isotopes.nspec} slots, the table '
+                             f'{self.nspec}')
+        self.isotopes = isotopes
         self.ttable = dev(ttable)
         self.tmin, self.tmax = float(np.min(ttable)), float(np.max(ttable))
         self.wn = dev(wn)
@@ -299,11 +308,26 @@ class TableSpectrum:
         else:
             self.intervals = dev(-np.diff(np.asarray(radius, float)))
 
-    def eval(self, temp, dens, continuum_density=None):
+    def eval(self, temp, dens, continuum_density=None, iso_pars=None):
         """temp[L] (K, inside the table's range -- the caller rejects the rest like
         line_sampling.py:426-427), dens[L, nspec] (molecules cm-3) -> spectrum[W].
         With a Continuum attached, continuum_density = {species: n[L]} feeds its terms
-        (pyrat/opacity.py:206-257: every model adds to the same ec)."""
+        (pyrat/opacity.py:206-257: every model adds to the same ec).  On a model with isotope
+        ratios dens[L, nspec] holds the density of every slot's SPECIES and is multiplied by the
+        slots' ratios (pb_iso_density): iso_pars[npars], a host vector of log10 ratios in
+        isotopes.pnames order (None: the defaults); a negative or non-finite ratio is refused
+        (ValueError), like a temperature outside the table."""
+        iso = getattr(self, 'isotopes', None)
+        if iso_pars is not None and iso is None:
+            raise ValueError('eval: iso_pars on a model without isotope ratios')
+        if iso is not None:
+            if iso_pars is not None:
+                iso_pars = np.asarray(iso_pars, float).reshape(1, -1)
+            # (the block's defaults can be bad too: fillers that sum above 1)
+            ratios = iso.iso_ratios if iso_pars is None else iso.ratios_host(iso_pars)[0]
+            if not np.all(np.isfinite(ratios) & (ratios >= 0.0)):
+                raise ValueError(f'eval: iso_pars give a negative or non-finite isotope ratio '
+                                 f'({ratios}; the reference carries on with a negative opacity)')
         temp_host = None if isinstance(temp, torch.Tensor) else np.asarray(temp, float)
         if temp_host is not None and (np.any(temp_host < self.tmin) or
                                       np.any(temp_host > self.tmax)):
@@ -315,6 +339,10 @@ class TableSpectrum:
                              'use eval_bands(..., tstar=)')
         self.temp = temp if isinstance(temp, torch.Tensor) else dev(temp)
         dens = dens if isinstance(dens, torch.Tensor) else dev(dens)
+        if iso is not None:
+            _, dens, _, _ = iso.scale(self.temp.reshape(1, -1), dens.unsqueeze(0),
+                                      None if iso_pars is None else dev(iso_pars))
+            dens = dens[0]
         t = self._timer
         if t is not None:
             t.start('extinction')
@@ -385,7 +413,8 @@ class TableSpectrum:
     def eval_bands(self, temps, dens, bands, radius=None, chunk=64, streams=None,
                    f_dilution=None, continuum_density=None, continuum_pars=None, rv=None,
                    deck_logp=None, f_patchy=None, alkali_density=None, spectra_out=None,
-                   contribution_out=None, contribution_pressure=None, tstar=None, rplanet=None):
+                   contribution_out=None, contribution_pressure=None, tstar=None, rplanet=None,
+                   iso_pars=None):
         """Batched-walker evaluation (the inner loop of a retrieval, pyrat_obj.py:225-385
         without the parameter mapping -- eval_params adds it): temps[nw, L], dens[nw, L, nspec] device tensors,
         optional per-walker radius[nw, L] (the hydrostatic profile changes with every model),
@@ -494,11 +523,22 @@ class TableSpectrum:
         bands without a grid are then allowed (tstar moves the irradiation only), and such a model
         without tstar is refused.  On a model built with a shared flux_top the irradiation is
         FROZEN at the temperature flux_top was formed with, whatever tstar is: tstar then moves
-        the eclipse factor only."""
+        the eclipse factor only.
+
+        Isotope ratios (a model built with isotopes=, an isotopes.IsotopeRatios; Line_Sample's
+        isotope_ratios, line_sampling.py:282-298, 451-456): dens[nw, L, nspec] holds the density
+        of every slot's SPECIES (a 12CO and a 13CO slot both CO's) and ONE launch per call
+        (pb_iso_density, before the chunks) multiplies it by the walkers' ratios: iso_pars[nw,
+        npars], a float64 device tensor of log10 ratios in isotopes.pnames order, None: the
+        block's defaults.  Every form above then runs on the scaled densities with no change.
+        DEVIATION: a walker with a negative or non-finite ratio (a fill slot whose fillers sum
+        above 1, a NaN parameter) is rejected, +inf like one outside the table's temperatures;
+        the reference carries on with a negative opacity.  iso_pars on a model without isotopes,
+        or of another shape, is refused (ValueError) before any launch."""
         call_ = self._batch_call(temps, dens, bands, radius, f_dilution, continuum_density,
                                  continuum_pars, rv, deck_logp, f_patchy, alkali_density,
                                  spectra_out, contribution_out, contribution_pressure, tstar,
-                                 rplanet)
+                                 rplanet, iso_pars)
         nw = call_.nw
         one_pass = self.rt_path == 'transit' and self._one_pass()
         call_facts = {'cloudy': call_.cloudy}
@@ -532,15 +572,18 @@ class TableSpectrum:
                 self._eval_chunk(plan, call_, w0, min(w0 + chunk, nw))
         for st in eval_streams:
             caller.wait_stream(st)
-        # (with CIA tables: the intersection of their temperature ranges and the table's)
-        call('pb_reject_walkers', _ptr(call_.out), _ptr(temps.contiguous()), call_.tmin,
+        # (with CIA tables: the intersection of their temperature ranges and the table's; with
+        # isotope ratios: the scaled call's temperatures, zeros for a walker they reject)
+        call('pb_reject_walkers', _ptr(call_.out), _ptr(call_.temps.contiguous()), call_.tmin,
              call_.tmax, self.nlayers, bands.nbands, nw, _stream())
         return call_.out
 
     def _batch_call(self, temps, dens, bands, radius, f_dilution, continuum_density,
                     continuum_pars, rv, deck_logp, f_patchy, alkali_density, spectra_out,
-                    contribution_out=None, contribution_pressure=None, tstar=None, rplanet=None):
-        """The arguments of eval_bands, checked and filled -> BatchCall (allocates `out`)."""
+                    contribution_out=None, contribution_pressure=None, tstar=None, rplanet=None,
+                    iso_pars=None):
+        """The arguments of eval_bands, checked and filled -> BatchCall (allocates `out`; on a
+        model with isotope ratios its one launch scales temps and dens, after every check)."""
         assert self.rt_path in ('transit', 'emission', 'two_stream'), \
             'eval_bands: transit, emission or two-stream geometry on sampled cross sections'
         two_stream_rt = self.rt_path == 'two_stream'
@@ -554,6 +597,17 @@ class TableSpectrum:
             'f_dilution: emission geometry'
         assert f_dilution is None or f_dilution.shape == (temps.shape[0],)
         nw = temps.shape[0]
+        iso = getattr(self, 'isotopes', None)
+        if iso is None and iso_pars is not None:
+            raise ValueError('eval_bands: iso_pars on a model without isotope ratios '
+                             '(TableSpectrum(..., isotopes=))')
+        if iso is not None:
+            iso.check_pars('eval_bands: iso_pars', iso_pars, nw)
+            if not isinstance(dens, torch.Tensor) or \
+                    tuple(dens.shape) != (nw, self.nlayers, self.nspec):
+                raise ValueError(f'eval_bands: dens must have shape '
+                                 f'{(nw, self.nlayers, self.nspec)} (slots {list(iso.species)}), '
+                                 f'got {tuple(getattr(dens, "shape", ()))}')
         grid = getattr(bands, 'star_grid', None)
         irradiation = getattr(self, 'irradiation', None)
         if tstar is not None or rplanet is not None:
@@ -670,6 +724,8 @@ class TableSpectrum:
                 dlogp = batch.contribution_dlogp(contribution_pressure, self.nlayers)
         elif contribution_pressure is not None:
             raise ValueError('eval_bands: contribution_pressure without contribution_out')
+        if iso is not None:
+            temps, dens, _, _ = iso.scale(temps, dens, iso_pars)
         out = torch.empty((nw, bands.nbands), dtype=torch.float64, device='cuda')
         if radius is None:
             radius = self.radius.view(1, -1)
@@ -709,7 +765,7 @@ class TableSpectrum:
         and the continuum / alkali densities in one launch (WalkerAtmosphere.evaluate), and those
         tensors go to eval_bands unchanged; kw: everything else eval_bands takes (continuum_pars,
         rv, deck_logp, f_patchy, f_dilution, chunk, streams, spectra_out, contribution_out,
-        contribution_pressure, tstar).  Walkers the atmosphere rejects
+        contribution_pressure, tstar, iso_pars).  Walkers the atmosphere rejects
         (non-positive temperature, trace abundances above qcap, ...: WalkerAtmosphere) come out
         as +inf like those outside the table's temperatures.  When the atmosphere has 'rplanet'
         free and the bands carry a stellar SED grid (PassBands.set_eclipse_grid), that column of
@@ -756,8 +812,9 @@ class TableSpectrum:
         order) of the chain -- each sample counts[i] times, np.percentile's bits, the expansion
         never formed.  -> posterior.PosteriorSummary of device tensors: spectrum[nq, nwave],
         bands[nq, nbands], temperature[nq, L], vmr[nq, L, nspec] (nspec: the table's species, the
-        atmosphere's dens output times k T / p), n_rejected, quantiles, stores (None unless
-        keep_stores=True: the four stores and the counts used).
+        atmosphere's dens output times k T / p -- on a model with isotope ratios the unscaled
+        one, as the reference stores atm.vmr: a 12CO and a 13CO slot both show CO's), n_rejected,
+        quantiles, stores (None unless keep_stores=True: the four stores and the counts used).
 
         DEVIATION: samples the batch rejects (+inf band fluxes: outside the table's temperatures,
         a radial velocity beyond rv_max; or a reject flag of the atmosphere) get count 0 before the
@@ -766,8 +823,8 @@ class TableSpectrum:
         of the expansion), otherwise launches only.  The spectrum store takes 8 nwave n bytes: a
         store that does not fit in free device memory is refused (ValueError) before anything is
         allocated.  kw: what eval_bands takes per walker (continuum_pars, rv, deck_logp, f_patchy,
-        f_dilution, tstar, rplanet) with one row per sample, and streams; a free 'rplanet' of the
-        atmosphere enters the eclipse factor of bands with a stellar SED grid as in eval_params.
+        f_dilution, tstar, rplanet, iso_pars) with one row per sample, and streams; a free
+        'rplanet' of the atmosphere enters the eclipse factor of bands with a stellar SED grid as in eval_params.
 
         contribution=True adds the reference's fifth product, the median over the chain of the
         band contribution functions (eval_bands' contribution_out, with atmosphere.pressure; pass
@@ -783,7 +840,12 @@ class TableSpectrum:
         """The radiative-equilibrium iteration (runmode = radeq, pyrat_obj.py:559-646) of a batch
         of profiles on this model's table, grid and Continuum, at fixed volume mixing ratios: a
         pyratbay_amd.radeq.RadiativeEquilibrium (its docstring has the keywords); .run(temp0,
-        nsamples) iterates on the device.  Two-stream geometry only."""
+        nsamples) iterates on the device.  Two-stream geometry only; a model with isotope ratios
+        is refused (ValueError)."""
+        if getattr(self, 'isotopes', None) is not None:
+            raise ValueError('radiative_equilibrium: a model with isotope ratios (isotopes=) is '
+                             'not supported: the iteration forms its densities from vmr and '
+                             'would not scale them')
         return RadiativeEquilibrium(self, pressure, vmr, mol_mass, **kw)
 
     def _ordered_supported(self):
