@@ -1,7 +1,8 @@
 // Two-stream fluxes (pyratbay/pyrat/spectrum.py:454-522; Heng et al. 2014 Eqs. B5-B6): the
 // statements of one layer interval, shared by the single-spectrum kernels (k_two_stream_trans,
-// k_two_stream) and the walker batch (k_two_stream_batch) -- every kernel forms them this way
-// (same bits).
+// k_two_stream), the walker batch (k_two_stream_batch) and the net-flux batch
+// (k_two_stream_net_batch, pb_radeq.hip) -- every kernel forms them this way (same bits).
+// tests/test_gpu_two_stream_exact.py holds all four to 50-digit values of these formulas.
 #pragma once
 
 #include "pb_common.h"
@@ -39,6 +40,16 @@ __device__ inline double two_stream_trans(double dtau0)
     return (1 - dtau0) * exp_s(-dtau0) + dtau0 * dtau0 * exp1_real(dtau0);
 }
 
+// 1 - exp(-dtau0) of the sweeps' bracket, from expm1.  A deviation from the reference's bits
+// (DESIGN.md): there the bracket -2/3 (1 - exp(-dtau0)) + dtau0 (1 - trans / 3) cancels from
+// O(dtau0) to O(dtau0^2) while 1 - exp(-dtau0) carries an absolute error of 2^-53, and
+// bp = dB / dtau0 multiplies what is left: pi |dB| 2^-53 / dtau0 per interval, O(1) of the flux at
+// dtau0 = 1e-15.  With expm1 both terms of the bracket are good to their own size.
+__device__ inline double two_stream_gone(double dtau0)
+{
+    return -expm1(-dtau0);
+}
+
 // downward sweep, interval (i, i+1): flux_down[i] -> flux_down[i+1]; btop = B[i], bbot = B[i+1]
 __device__ inline double two_stream_down(double down, double trans, double dtau0, double btop,
                                          double bbot)
@@ -46,7 +57,7 @@ __device__ inline double two_stream_down(double down, double trans, double dtau0
     const double pi = 3.141592653589793;
     const double bp = (bbot - btop) / dtau0;
     return trans * down + pi * btop * (1 - trans) +
-           pi * bp * (-2.0 / 3 * (1 - exp_s(-dtau0)) + dtau0 * (1 - trans / 3));
+           pi * bp * (-2.0 / 3 * two_stream_gone(dtau0) + dtau0 * (1 - trans / 3));
 }
 
 // upward sweep, interval (i, i+1): flux_up[i+1] -> flux_up[i]
@@ -56,7 +67,7 @@ __device__ inline double two_stream_up(double up, double trans, double dtau0, do
     const double pi = 3.141592653589793;
     const double bp = (bbot - btop) / dtau0;
     return trans * up + pi * bbot * (1 - trans) +
-           pi * bp * (2.0 / 3 * (1 - exp_s(-dtau0)) - dtau0 * (1 - trans / 3));
+           pi * bp * (2.0 / 3 * two_stream_gone(dtau0) - dtau0 * (1 - trans / 3));
 }
 
 }  // namespace pb

@@ -14,7 +14,8 @@
 // read; every thread owns its column) and trans[i] in work[nw][L-1][W].  That is 40 B of traffic
 // per (interval, column) -- 8 read + 16 written going down, 16 read going up -- against a second
 // exp1 (a 25-term series or a continued fraction of 20 + 80/x FP64 divisions) per cell if trans
-// were recomputed.  exp(-dtau0) is recomputed on the way up (25 instructions, no traffic).
+// were recomputed.  The bracket's 1 - exp(-dtau0) (pb_two_stream.h: from expm1) is recomputed on
+// the way up (no traffic).
 #include "pb_common.h"
 #include "pb_planck.h"
 #include "pb_two_stream.h"

@@ -14,7 +14,15 @@ layer's flux increment.  `fixture_bound` adds these up for every column:
 In the fixture (dtau from 1e-16 to 1e3) 705 of the 991 columns have bound <= 1e-10 -- there the
 oracle and the HIP kernel agree with the reference run to 2e-12 -- and the worst column has
 bound 3.4e-6 (measured error 9e-8, inside north_star's 1e-6).  Every column is held to its own
-bound; the well-conditioned synthetic case checks the implementation itself at 1e-11."""
+bound; the well-conditioned synthetic case checks the implementation itself at 1e-11.
+
+What `fixture_bound` describes is the error of the REFERENCE's run and of the oracle, which keeps
+the reference's form: the fixture's flux_up / flux_down carry that error themselves.  The HIP
+kernels no longer have it -- pb_two_stream.h forms the bracket's 1 - exp(-dtau) as -expm1(-dtau),
+a stated deviation from the reference's bits -- so their distance from this fixture on
+the thin columns is the fixture's own.  The kernels' error is measured in
+test_gpu_two_stream_exact.py, against 50-digit values of the formulas and a bound from rounding
+counts (two_stream_exact_cases.py); the bounds here are unchanged."""
 import numpy as np
 import pytest
 
