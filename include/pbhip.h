@@ -583,7 +583,16 @@ int pb_resample_cross_section(double *out_d, const double *in_d, const int32_t *
                               int nwave_out, int resample, int accumulate, void *stream);
 /* interp_ec (src_c/_extcoeff.c:367-418), assigning form, for a batch: temps_d[nwalkers,nlayers],
  * density_d[nwalkers,nlayers,nmol] -> ec_d[nwalkers,nlayers,nwave].  The table is read once per
- * chunk of walkers.  work_d: nwalkers*nlayers*136 bytes of device scratch.  nmol <= 8. */
+ * chunk of walkers.  work_d: pb_interp_ec_batch_work_doubles(...) doubles of device scratch (-1
+ * for a negative argument).  nmol <= 8. */
+int64_t pb_interp_ec_batch_work_doubles(int nlayers, int nwalkers);
+/* What a call of that shape would launch, with the PB_INTERP_* variables as they are now:
+ * out[6] (host) = walkers per chunk, two samples per thread (0/1), pair slots per thread, species
+ * held in registers (4 or 8), unpredicated species loop (0/1), grid.x.  aligned16: ec_d and
+ * etable_d both on 16 bytes; kcont: 0 no continuum, 1 continuum, 2 with H-; kalk: alkali lines.
+ * No device is touched: for tests of the launch decision, not a tuning interface. */
+int pb_interp_ec_batch_plan(int32_t *out, int nmol, int nlayers, int nwave, int nwalkers,
+                            int aligned16, int kcont, int kalk);
 int pb_interp_ec_batch(double *ec_d, const double *etable_d, const double *ttable_d,
                        const double *temps_d, const double *density_d, void *work_d, int nmol,
                        int ntemp, int nlayers, int nwave, int nwalkers, void *stream);

@@ -76,6 +76,8 @@ _PROTOS = {
     'pb_iso_partition': [vp, i64, i64, vp, i64, vp, i32, vp, i32, vp, vp],
     'pb_resample_cross_section': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
                                   i32, vp],
+    'pb_interp_ec_batch_work_doubles': [i32, i32],
+    'pb_interp_ec_batch_plan': [vp, i32, i32, i32, i32, i32, i32, i32],
     'pb_interp_ec_batch': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     'pb_transit_work_doubles': [i32, i32, i32, i32, i32],
     'pb_transit_spectrum_batch': [vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, i32, vp, vp],
@@ -183,6 +185,7 @@ _RESTYPES = {'pb_transit_work_doubles': C.c_int64, 'pb_two_stream_batch_work_dou
              'pb_weighted_quantiles_work_doubles': C.c_int64,
              'pb_weighted_quantiles_resident_rows': C.c_int,
              'pb_band_contribution_work_doubles': C.c_int64,
+             'pb_interp_ec_batch_work_doubles': C.c_int64,
              'pb_interp_ec_batch_cont_work_doubles': C.c_int64, 'pb_table_transit_work_doubles': C.c_int64,
              'pb_table_transit_supported': C.c_int, 'pb_voigt_destroy': None, 'pb_lines_destroy': None, 'pb_lbl_destroy': None,
              'pb_voigt_device_bytes': i64, 'pb_timer_destroy': None}

@@ -54,7 +54,8 @@ def interp_ec_batch(etable, ttable, temps, dens, out=None, tile_limit=None, row0
                  nlayers, nwave, nw, args, _ptr(tile_limit), int(row0), _ptr(gate), _stream())
         return out
     if work is None:
-        work = torch.empty(nw * nlayers * 17 + 8, dtype=torch.float64, device=etable.device)
+        work = torch.empty(_capi.lib().pb_interp_ec_batch_work_doubles(nlayers, nw),
+                           dtype=torch.float64, device=etable.device)
     if tile_limit is None and gate is None:
         call('pb_interp_ec_batch', _ptr(out), _ptr(etable), _ptr(ttable),
              _ptr(temps.contiguous()), _ptr(dens.contiguous()), _ptr(work), nmol, ntemp, nlayers,

@@ -2,7 +2,7 @@
 // of continuum.VanderWaals.voigt_det (pyratbay: opacity/alkali/alkali.py:48-82 ->
 // opacity/broadening.py:231-260), one value per (layer, line).  Shared by
 // pb_alkali_voigt_det_batch (pb_continuum.hip) and the batched continuum's k_cont_plan
-// (pb_interp.hip).
+// (pb_interp_cont.hip).
 #ifndef PB_ALKALI_VOIGT_H
 #define PB_ALKALI_VOIGT_H
 #include <hip/hip_runtime.h>

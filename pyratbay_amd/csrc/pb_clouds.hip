@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void k_deck_state(
 
 // ---------------------------------------------------------------------------
 // The factors of the cloud-type rank-1 models, with the expressions of k_cont_plan / k_cont_rows
-// (pb_interp.hip), which form the same models when they go into ec.
+// (pb_interp_cont.hip), which form the same models when they go into ec.
 // ---------------------------------------------------------------------------
 struct PlanArgs {
     double *f, *rows;

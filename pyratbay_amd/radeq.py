@@ -447,7 +447,7 @@ class RadiativeEquilibrium:
         d['work'] = new(max(int(_capi.lib().pb_two_stream_net_work_doubles(L, W, nw)), 1))
         cont = m.continuum
         if cont is None:
-            d['iwork'] = new(nw * L * 17 + 8)
+            d['iwork'] = new(int(_capi.lib().pb_interp_ec_batch_work_doubles(L, nw)))
         else:
             d['ops'] = cont.batch_operands(None)
             d['iwork'] = new(d['ops'].work_doubles(L, W, nw))

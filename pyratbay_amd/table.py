@@ -930,7 +930,8 @@ class TableSpectrum:
             return batch.interp_ec_batch(table, self.ttable, ci.temps, ci.dens, **ci.ckw), None
         n = ci.n
         flags = torch.zeros(n + 1, dtype=torch.int32, device=table.device)
-        iwork = torch.empty(n * self.nlayers * 17 + 8 if not ci.ckw else
+        iwork = torch.empty(_capi.lib().pb_interp_ec_batch_work_doubles(self.nlayers, n)
+                            if not ci.ckw else
                             ci.ckw['continuum'].work_doubles(self.nlayers, self.nwave, n),
                             dtype=torch.float64, device=table.device)
         twork = None

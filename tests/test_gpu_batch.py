@@ -297,7 +297,8 @@ def test_tile_limited_batch(eng, orc, L, itop, W):
         tile = tile.to(torch.int32).contiguous()
         flags = torch.zeros(nw + 1, dtype=torch.int32, device='cuda')
         ec = torch.full((nw, L, W), -7.0, dtype=torch.float64, device='cuda')
-        iwork = torch.empty(nw * L * 17 + 8, dtype=torch.float64, device='cuda')
+        iwork = torch.empty(eng._capi.lib().pb_interp_ec_batch_work_doubles(L, nw),
+                            dtype=torch.float64, device='cuda')
         eng.interp_ec_batch(eto, tt, td, dd, out=ec, tile_limit=tile, row0=itop, work=iwork)
         # what was written: exactly the layers itop ... itop + 16 (tile + 1) - 1 of each block
         # (a workgroup covers several blocks: up to the largest limit among them)

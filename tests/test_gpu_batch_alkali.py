@@ -49,11 +49,11 @@ def worst(got, want):
     return float(np.max(np.abs(np.asarray(got)[nz] / want[nz] - 1.0))) if nz.any() else 0.0
 
 
-def setup(g, nw, seed, L=None, full=True):
+def setup(g, nw, seed, L=None, full=True, tfac=None):
     """base.setup's table and walkers around G7's atmosphere; the continuum: Rayleigh H2 + He,
     Lecavelier, CIA H2-H2 + H2-He, H-, then Na and K (full), or Na and K alone."""
     from pyratbay_amd import continuum as ct
-    s = base.setup(g, nw, L=L, seed=seed, hminus=True, clouds=False)
+    s = base.setup(g, nw, L=L, seed=seed, hminus=True, clouds=False, tfac=tfac)
     wn, pressure = s['wn'], s['pressure']
     alk = alkali_models(g, ct, pressure)
     if full:
@@ -176,6 +176,22 @@ def test_ec_of_a_batch(eng, g):
     s = setup(g, nw, seed=42)
     got, want = host(fused_ec(eng, s, nw)), host(split_ec(eng, s, nw))
     print(f'ec, every term, against the split chain: {worst(got, want):.2e}')
+    np.testing.assert_allclose(got, want, rtol=1e-12)
+
+
+def test_epilogue_across_a_chunk(eng, g):
+    """64 walkers x 32 layers x 770 samples (both doublets inside) run in chunks of four walkers,
+    with CIA brackets shared and not shared inside a chunk: Na + K after every other term, against
+    the split chain at test_ec_of_a_batch's bound (walkers at 900 K and more)."""
+    nw, L, W = 64, 32, 770
+    gn = base.narrow(g, W)
+    s = setup(gn, nw, seed=47, L=L, tfac=base.chunk_tfac(np.random.default_rng(48), nw))
+    assert s['temps'].min() >= 900.0
+    base.assert_chunks_of_four(s, 3, 2)
+    for m in s['cont'].alkali:
+        assert gn['wn'][0] < min(m.wn0) and max(m.wn0) < gn['wn'][-1]
+    got, want = host(fused_ec(eng, s, nw)), host(split_ec(eng, s, nw))
+    print(f'chunks of four, every term, against the split chain: {worst(got, want):.2e}')
     np.testing.assert_allclose(got, want, rtol=1e-12)
 
 

@@ -50,7 +50,42 @@ def cia_models(g, ct):
     return out
 
 
-def setup(g, nw, L=None, seed=3, hminus=False, clouds=True):
+def narrow(g, W):
+    """G7 on its first W samples: the grid, and the CIA tables with their valid ranges."""
+    out = {k: g[k] for k in ('pressure', 'temp')}
+    out['wn'] = g['wn'][:W].copy()
+    for tag in ('h2h2', 'h2he'):
+        out[f'cia_{tag}_tab'] = np.ascontiguousarray(g[f'cia_{tag}_tab'][:, :W])
+        out[f'cia_{tag}_temps'] = g[f'cia_{tag}_temps']
+        out[f'cia_{tag}_lohi'] = np.minimum(g[f'cia_{tag}_lohi'], W)
+    return out
+
+
+def chunk_tfac(rng, nw):
+    """Temperature factors for walkers that run in chunks of four: the second walker of a chunk
+    0.02 % from the first (the same CIA bracket in nearly every layer), the others 4 % below and
+    above (other brackets); the chunks +-0.9 % apart.  Within setup()'s own +-5 %."""
+    return (np.tile([1.0, 1.0002, 0.96, 1.04], nw // 4) *
+            np.repeat(1 + 0.009 * rng.uniform(-1, 1, nw // 4), 4))[:, None]
+
+
+def assert_chunks_of_four(s, nmol, kcont):
+    """The launch runs four walkers per workgroup, and in every chunk there are layers where two
+    walkers share a CIA bracket and layers where two do not."""
+    import ctypes as C
+    from pyratbay_amd import _capi
+    nw, L = s['temps'].shape
+    out = (C.c_int32 * 6)()
+    _capi.call('pb_interp_ec_batch_plan', out, nmol, L, len(s['wn']), nw, 1, kcont, 0)
+    assert out[0] == 4
+    for m in s['cont'].cia:
+        idx = np.clip(np.searchsorted(m.temps, s['temps'], 'right') - 1, 0, len(m.temps) - 2)
+        idx = idx.reshape(nw // 4, 4, L)
+        assert np.all(np.any(idx[:, 0] == idx[:, 1], axis=1))
+        assert np.all(np.any(idx[:, 1] != idx[:, 2], axis=1))
+
+
+def setup(g, nw, L=None, seed=3, hminus=False, clouds=True, tfac=None):
     """A synthetic table on G7's grid, walkers around G7's atmosphere, and the continuum:
     Rayleigh H2 + He, [Lecavelier + CCSgray,] CIA H2-H2 + H2-He[, H-]."""
     from pyratbay_amd import continuum as ct
@@ -68,6 +103,8 @@ def setup(g, nw, L=None, seed=3, hminus=False, clouds=True):
     etable = 10.0**rng.uniform(-27, -22, (nspec, ntemp, L, 1)) * \
         10.0**rng.uniform(-1, 1, (nspec, 1, 1, W))
     temps = tbase * (1 + 0.05 * rng.uniform(-1, 1, (nw, 1)))
+    if tfac is not None:
+        temps = tbase * tfac
     ntot = pressure * 1e6 / temps / 1.380649e-16
     dens = ntot[:, :, None] * 10.0**rng.uniform(-7, -4, (nw, 1, nspec))
     models = [ct.Kurucz(wn, 'H2'), ct.Kurucz(wn, 'He')]
@@ -185,6 +222,27 @@ def test_fused_kernel_equals_interpolation_plus_continuum(eng, g):
     assert s2['cont'].species == ['H2', 'He', 'H', 'e-']
     assert np.array_equal(fused_ec(eng, s2, s2['cont'], None, 6),
                           split_ec(eng, s2, s2['cont'], None, 6))
+
+
+def test_epilogue_across_a_chunk(eng, g):
+    """64 walkers x 32 layers x 770 samples run in chunks of four walkers: the CIA rows a thread
+    holds while the next walker of its chunk shares the bracket, and reloads when it does not.
+    Rayleigh + CIA + H- bit for bit against the two steps; with Lecavelier and CCSgray 1e-14 (the
+    bounds of test_fused_kernel_equals_interpolation_plus_continuum)."""
+    nw, L, W = 64, 32, 770
+    gn = narrow(g, W)
+    rng = np.random.default_rng(61)
+    for clouds in (False, True):
+        s = setup(gn, nw, L=L, seed=62, hminus=True, clouds=clouds, tfac=chunk_tfac(rng, nw))
+        assert s['etable'].shape == (3, 11, L, W)
+        assert_chunks_of_four(s, 3, 2)
+        assert s['cont'].cia[0]._wn_hi_idx == 604 and s['cont'].cia[1]._wn_hi_idx == 754
+        want = split_ec(eng, s, s['cont'], s['pars'], nw)
+        got = fused_ec(eng, s, s['cont'], s['pars'], nw)
+        if clouds:
+            np.testing.assert_allclose(got, want, rtol=1e-14)
+        else:
+            assert np.array_equal(got, want)
 
 
 def test_transit_64_walkers(eng, orc, oc, g):

@@ -88,7 +88,9 @@ def limited_case(eng, rng):
     tile_d = eng.dev(tile, torch.int32)
     flags = torch.zeros(nw + 1, dtype=torch.int32, device='cuda')
     ec = torch.full((nw, L, W), -7.0, dtype=torch.float64, device='cuda')
-    iwork = torch.empty(nw * L * 17 + 8, dtype=torch.float64, device='cuda')
+    from pyratbay_amd import _capi
+    iwork = torch.empty(_capi.lib().pb_interp_ec_batch_work_doubles(L, nw), dtype=torch.float64,
+                        device='cuda')
     eng.interp_ec_batch(eto, tt, td, dd, out=ec, tile_limit=tile_d, row0=itop, work=iwork)
     written = ec != -7.0
     lay = torch.arange(L, device='cuda')[None, :, None]
