@@ -908,6 +908,88 @@ int pb_nested_finish(double *out_d, double *logw_d, double *logl_d, double *cdf_
 int pb_nested_resample(int64_t *counts_d, const double *cdf_d, int64_t n, int64_t nsamples,
                        uint64_t seed, void *stream);
 
+/* ---- Batched multi-start Levenberg-Marquardt (pb_optimize.hip): the maximum of the posterior and
+ * its Laplace covariance for nstarts starts at once, theta_d[nstarts,nfree], on residual vectors of
+ * m columns.  An iteration is pb_lm_probe -> the caller's residuals of probe_d -> pb_lm_normal ->
+ * pb_lm_step -> the caller's residuals of trial_d -> pb_lm_update, with nothing read back;
+ * pyratbay_amd/optimize.py states every kernel in NumPy (the specification).  Products and sums
+ * round separately; no atomics on doubles; every sum has one fixed order (below).  Refused with
+ * PB_ERR_ARG and a message: a null pointer, nfree outside 1 .. PB_RETRIEVAL_MAX_PARAMS, m < 1,
+ * ntrial outside 1 .. PB_LM_MAX_TRIALS, nu <= 1.  nstarts == 0: nothing launched.
+ *
+ * pb_lm_residuals: residuals_d[nw, ndata + ngauss] of a walker batch.  Column i < ndata is
+ * (data_i + offset - bandflux[w,i]) / uncert_i with the walker's offsets and uncertainty scaling
+ * exactly as pb_loglike_obs applies them; column ndata + j is (theta[w,k] - prior_k) / s_k,
+ * k = gauss_index_d[j] (an index outside 0 .. nfree - 1 gives +inf), s_k = priorlow_k for
+ * theta < prior_k, else priorup_k (prior_d, priorlow_d, priorup_d: [nfree]).  A walker with
+ * inside_d[w] == 0 or a non-finite band flux gets a row of +inf. */
+int pb_lm_residuals(double *residuals_d, const double *bandflux_d, const double *data_d,
+                    const double *uncert_d, const int32_t *offset_group_d,
+                    const double *offset_vals_d, double offset_unit, int noff,
+                    const int32_t *err_group_d, const int32_t *err_mode_d,
+                    const double *err_vals_d, double err_unit, int nerr, const double *theta_d,
+                    const int32_t *inside_d, const int32_t *gauss_index_d, const double *prior_d,
+                    const double *priorlow_d, const double *priorup_d, int ngauss, int nfree,
+                    int nwalkers, int ndata, void *stream);
+/* probe_d[nstarts, nfree + 1, nfree]: row 0 = theta, row k + 1 = theta + hs_k e_k with
+ * hs_k = h_k = fd_step scale_k, or -h_k where theta_k + h_k > pmax_k; step_d[nstarts, nfree] = hs. */
+int pb_lm_probe(double *probe_d, double *step_d, const double *theta_d, const double *pmax_d,
+                const double *scale_d, double fd_step, int nfree, int64_t nstarts, void *stream);
+/* The normal equations of every start from R_d[nstarts, nfree + 1, m], the residuals of probe_d:
+ * D_ik = R[s,k+1,i] - R[s,0,i]; S_kl = sum_i D_ik D_il, summed in index order by one thread;
+ *   A_d[s,k,l] = (S_kl / hs_min(k,l)) / hs_max(k,l)   (full, symmetric in bits)
+ *   g_d[s,k] = (sum_i D_ik R[s,0,i]) / hs_k           (index order)
+ *   cost_d[s] = 0.5 sum_i R[s,0,i]^2                  (64 lane-strided partial sums -- lane j takes
+ *               i = j, j + 64, ... -- then the xor butterfly 32, 16, .., 1)
+ * A column k with a non-finite D_ik is frozen: row and column k of A and g_k are 0.  Block =
+ * (start, 32 x 32 tile of the upper triangle), the m loop inside, PB_LM_CHUNK points of the tile's
+ * columns staged through LDS per step. */
+#define PB_LM_CHUNK 64
+#define PB_LM_MAX_TRIALS 16
+int pb_lm_normal(double *A_d, double *g_d, double *cost_d, const double *R_d, const double *step_d,
+                 int nfree, int m, int64_t nstarts, void *stream);
+/* doubles of work_d for pb_lm_step with ntrial trials and for pb_lm_covariance:
+ * nstarts nfree^2 max(ntrial, 2) (the Cholesky factors live there, one per block: a 128 x 128
+ * factor does not fit the 64 KiB of LDS a block gets). */
+int64_t pb_lm_work_doubles(int nfree, int ntrial, int64_t nstarts);
+/* The trial points trial_d[nstarts, ntrial, nfree].  Active set: k is active if theta_k <= pmin_k
+ * and g_k > 0, or theta_k >= pmax_k and g_k < 0, or A_kk == 0.  On the others (f), for
+ * lam_j = lam_d[s] nu^(j-1), j = 0 .. ntrial - 1 (lam / nu, then times nu per trial):
+ *   (A_ff + lam_j diag(A_ff)) delta = -g_f   by Cholesky (right-looking; column-oriented solves)
+ *   trial = min(max(theta + delta, pmin), pmax), active parameters unchanged.
+ * A pivot that is <= 0 or not finite, or a non-finite delta: trial = theta.
+ * pgrad_d[s] = max over f of |g_k| scale_k (0 without a free parameter). */
+int pb_lm_step(double *trial_d, double *pgrad_d, double *work_d, const double *A_d,
+               const double *g_d, const double *theta_d, const double *lam_d,
+               const double *pmin_d, const double *pmax_d, const double *scale_d, double nu,
+               int ntrial, int nfree, int64_t nstarts, void *stream);
+/* The decision of every start with status_d[s] == 0 (running) from Rt_d[nstarts, ntrial, m], the
+ * residuals of trial_d; a finished start is left untouched.  Status: 1 GTOL, 2 FTOL, 3 XTOL,
+ * 4 STALL, 5 MAXIT.  A non-finite cost_d[s]: STALL; else pgrad_d[s] <= gtol: GTOL (both without a
+ * step: picked_d[s] = -1, niter_d unchanged).  Otherwise the trial costs 0.5 |Rt|^2 in cost_d's
+ * order; the lowest finite one wins, ties to the lowest index.  Below cost_d[s]: accepted --
+ * theta_d[s] = that trial, cost_d[s] = its cost, lam = max(lam_j / nu, lam_min), picked_d[s] = j;
+ * FTOL if the decrease <= ftol max(cost, 1), else XTOL if max_k |dtheta_k| / scale_k <= xtol.
+ * Otherwise lam = lam nu^ntrial and picked_d[s] = -1.  Then niter_d[s] += 1; still running and
+ * lam > lam_max: STALL; still running and niter_d[s] >= max_iter: MAXIT.
+ * unfinished_d[0] = the number of starts still running (int32, always written). */
+int pb_lm_update(double *theta_d, double *cost_d, double *lam_d, int32_t *status_d,
+                 int32_t *niter_d, int32_t *picked_d, int32_t *unfinished_d,
+                 const double *trial_d, const double *Rt_d, const double *pgrad_d,
+                 const double *scale_d, double nu, double lam_min, double lam_max, double gtol,
+                 double ftol, double xtol, int max_iter, int ntrial, int nfree, int m,
+                 int64_t nstarts, void *stream);
+/* The Laplace covariance cov_d[nstarts, nfree, nfree] = (A_ff)^-1 on the parameters that are not
+ * active (pb_lm_step's rule; active_d[nstarts, nfree] = 1 / 0), 0 in the active rows and columns.
+ * Cholesky, one solve per column, the upper triangle mirrored: symmetric in bits.  Numerically
+ * singular -- a pivot that is not finite or not above nf eps A_pp, nf the free parameters, A_pp
+ * the diagonal before the factorisation --: NaN in the free block and singular_d[s] = 1 (else 0).
+ * work_d: pb_lm_work_doubles. */
+int pb_lm_covariance(double *cov_d, int32_t *active_d, int32_t *singular_d, double *work_d,
+                     const double *A_d, const double *g_d, const double *theta_d,
+                     const double *pmin_d, const double *pmax_d, int nfree, int64_t nstarts,
+                     void *stream);
+
 /* High-resolution data (eval()'s second exit, pyrat/pyrat_obj.py:331-356).
  * ps.inst_convolution's last step (spectrum/spec_tools.py:879) for a batch:
  *   out_d[w] = convolve(spectra_d[w] * sample_scale_d, taps_d, mode='same')

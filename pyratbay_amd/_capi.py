@@ -147,6 +147,15 @@ _PROTOS = {
                          vp],
     'pb_nested_finish': [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp],
     'pb_nested_resample': [vp, vp, i64, i64, u64, vp],
+    'pb_lm_residuals': [vp, vp, vp, vp, vp, vp, f64, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp,
+                        vp, i32, i32, i32, i32, vp],
+    'pb_lm_probe': [vp, vp, vp, vp, vp, f64, i32, i64, vp],
+    'pb_lm_normal': [vp, vp, vp, vp, vp, i32, i32, i64, vp],
+    'pb_lm_work_doubles': [i32, i32, i64],
+    'pb_lm_step': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, i32, i64, vp],
+    'pb_lm_update': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, f64,
+                     i32, i32, i32, i32, i64, vp],
+    'pb_lm_covariance': [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, vp],
     'pb_internal_flux': [vp, vp, f64, i32, vp],
     'pb_two_stream_net_parts': [i32],
     'pb_two_stream_net_work_doubles': [i32, i32, i32],
@@ -183,6 +192,7 @@ _EXP_PROTOS = {
 _RESTYPES = {'pb_transit_work_doubles': C.c_int64, 'pb_two_stream_batch_work_doubles': C.c_int64,
              'pb_two_stream_net_work_doubles': C.c_int64, 'pb_two_stream_net_parts': C.c_int,
              'pb_weighted_quantiles_work_doubles': C.c_int64,
+             'pb_lm_work_doubles': C.c_int64,
              'pb_weighted_quantiles_resident_rows': C.c_int,
              'pb_band_contribution_work_doubles': C.c_int64,
              'pb_interp_ec_batch_work_doubles': C.c_int64,

@@ -10,7 +10,9 @@ here (expand_host, split_host, log_prior_host, inside_host, prior_transform_host
 specification of the kernels in csrc/pb_retrieval.hip.  The sampler that drives the loop is this
 package's own (sampler.py: DEMC-zs on the device, csrc/pb_sampler.hip): draw_initial draws from the
 priors, sample builds and runs a sampler.DEMC over log_posterior, summary reduces its chain with
-model.posterior_summary.
+model.posterior_summary.  residuals is the same posterior as a residual vector, and optimize runs
+optimize.py's batched Levenberg-Marquardt over it (csrc/pb_optimize.hip): the maximum, the
+reference's `bestp`, and its Laplace covariance.
 
 DEVIATIONS from the reference:
   * a shared parameter (pstep < 0) whose target is itself shared is refused; the reference copies
@@ -18,7 +20,9 @@ DEVIATIONS from the reference:
   * a walker outside the bounds (inside == 0) is evaluated at the block's `value` column instead
     of its own row, so that no later kernel sees NaN or out-of-range input; it comes out as -inf
     from log_posterior and as -1e98 from log_likelihood;
-  * the Gaussian priors carry no normalisation term.
+  * the Gaussian priors carry no normalisation term;
+  * residuals and optimize refuse a retrieval with a free err_scale_* / err_quad_* parameter: its
+    objective is not a sum of squares (mc3's least-squares fit has the same limit).
 """
 from collections import namedtuple
 import ctypes as C
@@ -129,6 +133,29 @@ def below_split(u, lo, up):
         sh, sl = halves(s)
         ep = ((uh * sh - p) + uh * sl + ul * sh) + ul * sl
         return (p - lo) + (ep + u * es) < 0.0
+
+
+def residual_rows_host(obs, theta, inside, model, offsets, err_pars, gauss_index, prior, priorlow,
+                       priorup):
+    """The statement of pb_lm_residuals: obs, an Observation; theta[nw, nfree]; inside[nw];
+    model[nw, ndata]; offsets[nw, noff] and err_pars[nw, nerr] or None (the defaults);
+    gauss_index[ngauss], columns of theta; prior, priorlow, priorup [nfree] -> R[nw, ndata +
+    ngauss] (Retrieval.residuals_host).  A walker that is not inside, or has a non-finite model
+    value, gets a row of +inf."""
+    theta = np.asarray(theta, dtype=np.float64)
+    model = np.asarray(model, dtype=np.float64)
+    ig = np.asarray(gauss_index, dtype=np.int64)
+    nw, nd = model.shape
+    out = np.full((nw, nd + len(ig)), np.inf)
+    ok = (np.asarray(inside) != 0) & np.all(np.isfinite(model), axis=1)
+    for w in np.where(ok)[0]:
+        data = obs.offset_data_host(None if offsets is None else offsets[w])
+        uncert = obs.scale_errors_host(obs.err_defaults if err_pars is None else err_pars[w])
+        out[w, :nd] = (data - model[w]) / uncert
+        p = theta[w, ig]
+        s = np.where(p < prior[ig], priorlow[ig], priorup[ig])
+        out[w, nd:] = (p - prior[ig]) / s
+    return out
 
 
 class Retrieval:
@@ -652,6 +679,123 @@ class Retrieval:
         ns = NestedSampler(self.log_likelihood, self.prior_transform, self.nfree, nlive,
                            seed=seed, **kw).start()
         return ns if dlogz is None else ns.run_until(dlogz, **until)
+
+    # ------------------------------------------------------------------ the optimiser
+    def _check_least_squares(self):
+        """Refused: a free uncertainty-scaling parameter (also one shared with a free line).  Its
+        objective carries the term -0.5 sum log(2 pi uncert^2), which is no sum of squares; mc3's
+        least-squares fit has the same limit."""
+        free_err = [name for i, name in enumerate(self.pnames)
+                    if self.destination[i][0] == 'err_pars' and self.source[i] >= 0]
+        if free_err:
+            raise ValueError(f'the error parameters {free_err} are free: the objective of a '
+                             'retrieval with free err_scale_* / err_quad_* lines is not a sum of '
+                             'squares; fix them (pstep 0) for residuals and optimize')
+
+    @property
+    def igauss(self):
+        """The theta columns with a Gaussian prior, in order."""
+        f = self.ifree
+        return np.where((self.priorlow[f] != 0) | (self.priorup[f] != 0))[0].astype(np.int32)
+
+    def residuals_host(self, theta, model_host):
+        """theta[nw, nfree] and the model's band fluxes model_host[nw, ndata] -> R[nw, ndata +
+        ngauss]: column i < ndata is (data_i + offset_i unit - model_i) / uncert_i with the
+        walker's offsets and uncertainty scaling (Observation.offset_data_host /
+        scale_errors_host); then one column (theta_k - prior_k) / s_k per free parameter with a
+        Gaussian prior, s_k = priorlow below the prior, priorup from it upward.  So
+        -0.5 sum R^2 - 0.5 sum log(2 pi uncert^2) is log_posterior of a walker inside the bounds.
+        A walker outside the bounds, or with a non-finite band flux, gets a row of +inf."""
+        self._check_least_squares()
+        theta = self._theta_host(theta)
+        model = np.asarray(model_host, dtype=np.float64)
+        obs = self.observation
+        nw = theta.shape[0]
+        if model.shape != (nw, obs.nbands):
+            raise ValueError(f'model_host must have shape ({nw}, {obs.nbands}), got '
+                             f'{model.shape}')
+        split = self.split_host(theta)
+        f = self.ifree
+        return residual_rows_host(obs, theta, self.inside_host(theta), model,
+                                  split.get('offsets'), split.get('err_pars'), self.igauss,
+                                  self.prior[f], self.priorlow[f], self.priorup[f])
+
+    def residuals(self, theta):
+        """theta[nw, nfree] -> R[nw, ndata + ngauss] on the device (residuals_host): arguments ->
+        eval_params -> one launch of pb_lm_residuals; no torch arithmetic on the path."""
+        self._check_least_squares()
+        args = self.arguments(theta)
+        theta = self._theta_device('theta', theta)
+        obs = self.observation
+        bf = self.model.eval_params(self.atmosphere, args.params, self.bands, **args.kw,
+                                    **self.eval_kw)
+        nw = theta.shape[0]
+        if bf.dim() != 2 or tuple(bf.shape) != (nw, obs.nbands):
+            raise ValueError(f'residuals: the observation has {obs.nbands} data points, the '
+                             f'bands give {tuple(bf.shape)}')
+        d, o = self._resident(), obs._resident()
+        if 'gauss' not in d:
+            d['gauss'] = dev(self.igauss, torch.int32)
+        ngauss = d['gauss'].shape[0]
+        noff = obs.noff if args.offsets is not None else 0
+        err_pars = args.err_pars
+        if obs.nerr and err_pars is None:
+            err_pars = o['err_defaults'].view(1, -1).expand(nw, -1).contiguous()
+        out = torch.empty((nw, obs.nbands + ngauss), dtype=torch.float64, device=theta.device)
+        call('pb_lm_residuals', _ptr(out), _ptr(bf.contiguous()), _ptr(o['data']),
+             _ptr(o['uncert']), _ptr(o['offset_group']) if noff else None,
+             _ptr(args.offsets.contiguous()) if noff else None, obs.unit, noff,
+             _ptr(o['err_group']) if obs.nerr else None,
+             _ptr(o['err_mode']) if obs.nerr else None,
+             _ptr(err_pars.contiguous()) if obs.nerr else None, obs.unit, obs.nerr,
+             _ptr(theta), _ptr(args.inside), _ptr(d['gauss']) if ngauss else None,
+             _ptr(d['prior']), _ptr(d['priorlow']), _ptr(d['priorup']), ngauss, self.nfree, nw,
+             obs.nbands, _stream())
+        return out
+
+    def optimize(self, nstarts=64, seed=0, theta0=None, check_every=5, **kw):
+        """The maxima of the posterior from nstarts starts at once: an
+        optimize.LevenbergMarquardt over residuals, with scale = pstep of the free lines, run
+        until every start has a status.  theta0[ns, nfree] defaults to draw_initial(nstarts,
+        seed); a start outside the bounds is refused before the loop.  kw: the settings of
+        optimize.DEFAULTS (unmeasured on a real retrieval).  The residual store takes
+        8 ns (nfree + 1) m bytes: one that does not fit in free device memory is refused before
+        any launch.  -> an optimize.Optimum.
+
+        DEVIATION: a retrieval with a free err_scale_* or err_quad_* line is refused (its
+        objective is no sum of squares; mc3's least-squares fit has the same limit)."""
+        from .optimize import LevenbergMarquardt, Optimum
+        self._check_least_squares()
+        f = self.ifree
+        lm = LevenbergMarquardt(self.residuals, self.nfree, self.pmin[f], self.pmax[f],
+                                self.pstep[f], **kw)
+        if theta0 is None:
+            ns = int(nstarts)
+        else:
+            theta0 = np.asarray(theta0.cpu() if isinstance(theta0, torch.Tensor) else theta0,
+                                dtype=np.float64)
+            theta0 = self._theta_host(theta0)
+            ns = theta0.shape[0]
+            if not np.all(self.inside_host(theta0)):
+                raise ValueError(f'theta0: rows {list(np.where(~self.inside_host(theta0))[0])} '
+                                 'are outside the bounds')
+        if ns < 1:
+            raise ValueError('optimize: at least one start')
+        m = self.observation.nbands + len(self.igauss)
+        need = 8 * ns * (self.nfree + 1) * m
+        free = torch.cuda.mem_get_info()[0]
+        if need > free:
+            raise ValueError(f'optimize: the residual store of {ns} starts x {self.nfree + 1} '
+                             f'probe points x {m} residuals needs {need} bytes, {free} bytes of '
+                             'device memory are free')
+        if theta0 is None:
+            theta0 = self.draw_initial(ns, seed)
+            if not bool((self.arguments(theta0).inside != 0).all()):
+                raise ValueError('optimize: a draw from the priors is outside the bounds; give '
+                                 'theta0')
+        lm.start(theta0).run_until(check_every=check_every)
+        cov, active, singular = lm.covariance()
+        return Optimum(self, lm, self.log_posterior(lm.theta), cov, active, singular)
 
     def summary(self, sampler, burn=0, **kw):
         """The posterior summary of a sampler's chain: sampler.unique(burn) -> arguments ->
