@@ -908,6 +908,55 @@ int pb_nested_finish(double *out_d, double *logw_d, double *logl_d, double *cdf_
 int pb_nested_resample(int64_t *counts_d, const double *cdf_d, int64_t n, int64_t nsamples,
                        uint64_t seed, void *stream);
 
+/* ---- The posterior modes of a finished nested-sampling run (pb_modes.hip): the run does not
+ * cluster; its stored points are decomposed afterwards.  pyratbay_amd/modes.py states every kernel
+ * in NumPy (the specification), and the kernels have the statements' bits.  All rows are rows of
+ * the unit cube, finite by construction: there is no rule for NaN.  FP64 vector arithmetic, every
+ * product and sum rounded separately, no atomics on doubles.  Refused with PB_ERR_ARG and a
+ * message: a null pointer, nfree outside 1 .. PB_RETRIEVAL_MAX_PARAMS, more than
+ * PB_NESTED_MAX_LIVE rows, knn outside 1 .. PB_MODES_MAX_KNN, max_modes < 1.
+ *
+ * pb_modes_sqdist: d2_d[na,nb] of a_d[na,nfree] and b_d[nb,nfree]: d2 = 0, then for p = 0 ..
+ * nfree - 1 in order t = a[i,p] - b[j,p]; d2 = d2 + t * t.  A thread owns a point; tiles of 32
+ * rows of b are staged in LDS in chunks of 16 parameters, visited in ascending order, with the 32
+ * partial sums in registers.  Every kernel below takes its distances from the same sweep. */
+#define PB_MODES_MAX_KNN 32
+int pb_modes_sqdist(double *d2_d, const double *a_d, const double *b_d, int64_t na, int nb,
+                    int nfree, void *stream);
+/* Single linkage of r_d[n,nfree], 2 <= n <= PB_NESTED_MAX_LIVE, at the scale of the rows' own
+ * spacing.  k = min(knn, n - 1); dk_d[n]: the k-th smallest squared distance from row i to another
+ * row (a running list per row; duplicates count); ell2_d[0] = (link * link) * max dk.  Rows
+ * i != j are linked iff d2 <= ell2: bits_d[n, ceil(n / 32)] (32-bit words; bit j % 32 of word
+ * j / 32 of row i).  The components of the links come from one block with the labels in LDS:
+ * minimum-label propagation with pointer jumping until a pass changes nothing, which leaves every
+ * row the smallest row index of its component whatever the order of the updates.  In the canonical
+ * order -- size descending, ties to the component with the smallest row -- the first max_modes
+ * components of at least min_mode rows get the labels 0, 1, ... in labels_d[n]; every other row
+ * gets -1; the largest component is mode 0 whatever its size.  nmodes_d[0] >= 1.  The rule is
+ * conservative: a far outlier raises ell2 and merges modes, it never splits one.  dk_d and bits_d
+ * are the caller's work space. */
+int pb_modes_link(int32_t *labels_d, int32_t *nmodes_d, double *ell2_d, double *dk_d,
+                  int32_t *bits_d, const double *r_d, int n, int nfree, int knn, double link,
+                  int min_mode, int max_modes, void *stream);
+/* mode_d[np]: every point of p_d[np,nfree] takes the label of the row of r_d[n,nfree] with the
+ * smallest squared distance among the rows with labels_d >= 0, ties to the lower row (the minimum
+ * over (d2, row): no tiling changes it); -1 where no row has a label. */
+int pb_modes_assign(int32_t *mode_d, const double *p_d, const double *r_d,
+                    const int32_t *labels_d, int64_t np, int n, int nfree, void *stream);
+/* rows_d[cap] (int64): the indices i < n with counts_d[i] > 0, ascending, the first cap of them;
+ * nrows_d[0] (int64): how many there are.  One block. */
+int pb_modes_rows(int64_t *rows_d, int64_t *nrows_d, const int64_t *counts_d, int64_t n,
+                  int64_t cap, void *stream);
+/* pb_nested_finish's formulae per mode c < nmodes, one block each: m = the largest ln w with
+ * mode_d[i] == c, e = exp(ln w - m) there where ln w > -inf and 0 elsewhere, S = sum e,
+ *   ln_z_m_d[c] = m + ln S;   info_m_d[c] = (sum of e ln L over e > 0) / S - ln Z_m;
+ *   fraction_m_d[c] = exp(ln Z_m - ln_z_d[0])
+ * with the sums over all n rows in pb_nested_finish's 256 chunks and order.  A mode without
+ * weight: -inf, NaN, 0. */
+int pb_modes_evidence(double *ln_z_m_d, double *info_m_d, double *fraction_m_d,
+                      const double *logw_d, const double *logl_d, const int32_t *mode_d,
+                      const double *ln_z_d, int64_t n, int nmodes, void *stream);
+
 /* ---- Batched multi-start Levenberg-Marquardt (pb_optimize.hip): the maximum of the posterior and
  * its Laplace covariance for nstarts starts at once, theta_d[nstarts,nfree], on residual vectors of
  * m columns.  An iteration is pb_lm_probe -> the caller's residuals of probe_d -> pb_lm_normal ->

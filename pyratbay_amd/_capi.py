@@ -147,6 +147,11 @@ _PROTOS = {
                          vp],
     'pb_nested_finish': [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp],
     'pb_nested_resample': [vp, vp, i64, i64, u64, vp],
+    'pb_modes_sqdist': [vp, vp, vp, i64, i32, i32, vp],
+    'pb_modes_link': [vp, vp, vp, vp, vp, vp, i32, i32, i32, f64, i32, i32, vp],
+    'pb_modes_assign': [vp, vp, vp, vp, i64, i32, i32, vp],
+    'pb_modes_rows': [vp, vp, vp, i64, i64, vp],
+    'pb_modes_evidence': [vp, vp, vp, vp, vp, vp, vp, i64, i32, vp],
     'pb_lm_residuals': [vp, vp, vp, vp, vp, vp, f64, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp,
                         vp, i32, i32, i32, i32, vp],
     'pb_lm_probe': [vp, vp, vp, vp, vp, f64, i32, i64, vp],

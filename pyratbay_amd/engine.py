@@ -13,7 +13,7 @@ ec, depth and B never travel to the host unless asked for.  torch tensors are us
 only as owners of device memory; all arithmetic happens in libpbhip.so.
 
 This module is the front door: the code lives in one module per stage (_device, lbl, columns,
-batch, bands, observation, contribution, spectrum, table, retrieval, sampler, nested, optimize) and every public name is re-exported here.  The modules of the
+batch, bands, observation, contribution, spectrum, table, retrieval, sampler, nested, modes, optimize) and every public name is re-exported here.  The modules of the
 package import from those, not from here.
 """
 from . import _capi                                                     # noqa: F401
@@ -47,5 +47,6 @@ from . import sampler                                                   # noqa: 
 from .sampler import DEMC                                               # noqa: F401
 from . import nested                                                    # noqa: F401
 from .nested import NestedSampler                                       # noqa: F401
+from . import modes                                                     # noqa: F401
 from . import optimize                                                  # noqa: F401
 from .optimize import LevenbergMarquardt, Optimum                       # noqa: F401

@@ -301,7 +301,8 @@ class NestedSampler:
     run(a) then run(b) leaves the bits of run(a + b).  run_until(dlogz, check_every, max_iter)
     reads back one double, `remain`, per check.  Then logz() -> (ln Z, ln Z_err, H) as a device
     tensor, weighted() -> (theta, ln w, ln L), unique() -> (theta[n, nfree], counts[n] int64),
-    efficiency() and stuck().
+    efficiency() and stuck().  The run does not cluster: modes() separates the posterior's modes
+    afterwards (modes.py), and unique(mode=m) is the posterior of one of them.
 
     The defaults batch = nlive // 4 and nsteps = max(20, 5 nfree) come from the Gaussian target
     of the tests (a batch of nlive / 2 biased ln Z by about -0.07 there); they are unmeasured on
@@ -472,22 +473,82 @@ class NestedSampler:
         _, logw, logl, _ = self._finish()
         return self.prior_transform(self._cube()), logw, logl
 
-    def unique(self, burn=0, nsamples=None):
-        """(theta[n, nfree], counts[n] int64): the equal-weight posterior as rows and
-        multiplicities, nsamples draws (default: as many as there are rows, like the reference's
-        weighted_to_equal); rows nothing fell on are dropped.  Nested sampling has no burn-in:
-        burn != 0 is refused."""
+    def _resample(self, cdf, nsamples):
         import torch
         from ._capi import call
         from ._device import _ptr, _stream
+        n = cdf.shape[0]
+        counts = torch.empty(n, dtype=torch.int64, device='cuda')
+        call('pb_nested_resample', _ptr(counts), _ptr(cdf), n, int(nsamples), self.seed, _stream())
+        return counts
+
+    def modes(self, nsamples=4096, knn=10, link=1.0, min_mode=None, max_modes=16):
+        """The posterior modes of the run so far (modes.modes_host on the device; it changes
+        nothing of the run and keeps no state, so it can be taken at any time): a namespace of
+        device tensors nmodes (an int), mode[n] int32 in weighted()'s order, ln_z[nmodes],
+        info[nmodes] and fraction[nmodes] (the local evidences, their information and their
+        shares of the evidence), rows (the rows the modes were found on), labels (theirs) and
+        ell2 (the squared linking length in the unit cube).  Launches only, but for two counts
+        read back once each: the number of rows and nmodes.  A local evidence has no error bar
+        (modes.py says why; profiles/modes.md has the measured scatter)."""
+        import torch
+        from . import modes as md
+        from ._capi import call
+        from ._device import _ptr, _stream
+        out, logw, logl, cdf = self._finish()
+        cube = self._cube().contiguous()
+        N, nfree = cube.shape
+        md._check_link(2, nfree, knn, max_modes)
+        min_mode = md.default_min_mode(nfree) if min_mode is None else int(min_mode)
+        i32 = dict(dtype=torch.int32, device='cuda')
+        f64 = dict(dtype=torch.float64, device='cuda')
+        counts = self._resample(cdf, min(N, int(nsamples)))
+        rows = torch.empty(MAX_LIVE, dtype=torch.int64, device='cuda')
+        nrows = torch.empty(1, dtype=torch.int64, device='cuda')
+        call('pb_modes_rows', _ptr(rows), _ptr(nrows), _ptr(counts), N, MAX_LIVE, _stream())
+        n = int(nrows.item())
+        if n > MAX_LIVE:
+            raise ValueError(f'{n} rows: at most {MAX_LIVE} (nsamples = {nsamples})')
+        rows = rows[:n]
+        mode = torch.zeros(N, **i32)
+        labels = torch.zeros(n, **i32)
+        ell2 = torch.zeros(1, **f64)
+        nmodes = 1
+        if n >= 2:
+            R = cube[rows].contiguous()
+            count = torch.empty(1, **i32)
+            dk = torch.empty(n, **f64)
+            bits = torch.empty(n * ((n + 31) // 32), **i32)
+            call('pb_modes_link', _ptr(labels), _ptr(count), _ptr(ell2), _ptr(dk), _ptr(bits),
+                 _ptr(R), n, nfree, int(knn), float(link), min_mode, int(max_modes), _stream())
+            call('pb_modes_assign', _ptr(mode), _ptr(cube), _ptr(R), _ptr(labels), N, n, nfree,
+                 _stream())
+            nmodes = int(count.item())
+        ln_z, info, fraction = (torch.empty(nmodes, **f64) for _ in range(3))
+        call('pb_modes_evidence', _ptr(ln_z), _ptr(info), _ptr(fraction), _ptr(logw), _ptr(logl),
+             _ptr(mode), _ptr(out), N, nmodes, _stream())
+        return types.SimpleNamespace(nmodes=nmodes, mode=mode, ln_z=ln_z, info=info,
+                                     fraction=fraction, rows=rows, labels=labels, ell2=ell2[0])
+
+    def unique(self, burn=0, nsamples=None, mode=None):
+        """(theta[n, nfree], counts[n] int64): the equal-weight posterior as rows and
+        multiplicities, nsamples draws (default: as many as there are rows, like the reference's
+        weighted_to_equal); rows nothing fell on are dropped.  Nested sampling has no burn-in:
+        burn != 0 is refused.  mode=m: only the rows modes() assigns to mode m, with the counts
+        of the same one resample, so that the rows of the modes partition those of unique() and
+        their counts add up; an m outside 0 .. nmodes - 1 is refused."""
         if int(burn) != 0:
             raise ValueError(f'burn = {burn}: nested sampling has no burn-in to trim')
         _, _, _, cdf = self._finish()
         n = cdf.shape[0]
         nsamples = n if nsamples is None else int(nsamples)
-        counts = torch.empty(n, dtype=torch.int64, device='cuda')
-        call('pb_nested_resample', _ptr(counts), _ptr(cdf), n, nsamples, self.seed, _stream())
+        counts = self._resample(cdf, nsamples)
         keep = counts > 0
+        if mode is not None:
+            found = self.modes()
+            if int(mode) != mode or not 0 <= int(mode) < found.nmodes:
+                raise ValueError(f'mode = {mode}: the run has the modes 0 to {found.nmodes - 1}')
+            keep = keep & (found.mode == int(mode))
         theta = self.prior_transform(self._cube()[keep].contiguous())
         return theta, counts[keep].contiguous()
 

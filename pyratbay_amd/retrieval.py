@@ -797,12 +797,20 @@ class Retrieval:
         cov, active, singular = lm.covariance()
         return Optimum(self, lm, self.log_posterior(lm.theta), cov, active, singular)
 
-    def summary(self, sampler, burn=0, **kw):
+    def summary(self, sampler, burn=0, mode=None, **kw):
         """The posterior summary of a sampler's chain: sampler.unique(burn) -> arguments ->
         model.posterior_summary(atmosphere, params, counts, bands, ...); kw: what
         posterior_summary takes besides the per-sample tensors (quantiles, chunk,
-        contribution, ...)."""
-        theta, counts = sampler.unique(burn)
+        contribution, ...).  mode=m: the summary of one posterior mode of a nested sampler,
+        sampler.unique(burn, mode=m) (NestedSampler.modes); a sampler without modes (DEMC) is
+        refused."""
+        if mode is None:
+            theta, counts = sampler.unique(burn)
+        elif not hasattr(sampler, 'modes'):
+            raise ValueError(f'mode = {mode}: a {type(sampler).__name__} has no modes; only a '
+                             'nested sampler separates them')
+        else:
+            theta, counts = sampler.unique(burn, mode=mode)
         args = self.arguments(theta)
         return self.model.posterior_summary(self.atmosphere, args.params, counts, self.bands,
                                             **args.kw, **kw)
