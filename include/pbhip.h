@@ -200,7 +200,18 @@ int pb_lbl_last_state(pb_lbl *p, int32_t *ofactor_h, double *kmax_h, int nlayers
  * profile block each layer can select (block_h[nlayers]).  Synchronises the stream. */
 int pb_lbl_last_layer_kinds(pb_lbl *p, int32_t *resident_h, int32_t *block_h, int nlayers,
                             void *stream);
-/* The same call in two halves, for wavenumber shards on several GPUs.  _begin derives the layer
+/* Rows per barrier step of the LDS-staged gather.  Its row area holds two rows of `rowlds`
+ * samples (the longest row of the table, at most 1024) between zero pads of 256; where the rows
+ * of a (layer, isotope) are at most `rowlim` samples long and four or more slots of pitch
+ * rowlim + 256 (rounded down to even) fit the same area, a step stages and walks R = min(2, slots / 2)
+ * consecutive segments instead of one -- the same terms in the same order, fewer barriers.
+ * rows_per_step returns R and, when `pitch` is not null, the slot pitch in samples; it makes no
+ * HIP call.  last_rows_per_step: R of every (layer, isotope) of the last call
+ * (rows_h[nlayers * niso]; all 1 when that call did not run the staged gather, or ran it with
+ * PB_STAGE_ROWS=1, with rows via registers or with chunked long rows).  Synchronises the stream. */
+int pb_lbl_rows_per_step(int rowlds, int rowlim, int *pitch);
+int pb_lbl_last_rows_per_step(pb_lbl *p, int32_t *rows_h, int nlayers, int niso, void *stream);
+/* The same call in two halves, for wavenumber shards on several GPUs. _begin derives the layer
  * state and the records of the groups within reach of the shard, with the per-row maxima
  * (_extcoeff.c:203-226) over THOSE groups only -- 1/N of the exp() work; the caller then
  * all-reduces (MAX) the buffer pb_lbl_kmax_buffer returns over the ranks -- count 64-bit words

@@ -65,6 +65,8 @@ _PROTOS = {
     'pb_lbl_extinction_end': [vp, vp],
     'pb_lbl_last_state': [vp, vp, vp, i32, i32, vp],
     'pb_lbl_last_layer_kinds': [vp, vp, vp, i32, vp],
+    'pb_lbl_rows_per_step': [i32, i32, C.POINTER(i32)],
+    'pb_lbl_last_rows_per_step': [vp, vp, i32, i32, vp],
     'pb_lbl_last_work': [vp, C.POINTER(i64 * 3), vp],
     'pb_lbl_last_table_samples': [vp, C.POINTER(i64), vp],
     'pb_lbl_timing_begin': [vp, i32],
@@ -203,7 +205,8 @@ _RESTYPES = {'pb_transit_work_doubles': C.c_int64, 'pb_two_stream_batch_work_dou
              'pb_interp_ec_batch_work_doubles': C.c_int64,
              'pb_interp_ec_batch_cont_work_doubles': C.c_int64, 'pb_table_transit_work_doubles': C.c_int64,
              'pb_table_transit_supported': C.c_int, 'pb_voigt_destroy': None, 'pb_lines_destroy': None, 'pb_lbl_destroy': None,
-             'pb_voigt_device_bytes': i64, 'pb_timer_destroy': None}
+             'pb_voigt_device_bytes': i64, 'pb_timer_destroy': None,
+             'pb_lbl_rows_per_step': C.c_int}
 _NO_CHECK = set(_RESTYPES) | {'pb_version', 'pb_roctx_available'}
 
 

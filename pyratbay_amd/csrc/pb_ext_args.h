@@ -42,6 +42,38 @@ constexpr int kBinSamples = 256;     // output samples per bin of the phase-list
 constexpr int kStagePad = 256;       // zero samples on either side of a staged row
 constexpr int kStageSpan = 256;      // samples per wavefront and sub-tile (4 chunks of 64)
 constexpr int kStageRowMax = 1024;   // longest phase row the staged kernels keep in one piece
+constexpr int kStageRowsMax = 2;     // most rows (segments) one barrier step of k_ext_staged stages
+constexpr int kStageRowsDefault = kStageRowsMax;   // the cap of a call that PB_STAGE_ROWS does not set
+
+// Rows per barrier step of the staged gather (LDS-DMA path) and the pitch of their slots.  The
+// row area of a workgroup is sized for two rows of `rowlds` samples, [pad][row][pad][row][pad]
+// with pads of kStagePad samples; the rows of a (layer, isotope) are at most `rowlim` samples
+// long, and where four or more slots of pitch rowlim + kStagePad (rounded down to even) fit the
+// same area a step stages `rows` consecutive segments instead of one: slots [0, rows) on even
+// steps, [rows, 2 rows) on odd ones, the pad after a slot being the pad before the next.
+// The pad that is needed: a visit reads the 256 positions of a span of which at least one holds
+// row data, so it reaches at most 255 positions beyond either end of the data, which lies in
+// [0, rowlim) of its slot -- slots may follow each other at rowlim + 255, the next even number
+// for an odd rowlim (slots start 16-byte aligned).  A piece of a row's DMA writes zeros up to 127
+// samples past rowlim: inside the pad for every pitch.
+// rows == 1 keeps the pitch of two full rows (rowlds is even where the planner sets it; an odd
+// one is rounded down like the others, whatever the caller passes).
+struct StageSlots {
+    int pitch, rows;
+};
+__host__ __device__ inline StageSlots stage_slots(int rowlds, int rowlim, int cap = kStageRowsMax)
+{
+    const int area = 2 * (rowlds + kStagePad);
+    const int pitch = (rowlim + kStagePad) & ~1;
+    int rows = area / pitch / 2;
+    if (rows > cap)
+        rows = cap;
+    if (rows > kStageRowsMax)
+        rows = kStageRowsMax;
+    if (rows < 2)
+        return {(rowlds + kStagePad) & ~1, 1};
+    return {pitch, rows};
+}
 
 // staged gather (k_ext_staged): wavefronts and threads of a workgroup
 constexpr int kStagedWaves = 8;
@@ -108,6 +140,7 @@ struct LblArgs {
     int ph_nbins;
     int rowcap;                       // longest phase row of the table (samples)
     int rowlds;                       // longest row (or row chunk) a staged LDS buffer holds
+    int rows_cap;                     // most rows per barrier step (stage_slots()); 1 = one everywhere
     const int32_t *ph_iso;            // isotope of every phase-sorted group
     const int32_t *giso;              // isotope of every position-sorted group
     // group list that k_records walks (phase-sorted or position-sorted) and whether the

@@ -291,7 +291,8 @@ __global__ __launch_bounds__(NW * 64) void k_ext_resample(LblArgs a)
 //     15 the lifetime on the 100-MHz wall clock (s_memrealtime), 16 two back-to-back stamp
 //     intervals with an empty LDS queue, 17 wavefronts, 18 the interval of category 4 in the
 //     wavefronts that did NOT request a row (a stamp right after a barrier release), 19 rows
-//     requested, 20 the part of category 4 up to the first load (descriptor read + decode).
+//     requested, 20 the part of category 4 up to the first load (descriptor read + decode),
+//     21 segments walked (a step, 10, is what ends at a barrier: up to kStageRowsMax segments).
 //     A stamp is s_memtime + s_waitcnt lgkmcnt(0): it also drains the LDS queue, which is why
 //     the probe is not the product kernel (profiles/r05_step_account.md gives both times).
 // kIssue (kDma only): who requests a row's LDS-DMA.  0 = ONE wavefront per segment, the wavefronts
@@ -300,7 +301,11 @@ __global__ __launch_bounds__(NW * 64) void k_ext_resample(LblArgs a)
 // wavefront requests its own 128-sample slice of the row (one load each), from a descriptor it
 // fetched one step ahead.  Why: the cycle account (profiles/r05_step_account.md) shows the
 // requesting wavefront ~700 cycles behind its peers in every step, who wait for it at the barrier.
-template <int NW, int S, bool kDma, int kProbe = 0, int kIssue = 0>
+// kRows (kDma, kIssue == 0): the most rows (segments) a barrier step stages.  1 = one row per step
+// in two buffers; > 1 = stage_slots() (pb_ext_args.h) says per (layer, isotope) how many slots the
+// same LDS holds, and a step stages and walks up to that many consecutive segments.  The sums are
+// the same bits either way; plan_gather() / staged_kernel() choose.
+template <int NW, int S, bool kDma, int kProbe = 0, int kIssue = 0, int kRows = 1>
 __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
 {
     constexpr int kThreads = NW * 64;
@@ -368,7 +373,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned long long pc[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long pc[22] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     auto tick = [&]() -> unsigned long long {
         if constexpr (kProbe == 4)
             return (unsigned long long)__builtin_amdgcn_s_memtime();
@@ -427,6 +432,12 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
     // Rows of this (layer, isotope) are at most `rowlim` samples long: wavefronts whose
     // lanes lie beyond it do not store (the buffers are zeroed per isotope).
     int rowlim = a.rowlds;
+    // kRows > 1: `nrow` rows per barrier step in slots of `pitch` samples (stage_slots(),
+    // pb_ext_args.h), set with rowlim; every other instance keeps one row per step, two buffers
+    constexpr bool kMulti = kDma && kIssue == 0 && kRows > 1;
+    int pitch = rowspan, nrow = 1;
+    static_assert(kRows <= kStageRowsMax && kStageRowsMax <= NW,
+                  "a wavefront requests at most one row of a step");
     // kDma: the row of a segment goes global -> LDS directly (`buffer_load_dwordx4 ... lds`,
     // 1 KiB = 128 samples per wave-instruction), issued by ONE wavefront per segment (the
     // wavefronts take turns), one step ahead of the walk.  No row registers, no LDS stores
@@ -457,7 +468,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
         rsrc.z = __builtin_amdgcn_readfirstlane(len * 8);
         rsrc.w = 0x00020000;
         int voff = (2 * lane - (mlo & ~1)) * 8;
-        unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(row_lds0 + buf * rowspan * 8));
+        unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(row_lds0 + buf * (kMulti ? pitch : rowspan) * 8));
         if constexpr (kProbe == 4) {
             if (tref)
                 pc[20] += tick() - tref;
@@ -551,6 +562,11 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                 for (int i = tid; i < kNB * rowspan + kStagePad; i += kThreads)
                     s_row[i] = 0.0;
                 rowlim = lim;
+                if constexpr (kMulti) {
+                    const StageSlots sl = stage_slots(a.rowlds, lim, min(kRows, a.rows_cap));
+                    pitch = sl.pitch;
+                    nrow = sl.rows;
+                }
             }
         }
         // "virtual phases": (phase p, chunk c) pairs, pv = p*nch + c; nch = 1 unless the rows of
@@ -804,7 +820,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                 bool any = false;
                 // byte address of this lane's first sample in the staged row
                 const char *rowp = reinterpret_cast<const char *>(
-                    s_row + kStagePad + buf * rowspan + rlo + lane);
+                    s_row + kStagePad + buf * (kMulti ? pitch : rowspan) + rlo + lane);
 #pragma unroll
                 for (int u = 0; u < S; u++) {
                     const unsigned h = (unsigned)__builtin_amdgcn_readlane((int)hits[u], sg & 63);
@@ -957,9 +973,69 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                     }
                     continue;
                 }
+                if constexpr (!kMulti) {
+                    unsigned long long ta = tick();
+                    if (wave == 0)
+                        dma_row(0, 0);
+                    __builtin_amdgcn_s_waitcnt(0x0f70);           // vmcnt(0)
+                    __syncthreads();
+                    if constexpr (kProbe == 4) {
+                        const unsigned long long tb = tick();
+                        pc[8] += tb - ta;
+                        ta = tb;
+                    }
+                    for (int sg = 0; sg < nseg; sg++) {
+                        if (sg + 1 < nseg && wave == ((sg + 1) & (NW - 1)))
+                            dma_row(sg + 1, (sg + 1) & 1, ta);
+                        if constexpr (kProbe == 4) {
+                            const unsigned long long tb = tick();
+                            // (4: the wavefront whose turn it was to request the row; 18: the
+                            // others, i.e. the cost of the stamp itself right after a barrier release)
+                            if (sg + 1 < nseg && wave == ((sg + 1) & (NW - 1))) {
+                                pc[4] += tb - ta;
+                                pc[19] += 1;
+                            } else {
+                                pc[18] += tb - ta;
+                            }
+                            ta = tb;
+                            const unsigned long long f0 = pc[3];
+                            walk(sg, sg & 1);
+                            // (every LDS value of the walk has been consumed by its FMA: lgkmcnt(0))
+                            const unsigned long long tc = tick();
+                            pc[5] += (tc - ta) - (pc[3] - f0);
+                            __builtin_amdgcn_s_waitcnt(0x0f70);
+                            const unsigned long long td = tick();
+                            pc[6] += td - tc;
+                            __syncthreads();
+                            ta = tick();
+                            pc[7] += ta - td;
+                            pc[10] += 1;
+                            pc[21] += 1;
+                            continue;
+                        }
+                        walk(sg, sg & 1);
+                        __builtin_amdgcn_s_waitcnt(0x0f70);       // the row of sg+1 has landed
+                        __syncthreads();
+                    }
+                    continue;
+                }
+                // A step stages and walks the segments [sg, se): at most nrow of them, fewer at
+                // the end of the batch and before a multiple of 64 (find_hits serves 64 segments
+                // at a time).  Its rows lie in the slots half * nrow + (segment - sg), the two
+                // halves of the slots taking turns; the rows of the next step [se, sn) are
+                // requested into the other half while this one is walked, segment g by wavefront
+                // g mod NW, so no wavefront requests two rows in a row.  One wait and one barrier
+                // end a step; with nrow == 1 this is one row per step in two buffers.
+                auto step_end = [&](int s0) { return min(min(s0 + nrow, nseg), (s0 | 63) + 1); };
+                auto request = [&](int s0, int s1, int slot0, unsigned long long tref) {
+                    const int g = s0 + ((wave - s0) & (NW - 1));   // my segment of the step, if any
+                    if (g < s1)
+                        dma_row(g, slot0 + (g - s0), tref);
+                    return g < s1;
+                };
                 unsigned long long ta = tick();
-                if (wave == 0)
-                    dma_row(0, 0);
+                int sg = 0, se = step_end(0), half = 0;
+                request(0, se, 0, 0);
                 __builtin_amdgcn_s_waitcnt(0x0f70);           // vmcnt(0)
                 __syncthreads();
                 if constexpr (kProbe == 4) {
@@ -967,14 +1043,14 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                     pc[8] += tb - ta;
                     ta = tb;
                 }
-                for (int sg = 0; sg < nseg; sg++) {
-                    if (sg + 1 < nseg && wave == ((sg + 1) & (NW - 1)))
-                        dma_row(sg + 1, (sg + 1) & 1, ta);
+                while (sg < nseg) {
+                    const int sn = step_end(se);
+                    const bool asked = request(se, sn, (half ^ 1) * nrow, ta);
                     if constexpr (kProbe == 4) {
                         const unsigned long long tb = tick();
-                        // (4: the wavefront whose turn it was to request the row; 18: the others,
+                        // (4: the wavefronts whose turn it was to request a row; 18: the others,
                         // i.e. the cost of the stamp itself right after a barrier release)
-                        if (sg + 1 < nseg && wave == ((sg + 1) & (NW - 1))) {
+                        if (asked) {
                             pc[4] += tb - ta;
                             pc[19] += 1;
                         } else {
@@ -982,7 +1058,8 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         }
                         ta = tb;
                         const unsigned long long f0 = pc[3];
-                        walk(sg, sg & 1);
+                        for (int g = sg; g < se; g++)
+                            walk(g, half * nrow + (g - sg));
                         // (every LDS value of the walk has been consumed by its FMA: lgkmcnt(0))
                         const unsigned long long tc = tick();
                         pc[5] += (tc - ta) - (pc[3] - f0);
@@ -993,11 +1070,17 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         ta = tick();
                         pc[7] += ta - td;
                         pc[10] += 1;
-                        continue;
+                        pc[21] += (unsigned long long)(se - sg);
+                    } else {
+                        (void)asked;
+                        for (int g = sg; g < se; g++)
+                            walk(g, half * nrow + (g - sg));
+                        __builtin_amdgcn_s_waitcnt(0x0f70);   // the rows of [se, sn) have landed
+                        __syncthreads();
                     }
-                    walk(sg, sg & 1);
-                    __builtin_amdgcn_s_waitcnt(0x0f70);       // the row of sg+1 has landed
-                    __syncthreads();
+                    sg = se;
+                    se = sn;
+                    half ^= 1;
                 }
             } else if (nseg > 0) {
                 run(std::integral_constant<int, 2>(), std::integral_constant<int, kRowRegs>());
@@ -1021,7 +1104,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
         pc[9] = t_end - t_birth;
         pc[15] = (unsigned long long)__builtin_amdgcn_s_memrealtime() - real_birth;
         if (lane == 0 && a.probe)
-            for (int i = 0; i < 21; i++)
+            for (int i = 0; i < 22; i++)
                 atomicAdd(&a.probe[(int64_t)layer * 24 + i], pc[i]);
     }
 }
@@ -1425,8 +1508,13 @@ __global__ __launch_bounds__(kBlock) void k_combine_layer_parts(double *ext, con
 
 namespace pbx {
 
-GatherKernel staged_kernel(int S, bool dma)
+GatherKernel staged_kernel(int S, bool dma, int rows)
 {
+    constexpr int R = kStageRowsMax;
+    if (dma && rows > 1)
+        return S == 4   ? k_ext_staged<kStagedWaves, 4, true, 0, 0, R>
+               : S == 2 ? k_ext_staged<kStagedWaves, 2, true, 0, 0, R>
+                        : k_ext_staged<kStagedWaves, 1, true, 0, 0, R>;
     return dma ? (S == 4   ? k_ext_staged<kStagedWaves, 4, true>
                   : S == 2 ? k_ext_staged<kStagedWaves, 2, true>
                            : k_ext_staged<kStagedWaves, 1, true>)
@@ -1563,7 +1651,8 @@ static int exp_stage_probe_begin(LblArgs &a, const GatherPlan &g, const Tuning &
         *kern = e == 11 ? k_ext_staged<kStagedWaves, 2, true, 0, 1>
                         : k_ext_staged<kStagedWaves, 2, true, 0, 2>;
     if (e == 4) {                                         // the cycle account (valid sums)
-        *kern = k_ext_staged<kStagedWaves, 2, true, 4>;
+        *kern = a.rows_cap > 1 ? k_ext_staged<kStagedWaves, 2, true, 4, 0, kStageRowsMax>
+                               : k_ext_staged<kStagedWaves, 2, true, 4>;
         PB_HIP(hipMalloc(&a.probe, (size_t)a.nlayers * 24 * 8));
         PB_HIP(hipMemsetAsync(a.probe, 0, (size_t)a.nlayers * 24 * 8, s));
     }
@@ -1586,7 +1675,7 @@ static int exp_stage_probe_end(LblArgs &a, hipStream_t s)
     for (int layer = 0; layer < a.nlayers; layer++) {
         fprintf(stderr, "STAGE_PROBE layer %d rowmax %d :", layer,
                 rowmax[(size_t)layer * a.niso]);
-        for (int i = 0; i < 21; i++)
+        for (int i = 0; i < 22; i++)
             fprintf(stderr, " %llu", h[(size_t)layer * 24 + i]);
         fprintf(stderr, "\n");
     }
@@ -1754,7 +1843,7 @@ int launch_staged(pb_lbl *p, LblArgs &a, const GatherPlan &g, const Tuning &tn, 
     a.ntiles = pb::div_up(wcount, g.S * kStagedSub);
     const int unit_groups = (nunits + 7) / 8;               // (layer, split) units per XCD
     dim3 grid((unsigned)(8 * a.ntiles * unit_groups), a.nrows);
-    GatherKernel kern = staged_kernel(g.S, g.dma);
+    GatherKernel kern = staged_kernel(g.S, g.dma, a.rows_cap);
     if (int rc = exp_stage_probe_begin(a, g, tn, &kern, s))
         return rc;
     if (int rc = allow_lds(reinterpret_cast<const void *>(kern), g.lds))

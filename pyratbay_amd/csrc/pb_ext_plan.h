@@ -89,6 +89,9 @@ struct pb_lbl {
     int ut_units = 0;
     int concurrency = 1;     // independent calls the caller keeps in flight beside this plan's
     int gather_mode = 0;     // 0 = choose, 1 = global gather, 2 = LDS-staged, 3 = resident+global
+    // a constant-step sub-plan of a `resolution` plan's dynamic grids (pb_ext_resolution.hip): its
+    // staged launches keep one row per barrier step (measured slower with two: profiles/rows_per_step.md)
+    bool dyn_child = false;
     int last_gather = 0;     // last call: 1 global, 2 staged, 3 linterp; +8 = resident kernel too
     double stage_threshold = 8.0;   // groups per (2048-sample tile, phase) to go staged
     // optional per-launch timing of the gather kernel (bench.py's roofline figure)
@@ -171,6 +174,7 @@ struct Tuning {
     bool no_long_rows = false;     // PB_NO_LONG_ROWS (set at all)
     int stage_s = 0;               // PB_STAGE_S as 1, 2 or 4; 0 = not set
     int stage_split = 0;           // PB_STAGE_SPLIT as 1..8; 0 = not set
+    int stage_rows = 0;            // PB_STAGE_ROWS as 1..kStageRowsMax; 0 = not set
     bool poison = false;           // PB_POISON_RECORDS (set and not 0)
     bool budget_set = false;       // PB_RECORD_BUDGET
     size_t budget = 0;
@@ -239,7 +243,7 @@ int launch_kmax(const LblArgs &a, hipStream_t s);
 size_t records_lds(const LblArgs &a, int per);
 int launch_records(const LblArgs &a, int fmt, int per, dim3 grid, size_t lds, hipStream_t s);
 // pb_ext_gather.hip
-GatherKernel staged_kernel(int S, bool dma);
+GatherKernel staged_kernel(int S, bool dma, int rows);   // rows: LblArgs::rows_cap
 int allow_lds(const void *kern, size_t lds);
 int launch_staged(pb_lbl *p, LblArgs &a, const GatherPlan &g, const Tuning &tn, hipStream_t s);
 int launch_global(LblArgs &a, const Tuning &tn, hipStream_t s);

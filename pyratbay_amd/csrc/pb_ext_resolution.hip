@@ -257,6 +257,7 @@ static int dyn_subplan(pb_lbl *p, int f, hipStream_t s, pb_lbl::DynSub **out)
     // to the global gather (c2-res: 180-580 us per layer against 55-200 staged)
     if (!getenv("PB_GATHER"))
         d.plan->gather_mode = 2;
+    d.plan->dyn_child = true;
     p->dyn.push_back(d);
     *out = &p->dyn.back();
     return PB_OK;

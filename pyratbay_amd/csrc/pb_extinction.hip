@@ -484,6 +484,8 @@ static Tuning read_tuning()
         t.stage_s = atoi(e) >= 4 ? 4 : atoi(e) >= 2 ? 2 : 1;
     if (const char *e = getenv("PB_STAGE_SPLIT"))
         t.stage_split = std::max(1, std::min(8, atoi(e)));
+    if (const char *e = getenv("PB_STAGE_ROWS"))
+        t.stage_rows = std::max(1, std::min(kStageRowsMax, atoi(e)));
     if (const char *e = getenv("PB_POISON_RECORDS"))
         t.poison = atoi(e) != 0;
     if (const char *e = getenv("PB_RECORD_BUDGET")) {
@@ -1032,7 +1034,7 @@ static int run_chunked(pb_lbl *p, LblArgs &a, const GatherPlan &g, hipStream_t s
     a.ntiles = pb::div_up(a.wcount, g.S * kStagedSub);
     const int unit_groups = (nlayers + 7) / 8;
     dim3 ggrid((unsigned)(8 * a.ntiles * unit_groups), a.nrows);
-    GatherKernel kern = staged_kernel(g.S, g.dma);
+    GatherKernel kern = staged_kernel(g.S, g.dma, a.rows_cap);
     if (int rc = allow_lds(reinterpret_cast<const void *>(kern), g.lds))
         return rc;
     for (size_t c = 0; c < g.chunks.size(); c++) {
@@ -1200,6 +1202,12 @@ int lbl_extinction(pb_lbl *p, const Call &c, void *stream, int phase)
     p->last_chunks = (int)g.chunks.size();
     a.nch_max = g.nch_max;
     a.rowlds = g.rowlds;
+    // rows per barrier step of the staged gather: stage_slots() up to this cap on the LDS-DMA
+    // path with rows in one piece, one row per step otherwise (PB_STAGE_ROWS=1: everywhere)
+    // (the launches of a dynamic-grid sub-plan: one unless PB_STAGE_ROWS says otherwise)
+    a.rows_cap = g.dma && g.nch_max == 1
+                     ? (tn.stage_rows ? tn.stage_rows : p->dyn_child ? 1 : kStageRowsDefault)
+                     : 1;
     a.res_cap = g.resident && !chunked ? p->res_cap : 0;   // (chunked: every layer through the staged gather)
     if (int rc = bind_records(p, a, g, tn, s))
         return rc;
@@ -1354,6 +1362,32 @@ int pb_lbl_last_layer_kinds(pb_lbl *p, int32_t *resident_h, int32_t *block_h, in
         PB_HIP(hipMemcpy(resident_h, p->ls_resident, (size_t)nlayers * 4, hipMemcpyDeviceToHost));
     if (block_h)
         PB_HIP(hipMemcpy(block_h, p->ls_block, (size_t)nlayers * 4, hipMemcpyDeviceToHost));
+    return PB_OK;
+}
+
+int pb_lbl_rows_per_step(int rowlds, int rowlim, int *pitch)
+{
+    const StageSlots sl = stage_slots(rowlds, rowlim);
+    if (pitch)
+        *pitch = sl.pitch;
+    return sl.rows;
+}
+
+int pb_lbl_last_rows_per_step(pb_lbl *p, int32_t *rows_h, int nlayers, int niso, void *stream)
+{
+    PB_REQUIRE(p && rows_h, "pb_lbl_last_rows_per_step: null pointer");
+    PB_REQUIRE(nlayers >= 1 && nlayers <= p->max_layers && niso == p->niso,
+               "pb_lbl_last_rows_per_step: bad sizes");
+    PB_HIP(hipStreamSynchronize(pb::as_stream(stream)));
+    const size_t n = (size_t)nlayers * niso;
+    const LblArgs &a = p->last_args;
+    if ((p->last_gather & 7) != 2 || a.rows_cap <= 1) {       // not the staged gather, or one row per step
+        std::fill(rows_h, rows_h + n, 1);
+        return PB_OK;
+    }
+    PB_HIP(hipMemcpy(rows_h, p->li_rowmax, n * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++)
+        rows_h[i] = stage_slots(a.rowlds, std::min(a.rowlds, rows_h[i]), a.rows_cap).rows;
     return PB_OK;
 }
 

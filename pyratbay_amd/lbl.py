@@ -320,6 +320,13 @@ class LBL:
         call('pb_lbl_last_layer_kinds', self._h, hptr(resident), hptr(block), nlayers, _stream())
         return resident, block
 
+    def last_rows_per_step(self, nlayers, niso):
+        """rows[L, niso]: segments per barrier step of the staged gather in every (layer,
+        isotope) of the last call (pb_lbl_last_rows_per_step)."""
+        rows = np.zeros((nlayers, niso), np.int32)
+        call('pb_lbl_last_rows_per_step', self._h, hptr(rows), nlayers, niso, _stream())
+        return rows
+
     def last_wave_layers(self, nlayers):
         """wave[L] 0/1: the layers of the last call the wave-autonomous kernel computed."""
         wave = np.zeros(nlayers, np.int32)

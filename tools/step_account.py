@@ -80,12 +80,12 @@ def main():
     info, rows = run_child(name, steps, True)
     nl = info['nlayers']
     import numpy as np
-    data = np.zeros((nl, 21))
+    data = np.zeros((nl, 22))
     rowmax = np.zeros(nl, int)
-    for r in rows:                       # STAGE_PROBE layer L rowmax R : v0 ... v14  (summed over launches)
+    for r in rows:                       # STAGE_PROBE layer L rowmax R : v0 ... v21  (summed over launches)
         layer = int(r[2])
         rowmax[layer] = int(r[4])
-        data[layer] += np.array([float(x) for x in r[6:27]])
+        data[layer] += np.array([float(x) for x in r[6:28]])
     data /= steps
     # calibration from the probe itself: s_memtime ticks per 10-ns tick of the 100-MHz wall clock
     # (s_memrealtime), both taken over every wavefront's lifetime; the cost of one stamp with an
@@ -159,6 +159,11 @@ def main():
     print('| layers | ' + ' | '.join(str(int(m.sum())) for _, m in classes) + ' |')
     print('| steps per (tile, wavefront) launch-wide: steps | ' +
           ' | '.join(f'{data[m, 10].sum():.3g}' for _, m in classes) + ' |')
+    # (a step is what ends at a barrier: it walks up to kStageRowsMax segments, counter 21)
+    print('| segments walked, launch-wide | ' +
+          ' | '.join(f'{data[m, 21].sum():.3g}' for _, m in classes) + ' |')
+    print('| segments per step | ' +
+          ' | '.join(f'{data[m, 21].sum() / max(data[m, 10].sum(), 1):.2f}' for _, m in classes) + ' |')
     print('| (record, sub-tile) visits per step and wavefront | ' +
           ' | '.join(f'{data[m, 12].sum() / max(data[m, 10].sum(), 1):.2f}' for _, m in classes) + ' |')
     print('| steps in which a wavefront visits anything | ' +
@@ -166,7 +171,7 @@ def main():
     print('| records per batch of 512 slots: batches | ' +
           ' | '.join(f'{data[m, 11].sum() / 8:.3g}' for _, m in classes) + ' |')
     print()
-    print('Raw per-layer sums (ticks per launch): layer, rowmax, ' + ', '.join(str(i) for i in range(21)))
+    print('Raw per-layer sums (ticks per launch): layer, rowmax, ' + ', '.join(str(i) for i in range(22)))
     for layer in range(nl):
         print(f'    {layer} {rowmax[layer]} ' + ' '.join(f'{v:.0f}' for v in data[layer]))
 
