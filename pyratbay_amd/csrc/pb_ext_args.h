@@ -35,8 +35,10 @@ static_assert(kTile < 65536, "window coordinates are packed in 16 bits");
 // packed records (k_records writes them; the staged gather and the planner decode them)
 constexpr int kLongLenBits = 14;   // window length in a long-row record (rows of up to 16 x 1024 samples)
 constexpr int kChunkRow = 1024;      // samples per chunk of a long phase row (= kStageRowMax)
-constexpr int kRecLayers = 4;        // layers per thread of k_records (group data loaded once);
-                                     // 1 for launches of few layers (multi-GPU ranks)
+constexpr int kRecLayers = 8;        // layers per thread of k_records (group data loaded once, the
+                                     // sample index and the Doppler column carried from layer to
+                                     // layer; 4 / 8 / 10 / 16: 96 / 86 / 87 / 95 us at C2);
+                                     // PB_REC_LAYERS=1: one
 
 constexpr int kBinSamples = 256;     // output samples per bin of the phase-list position index
 constexpr int kStagePad = 256;       // zero samples on either side of a staged row
@@ -268,6 +270,8 @@ struct LblArgs {
     VSeg *vseg;
     int32_t *vrnd;     // first visit record of every round (+ one past the last)
     UnitHdr *uhdr;
+    // k_records: 1 / ls_dwnstep of every layer (trunc_quot_inv)
+    double *ls_inv_dwnstep;
 };
 
 size_t rounds_prep_lds(const LblArgs &a);
@@ -384,8 +388,92 @@ __device__ inline int trunc_div_inv(int a, double inv)
     return a >= 0 ? floor_div_inv(a, inv) : -floor_div_inv(-a, inv);
 }
 
+// (int)(x / d) without the division, for a divisor whose reciprocal inv = RN(1 / d) a layer
+// prepares once (k_layer_state: ls_inv_dwnstep).  q = RN(x * inv) carries two roundings,
+// |q - x / d| <= |x / d| (2^-52 + 2^-106), and RN(x / d) one more of 2^-53: for |x / d| < 2^31 (the
+// result is an int) q and RN(x / d) are less than 2^31 (2^-52 + 2^-53 + 2^-106) < 2^-19 apart.  So
+// when q is farther than 2^-19 from every integer, both lie strictly between the same two
+// consecutive integers and truncate to the same one.  Otherwise -- a line on a sample of the
+// layer's grid to within 2^-19 of a step, x = 0, a quotient beyond the int range (q - (int)q is
+// then 1 or more), a NaN -- the division itself decides: one test of the result, like
+// line_strength's.  tests/test_records_quotient_cpu.py restates this against the division.
+__device__ __forceinline__ int trunc_quot_inv(double x, double d, double inv)
+{
+    const double q = x * inv;
+    const int t = (int)q;
+    const double f = fabs(q - (double)t);
+    if (__builtin_expect(!(fabs(f - 0.5) < 0.5 - 0x1p-19), 0))
+        return (int)(x / d);
+    return t;
+}
+
+// trunc_div_inv() without its select: a select between two calls is compiled to two predicated
+// blocks, and a wavefront issues both whatever its lanes hold
+__device__ __forceinline__ int trunc_div_inv_abs(int a, double inv)
+{
+    const int q = floor_div_inv(abs(a), inv);
+    return a < 0 ? -q : q;
+}
+
+// Index of the element of the sorted a[0..n-1] closest to v, as pb::nearest_index(a, v, 0, n - 1)
+// finds it, from the answer `prev` of a neighbouring search (< 0: none).  The bisection ends on
+// the one pair lo, lo + 1 with a[lo] <= v < a[lo + 1] whatever range it started from, as long as
+// the range holds such a pair; [prev - 1, prev + 1] does when a[prev - 1] <= v < a[prev + 1], and
+// the middle element says which half.  Everything else -- no neighbour, a neighbour at either end
+// of the grid, v outside those three elements or outside the grid -- takes the whole range.
+__device__ __forceinline__ int nearest_index_near(const double *a, double v, int n, int prev)
+{
+    int lo = 0, hi = n - 1;
+    if (prev >= 1 && prev <= n - 2) {
+        const double below = a[prev - 1], at = a[prev], above = a[prev + 1];
+        if (below <= v && v < above) {
+            lo = at > v ? prev - 1 : prev;
+            hi = lo + 1;
+        }
+    }
+    return pb::nearest_index(a, v, lo, hi);
+}
+
 // cutsteps = cutoff / dwnstep and inv_ofactor = 1.0 / ofactor are per-layer values prepared by
-// k_layer_state (the same quotients the reference forms per line, _extcoeff.c:281-299)
+// k_layer_state (the same quotients the reference forms per line, _extcoeff.c:281-299).
+// window_at(): the window from the group's sample idwn of the layer's grid, its sub-sample offset
+// subw = iown - idwn * ofactor, its table cell and the cutoff's bounds mincut = (int)(idwn -
+// cutsteps), maxcut = (int)(idwn + cutsteps) (used when the plan has a cutoff).
+// kRec: the forms k_records takes (the quotients by an ofactor of 1 left out -- a wave-uniform
+// branch -- and the others without a select), the same integers.
+template <bool kRec>
+__device__ __forceinline__ Window window_at(const LblArgs &a, int idwn, int subw, int cell,
+                                            int ofactor, long dnwn, int mincut, int maxcut,
+                                            double inv_ofactor, bool clip_lo, bool clip_hi)
+{
+    Window w;
+    w.cell = cell;
+    w.half = a.psize[cell];
+    if (kRec && ofactor == 1) {
+        w.minj = idwn - (w.half - subw);
+        w.maxj = idwn + (w.half + subw);
+    } else if (kRec) {
+        w.minj = idwn - trunc_div_inv_abs(w.half - subw, inv_ofactor);
+        w.maxj = idwn + trunc_div_inv_abs(w.half + subw, inv_ofactor);
+    } else {
+        w.minj = idwn - trunc_div_inv(w.half - subw, inv_ofactor);
+        w.maxj = idwn + trunc_div_inv(w.half + subw, inv_ofactor);
+    }
+    // (the packed records of the staged gathers keep a window that leaves the grid unclipped:
+    // see k_records)
+    if (clip_lo && w.minj < 0)
+        w.minj = 0;
+    if (clip_hi && w.maxj > dnwn)
+        w.maxj = dnwn;
+    if (a.cutoff > 0.0) {
+        if (mincut > w.minj)
+            w.minj = mincut;
+        if (maxcut < w.maxj)
+            w.maxj = maxcut;
+    }
+    return w;
+}
+
 __device__ inline Window group_window(const LblArgs &a, double wavn, int iown, int ilor,
                                       double alphad, int ofactor, double dwnstep,
                                       int64_t dnwn, int idop_lo, int idop_hi,
@@ -396,32 +484,14 @@ __device__ inline Window group_window(const LblArgs &a, double wavn, int iown, i
     // [idop_lo, idop_hi] brackets the answer (nearest index is monotonic in wavn), which
     // turns the bisection over the whole Doppler grid into 0-2 steps; `doppler` may point
     // to an LDS copy of the grid
-    Window w;
     const int idwn = (int)((wavn - a.own0) / dwnstep);
     const int idop = idop_lo == idop_hi
                          ? idop_lo
                          : pb::nearest_index(doppler ? doppler : a.doppler, alphad * wavn,
                                              idop_lo, idop_hi);
-    w.cell = ilor * a.ndop + idop;
-    w.half = a.psize[w.cell];
-    const int subw = iown - idwn * ofactor;
-    w.minj = idwn - trunc_div_inv(w.half - subw, inv_ofactor);
-    w.maxj = idwn + trunc_div_inv(w.half + subw, inv_ofactor);
-    // (the packed records of the staged gathers keep a window that leaves the grid unclipped:
-    // see k_records)
-    if (clip_lo && w.minj < 0)
-        w.minj = 0;
-    if (clip_hi && w.maxj > dnwn)
-        w.maxj = dnwn;
-    if (a.cutoff > 0.0) {
-        const int mincut = (int)(idwn - cutsteps);
-        const int maxcut = (int)(idwn + cutsteps);
-        if (mincut > w.minj)
-            w.minj = mincut;
-        if (maxcut < w.maxj)
-            w.maxj = maxcut;
-    }
-    return w;
+    return window_at<false>(a, idwn, iown - idwn * ofactor, ilor * a.ndop + idop, ofactor,
+                            (long)dnwn, (int)(idwn - cutsteps), (int)(idwn + cutsteps),
+                            inv_ofactor, clip_lo, clip_hi);
 }
 
 // Co-added strength of a group (left-to-right sum of its members, _extcoeff.c:248-262)

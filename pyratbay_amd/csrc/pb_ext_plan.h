@@ -25,7 +25,7 @@ struct pb_lbl {
     int32_t *li_rowmax = nullptr, *li_hlo = nullptr, *li_hhi = nullptr;
     int64_t *ls_dnwn = nullptr;
     double *ls_dwnstep = nullptr, *li_alphad = nullptr, *li_dens = nullptr, *li_z = nullptr;
-    double *ls_quot = nullptr;        // [4][max_layers]: cutsteps, 1/ofactor, 1/scale, 1/temp
+    double *ls_quot = nullptr;        // [5][max_layers]: cutsteps, 1/ofactor, 1/scale, 1/temp, 1/dwnstep
     double *li_invz = nullptr;        // [max_layers][niso] 1 / partition function
     unsigned long long *kmax_bits = nullptr;
     int kmax_rows = 0;

@@ -96,6 +96,7 @@ __global__ __launch_bounds__(64) void k_layer_state(LblArgs a)
         const int ofactor = s_div[d - 1];
         a.ls_ofactor[layer] = ofactor;
         a.ls_dwnstep[layer] = a.ownstep * ofactor;
+        a.ls_inv_dwnstep[layer] = 1.0 / (a.ownstep * ofactor);
         a.ls_cutsteps[layer] = a.cutoff / (a.ownstep * ofactor);
         a.ls_inv_ofactor[layer] = 1.0 / (double)ofactor;
         a.ls_inv_temp[layer] = 1.0 / temp;
@@ -168,6 +169,11 @@ __global__ __launch_bounds__(kBlock) void k_kmax(LblArgs a, int lines_per_block)
 // kernel are in position order and always use the SoA arrays.  The two orders are two passes
 // with their own pointer sets (one body instantiated twice): with both sets and every record
 // format live at once the kernel held a third of its scalar state in spilled registers.
+// What does not depend on the layer is formed once per thread, before the layer loop: the output
+// row and the abundance of the group's isotope, and -- while consecutive layers of the thread
+// share their ofactor, a wave-uniform test -- the group's sample of the layer's grid (idwn, one
+// FP64 quotient), its sub-sample offset and the cutoff's bounds; the Doppler column is searched
+// around the previous layer's.  Figures: profiles/records_diet.md.
 template <int kFmt, int kRecLayers>
 __global__ __launch_bounds__(kBlock) void k_records(LblArgs a)
 {
@@ -247,6 +253,17 @@ __global__ __launch_bounds__(kBlock) void k_records(LblArgs a)
             elow = (kPos ? a.g_lead + a.ngroups : a.rk_elow)[g];
             gf = (kPos ? a.g_lead + 2 * a.ngroups : a.rk_gf)[g];
         }
+        // (the lanes that form records are the same in every layer: have, the row and inwin do
+        // not depend on it, so what a lane carries from one layer is its own in the next)
+        int row0 = -1;
+        double ratio = 0.0;
+        if (have) {
+            row0 = s_iext[iso];
+            if (row0 >= 0 && a.add)
+                row0 = 0;
+            ratio = s_ratio[iso];
+        }
+        int of_prev = 0, idwn = 0, subw = 0, mincut = 0, maxcut = 0, idop = -1;
         for (int i = 0; i < kRecLayers; i++) {
             const int layer = layer0 + i;
             if (layer >= a.nlayers)
@@ -254,17 +271,17 @@ __global__ __launch_bounds__(kBlock) void k_records(LblArgs a)
             const bool pos = kFmt == 3 || (a.res_cap > 0 && uniform_load(a.ls_resident, layer));
             if (pos != kPos)                                          // wave-uniform
                 continue;
+            const int ofactor = uniform_load(a.ls_ofactor, layer);
+            const bool of_new = ofactor != of_prev;                   // wave-uniform
+            of_prev = ofactor;
             double k = 0.0, lmax = 0.0;
-            int ulo = 0, uhi = 0, q = 0, cell = 0, phi = 0, row = -1;
+            int ulo = 0, uhi = 0, q = 0, cell = 0, phi = 0;
+            const int row = row0;
             if (have) {
-                row = s_iext[iso];
-                if (row >= 0 && a.add)
-                    row = 0;
                 if (row >= 0) {
                     const int e = i * a.niso + iso;
                     const double temp = uniform_load(a.temp, layer);
                     const double inv_temp = uniform_load(a.ls_inv_temp, layer);
-                    const double ratio = s_ratio[iso];
                     const double z = s_z[e], inv_z = s_invz[e];
                     k = line_strength(ratio, gf, elow, wavn, temp, inv_temp, z, inv_z);
                     lmax = k;
@@ -281,8 +298,7 @@ __global__ __launch_bounds__(kBlock) void k_records(LblArgs a)
                                   (unsigned long long)__double_as_longlong(lmax));
                         continue;
                     }
-                    const int ofactor = uniform_load(a.ls_ofactor, layer);
-                    const int64_t dnwn = uniform_load(a.ls_dnwn, layer);
+                    const long dnwn = uniform_load(a.ls_dnwn, layer);
                     const double inv_scale = uniform_load(a.ls_inv_scale, layer);
                     // The packed records of the staged gathers keep the window of a group that
                     // leaves the grid UNCLIPPED: their consumers clamp every window to the tile
@@ -293,21 +309,41 @@ __global__ __launch_bounds__(kBlock) void k_records(LblArgs a)
                     // one barrier step per RECORD: the first and the last tile of a layer ran
                     // twice as long as the others and ended the launch (904 of 1003 us at C2).
                     constexpr bool kPacked = (kFmt == 1 || kFmt == 2) && !kPos;
+                    // (ceil(dnwn / scale) >= nwave in integers: dnwn > (nwave - 1) scale -- scalar
+                    // instructions for a wave-uniform value)
+                    const int scale = uniform_load(a.ls_scale, layer);
                     const bool hi_free =
-                        kPacked && -floor_div_inv(-(int)dnwn, inv_scale) >= a.nwave;
-                    const Window w = group_window(a, wavn, iown, s_ilor[e], s_alphad[e],
-                                                  ofactor, uniform_load(a.ls_dwnstep, layer), dnwn,
-                                                  0, a.ndop - 1, s_dop, uniform_load(a.ls_cutsteps, layer),
-                                                  uniform_load(a.ls_inv_ofactor, layer), !kPacked,
-                                                  !hi_free);
+                        kPacked && (int64_t)(int)dnwn > (int64_t)(a.nwave - 1) * scale;
+                    if (of_new) {
+                        // (cutsteps = cutoff / dwnstep follows the factor too)
+                        const double cutsteps = uniform_load(a.ls_cutsteps, layer);
+                        idwn = trunc_quot_inv(wavn - a.own0, uniform_load(a.ls_dwnstep, layer),
+                                              uniform_load(a.ls_inv_dwnstep, layer));
+                        subw = iown - idwn * ofactor;
+                        mincut = (int)(idwn - cutsteps);
+                        maxcut = (int)(idwn + cutsteps);
+                    }
+                    // (the Doppler column of the thread's previous layer brackets this one's:
+                    // alphad moves by a few per cent from layer to layer, a column by more)
+                    idop = nearest_index_near(s_dop, s_alphad[e] * wavn, a.ndop, idop);
+                    const Window w = window_at<true>(
+                        a, idwn, subw, s_ilor[e] * a.ndop + idop, ofactor, dnwn, mincut, maxcut,
+                        uniform_load(a.ls_inv_ofactor, layer), !kPacked, !hi_free);
                     // kept samples: minj <= scale*jo < maxj, inside the profile and the grid
-                    ulo = -floor_div_inv(-(int)w.minj, inv_scale);
-                    uhi = -floor_div_inv(-(int)w.maxj, inv_scale);
-                    ulo = max(ulo, -floor_div_inv(w.half - iown, a.inv_osamp));
+                    // (a layer whose grid has the output grid's step -- scale 1, wave-uniform --
+                    // needs no quotient)
+                    if (scale == 1) {
+                        ulo = (int)w.minj;
+                        uhi = (int)w.maxj;
+                    } else {
+                        ulo = -floor_div_inv(-(int)w.minj, inv_scale);
+                        uhi = -floor_div_inv(-(int)w.maxj, inv_scale);
+                    }
+                    q = floor_div_inv(w.half - iown, a.inv_osamp);
+                    ulo = max(ulo, -q);
                     uhi = min(uhi, floor_div_inv(iown + w.half, a.inv_osamp) + 1);
                     if (!hi_free)
                         uhi = min(uhi, a.nwave);
-                    q = floor_div_inv(w.half - iown, a.inv_osamp);
                     phi = (w.half - iown) - q * a.osamp;
                     cell = w.cell;
                     if (uhi < ulo)
@@ -498,7 +534,7 @@ size_t records_lds(const LblArgs &a, int per)
 
 // fmt: 0 SoA records, 1 packed, 2 packed with row chunks, 3 the scatter kernel's.  (The kernels
 // lie in the code object in the order they are first named: the packed formats of the usual
-// call first, as they always did, so that the device code stays byte for byte the same.)
+// call first, as they always did.)
 int launch_records(const LblArgs &a, int fmt, int per, dim3 grid, size_t lds, hipStream_t s)
 {
     GatherKernel krec;

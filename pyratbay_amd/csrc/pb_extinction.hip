@@ -237,7 +237,7 @@ int pb_lbl_create(pb_lbl **out, pb_voigt *voigt, pb_lines *lines, const double *
     alloc((void **)&p->ls_scale, L * 4);
     alloc((void **)&p->ls_dnwn, L * 8);
     alloc((void **)&p->ls_dwnstep, L * 8);
-    alloc((void **)&p->ls_quot, 4 * L * 8);
+    alloc((void **)&p->ls_quot, 5 * L * 8);
     alloc((void **)&p->li_invz, LI * 8);
     alloc((void **)&p->li_alphad, LI * 8);
     alloc((void **)&p->li_dens, LI * 8);
@@ -623,6 +623,7 @@ static LblArgs fill_args(const pb_lbl *p, const Call &c)
     a.ls_inv_ofactor = p->ls_quot + p->max_layers;
     a.ls_inv_scale = p->ls_quot + 2 * (size_t)p->max_layers;
     a.ls_inv_temp = p->ls_quot + 3 * (size_t)p->max_layers;
+    a.ls_inv_dwnstep = p->ls_quot + 4 * (size_t)p->max_layers;
     a.li_invz = p->li_invz;
     a.li_alphad = p->li_alphad;
     a.li_dens = p->li_dens;
@@ -1120,7 +1121,7 @@ static int window_map(pb_lbl *p, LblArgs &a, bool staged, hipStream_t s)
 static int make_records(pb_lbl *p, LblArgs &a, const GatherPlan &g, const Tuning &tn, hipStream_t s)
 {
     // (one layer per thread for launches of few layers measured slower: 10 layers of C2
-    // 49 us against 27 us with four; PB_REC_LAYERS=1 selects it)
+    // 49 us against 27 us with four -- kRecLayers was 4 then; PB_REC_LAYERS=1 selects it)
     const int per = tn.rec_layers_1 ? 1 : kRecLayers;
     int64_t rec_threads = a.ngroups;
     if (a.kmax_local && a.rec_flo != INT64_MIN && !p->h_ph_iown.empty() && !tn.no_window_map) {
