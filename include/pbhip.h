@@ -1310,6 +1310,8 @@ typedef struct pb_atm_model {
     const double *log10p_d, *lnp_d;     /* NumPy's log10 and log of it */
     const double *mass_d;               /* [nspecies] g mol-1 */
     int rmodel;
+    int base_vmr_stride;                /* doubles from one walker's base_vmr_d to the next's;
+                                           0: one base VMR shared by all walkers */
     double mplanet, gplanet, rplanet, refpressure;
     int par_rplanet, par_log_refpressure, par_mplanet;
     int has_qcap;
@@ -1322,6 +1324,78 @@ typedef struct pb_atm_model {
 int pb_walker_atmosphere(const pb_atm_model *model, const double *params_d, int nwalkers,
                          double *temps_d, double *dens_d, double *radius_d, double *mm_d,
                          double *cont_dens_d, double *alk_dens_d, int32_t *reject_d, void *stream);
+
+/* ---- Equilibrium chemistry per walker (pb_chemistry.hip, pb_atmosphere.hip): the VMRs of every
+ * (walker, layer) cell from the walkers' [M/H], [X/H] and X/Y, where the reference calls chemcat
+ * (pyrat/atmosphere.py:445-473).  Three launches, nothing read back, no allocation:
+ *   pb_walker_temperature     temps_d[nw][L]: the T(p) model of pb_walker_atmosphere (the same
+ *                             statements, the same bits), as formed: no reject contract
+ *   pb_equilibrium_vmr        vmr_d[nw][L][S], status_d[nw][L]
+ *   pb_walker_atmosphere_chem pb_walker_atmosphere with model->base_vmr_d[nw][L][S] read per walker
+ *                             (base_vmr_stride = L * S), nvmr = 0 and nbulk = 0 allowed (the
+ *                             reference balances no bulk in equilibrium), and chem_status_d[nw][L]
+ *                             folded into reject_d under PB_ATM_REJECT_CHEMISTRY: a status below 0
+ *                             other than PB_CHEM_REJECTED, which is the temperature's own reject.
+ *
+ * pb_equilibrium_vmr: one wavefront per cell, lane i = species i, the gas-phase reduced Newton
+ * iteration of Gordon & McBride (NASA RP-1311, section 2.3) on ln n_i and ln n from the cold start
+ * n_i = 0.1 / S, n = 0.1, with mu_i = g_i + ln n_i - ln n + ln p (p in bar), g_i = np.interp of
+ * column i of gibbs_d[ntemps][S] (G°/RT at 1 bar) at the cell's temperature; the symmetric system
+ * of order E + 1 is summed by butterfly reductions and solved in every lane by Gaussian elimination
+ * with partial pivoting; damping lambda = min(1, l1, l2) of RP-1311 eqs. 3.1-3.3; converged when
+ * lambda == 1, n_i |dln n_i| / sum n < tolerance for every species and |dln n| < tolerance.
+ * The elemental abundances b[E] come from the walker's parameters: dex = base_dex; elements with
+ * is_metal get + params[par_metal] (par_metal -1: 0); [X/H] k sets dex[scale_element[k]] =
+ * base_dex + params[scale_par[k]]; then X/Y k, in order, sets dex[ratio_num[k]] =
+ * dex[ratio_den[k]] + log10(params[ratio_par[k]]); b_j = pow(10, dex_j - dex[ihydrogen]).
+ * Hybrid k (a free log10 VMR on top of the equilibrium, the reference's hybrid_vmr): the column of
+ * species hybrid_species[k] becomes clip(pow(10, params[hybrid_par[k]]), 0, max_vmr), max_vmr the
+ * minimum over the species' elements j of (sum_i vmr_i a_ij) / a_kj, from the equilibrium VMRs;
+ * nothing is renormalised.
+ * status: the iteration count of a converged cell, or PB_CHEM_*; a cell with a negative status has
+ * zeros in vmr_d and (but for PB_CHEM_NOT_CONVERGED) iterated nothing.  params_d may be NULL when
+ * npar == 0.  The model struct (a host struct) is checked before any HIP call. */
+#define PB_ATM_REJECT_CHEMISTRY 64  /* an equilibrium cell that did not converge, a temperature
+                                       outside the Gibbs table, a bad element ratio (32 is
+                                       PB_ISO_REJECT) */
+#define PB_CHEM_MAX_SPECIES 64
+#define PB_CHEM_MAX_ELEMENTS 8
+#define PB_CHEM_MAX_HYBRID 16
+#define PB_CHEM_REJECTED (-1)       /* temperature <= 0 or NaN: rejected before the chemistry */
+#define PB_CHEM_TEMPERATURE (-2)    /* temperature outside gibbs_temps                        */
+#define PB_CHEM_RATIO (-3)          /* an X/Y <= 0, an abundance not finite and positive      */
+#define PB_CHEM_NOT_CONVERGED (-4)  /* max_iterations without a converged full step           */
+typedef struct pb_chem_model {
+    int nspecies, nelements, ntemps, nlayers, npar;
+    int ihydrogen;
+    double base_dex[PB_CHEM_MAX_ELEMENTS];
+    int is_metal[PB_CHEM_MAX_ELEMENTS];
+    int par_metal;
+    int nscale;
+    int scale_element[PB_CHEM_MAX_ELEMENTS];
+    int scale_par[PB_CHEM_MAX_ELEMENTS];
+    int nratio;
+    int ratio_num[PB_CHEM_MAX_ELEMENTS];
+    int ratio_den[PB_CHEM_MAX_ELEMENTS];
+    int ratio_par[PB_CHEM_MAX_ELEMENTS];
+    int nhybrid;
+    int hybrid_species[PB_CHEM_MAX_HYBRID];
+    int hybrid_par[PB_CHEM_MAX_HYBRID];
+    int max_iterations;
+    double tolerance;
+    const double *gibbs_temps_d;        /* [ntemps] K, ascending */
+    const double *gibbs_d;              /* [ntemps][nspecies] */
+    const int32_t *stoich_d;            /* [nspecies][nelements] */
+    const double *pressure_d;           /* [nlayers] bar */
+} pb_chem_model;
+int pb_equilibrium_vmr(const pb_chem_model *model, const double *temps_d, const double *params_d,
+                       int nwalkers, double *vmr_d, int32_t *status_d, void *stream);
+int pb_walker_temperature(const pb_atm_model *model, const double *params_d, int nwalkers,
+                          double *temps_d, void *stream);
+int pb_walker_atmosphere_chem(const pb_atm_model *model, const double *params_d, int nwalkers,
+                              const int32_t *chem_status_d, double *temps_d, double *dens_d,
+                              double *radius_d, double *mm_d, double *cont_dens_d,
+                              double *alk_dens_d, int32_t *reject_d, void *stream);
 
 /* ---- Isotope ratios of the table's slots (pb_isotopes.hip): Line_Sample's isotope_ratios
  * (pyratbay/opacity/line_sampling.py:282-298, 451-456: density * iso_ratios before interp_ec) for

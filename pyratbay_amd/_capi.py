@@ -108,6 +108,9 @@ _PROTOS = {
     'pb_cloudy_emission_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f64, i32, i32, i32,
                                  i32, vp, vp, vp, vp, vp],
     'pb_walker_atmosphere': [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    'pb_walker_temperature': [vp, vp, i32, vp, vp],
+    'pb_equilibrium_vmr': [vp, vp, vp, i32, vp, vp, vp],
+    'pb_walker_atmosphere_chem': [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     'pb_iso_density': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
     'pb_optdepth': [vp, vp, i64, vp, i32, f64, vp, i32, i32, vp],
     'pb_optical_depth_transit': [vp, vp, vp, vp, i32, i32, f64, i32, i32, vp],

@@ -8,7 +8,9 @@ Two forms of the same arithmetic:
     ScaleVMR, SlantVMR, vmr_scale, ideal_gas_density, mean_weight, hydro_m, hydro_g, qcapcheck),
     for TableSpectrum.eval() users and CPU tests;
   * WalkerAtmosphere.evaluate: params[nw, npar] -> the device tensors TableSpectrum.eval_bands
-    takes, one launch of pb_walker_atmosphere (csrc/pb_atmosphere.hip), nothing read back.
+    takes, one launch of pb_walker_atmosphere (csrc/pb_atmosphere.hip), nothing read back; with
+    chemistry=ChemNetwork(...) (chemistry.py) the VMRs are the equilibrium of every layer at the
+    walker's [M/H], [X/H] and X/Y, three launches.
 
 Constants: those of pyratbay.constants (CODATA 2018 as scipy.constants carries them, the products
 NumPy forms), not the legacy set of the reference's C extensions.
@@ -34,11 +36,15 @@ MAX_SPECIES, MAX_VMR, MAX_BULK, MAX_LAYERS = 32, 16, 4, 1024
 MAX_ISO_SLOTS, MAX_ISO_FILLERS = 32, 7
 REJECT_TEMP, REJECT_MADHU, REJECT_QCAP, REJECT_REFPRESSURE, REJECT_DIVERGENT = 1, 2, 4, 8, 16
 REJECT_ISOTOPE = 32                    # a non-finite or negative isotope ratio (isotopes.py)
+# (32 is taken by the isotope ratios, which share the mask: the chemistry's bit is the next one)
+REJECT_CHEMISTRY = 64                  # an equilibrium cell without VMRs (chemistry.py)
 REJECT_NAMES = {REJECT_TEMP: 'temperature <= 0 or not finite', REJECT_MADHU: 'madhu log_p1 > log_p3',
                 REJECT_QCAP: 'trace abundances above qcap',
                 REJECT_REFPRESSURE: 'reference pressure outside the grid',
                 REJECT_DIVERGENT: 'divergent hydro_m profile, or a radius <= 0 or not finite',
-                REJECT_ISOTOPE: 'a negative or non-finite isotope ratio'}
+                REJECT_ISOTOPE: 'a negative or non-finite isotope ratio',
+                REJECT_CHEMISTRY: 'equilibrium chemistry: not converged, a temperature outside '
+                                  'the Gibbs table, or an element ratio <= 0'}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -259,6 +265,55 @@ class SlantVMR:
         return 10.0**np.clip(log_vmr, vmr_min, vmr_max)
 
 
+# Equilibrium-chemistry models (vmr_models.py:60-126): the names of the parameters that set the
+# elemental abundances of a chemistry.ChemNetwork; they carry no arithmetic of their own
+# (ChemNetwork.element_abundances_host has the rule).
+class MetalEquil:
+    """Metallicity of a thermochemical-equilibrium model: [M/H], in dex relative to solar, on
+    every element but H and He."""
+
+    def __init__(self):
+        self.name = 'metal_equil'
+        self.pnames = ['[M/H]']
+        self.texnames = ['[M/H]']
+        self.npars = 1
+        self.type = 'equil'
+
+
+class ScaleEquil:
+    """Abundance of one element of a thermochemical-equilibrium model: name '[X/H]' (e.g. '[C/H]'),
+    in dex relative to solar; overrides the metallicity for X."""
+
+    def __init__(self, name):
+        name = str(name)
+        if len(name) < 5 or name[0] != '[' or name[-3:] != '/H]':
+            raise ValueError(f"ScaleEquil: the format is [X/H], got '{name}'")
+        self.name = 'scale_equil'
+        self.element = name[1:-3]
+        self.pnames = [name]
+        self.texnames = [name]
+        self.npars = 1
+        self.type = 'equil'
+
+
+class RatioEquil:
+    """Abundance ratio of two elements of a thermochemical-equilibrium model: name 'X/Y' (e.g.
+    'C/O'), the ratio itself (not its logarithm); sets X from Y."""
+
+    def __init__(self, name):
+        name = str(name)
+        if name.count('/') != 1 or name[0] == '/' or name[-1] == '/':
+            raise ValueError(f"RatioEquil: the format is X/Y, got '{name}'")
+        self.name = 'ratio_equil'
+        idx = name.index('/')
+        self.elements = [name[0:idx], name[idx + 1:]]
+        self.element_ratio = name.replace('/', '_')
+        self.pnames = [name]
+        self.texnames = [name]
+        self.npars = 1
+        self.type = 'equil'
+
+
 # ---------------------------------------------------------------------------------------------
 # Abundance scaling (pyratbay/atmosphere/vmr_scaling.py)
 # ---------------------------------------------------------------------------------------------
@@ -400,6 +455,7 @@ class AtmModelStruct(C.Structure):
         ('log10p_d', C.c_void_p), ('lnp_d', C.c_void_p),
         ('mass_d', C.c_void_p),
         ('rmodel', C.c_int),
+        ('base_vmr_stride', C.c_int),
         ('mplanet', C.c_double), ('gplanet', C.c_double), ('rplanet', C.c_double),
         ('refpressure', C.c_double),
         ('par_rplanet', C.c_int), ('par_log_refpressure', C.c_int), ('par_mplanet', C.c_int),
@@ -415,6 +471,11 @@ Profiles = collections.namedtuple(
     'Profiles', 'temps dens radius mm continuum_density alkali_density reject')
 
 _TMODELS = {Isothermal: 0, Guillot: 1, Madhu: 2}
+
+
+def _chemistry():
+    from . import chemistry
+    return chemistry
 _SCALARS = ('rplanet', 'log_refpressure', 'mplanet')
 
 
@@ -450,11 +511,30 @@ class WalkerAtmosphere:
     radius of the base model, and a base model needs a parameter vector, so when base_radius is
     None, base_params[npar] (in `free` order) must be given; it is used for nothing else.
 
-    Equilibrium-chemistry and hybrid VMR models are not supported (ValueError)."""
+    chemistry (an ADDITION: the reference asks chemcat): None, or a chemistry.ChemNetwork; then
+    the VMRs are the gas-phase equilibrium of every layer at the walker's elemental abundances
+    (Atmosphere.calc_profiles' chemistry == 'equilibrium' branch, pyrat/atmosphere.py:445-473):
+      * species must be the network's; base_vmr, bulk and qcap are not taken (pass None): the
+        reference balances no bulk in equilibrium;
+      * vmr_models holds MetalEquil(), ScaleEquil('[C/H]'), RatioEquil('C/O') (the rule:
+        ChemNetwork.element_abundances_host) and IsoVMR models on network species, the hybrid
+        ones: their column is clip(10**value, 0, max_vmr) on top of the equilibrium, max_vmr
+        from the elements the equilibrium mixture holds (hybrid_vmr, vmr_models.py:40-57),
+        nothing renormalised.  ScaleVMR and SlantVMR are refused, as the reference's hybrid is
+        hard-wired to IsoVMR.  The reference's out-of-bounds flag of a hybrid value above its cap
+        is inert (it sets out_of_bounds_vmr, the check reads _out_of_bounds_vmr,
+        pyrat/atmosphere.py:473, 494), so no walker is rejected for it here either;
+      * evaluate is three launches with nothing read back: the temperatures
+        (pb_walker_temperature), the equilibrium of every (walker, layer) cell
+        (pb_equilibrium_vmr), then pb_walker_atmosphere_chem on those VMRs;
+      * a walker with a cell that did not converge, a temperature outside the network's Gibbs
+        table or an X/Y <= 0 is rejected under REJECT_CHEMISTRY (64: 32 is the isotope ratios').
+    Without a network the equilibrium models are refused (ValueError)."""
 
     def __init__(self, pressure, species, mol_mass, base_vmr, bulk, tmodel, vmr_models,
                  rmodel='hydro_m', mplanet=None, gplanet=None, rplanet=None, refpressure=None,
-                 qcap=None, base_radius=None, free=None, base_params=None):
+                 qcap=None, base_radius=None, free=None, base_params=None, chemistry=None):
+        self.chemistry = chemistry
         self.pressure = np.ascontiguousarray(pressure, float)
         L = self.nlayers = len(self.pressure)
         if self.pressure.ndim != 1 or not 2 <= L <= MAX_LAYERS:
@@ -467,19 +547,32 @@ class WalkerAtmosphere:
         if not 1 <= S <= MAX_SPECIES or len(set(self.species)) != S:
             raise ValueError(f'species: 1 ... {MAX_SPECIES} distinct names, got {self.species}')
         self.mol_mass = np.ascontiguousarray(mol_mass, float)
-        self.base_vmr = np.ascontiguousarray(base_vmr, float)
         if self.mol_mass.shape != (S,):
             raise ValueError(f'mol_mass must have shape {(S,)}, got {self.mol_mass.shape}')
-        if self.base_vmr.shape != (L, S):
-            raise ValueError(f'base_vmr must have shape {(L, S)}, got {self.base_vmr.shape}')
-        self.bulk = [str(b) for b in bulk]
-        if not 1 <= len(self.bulk) <= MAX_BULK or len(set(self.bulk)) != len(self.bulk):
-            raise ValueError(f'bulk: 1 ... {MAX_BULK} distinct species, got {self.bulk}')
-        for b in self.bulk:
-            if b not in self.species:
-                raise ValueError(f'bulk species {b} is not in the atmosphere ({self.species})')
-        self.ibulk = [self.species.index(b) for b in self.bulk]
-        self.bratio, self.invsrat = ratio(self.base_vmr, self.ibulk)
+        if chemistry is None:
+            self.base_vmr = np.ascontiguousarray(base_vmr, float)
+            if self.base_vmr.shape != (L, S):
+                raise ValueError(f'base_vmr must have shape {(L, S)}, got {self.base_vmr.shape}')
+            self.bulk = [str(b) for b in bulk]
+            if not 1 <= len(self.bulk) <= MAX_BULK or len(set(self.bulk)) != len(self.bulk):
+                raise ValueError(f'bulk: 1 ... {MAX_BULK} distinct species, got {self.bulk}')
+            for b in self.bulk:
+                if b not in self.species:
+                    raise ValueError(f'bulk species {b} is not in the atmosphere ({self.species})')
+            self.ibulk = [self.species.index(b) for b in self.bulk]
+            self.bratio, self.invsrat = ratio(self.base_vmr, self.ibulk)
+        else:
+            if self.species != list(chemistry.species):
+                raise ValueError(f'chemistry: species must be the network\'s {chemistry.species}, '
+                                 f'got {self.species}')
+            if base_vmr is not None or (bulk is not None and len(bulk)):
+                raise ValueError('chemistry: base_vmr and bulk are not taken (pass None): the '
+                                 'equilibrium gives every VMR, and the reference balances no bulk '
+                                 'in equilibrium')
+            if qcap is not None:
+                raise ValueError('chemistry: qcap is not taken (there are no bulk species)')
+            self.base_vmr, self.bulk, self.ibulk = None, [], []
+            self.bratio = self.invsrat = None
 
         if type(tmodel) not in _TMODELS:
             raise ValueError('tmodel: an Isothermal, Guillot or Madhu of pyratbay_amd.atmosphere, '
@@ -496,13 +589,37 @@ class WalkerAtmosphere:
         if len(self.vmr_models) > MAX_VMR:
             raise ValueError(f'at most {MAX_VMR} VMR models, got {len(self.vmr_models)}')
         taken = set(self.bulk)
+        self._equil = dict(par_metal=-1, scales=[], ratios=[], hybrids=[])
+        for model in self.vmr_models if chemistry is not None else []:
+            if not isinstance(model, (MetalEquil, ScaleEquil, RatioEquil, IsoVMR)):
+                raise ValueError(
+                    f'VMR model {getattr(model, "name", type(model).__name__)}: with chemistry, '
+                    'only MetalEquil, ScaleEquil, RatioEquil and (hybrid) IsoVMR models are '
+                    'taken; the reference\'s hybrid is hard-wired to IsoVMR')
+            if isinstance(model, ScaleEquil):
+                chemistry.element_index(model.element)
+                if model.element == 'H':
+                    raise ValueError('ScaleEquil: [H/H] is no parameter (abundances are relative '
+                                     'to hydrogen)')
+            if isinstance(model, RatioEquil):
+                chemistry.ratio_elements(model.pnames[0])
+        if chemistry is not None:
+            pnames = [n for m in self.vmr_models for n in m.pnames]
+            if len(set(pnames)) != len(pnames):
+                raise ValueError(f'VMR models: a parameter is named twice ({pnames})')
+            limit = _chemistry().MAX_ELEMENTS
+            for cls in (ScaleEquil, RatioEquil):
+                if sum(isinstance(m, cls) for m in self.vmr_models) > limit:
+                    raise ValueError(f'at most {limit} {cls.__name__} models')
         for model in self.vmr_models:
+            if chemistry is not None and not isinstance(model, IsoVMR):
+                continue
             if getattr(model, 'type', 'free') != 'free' or \
                     not isinstance(model, (IsoVMR, ScaleVMR, SlantVMR)):
                 raise ValueError(
                     f'VMR model {getattr(model, "name", type(model).__name__)}: '
-                    'equilibrium-chemistry and hybrid models are not supported, only IsoVMR, '
-                    'ScaleVMR and SlantVMR')
+                    'equilibrium-chemistry and hybrid models are not supported without '
+                    'chemistry=ChemNetwork(...), only IsoVMR, ScaleVMR and SlantVMR')
             if model.species not in self.species:
                 raise ValueError(f'VMR model {model.name}: species {model.species} is not in the '
                                  f'atmosphere ({self.species})')
@@ -512,7 +629,8 @@ class WalkerAtmosphere:
             taken.add(model.species)
             if not np.array_equal(np.asarray(model.pressure, float), self.pressure):
                 raise ValueError(f'VMR model {model.name} is defined on another pressure grid')
-        self.iscale = [self.species.index(m.species) for m in self.vmr_models]
+        self.iscale = [self.species.index(m.species) if hasattr(m, 'species') else -1
+                       for m in self.vmr_models]
 
         names = list(tmodel.pnames)
         self.tpar = slice(0, tmodel.npars)
@@ -520,6 +638,16 @@ class WalkerAtmosphere:
         for model in self.vmr_models:
             self.vmr_par.append(len(names))
             names += list(model.pnames)
+        for model, col, isp in zip(self.vmr_models if chemistry is not None else [],
+                                   self.vmr_par, self.iscale):
+            if isinstance(model, MetalEquil):
+                self._equil['par_metal'] = col
+            elif isinstance(model, ScaleEquil):
+                self._equil['scales'].append((chemistry.element_index(model.element), col))
+            elif isinstance(model, RatioEquil):
+                self._equil['ratios'].append(chemistry.ratio_elements(model.pnames[0]) + (col,))
+            else:
+                self._equil['hybrids'].append((isp, col))
         nmodel = len(names)
         free = names if free is None else [str(f) for f in free]
         if free[:nmodel] != names:
@@ -557,6 +685,7 @@ class WalkerAtmosphere:
         self._maps = None
         self._dev = None
         self._struct = None
+        self._chem_buffers = {}
         # (kept for the retrieval front end: the value of a column no retrieval parameter names)
         self.base_params = None if base_params is None else \
             np.array(base_params, dtype=np.float64)
@@ -587,12 +716,21 @@ class WalkerAtmosphere:
             reject |= REJECT_MADHU
         if np.any(~(temp > 0)) or not np.all(np.isfinite(temp)):
             reject |= REJECT_TEMP
-        pars = [params[o:o + m.npars] for o, m in zip(self.vmr_par, self.vmr_models)]
-        vmr = vmr_scale(self.base_vmr, self.species, self.vmr_models, pars, self.bulk,
-                        iscale=self.iscale, ibulk=self.ibulk, bratio=self.bratio,
-                        invsrat=self.invsrat)
-        if qcapcheck(vmr, self.qcap, self.ibulk):
-            reject |= REJECT_QCAP
+        no_vmr = False
+        if self.chemistry is not None:
+            vmr, status = self.equilibrium_host(params, temp)
+            if np.any((status < 0) & (status != _chemistry().STATUS_REJECTED)):
+                reject |= REJECT_CHEMISTRY
+            # a cell without VMRs has no mean mass: the walker is rejected already (this bit, or
+            # the temperature's), and its radius is not judged
+            no_vmr = bool(np.any(status < 0))
+        else:
+            pars = [params[o:o + m.npars] for o, m in zip(self.vmr_par, self.vmr_models)]
+            vmr = vmr_scale(self.base_vmr, self.species, self.vmr_models, pars, self.bulk,
+                            iscale=self.iscale, ibulk=self.ibulk, bratio=self.bratio,
+                            invsrat=self.invsrat)
+            if qcapcheck(vmr, self.qcap, self.ibulk):
+                reject |= REJECT_QCAP
         with np.errstate(all='ignore'):
             dens = ideal_gas_density(vmr, self.pressure, temp)
             mm = mean_weight(vmr, mass=self.mol_mass)
@@ -606,6 +744,8 @@ class WalkerAtmosphere:
             radius = None
             if not (p0 >= self.pressure[0] and p0 <= self.pressure[-1]):
                 reject |= REJECT_REFPRESSURE
+            elif no_vmr:
+                pass
             elif self.rmodel == 'hydro_m':
                 radius = hydro_m(self.pressure, temp, mm, mass, p0, r0)
                 # (hydro_m has marked the layers above a turn-over with inf)
@@ -617,6 +757,23 @@ class WalkerAtmosphere:
             if radius is not None and not (np.all(np.isfinite(radius)) and np.all(radius > 0)):
                 reject |= REJECT_DIVERGENT
         return dict(temps=temp, vmr=vmr, dens=dens, mm=mm, radius=radius, reject=reject)
+
+    def equilibrium_host(self, params, temp):
+        """The VMRs of one walker with chemistry: the elemental abundances from its [M/H], [X/H]
+        and X/Y, the equilibrium of every layer, then the hybrid columns, each capped from the
+        equilibrium VMRs -> vmr[L, S], status[L] (chemistry.equilibrium_host's)."""
+        net, eq = self.chemistry, self._equil
+        metallicity = None if eq['par_metal'] < 0 else params[eq['par_metal']]
+        e_scale = {net.elements[j]: params[col] for j, col in eq['scales']}
+        e_ratio = {f'{net.elements[x]}/{net.elements[y]}': params[col]
+                   for x, y, col in eq['ratios']}
+        b = net.element_abundances_host(metallicity, e_scale, e_ratio)
+        equil, _, status = net.equilibrium_host(temp, self.pressure, b)
+        vmr = equil.copy()
+        for isp, col in eq['hybrids']:
+            column = net.hybrid_host(equil, self.species[isp], params[col])
+            vmr[:, isp] = np.where(status > 0, column, 0.0)
+        return vmr, status
 
     def evaluate_host(self, params):
         """One walker through the host forms: the same result tuple as evaluate() (NumPy arrays,
@@ -669,9 +826,10 @@ class WalkerAtmosphere:
             d['pressure'] = dev(self.pressure)
             d['log10p'] = dev(np.log10(self.pressure))
             d['lnp'] = dev(np.log(self.pressure))
-            d['base_vmr'] = dev(self.base_vmr)
-            d['bratio'] = dev(self.bratio)
-            d['invsrat'] = dev(self.invsrat)
+            if self.chemistry is None:
+                d['base_vmr'] = dev(self.base_vmr)
+                d['bratio'] = dev(self.bratio)
+                d['invsrat'] = dev(self.invsrat)
             d['mass'] = dev(self.mol_mass)
             d['base_radius'] = dev(self.base_radius)
             if isinstance(self.tmodel, Madhu):
@@ -688,14 +846,36 @@ class WalkerAtmosphere:
         st = self.model_struct()
         st.madhu_weights_d = d['weights'].data_ptr() if 'weights' in d else None
         st.vmr0_d = d['vmr0'].data_ptr()
-        st.bulk_ratio_d, st.invsrat_d = d['bratio'].data_ptr(), d['invsrat'].data_ptr()
-        st.base_vmr_d, st.pressure_d = d['base_vmr'].data_ptr(), d['pressure'].data_ptr()
+        if self.chemistry is None:
+            st.bulk_ratio_d, st.invsrat_d = d['bratio'].data_ptr(), d['invsrat'].data_ptr()
+            st.base_vmr_d = d['base_vmr'].data_ptr()
+        else:                   # base_vmr_d: the equilibrium VMRs of a call (_chemistry_buffers)
+            self._chem_struct = self.chemistry.bound_struct(d['pressure'], self.npar,
+                                                            **self._equil)
+        st.pressure_d = d['pressure'].data_ptr()
         st.log10p_d, st.lnp_d = d['log10p'].data_ptr(), d['lnp'].data_ptr()
         st.mass_d, st.base_radius_d = d['mass'].data_ptr(), d['base_radius'].data_ptr()
         st.tab_map_d = d['tab_map'].data_ptr()
         st.cont_map_d = d['cont_map'].data_ptr() if self._cont_species else None
         st.alk_map_d = d['alk_map'].data_ptr() if self._alk_species else None
         self._struct = st
+        self._chem_buffers = {}
+
+    def _chemistry_buffers(self, nw, device):
+        """The buffers between the three launches of a call with chemistry, kept per nw so that a
+        call with `out` allocates nothing: the temperatures as formed, the equilibrium VMRs and
+        cell statuses, and this model's struct pointing at those VMRs."""
+        import torch
+        key = (nw, str(device))
+        if key not in self._chem_buffers:
+            L, S = self.nlayers, self.nspecies
+            temps = torch.empty((nw, L), dtype=torch.float64, device=device)
+            vmr = torch.empty((nw, L, S), dtype=torch.float64, device=device)
+            status = torch.empty((nw, L), dtype=torch.int32, device=device)
+            st = AtmModelStruct.from_buffer_copy(self._struct)
+            st.base_vmr_d, st.base_vmr_stride = vmr.data_ptr(), L * S
+            self._chem_buffers[key] = (temps, vmr, status, st)
+        return self._chem_buffers[key]
 
     def model_struct(self):
         """The pb_atm_model of this model with its scalar fields set (device pointers: null)."""
@@ -709,8 +889,9 @@ class WalkerAtmosphere:
         if isinstance(self.tmodel, Madhu):
             st.madhu_radius = (len(self.tmodel.weights) - 1) // 2
             st.madhu_logp0, st.madhu_loge = float(self.tmodel.logp0), float(self.tmodel.loge)
-        st.nvmr = len(self.vmr_models)
-        for i, model in enumerate(self.vmr_models):
+        # (with chemistry every VMR comes from the equilibrium launch: no model, no bulk here)
+        st.nvmr = len(self.vmr_models) if self.chemistry is None else 0
+        for i, model in enumerate(self.vmr_models if self.chemistry is None else []):
             st.vmr_kind[i], st.vmr_species[i] = model.kind, self.iscale[i]
             st.vmr_par[i] = self.vmr_par[i]
         st.nbulk = len(self.ibulk)
@@ -774,6 +955,21 @@ class WalkerAtmosphere:
                                             t.dtype != dtype or t.device != params.device)):
                     raise ValueError(f'evaluate: out.{name} must be a contiguous {dtype} tensor '
                                      f'of shape {shape} on {params.device}')
+        outputs = (out.temps.data_ptr(), out.dens.data_ptr(), out.radius.data_ptr(),
+                   out.mm.data_ptr(),
+                   None if out.continuum_density is None else out.continuum_density.data_ptr(),
+                   None if out.alkali_density is None else out.alkali_density.data_ptr(),
+                   out.reject.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if self.chemistry is not None:
+            temps, vmr, status, cst = self._chemistry_buffers(nw, params.device)
+            stream = outputs[-1]
+            call('pb_walker_temperature', C.byref(st), params.data_ptr(), nw, temps.data_ptr(),
+                 stream)
+            call('pb_equilibrium_vmr', C.byref(self._chem_struct), temps.data_ptr(),
+                 params.data_ptr(), nw, vmr.data_ptr(), status.data_ptr(), stream)
+            call('pb_walker_atmosphere_chem', C.byref(cst), params.data_ptr(), nw,
+                 status.data_ptr(), *outputs)
+            return out
         call('pb_walker_atmosphere', C.byref(st), params.data_ptr(), nw,
              out.temps.data_ptr(), out.dens.data_ptr(), out.radius.data_ptr(),
              out.mm.data_ptr(),

@@ -1,5 +1,8 @@
 // pb_walker_atmosphere: the walkers' atmospheres from their parameter vectors, one launch
 // (Atmosphere.calc_profiles, pyratbay/pyrat/atmosphere.py:399-526, for a batch).
+// pb_walker_atmosphere_chem is the same kernel on per-walker base VMRs (those of pb_equilibrium_vmr,
+// pb_chemistry.hip, whose cell statuses it folds into the reject mask); pb_walker_temperature runs
+// the T(p) model alone, for the equilibrium to read.
 //
 // One wavefront per walker, lanes over layers (looping when nlayers > 64), the profile in LDS.
 // Everything in binary64, in the reference's order of operations; the build's -ffp-contract=off
@@ -32,6 +35,7 @@ struct AtmArgs {
     const double *params;
     double *temps, *dens, *radius, *mm, *cdens, *adens;
     int32_t *reject;
+    const int32_t *chem_status;   // [nw][L] of pb_equilibrium_vmr, or null
 };
 
 // Exponential integral E2(x), x >= 0, from its definitions (Abramowitz & Stegun 5.1.12, 5.1.22):
@@ -101,14 +105,15 @@ __device__ double numpy_row_sum(const double *v, int stride, const double *mass,
 }
 
 // The VMRs of layer l into column `lane` of s_vmr[nspecies][64]: the models, then the bulk balance.
+// base_vmr: the walker's [nlayers][nspecies] (the shared one when base_vmr_stride is 0).
 // Returns the mean molecular mass; *over_cap: the trace VMRs sum above qcap.
-__device__ double layer_vmr(const pb_atm_model &m, const double *par, int l, int lane,
-                            double *s_vmr, const double *s_pow, unsigned bulk_mask,
+__device__ double layer_vmr(const pb_atm_model &m, const double *base_vmr, const double *par, int l,
+                            int lane, double *s_vmr, const double *s_pow, unsigned bulk_mask,
                             bool *over_cap)
 {
     const int S = m.nspecies;
     for (int sp = 0; sp < S; sp++)
-        s_vmr[sp * kWave + lane] = m.base_vmr_d[(int64_t)l * S + sp];
+        s_vmr[sp * kWave + lane] = base_vmr[(int64_t)l * S + sp];
     for (int i = 0; i < m.nvmr; i++) {
         const double *p = par + m.vmr_par[i];
         double v;
@@ -155,25 +160,16 @@ __device__ void gather_density(double *out, int64_t base, const int32_t *map, in
     }
 }
 
-__global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
+// The walkers' T(p) (tmodels.py) into s_temp[L], s_aux[L] as work space (madhu's raw profile): one
+// wavefront, the statements both k_walker_atmosphere and k_walker_temperature run (same bits).
+// Returns the reject bits the model itself sets (madhu: log_p1 > log_p3).  The caller synchronises
+// before it reads s_temp.
+__device__ int walker_temperature(const pb_atm_model &m, const double *par, int lane, double *s_temp,
+                                  double *s_aux)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const pb_atm_model &m = a.m;
-    const int L = m.nlayers, S = m.nspecies;
-    const int lane = threadIdx.x;
-    const int64_t w = blockIdx.x;
-    const int Lp = lds_row(L);
-    double *s_temp = reinterpret_cast<double *>(smem);   // temperatures
-    double *s_aux = s_temp + Lp;                         // madhu's raw profile; integrand; radius
-    double *s_mm = s_aux + Lp;                           // mean molecular mass
-    double *s_int = s_mm + Lp;                           // cumulative trapezoid
-    double *s_vmr = s_int + Lp;                          // [S][64] VMRs of a chunk of layers
-    double *s_pow = s_vmr + S * kWave;                   // [nvmr] 10^p of the Iso / Scale models
-    const double *par = a.params + w * m.npar;
+    const int L = m.nlayers;
     const double *pressure = m.pressure_d;
     int flags = 0;
-
-    // ---- temperature (tmodels.py)
     if (m.tmodel == 0) {
         for (int l = lane; l < L; l += kWave)
             s_temp[l] = par[0];
@@ -231,6 +227,30 @@ __global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
             }
         }
     }
+    return flags;
+}
+
+__global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const pb_atm_model &m = a.m;
+    const int L = m.nlayers, S = m.nspecies;
+    const int lane = threadIdx.x;
+    const int64_t w = blockIdx.x;
+    const int Lp = lds_row(L);
+    double *s_temp = reinterpret_cast<double *>(smem);   // temperatures
+    double *s_aux = s_temp + Lp;                         // madhu's raw profile; integrand; radius
+    double *s_mm = s_aux + Lp;                           // mean molecular mass
+    double *s_int = s_mm + Lp;                           // cumulative trapezoid
+    double *s_vmr = s_int + Lp;                          // [S][64] VMRs of a chunk of layers
+    double *s_pow = s_vmr + S * kWave;                   // [nvmr] 10^p of the Iso / Scale models
+    const double *par = a.params + w * m.npar;
+    const double *pressure = m.pressure_d;
+    const double *base_vmr = m.base_vmr_d + w * m.base_vmr_stride;
+    int flags = 0;
+
+    // ---- temperature (tmodels.py)
+    flags |= walker_temperature(m, par, lane, s_temp, s_aux);
     for (int i = lane; i < m.nvmr; i += kWave)
         s_pow[i] = m.vmr_kind[i] == 2 ? 0.0 : pow(10.0, par[m.vmr_par[i]]);
     __syncthreads();
@@ -239,6 +259,21 @@ __global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
         if (!(t > 0.0) || !(fabs(t) <= 1.79769313486231570815e308))
             flags |= PB_ATM_REJECT_TEMP;
     }
+    // the cells of the equilibrium chemistry that gave no VMRs (PB_CHEM_REJECTED is the
+    // temperature's own reject, flagged above)
+    // A walker with any cell without VMRs has no mean mass there, so its radius is not judged (it
+    // is rejected already).
+    bool no_vmr = false;
+    if (a.chem_status) {
+        bool missing = false;
+        for (int l = lane; l < L; l += kWave) {
+            const int32_t s = a.chem_status[w * L + l];
+            missing = missing || s < 0;
+            if (s < 0 && s != PB_CHEM_REJECTED)
+                flags |= PB_ATM_REJECT_CHEMISTRY;
+        }
+        no_vmr = __any(missing) != 0;            // the block is one wavefront
+    }
 
     // ---- abundances: the cap on the traces and the mean molecular mass of every layer
     unsigned bulk_mask = 0;
@@ -246,7 +281,7 @@ __global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
         bulk_mask |= 1u << m.bulk_species[j];
     for (int l = lane; l < L; l += kWave) {
         bool over;
-        s_mm[l] = layer_vmr(m, par, l, lane, s_vmr, s_pow, bulk_mask, &over);
+        s_mm[l] = layer_vmr(m, base_vmr, par, l, lane, s_vmr, s_pow, bulk_mask, &over);
         if (over)
             flags |= PB_ATM_REJECT_QCAP;
     }
@@ -272,9 +307,9 @@ __global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
         // a radius that is not finite and positive is no geometry for either model (a free
         // rplanet or mplanet that is NaN, zero or negative; every <= below is false on NaN)
         for (int l = lane; l < L; l += kWave)
-            if (!(s_aux[l] > 0.0) || !(s_aux[l] <= 1.79769313486231570815e308))
+            if (!no_vmr && (!(s_aux[l] > 0.0) || !(s_aux[l] <= 1.79769313486231570815e308)))
                 flags |= PB_ATM_REJECT_DIVERGENT;
-        if (m.rmodel == 0)
+        if (m.rmodel == 0 && !no_vmr)
             for (int l = lane; l < L - 1; l += kWave)
                 if (s_aux[l] <= s_aux[l + 1])
                     flags |= PB_ATM_REJECT_DIVERGENT;
@@ -299,7 +334,7 @@ __global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
         __syncthreads();
         if (!rejected && lane < nl) {
             bool over;
-            layer_vmr(m, par, l0 + lane, lane, s_vmr, s_pow, bulk_mask, &over);
+            layer_vmr(m, base_vmr, par, l0 + lane, lane, s_vmr, s_pow, bulk_mask, &over);
         }
         __syncthreads();
         gather_density(a.dens, w * L * m.ntab, m.tab_map_d, m.ntab, l0, nl, s_vmr, s_temp,
@@ -313,7 +348,24 @@ __global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
     }
 }
 
-int atm_check(const pb_atm_model *m)
+// One wavefront per walker: the T(p) model alone, as formed (no reject contract).
+__global__ __launch_bounds__(kWave) void k_walker_temperature(pb_atm_model m, const double *params,
+                                                              double *temps)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int L = m.nlayers;
+    const int lane = threadIdx.x;
+    const int64_t w = blockIdx.x;
+    double *s_temp = reinterpret_cast<double *>(smem);
+    double *s_aux = s_temp + lds_row(L);
+    walker_temperature(m, params + w * m.npar, lane, s_temp, s_aux);
+    __syncthreads();
+    for (int l = lane; l < L; l += kWave)
+        temps[w * L + l] = s_temp[l];
+}
+
+// chem: the call of pb_walker_atmosphere_chem, which may come without bulk species
+int atm_check(const pb_atm_model *m, bool chem)
 {
     PB_REQUIRE(m, "pb_walker_atmosphere: null model struct");
     PB_REQUIRE(m->nlayers >= 2 && m->nlayers <= PB_ATM_MAX_LAYERS,
@@ -335,8 +387,11 @@ int atm_check(const pb_atm_model *m)
                    m->madhu_radius);
     PB_REQUIRE(m->nvmr >= 0 && m->nvmr <= PB_ATM_MAX_VMR,
                "pb_walker_atmosphere: at most %d VMR models, not %d", PB_ATM_MAX_VMR, m->nvmr);
-    PB_REQUIRE(m->nbulk >= 1 && m->nbulk <= PB_ATM_MAX_BULK,
+    PB_REQUIRE(m->nbulk >= (chem ? 0 : 1) && m->nbulk <= PB_ATM_MAX_BULK,
                "pb_walker_atmosphere: 1-%d bulk species, not %d", PB_ATM_MAX_BULK, m->nbulk);
+    PB_REQUIRE(m->base_vmr_stride == 0 || m->base_vmr_stride == m->nlayers * m->nspecies,
+               "pb_walker_atmosphere: base_vmr_stride %d (0: shared, or nlayers * nspecies = %d)",
+               m->base_vmr_stride, m->nlayers * m->nspecies);
     unsigned used = 0;
     for (int j = 0; j < m->nbulk; j++) {
         PB_REQUIRE(m->bulk_species[j] >= 0 && m->bulk_species[j] < m->nspecies,
@@ -363,7 +418,8 @@ int atm_check(const pb_atm_model *m)
         scale = scale || m->vmr_kind[i] == 1;
     }
     PB_REQUIRE(!scale || m->vmr0_d, "pb_walker_atmosphere: null vmr0 (ScaleVMR)");
-    PB_REQUIRE(m->bulk_ratio_d && m->invsrat_d && m->base_vmr_d && m->pressure_d && m->log10p_d &&
+    PB_REQUIRE((m->nbulk == 0 || (m->bulk_ratio_d && m->invsrat_d)) && m->base_vmr_d &&
+                   m->pressure_d && m->log10p_d &&
                    m->lnp_d && m->mass_d && m->base_radius_d,
                "pb_walker_atmosphere: null model array");
     PB_REQUIRE(m->rmodel == 0 || m->rmodel == 1,
@@ -392,11 +448,14 @@ int atm_check(const pb_atm_model *m)
 
 }  // namespace
 
-int pb_walker_atmosphere(const pb_atm_model *model, const double *params_d, int nwalkers,
-                         double *temps_d, double *dens_d, double *radius_d, double *mm_d,
-                         double *cont_dens_d, double *alk_dens_d, int32_t *reject_d, void *stream)
+namespace {
+
+int walker_atmosphere(const pb_atm_model *model, const double *params_d, int nwalkers,
+                      const int32_t *chem_status_d, bool chem, double *temps_d, double *dens_d,
+                      double *radius_d, double *mm_d, double *cont_dens_d, double *alk_dens_d,
+                      int32_t *reject_d, void *stream)
 {
-    const int rc = atm_check(model);
+    const int rc = atm_check(model, chem);
     if (rc != PB_OK)
         return rc;
     PB_REQUIRE(nwalkers >= 0, "pb_walker_atmosphere: %d walkers", nwalkers);
@@ -406,8 +465,60 @@ int pb_walker_atmosphere(const pb_atm_model *model, const double *params_d, int 
                    (model->ncont == 0 || cont_dens_d) && (model->nalk == 0 || alk_dens_d),
                "pb_walker_atmosphere: null pointer");
     const size_t lds = sizeof(double) * lds_doubles(model->nlayers, model->nspecies);
-    AtmArgs a{*model, params_d, temps_d, dens_d, radius_d, mm_d, cont_dens_d, alk_dens_d, reject_d};
+    PB_REQUIRE(!chem || chem_status_d, "pb_walker_atmosphere_chem: null chem_status");
+    AtmArgs a{*model, params_d, temps_d, dens_d, radius_d, mm_d, cont_dens_d, alk_dens_d, reject_d,
+              chem_status_d};
     k_walker_atmosphere<<<nwalkers, kWave, lds, pb::as_stream(stream)>>>(a);
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
+
+}  // namespace
+
+int pb_walker_atmosphere(const pb_atm_model *model, const double *params_d, int nwalkers,
+                         double *temps_d, double *dens_d, double *radius_d, double *mm_d,
+                         double *cont_dens_d, double *alk_dens_d, int32_t *reject_d, void *stream)
+{
+    return walker_atmosphere(model, params_d, nwalkers, nullptr, false, temps_d, dens_d, radius_d,
+                             mm_d, cont_dens_d, alk_dens_d, reject_d, stream);
+}
+
+int pb_walker_atmosphere_chem(const pb_atm_model *model, const double *params_d, int nwalkers,
+                              const int32_t *chem_status_d, double *temps_d, double *dens_d,
+                              double *radius_d, double *mm_d, double *cont_dens_d,
+                              double *alk_dens_d, int32_t *reject_d, void *stream)
+{
+    return walker_atmosphere(model, params_d, nwalkers, chem_status_d, true, temps_d, dens_d,
+                             radius_d, mm_d, cont_dens_d, alk_dens_d, reject_d, stream);
+}
+
+int pb_walker_temperature(const pb_atm_model *model, const double *params_d, int nwalkers,
+                          double *temps_d, void *stream)
+{
+    PB_REQUIRE(model, "pb_walker_temperature: null model struct");
+    PB_REQUIRE(model->nlayers >= 2 && model->nlayers <= PB_ATM_MAX_LAYERS,
+               "pb_walker_temperature: 2-%d layers, not %d", PB_ATM_MAX_LAYERS, model->nlayers);
+    PB_REQUIRE(model->tmodel >= 0 && model->tmodel <= 2,
+               "pb_walker_temperature: temperature model %d (0 isothermal, 1 guillot, 2 madhu)",
+               model->tmodel);
+    PB_REQUIRE(model->npar >= (model->tmodel == 0 ? 1 : 6),
+               "pb_walker_temperature: %d parameters, the temperature model takes %d", model->npar,
+               model->tmodel == 0 ? 1 : 6);
+    if (model->tmodel == 1)
+        PB_REQUIRE(model->guillot_gravity > 0.0, "pb_walker_temperature: guillot gravity %g",
+                   model->guillot_gravity);
+    if (model->tmodel == 2)
+        PB_REQUIRE(model->madhu_radius >= 0 && model->madhu_weights_d && model->madhu_loge > 0.0,
+                   "pb_walker_temperature: madhu needs its smoothing weights (radius %d)",
+                   model->madhu_radius);
+    PB_REQUIRE(model->pressure_d && model->log10p_d, "pb_walker_temperature: null model array");
+    PB_REQUIRE(nwalkers >= 0, "pb_walker_temperature: %d walkers", nwalkers);
+    if (nwalkers == 0)
+        return PB_OK;
+    PB_REQUIRE(params_d && temps_d, "pb_walker_temperature: null pointer");
+    const size_t lds = sizeof(double) * 2 * lds_row(model->nlayers);
+    k_walker_temperature<<<nwalkers, kWave, lds, pb::as_stream(stream)>>>(*model, params_d,
+                                                                          temps_d);
     PB_LAUNCH_CHECK();
     return PB_OK;
 }

@@ -1,0 +1,370 @@
+// pb_equilibrium_vmr: gas-phase thermochemical equilibrium of every (walker, layer) cell, one launch
+// (what the reference asks chemcat for, pyratbay/pyrat/atmosphere.py:445-473; the statement of the
+// arithmetic is ChemNetwork.equilibrium_host of pyratbay_amd/chemistry.py).
+//
+// One wavefront per cell, four cells per 256-thread block; lane i holds species i (its
+// stoichiometry row, g_i, ln n_i), lanes >= S hold n = 0.  No LDS, no barriers, no atomics: every
+// sum over species is one xor-butterfly reduction, after which all lanes hold the same bits, and
+// every lane then solves the (E + 1) x (E + 1) system for itself.  The kernel is a template on E so
+// that the matrix lives in compile-time-indexed registers (a runtime-indexed register array would go
+// to scratch); the pivot row is found by compare-and-swap down the column for the same reason.
+// Everything in binary64; the build's -ffp-contract=off keeps products and sums apart.
+#include "pb_common.h"
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kCellsPerBlock = 4;
+constexpr double kMinor = 1.0e-8;          // n_i / n at and below which a species is a minor one
+constexpr double kLnMinor = 9.2103404;     // RP-1311 eq. 3.2: -ln(1e-4)
+constexpr double kDblMax = 1.79769313486231570815e308;
+
+struct ChemArgs {
+    pb_chem_model m;
+    const double *temps, *params;
+    double *vmr;
+    int32_t *status;
+    int64_t ncells;
+};
+
+// xor butterflies in a fixed order: lane and partner add the same two values, so every lane ends
+// with the same bits
+__device__ inline double wave_sum(double v)
+{
+    for (int off = kWave / 2; off >= 1; off >>= 1)
+        v += __shfl_xor(v, off, kWave);
+    return v;
+}
+__device__ inline double wave_max(double v)
+{
+    for (int off = kWave / 2; off >= 1; off >>= 1)
+        v = fmax(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+__device__ inline double wave_min(double v)
+{
+    for (int off = kWave / 2; off >= 1; off >>= 1)
+        v = fmin(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+
+// np.interp(x, xp[n], fp[0 : n * stride : stride]) for xp[0] <= x <= xp[n - 1] (the caller's check)
+__device__ inline double interp_inside(const double *xp, const double *fp, int stride, int n,
+                                       double x)
+{
+    int lo = 0, hi = n - 1;                    // largest lo with xp[lo] <= x
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (xp[mid] <= x)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    if (xp[hi] <= x)
+        lo = hi;
+    const double f0 = fp[(int64_t)lo * stride];
+    if (lo == n - 1 || xp[lo] == x)
+        return f0;
+    const double slope = (fp[(int64_t)(lo + 1) * stride] - f0) / (xp[lo + 1] - xp[lo]);
+    return slope * (x - xp[lo]) + f0;
+}
+
+// x of A x = r, in place (the solution in r): Gaussian elimination with partial pivoting, every
+// index a compile-time constant
+template <int N>
+__device__ inline void gauss_solve(double (&A)[N][N], double (&r)[N])
+{
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+#pragma unroll
+        for (int i = k + 1; i < N; i++) {
+            const bool swap = fabs(A[i][k]) > fabs(A[k][k]);
+#pragma unroll
+            for (int j = k; j < N; j++) {
+                const double ai = A[i][j], ak = A[k][j];
+                A[i][j] = swap ? ak : ai;
+                A[k][j] = swap ? ai : ak;
+            }
+            const double ri = r[i], rk = r[k];
+            r[i] = swap ? rk : ri;
+            r[k] = swap ? ri : rk;
+        }
+#pragma unroll
+        for (int i = k + 1; i < N; i++) {
+            const double f = A[i][k] / A[k][k];
+#pragma unroll
+            for (int j = k + 1; j < N; j++)
+                A[i][j] -= f * A[k][j];
+            r[i] -= f * r[k];
+        }
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; i--) {
+        double acc = r[i];
+#pragma unroll
+        for (int j = i + 1; j < N; j++)
+            acc -= A[i][j] * r[j];
+        r[i] = acc / A[i][i];
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(kWave * kCellsPerBlock) void k_equilibrium_vmr(ChemArgs a)
+{
+    constexpr int N = E + 1;
+    const pb_chem_model &m = a.m;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t cell = (int64_t)blockIdx.x * kCellsPerBlock + (threadIdx.x >> 6);
+    if (cell >= a.ncells)                      // a whole wavefront: the kernel has no barrier
+        return;
+    const int S = m.nspecies, L = m.nlayers;
+    const int64_t w = cell / L;
+    const int l = (int)(cell - w * L);
+    const bool live = lane < S;
+    const double *par = a.params + w * m.npar;   // dereferenced only at a column >= 0 (the check)
+    const double t = a.temps[cell];
+
+    int status = 0;
+    if (!(t > 0.0))
+        status = PB_CHEM_REJECTED;
+
+    // ---- elemental abundances (ChemNetwork.element_abundances_host, the same statements)
+    double b[E] = {};
+    if (status == 0) {
+        double dex[E];
+        const double metal = m.par_metal >= 0 ? par[m.par_metal] : 0.0;
+#pragma unroll
+        for (int j = 0; j < E; j++)
+            dex[j] = m.is_metal[j] ? m.base_dex[j] + metal : m.base_dex[j];
+        for (int k = 0; k < m.nscale; k++) {
+            const double v = par[m.scale_par[k]];
+#pragma unroll
+            for (int j = 0; j < E; j++)
+                if (m.scale_element[k] == j)
+                    dex[j] = m.base_dex[j] + v;
+        }
+        bool bad = false;
+        for (int k = 0; k < m.nratio; k++) {
+            const double v = par[m.ratio_par[k]];
+            if (!(v > 0.0))
+                bad = true;
+            double den = 0.0;
+#pragma unroll
+            for (int j = 0; j < E; j++)
+                if (m.ratio_den[k] == j)
+                    den = dex[j];
+            const double num = den + log10(v);
+#pragma unroll
+            for (int j = 0; j < E; j++)
+                if (m.ratio_num[k] == j)
+                    dex[j] = num;
+        }
+        double dex_h = 0.0;
+#pragma unroll
+        for (int j = 0; j < E; j++)
+            if (m.ihydrogen == j)
+                dex_h = dex[j];
+#pragma unroll
+        for (int j = 0; j < E; j++) {
+            b[j] = pow(10.0, dex[j] - dex_h);
+            if (!(b[j] > 0.0) || !(b[j] <= kDblMax))
+                bad = true;
+        }
+        if (bad)
+            status = PB_CHEM_RATIO;
+    }
+    if (status == 0 && !(t >= m.gibbs_temps_d[0] && t <= m.gibbs_temps_d[m.ntemps - 1]))
+        status = PB_CHEM_TEMPERATURE;
+
+    double x = 0.0;                            // this lane's VMR
+    double stoich[E];
+#pragma unroll
+    for (int j = 0; j < E; j++)
+        stoich[j] = live ? (double)m.stoich_d[lane * E + j] : 0.0;
+
+    if (status == 0) {
+        const double g = live ? interp_inside(m.gibbs_temps_d, m.gibbs_d + lane, S, m.ntemps, t)
+                              : 0.0;
+        const double lnp = log(m.pressure_d[l]);
+        double ln_ni = live ? log(0.1 / (double)S) : 0.0;
+        double ln_n = log(0.1);
+        int iterations = 0;
+        bool converged = false;
+        for (int it = 1; it <= m.max_iterations && !converged; it++) {
+            const double ni = live ? exp(ln_ni) : 0.0;
+            const double n = exp(ln_n);
+            const double mu = live ? ((g + ln_ni) - ln_n) + lnp : 0.0;
+            double an[E];
+#pragma unroll
+            for (int k = 0; k < E; k++)
+                an[k] = stoich[k] * ni;
+            double A[N][N], r[N];
+#pragma unroll
+            for (int k = 0; k < E; k++) {
+#pragma unroll
+                for (int j = k; j < E; j++) {
+                    const double s = wave_sum(stoich[k] * an[j]);
+                    A[k][j] = s;
+                    A[j][k] = s;
+                }
+                const double col = wave_sum(an[k]);
+                A[k][E] = col;
+                A[E][k] = col;
+                r[k] = (b[k] - col) + wave_sum(an[k] * mu);
+            }
+            const double sn = wave_sum(ni);
+            A[E][E] = sn - n;
+            r[E] = (n - sn) + wave_sum(ni * mu);
+            gauss_solve<N>(A, r);
+            const double dln_n = r[E];
+            double api = 0.0;
+#pragma unroll
+            for (int j = 0; j < E; j++)
+                api += stoich[j] * r[j];
+            const double dln_ni = live ? (-mu + dln_n) + api : 0.0;
+
+            // ---- damping (RP-1311 eqs. 3.1-3.3)
+            const bool major = live && ni / n > kMinor;
+            const double step = wave_max(major ? fabs(dln_ni) : 0.0);
+            const double l1 = 2.0 / fmax(5.0 * fabs(dln_n), step);
+            const bool minor = live && !major && dln_ni >= 0.0;
+            const double q = minor ? fabs((-(ln_ni - ln_n) - kLnMinor) / (dln_ni - dln_n))
+                                   : INFINITY;
+            const double l2 = wave_min(q);
+            const double lambda = fmin(1.0, fmin(l1, l2));
+            ln_ni += lambda * dln_ni;
+            ln_n += lambda * dln_n;
+            iterations = it;
+            // n_i |dln n_i| / sum n < tolerance in every lane (false on NaN, like the host's)
+            const bool open = live && !((ni * fabs(dln_ni)) / sn < m.tolerance);
+            converged = lambda == 1.0 && !__any(open) && fabs(dln_n) < m.tolerance;
+        }
+        if (converged) {
+            const double ni = live ? exp(ln_ni) : 0.0;
+            x = ni / wave_sum(ni);
+            status = iterations;
+        } else {
+            status = PB_CHEM_NOT_CONVERGED;
+        }
+    }
+
+    // ---- hybrid models: free log10(VMR)s on top of the equilibrium, capped by the elements the
+    // equilibrium mixture holds (vmr_models.py:40-57); nothing is renormalised
+    if (status > 0 && m.nhybrid > 0) {
+        double total[E];
+#pragma unroll
+        for (int j = 0; j < E; j++)
+            total[j] = wave_sum(x * stoich[j]);
+        double out = x;
+        for (int k = 0; k < m.nhybrid; k++) {
+            const int sp = m.hybrid_species[k];
+            double cap = INFINITY;
+#pragma unroll
+            for (int j = 0; j < E; j++) {
+                const int sj = m.stoich_d[sp * E + j];
+                if (sj > 0) {
+                    const double c = total[j] / (double)sj;
+                    cap = c < cap ? c : cap;
+                }
+            }
+            // np.clip = minimum(maximum(v, 0), cap)
+            double v = pow(10.0, par[m.hybrid_par[k]]);
+            v = v < 0.0 ? 0.0 : v;
+            v = v > cap ? cap : v;
+            if (lane == sp)
+                out = v;
+        }
+        x = out;
+    }
+
+    // ---- outputs, each written once
+    if (live)
+        a.vmr[cell * S + lane] = status > 0 ? x : 0.0;
+    if (lane == 0)
+        a.status[cell] = status;
+}
+
+int chem_check(const pb_chem_model *m)
+{
+    PB_REQUIRE(m, "pb_equilibrium_vmr: null model struct");
+    PB_REQUIRE(m->nspecies >= 1 && m->nspecies <= PB_CHEM_MAX_SPECIES,
+               "pb_equilibrium_vmr: 1-%d species, not %d", PB_CHEM_MAX_SPECIES, m->nspecies);
+    PB_REQUIRE(m->nelements >= 1 && m->nelements <= PB_CHEM_MAX_ELEMENTS,
+               "pb_equilibrium_vmr: 1-%d elements, not %d", PB_CHEM_MAX_ELEMENTS, m->nelements);
+    PB_REQUIRE(m->ntemps >= 1, "pb_equilibrium_vmr: %d Gibbs temperatures", m->ntemps);
+    PB_REQUIRE(m->nlayers >= 1, "pb_equilibrium_vmr: %d layers", m->nlayers);
+    PB_REQUIRE(m->npar >= 0, "pb_equilibrium_vmr: %d parameters", m->npar);
+    PB_REQUIRE(m->ihydrogen >= 0 && m->ihydrogen < m->nelements,
+               "pb_equilibrium_vmr: hydrogen is element %d of %d", m->ihydrogen, m->nelements);
+    PB_REQUIRE(m->par_metal >= -1 && m->par_metal < m->npar,
+               "pb_equilibrium_vmr: [M/H] in column %d of %d", m->par_metal, m->npar);
+    PB_REQUIRE(m->nscale >= 0 && m->nscale <= PB_CHEM_MAX_ELEMENTS,
+               "pb_equilibrium_vmr: at most %d [X/H], not %d", PB_CHEM_MAX_ELEMENTS, m->nscale);
+    for (int k = 0; k < m->nscale; k++)
+        PB_REQUIRE(m->scale_element[k] >= 0 && m->scale_element[k] < m->nelements &&
+                       m->scale_par[k] >= 0 && m->scale_par[k] < m->npar,
+                   "pb_equilibrium_vmr: [X/H] %d: element %d of %d, column %d of %d", k,
+                   m->scale_element[k], m->nelements, m->scale_par[k], m->npar);
+    PB_REQUIRE(m->nratio >= 0 && m->nratio <= PB_CHEM_MAX_ELEMENTS,
+               "pb_equilibrium_vmr: at most %d X/Y, not %d", PB_CHEM_MAX_ELEMENTS, m->nratio);
+    for (int k = 0; k < m->nratio; k++)
+        PB_REQUIRE(m->ratio_num[k] >= 0 && m->ratio_num[k] < m->nelements &&
+                       m->ratio_den[k] >= 0 && m->ratio_den[k] < m->nelements &&
+                       m->ratio_par[k] >= 0 && m->ratio_par[k] < m->npar,
+                   "pb_equilibrium_vmr: X/Y %d: elements %d and %d of %d, column %d of %d", k,
+                   m->ratio_num[k], m->ratio_den[k], m->nelements, m->ratio_par[k], m->npar);
+    PB_REQUIRE(m->nhybrid >= 0 && m->nhybrid <= PB_CHEM_MAX_HYBRID,
+               "pb_equilibrium_vmr: at most %d hybrid models, not %d", PB_CHEM_MAX_HYBRID,
+               m->nhybrid);
+    for (int k = 0; k < m->nhybrid; k++)
+        PB_REQUIRE(m->hybrid_species[k] >= 0 && m->hybrid_species[k] < m->nspecies &&
+                       m->hybrid_par[k] >= 0 && m->hybrid_par[k] < m->npar,
+                   "pb_equilibrium_vmr: hybrid model %d: species %d of %d, column %d of %d", k,
+                   m->hybrid_species[k], m->nspecies, m->hybrid_par[k], m->npar);
+    PB_REQUIRE(m->max_iterations >= 1 && m->max_iterations <= 10000,
+               "pb_equilibrium_vmr: max_iterations %d (1-10000)", m->max_iterations);
+    PB_REQUIRE(m->tolerance > 0.0, "pb_equilibrium_vmr: tolerance %g", m->tolerance);
+    PB_REQUIRE(m->gibbs_temps_d && m->gibbs_d && m->stoich_d && m->pressure_d,
+               "pb_equilibrium_vmr: null model array");
+    return PB_OK;
+}
+
+template <int E>
+void launch(const ChemArgs &a, unsigned blocks, hipStream_t stream)
+{
+    k_equilibrium_vmr<E><<<blocks, kWave * kCellsPerBlock, 0, stream>>>(a);
+}
+
+}  // namespace
+
+int pb_equilibrium_vmr(const pb_chem_model *model, const double *temps_d, const double *params_d,
+                       int nwalkers, double *vmr_d, int32_t *status_d, void *stream)
+{
+    const int rc = chem_check(model);
+    if (rc != PB_OK)
+        return rc;
+    PB_REQUIRE(nwalkers >= 0, "pb_equilibrium_vmr: %d walkers", nwalkers);
+    if (nwalkers == 0)
+        return PB_OK;
+    PB_REQUIRE(temps_d && vmr_d && status_d, "pb_equilibrium_vmr: null pointer");
+    PB_REQUIRE(params_d || model->npar == 0, "pb_equilibrium_vmr: null params with %d columns",
+               model->npar);
+    const int64_t ncells = (int64_t)nwalkers * model->nlayers;
+    const int64_t blocks = (ncells + kCellsPerBlock - 1) / kCellsPerBlock;
+    PB_REQUIRE(blocks <= 0x7fffffffLL, "pb_equilibrium_vmr: %lld cells are too many for one launch",
+               (long long)ncells);
+    ChemArgs a{*model, temps_d, params_d, vmr_d, status_d, ncells};
+    hipStream_t s = pb::as_stream(stream);
+    switch (model->nelements) {
+    case 1: launch<1>(a, (unsigned)blocks, s); break;
+    case 2: launch<2>(a, (unsigned)blocks, s); break;
+    case 3: launch<3>(a, (unsigned)blocks, s); break;
+    case 4: launch<4>(a, (unsigned)blocks, s); break;
+    case 5: launch<5>(a, (unsigned)blocks, s); break;
+    case 6: launch<6>(a, (unsigned)blocks, s); break;
+    case 7: launch<7>(a, (unsigned)blocks, s); break;
+    default: launch<8>(a, (unsigned)blocks, s); break;
+    }
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
