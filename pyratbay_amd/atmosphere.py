@@ -4,32 +4,30 @@
 mean molecular mass, hydrostatic radius.
 
 Two forms of the same arithmetic:
-  * host forms in plain NumPy with the reference's names (Isothermal, Guillot, Madhu, IsoVMR,
-    ScaleVMR, SlantVMR, vmr_scale, ideal_gas_density, mean_weight, hydro_m, hydro_g, qcapcheck),
-    for TableSpectrum.eval() users and CPU tests;
+  * host forms in plain NumPy with the reference's names (atm_models.py; every name of that
+    module is a name of this one too: atmosphere.Guillot, atmosphere.vmr_scale, ...);
   * WalkerAtmosphere.evaluate: params[nw, npar] -> the device tensors TableSpectrum.eval_bands
-    takes, one launch of pb_walker_atmosphere (csrc/pb_atmosphere.hip), nothing read back; with
-    chemistry=ChemNetwork(...) (chemistry.py) the VMRs are the equilibrium of every layer at the
-    walker's [M/H], [X/H] and X/Y, three launches.
-
-Constants: those of pyratbay.constants (CODATA 2018 as scipy.constants carries them, the products
-NumPy forms), not the legacy set of the reference's C extensions.
+    takes, nothing read back.  Where a walker's VMRs come from is one object the constructor
+    picks: _FreeVmr (base VMR, Iso / Scale / Slant models, bulk balance, qcap: one launch of
+    pb_walker_atmosphere, csrc/pb_atmosphere.hip) or, with chemistry=ChemNetwork(...)
+    (chemistry.py), _EquilibriumVmr (the equilibrium of every layer at the walker's [M/H], [X/H]
+    and X/Y: three launches).  Each owns its constructor checks, its host step, its part of
+    pb_atm_model and its launches.
 """
 import collections
 import ctypes as C
-from collections.abc import Iterable
+import functools
 
 import numpy as np
+import torch
 
+from ._capi import call
 from ._device import dev, require_gpu
-
-# pyratbay.constants: k = sc.k * 1e7, G = sc.G * 1e3, sc.N_A, bar
-K_BOLTZ = 1.380649e-23 * 1e7
-G_GRAV = 6.67430e-11 * 1e3
-N_AVOGADRO = 6.02214076e23
-BAR = 1e6
-EULER = 0.57721566490153286061
-E2_CUTOFF = 88.029691931113054296     # log(2**127): the reference's E2 returns 0 above it
+from .atm_models import (  # noqa: F401 -- imported back: every earlier spelling keeps working
+    BAR, E2_CUTOFF, EULER, G_GRAV, K_BOLTZ, N_AVOGADRO, TCEA, Guillot, IsoVMR, Isothermal, Madhu,
+    MetalEquil, RatioEquil, ScaleEquil, ScaleVMR, SlantVMR, balance, correlate_nearest, expn2,
+    gaussian_weights, hydro_g, hydro_m, ideal_gas_density, mean_weight, qcapcheck, ratio,
+    vmr_scale)
 
 MAX_SPECIES, MAX_VMR, MAX_BULK, MAX_LAYERS = 32, 16, 4, 1024
 # isotope ratios of the table's slots (isotopes.py): labelled slots, fillers of one fill slot
@@ -45,389 +43,6 @@ REJECT_NAMES = {REJECT_TEMP: 'temperature <= 0 or not finite', REJECT_MADHU: 'ma
                 REJECT_ISOTOPE: 'a negative or non-finite isotope ratio',
                 REJECT_CHEMISTRY: 'equilibrium chemistry: not converged, a temperature outside '
                                   'the Gibbs table, or an element ratio <= 0'}
-
-
-# ---------------------------------------------------------------------------------------------
-# Temperature models (pyratbay/atmosphere/tmodels/tmodels.py)
-# ---------------------------------------------------------------------------------------------
-def expn2(x):
-    """Exponential integral E2(x) for x >= 0, from its definitions (Abramowitz & Stegun 5.1.12,
-    5.1.22): the power series for x <= 1, the continued fraction (modified Lentz) above; 0 for
-    x > log(2**127) like the reference's.  The device evaluates the same steps in the same order."""
-    x = np.atleast_1d(np.asarray(x, float))
-    out = np.zeros_like(x)
-    out[x == 0.0] = 1.0
-    small = (x > 0.0) & (x <= 1.0)
-    if np.any(small):
-        xs = x[small]
-        term = -xs
-        total = np.zeros_like(xs)
-        for m in range(2, 25):
-            term = term * (-xs) / float(m)
-            total += term / float(m - 1)
-        out[small] = (1.0 + (-xs) * ((1.0 - EULER) - np.log(xs))) - total
-    large = (x > 1.0) & (x <= E2_CUTOFF)
-    if np.any(large):
-        xl = x[large]
-        b = xl + 2.0
-        c = np.full_like(xl, 1.0e300)
-        d = 1.0 / b
-        h = d.copy()
-        live = np.ones(xl.shape, bool)
-        for i in range(1, 401):
-            an = -float(i) * float(i + 1)
-            b = b + 2.0
-            d = np.where(live, 1.0 / (an * d + b), d)
-            c = np.where(live, b + an / c, c)
-            delta = c * d
-            h = np.where(live, h * delta, h)
-            live = live & ~(np.abs(delta - 1.0) < 1.0e-16)
-            if not np.any(live):
-                break
-        out[large] = h * np.exp(-xl)
-    return out
-
-
-class Isothermal:
-    """Isothermal temperature profile model."""
-
-    def __init__(self, pressure):
-        self.name = 'isothermal'
-        self.pnames = ['T_iso']
-        self.npars = 1
-        self.pressure = np.asarray(pressure, float)
-
-    def __call__(self, params):
-        _check_npars(self, params)
-        value = params[0] if isinstance(params, Iterable) else params
-        return np.full(len(self.pressure), value, np.double)
-
-
-def _check_npars(model, params):
-    if np.size(params) != model.npars:
-        raise ValueError(f'Number of parameters ({np.size(params)}) does not match the required '
-                         f'number of parameters ({model.npars}) of the {model.name} model')
-
-
-class Guillot:
-    """Guillot (2010) profile in the parameterization of Line et al. (2013): src_c/_pt.c:11-15,
-    88-109.  gravity: None (taken as 1), a scalar or a profile (cm s-2)."""
-
-    def __init__(self, pressure, gravity=None):
-        self.name = 'guillot'
-        self.pnames = ["log_kappa'", 'log_gamma1', 'log_gamma2', 'alpha', 'T_irr', 'T_int']
-        self.npars = 6
-        self.pressure = np.asarray(pressure, float)
-        self.gravity_scalar = 1.0 if gravity is None else \
-            (float(gravity) if np.isscalar(gravity) else None)
-        if gravity is None:
-            gravity = np.tile(1.0, len(self.pressure))
-        elif np.isscalar(gravity):
-            gravity = np.tile(float(gravity), len(self.pressure))
-        self.gravity = np.asarray(gravity, float)
-
-    @staticmethod
-    def _xi(gamma, tau):
-        gt = gamma * tau
-        return (2.0 / 3.0) * (((1.0 / gamma) * (1.0 + ((0.5 * gamma) * tau - 1.0) * np.exp(-gt)) +
-                               (gamma * (1.0 - 0.5 * (tau * tau))) * expn2(gt)) + 1.0)
-
-    def __call__(self, params):
-        _check_npars(self, params)
-        params = np.asarray(params, np.double)
-        kappa, gamma1, gamma2 = (np.float64(10.0)**params[i] for i in range(3))
-        alpha, t_irr, t_int = params[3], params[4], params[5]
-        tau = kappa * (self.pressure * BAR) / self.gravity
-        tirr4, tint4 = t_irr**4.0, t_int**4.0
-        with np.errstate(invalid='ignore', over='ignore'):
-            xi1, xi2 = self._xi(gamma1, tau), self._xi(gamma2, tau)
-            return (0.75 * ((tint4 * (2.0 / 3.0 + tau) + (tirr4 * (1.0 - alpha)) * xi1) +
-                            (tirr4 * alpha) * xi2))**0.25
-
-
-TCEA = Guillot
-
-
-def gaussian_weights(sigma):
-    """The kernel scipy.ndimage.gaussian_filter1d(sigma=sigma) correlates with (truncate = 4):
-    radius int(4 sigma + 0.5), exp(-0.5 x^2 / sigma^2) normalised to a sum of 1."""
-    radius = int(4.0 * float(sigma) + 0.5)
-    x = np.arange(-radius, radius + 1)
-    phi = np.exp(-0.5 / (sigma * sigma) * x**2)
-    return phi / phi.sum()
-
-
-def correlate_nearest(values, weights):
-    """scipy.ndimage.correlate1d(values, weights, mode='nearest') for symmetric weights, in its
-    order: the centre tap, then the pairs from the outermost inwards.  The radius may exceed
-    len(values)."""
-    values = np.asarray(values, float)
-    n, radius = len(values), (len(weights) - 1) // 2
-    idx = np.arange(n)
-    out = values * weights[radius]
-    for k in range(-radius, 0):
-        out = out + (values[np.maximum(idx + k, 0)] + values[np.minimum(idx - k, n - 1)]) \
-            * weights[k + radius]
-    return out
-
-
-class Madhu:
-    """Temperature profile model by Madhusudhan & Seager (2009): tmodels.py:232-325."""
-
-    def __init__(self, pressure):
-        self.name = 'madhu'
-        self.pnames = ['log_p1', 'log_p2', 'log_p3', 'a1', 'a2', 'T0']
-        self.npars = 6
-        self.pressure = np.asarray(pressure, float)
-        self.logp = np.log10(self.pressure)
-        self.logp0 = np.amin(self.logp)
-        # standard deviation of the smoothing kernel (~0.3 dex in pressure), in layers
-        self.fsmooth = 0.33 / np.ediff1d(self.logp)[0]
-        self.loge = np.log10(np.e)
-        self.weights = gaussian_weights(self.fsmooth)
-
-    def __call__(self, params):
-        _check_npars(self, params)
-        logp1, logp2, logp3, a1, a2, T0 = (np.float64(p) for p in params)
-        if logp1 > logp3:
-            return np.zeros(len(self.pressure))
-        d1, d2 = a1 * self.loge, a2 * self.loge
-        q1, q2, q3 = (logp1 - self.logp0) / d1, (logp1 - logp2) / d2, (logp3 - logp2) / d2
-        T1 = T0 + q1 * q1
-        T2 = T1 - q2 * q2
-        T3 = T2 + q3 * q3
-        layer1 = self.logp < logp1
-        layer2 = (self.logp >= logp1) & (self.logp < logp3)
-        temperature = np.full(len(self.pressure), T3)
-        temperature[layer1] = T0 + ((self.logp[layer1] - self.logp0) / d1)**2
-        temperature[layer2] = T2 + ((self.logp[layer2] - logp2) / d2)**2
-        return correlate_nearest(temperature, self.weights)
-
-
-# ---------------------------------------------------------------------------------------------
-# VMR models (pyratbay/atmosphere/vmr_models/vmr_models.py:129-347)
-# ---------------------------------------------------------------------------------------------
-class IsoVMR:
-    """Isobaric VMR model: one parameter, log10(VMR)."""
-    kind = 0
-
-    def __init__(self, species, pressure):
-        self.species = species
-        self.name = f'log_{species}'
-        self.pnames = [f'log_{species}']
-        self.npars = 1
-        self.pressure = np.asarray(pressure, float)
-        self.type = 'free'
-
-    def __call__(self, params):
-        _check_npars(self, params)
-        value = params[0] if isinstance(params, Iterable) else params
-        return np.full(len(self.pressure), np.float64(10.0)**value)
-
-
-class ScaleVMR:
-    """Scaled VMR model: vmr0 * 10**parameter."""
-    kind = 1
-
-    def __init__(self, species, pressure, vmr0):
-        self.species = species
-        self.name = f'scale_{species}'
-        self.pnames = [f'log_{species}']
-        self.npars = 1
-        self.pressure = np.asarray(pressure, float)
-        self.vmr0 = np.array(vmr0, float)
-        self.type = 'free'
-
-    def __call__(self, params):
-        _check_npars(self, params)
-        value = params[0] if isinstance(params, Iterable) else params
-        return self.vmr0 * np.float64(10.0)**value
-
-
-class SlantVMR:
-    """Slanted VMR model: slope, log VMR0, log p0, min log VMR, max log VMR."""
-    kind = 2
-
-    def __init__(self, species, pressure):
-        self.species = species
-        self.name = f'slant_{species}'
-        self.pnames = [f'slope_{species}', f'log_VMR0_{species}', f'log_p0_{species}',
-                       f'min_log_{species}', f'max_log_{species}']
-        self.npars = 5
-        self.pressure = np.asarray(pressure, float)
-        self.log_press = np.log10(self.pressure)
-        self.type = 'free'
-
-    def __call__(self, params):
-        _check_npars(self, params)
-        slope, vmr_0, log_p0, vmr_min, vmr_max = params
-        log_vmr = slope * (self.log_press - log_p0) + vmr_0
-        return 10.0**np.clip(log_vmr, vmr_min, vmr_max)
-
-
-# Equilibrium-chemistry models (vmr_models.py:60-126): the names of the parameters that set the
-# elemental abundances of a chemistry.ChemNetwork; they carry no arithmetic of their own
-# (ChemNetwork.element_abundances_host has the rule).
-class MetalEquil:
-    """Metallicity of a thermochemical-equilibrium model: [M/H], in dex relative to solar, on
-    every element but H and He."""
-
-    def __init__(self):
-        self.name = 'metal_equil'
-        self.pnames = ['[M/H]']
-        self.texnames = ['[M/H]']
-        self.npars = 1
-        self.type = 'equil'
-
-
-class ScaleEquil:
-    """Abundance of one element of a thermochemical-equilibrium model: name '[X/H]' (e.g. '[C/H]'),
-    in dex relative to solar; overrides the metallicity for X."""
-
-    def __init__(self, name):
-        name = str(name)
-        if len(name) < 5 or name[0] != '[' or name[-3:] != '/H]':
-            raise ValueError(f"ScaleEquil: the format is [X/H], got '{name}'")
-        self.name = 'scale_equil'
-        self.element = name[1:-3]
-        self.pnames = [name]
-        self.texnames = [name]
-        self.npars = 1
-        self.type = 'equil'
-
-
-class RatioEquil:
-    """Abundance ratio of two elements of a thermochemical-equilibrium model: name 'X/Y' (e.g.
-    'C/O'), the ratio itself (not its logarithm); sets X from Y."""
-
-    def __init__(self, name):
-        name = str(name)
-        if name.count('/') != 1 or name[0] == '/' or name[-1] == '/':
-            raise ValueError(f"RatioEquil: the format is X/Y, got '{name}'")
-        self.name = 'ratio_equil'
-        idx = name.index('/')
-        self.elements = [name[0:idx], name[idx + 1:]]
-        self.element_ratio = name.replace('/', '_')
-        self.pnames = [name]
-        self.texnames = [name]
-        self.npars = 1
-        self.type = 'equil'
-
-
-# ---------------------------------------------------------------------------------------------
-# Abundance scaling (pyratbay/atmosphere/vmr_scaling.py)
-# ---------------------------------------------------------------------------------------------
-def qcapcheck(vmr, qcap, ibulk):
-    """Whether the trace abundances sum above qcap in any layer (vmr_scaling.py:52-66)."""
-    if qcap is None:
-        return False
-    nspecies = np.shape(vmr)[1]
-    itrace = np.setdiff1d(np.arange(nspecies), ibulk)
-    return bool(np.any(np.sum(np.asarray(vmr)[:, itrace], axis=1) > qcap))
-
-
-def ratio(vmr, ibulk):
-    """Abundance ratios of the bulk species relative to the first, and the inverse of their sum."""
-    vmr = np.asarray(vmr, float)
-    bratio = np.ones((vmr.shape[0], len(ibulk)))
-    for j in range(1, len(ibulk)):
-        bratio[:, j] = vmr[:, ibulk[j]] / vmr[:, ibulk[0]]
-    return bratio, 1.0 / np.sum(bratio, axis=1)
-
-
-def balance(vmr, ibulk, bratio, invsrat):
-    """Set the bulk species such that sum(vmr) = 1 in each layer (in place)."""
-    itrace = np.setdiff1d(np.arange(vmr.shape[1]), ibulk)
-    rest = 1.0 - np.sum(vmr[:, itrace], axis=1)
-    for j in range(len(ibulk)):
-        vmr[:, ibulk[j]] = bratio[:, j] * rest * invsrat
-
-
-def vmr_scale(vmr, species, vmr_models, vmr_pars, bulk, qsat=None, iscale=None, ibulk=None,
-              bratio=None, invsrat=None):
-    """Scale the modelled species and balance the bulk (vmr_scaling.py:178-280; qsat = None)."""
-    if qsat is not None:
-        raise ValueError('vmr_scale: qsat is not supported (the reference marks it for removal)')
-    if not isinstance(vmr_models, Iterable):
-        vmr_models, vmr_pars = [vmr_models], [vmr_pars]
-    species = list(species)
-    if iscale is None:
-        iscale = [species.index(model.species) for model in vmr_models]
-    if ibulk is None:
-        ibulk = [species.index(mol) for mol in bulk]
-    if bratio is None:
-        bratio, invsrat = ratio(vmr, ibulk)
-    scaled = np.array(vmr, float)
-    for i, model in enumerate(vmr_models):
-        scaled[:, iscale[i]] = model(vmr_pars[i])
-    balance(scaled, ibulk, bratio, invsrat)
-    return scaled
-
-
-# ---------------------------------------------------------------------------------------------
-# Density, mean mass, hydrostatic radius (pyratbay/atmosphere/atmosphere.py)
-# ---------------------------------------------------------------------------------------------
-def ideal_gas_density(abundances, pressure, temperature):
-    """Number density (molecules cm-3): atmosphere.py:629-664."""
-    abundances = np.asarray(abundances, float)
-    pressure, temperature = np.asarray(pressure, float), np.asarray(temperature, float)
-    if np.shape(abundances) == np.shape(pressure):
-        return abundances * (pressure * BAR) / (temperature * K_BOLTZ)
-    return abundances * np.expand_dims(pressure / temperature, axis=1) * BAR / K_BOLTZ
-
-
-def mean_weight(abundances, species=None, molfile=None, mass=None):
-    """Mean molecular mass per layer (atmosphere.py:581-626); the masses must be given."""
-    if mass is None:
-        raise ValueError('mean_weight: give the species masses (mass=...); this package ships '
-                         'no molecules file')
-    return np.sum(np.atleast_2d(abundances) * np.asarray(mass, float), axis=1)
-
-
-def _cumulative_trapezoid(y, x):
-    return np.concatenate(([0.0], np.cumsum(np.diff(x) * (y[1:] + y[:-1]) / 2.0)))
-
-
-def _slinear_at(x, y, x0):
-    """scipy.interpolate.interp1d(x, y, kind='slinear')(x0) for a scalar x0: SciPy's first-order
-    spline (its de Boor recurrence) and interp1d's error outside the range."""
-    if not (x0 >= x[0]):
-        raise ValueError(f"A value ({x0}) in x_new is below the interpolation range's minimum "
-                         f"value ({x[0]}).")
-    if not (x0 <= x[-1]):
-        raise ValueError(f"A value ({x0}) in x_new is above the interpolation range's maximum "
-                         f"value ({x[-1]}).")
-    lo = int(np.clip(np.searchsorted(x, x0, 'right') - 1, 0, len(x) - 2))
-    xa, xb = x[lo], x[lo + 1]
-    w = 1.0 / (xb - xa)
-    return y[lo] * (w * (xb - x0)) + y[lo + 1] * (w * (x0 - xa))
-
-
-def hydro_g(pressure, temperature, mu, g, p0=None, r0=None):
-    """Hydrostatic radius with a constant gravity (atmosphere.py:350-415)."""
-    pressure, temperature = np.asarray(pressure, float), np.asarray(temperature, float)
-    radius = _cumulative_trapezoid(-K_BOLTZ * N_AVOGADRO * temperature / (np.asarray(mu) * g),
-                                   np.log(pressure))
-    if p0 is not None and r0 is not None:
-        radius += r0 - _slinear_at(pressure, radius, p0)
-    else:
-        radius -= radius[-1]
-    return radius
-
-
-def hydro_m(pressure, temperature, mu, mass, p0, r0):
-    """Hydrostatic radius with g(r) = G mass / r^2 (atmosphere.py:418-485).  A divergent profile
-    has inf above the layer where the radius stops decreasing."""
-    pressure, temperature = np.asarray(pressure, float), np.asarray(temperature, float)
-    integral = _cumulative_trapezoid(
-        K_BOLTZ * N_AVOGADRO * temperature / (G_GRAV * np.asarray(mu) * mass), np.log(pressure))
-    i0 = _slinear_at(pressure, integral, p0)
-    with np.errstate(divide='ignore'):
-        radius = 1.0 / (integral - i0 + 1 / r0)
-    for j in range(len(radius) - 1):
-        if radius[j] <= radius[j + 1]:
-            radius[0:j + 1] = np.inf
-    return radius
 
 
 # ---------------------------------------------------------------------------------------------
@@ -471,16 +86,224 @@ Profiles = collections.namedtuple(
     'Profiles', 'temps dens radius mm continuum_density alkali_density reject')
 
 _TMODELS = {Isothermal: 0, Guillot: 1, Madhu: 2}
+_SCALARS = ('rplanet', 'log_refpressure', 'mplanet')
 
 
 def _chemistry():
     from . import chemistry
     return chemistry
-_SCALARS = ('rplanet', 'log_refpressure', 'mplanet')
+
+
+def _check_free_model(atm, model, taken):
+    """What either composition path asks of a model that sets the column of one species: its
+    class, a species of the atmosphere that no bulk and no earlier model has (`taken`, which
+    gains it), the atmosphere's pressure grid."""
+    if getattr(model, 'type', 'free') != 'free' or \
+            not isinstance(model, (IsoVMR, ScaleVMR, SlantVMR)):
+        raise ValueError(
+            f'VMR model {getattr(model, "name", type(model).__name__)}: '
+            'equilibrium-chemistry and hybrid models are not supported without '
+            'chemistry=ChemNetwork(...), only IsoVMR, ScaleVMR and SlantVMR')
+    if model.species not in atm.species:
+        raise ValueError(f'VMR model {model.name}: species {model.species} is not in the '
+                         f'atmosphere ({atm.species})')
+    if model.species in taken:
+        raise ValueError(f'VMR model {model.name}: species {model.species} is a bulk '
+                         'species or has a model already')
+    taken.add(model.species)
+    if not np.array_equal(np.asarray(model.pressure, float), atm.pressure):
+        raise ValueError(f'VMR model {model.name} is defined on another pressure grid')
+
+
+class _FreeVmr:
+    """Free VMRs: the base VMR, the IsoVMR / ScaleVMR / SlantVMR models, the bulk balance and the
+    qcap cap, all inside the one launch of pb_walker_atmosphere.  The constructor sets the
+    atmosphere's base_vmr, bulk, ibulk, bratio, invsrat and qcap."""
+
+    def __init__(self, atm, base_vmr, bulk, qcap):
+        self.atm = atm
+        L, S = atm.nlayers, atm.nspecies
+        atm.base_vmr = np.ascontiguousarray(base_vmr, float)
+        if atm.base_vmr.shape != (L, S):
+            raise ValueError(f'base_vmr must have shape {(L, S)}, got {atm.base_vmr.shape}')
+        atm.bulk = [str(b) for b in bulk]
+        if not 1 <= len(atm.bulk) <= MAX_BULK or len(set(atm.bulk)) != len(atm.bulk):
+            raise ValueError(f'bulk: 1 ... {MAX_BULK} distinct species, got {atm.bulk}')
+        for b in atm.bulk:
+            if b not in atm.species:
+                raise ValueError(f'bulk species {b} is not in the atmosphere ({atm.species})')
+        atm.ibulk = [atm.species.index(b) for b in atm.bulk]
+        atm.bratio, atm.invsrat = ratio(atm.base_vmr, atm.ibulk)
+        atm.qcap = None if qcap is None else float(qcap)
+
+    def check_models(self):
+        taken = set(self.atm.bulk)
+        for model in self.atm.vmr_models:
+            _check_free_model(self.atm, model, taken)
+
+    def host_vmr(self, params, temp):
+        """-> vmr[L, S], its reject bits, whether a layer is without VMRs (never)."""
+        a = self.atm
+        pars = [params[o:o + m.npars] for o, m in zip(a.vmr_par, a.vmr_models)]
+        vmr = vmr_scale(a.base_vmr, a.species, a.vmr_models, pars, a.bulk, iscale=a.iscale,
+                        ibulk=a.ibulk, bratio=a.bratio, invsrat=a.invsrat)
+        return vmr, REJECT_QCAP if qcapcheck(vmr, a.qcap, a.ibulk) else 0, False
+
+    def scalars(self, st):
+        a = self.atm
+        st.nvmr = len(a.vmr_models)
+        for i, model in enumerate(a.vmr_models):
+            st.vmr_kind[i], st.vmr_species[i] = model.kind, a.iscale[i]
+            st.vmr_par[i] = a.vmr_par[i]
+        st.nbulk = len(a.ibulk)
+        for j, i in enumerate(a.ibulk):
+            st.bulk_species[j] = i
+        st.has_qcap = int(a.qcap is not None)
+        st.qcap = a.qcap if a.qcap is not None else 0.0
+
+    def device(self, st, d):
+        """Its arrays into d (once) and their pointers into st."""
+        a = self.atm
+        if 'base_vmr' not in d:
+            d['base_vmr'], d['bratio'], d['invsrat'] = (dev(x) for x in
+                                                       (a.base_vmr, a.bratio, a.invsrat))
+            vmr0 = np.zeros((max(len(a.vmr_models), 1), a.nlayers))
+            for i, model in enumerate(a.vmr_models):
+                if isinstance(model, ScaleVMR):
+                    vmr0[i] = model.vmr0
+            d['vmr0'] = dev(vmr0)
+        st.vmr0_d, st.base_vmr_d = d['vmr0'].data_ptr(), d['base_vmr'].data_ptr()
+        st.bulk_ratio_d, st.invsrat_d = d['bratio'].data_ptr(), d['invsrat'].data_ptr()
+
+    def launch(self, st, params, nw, outputs):
+        call('pb_walker_atmosphere', C.byref(st), params.data_ptr(), nw, *outputs)
+
+
+class _EquilibriumVmr:
+    """Equilibrium chemistry on atm.chemistry (a chemistry.ChemNetwork): the VMRs of every layer
+    from the walker's [M/H], [X/H] and X/Y, hybrid IsoVMR columns on top; no base VMR, no bulk,
+    no cap.  Three launches: pb_walker_temperature, pb_equilibrium_vmr, then
+    pb_walker_atmosphere_chem on those VMRs, through buffers kept per nw."""
+
+    def __init__(self, atm, base_vmr, bulk, qcap):
+        self.atm, self.net = atm, atm.chemistry
+        if atm.species != list(self.net.species):
+            raise ValueError(f'chemistry: species must be the network\'s {self.net.species}, '
+                             f'got {atm.species}')
+        if base_vmr is not None or (bulk is not None and len(bulk)):
+            raise ValueError('chemistry: base_vmr and bulk are not taken (pass None): the '
+                             'equilibrium gives every VMR, and the reference balances no bulk '
+                             'in equilibrium')
+        if qcap is not None:
+            raise ValueError('chemistry: qcap is not taken (there are no bulk species)')
+        atm.base_vmr, atm.bulk, atm.ibulk = None, [], []
+        atm.bratio = atm.invsrat = atm.qcap = None
+        self._buffers = {}
+
+    def check_models(self):
+        models = self.atm.vmr_models
+        for model in models:
+            if not isinstance(model, (MetalEquil, ScaleEquil, RatioEquil, IsoVMR)):
+                raise ValueError(
+                    f'VMR model {getattr(model, "name", type(model).__name__)}: with chemistry, '
+                    'only MetalEquil, ScaleEquil, RatioEquil and (hybrid) IsoVMR models are '
+                    'taken; the reference\'s hybrid is hard-wired to IsoVMR')
+            if isinstance(model, ScaleEquil):
+                self.net.element_index(model.element)
+                if model.element == 'H':
+                    raise ValueError('ScaleEquil: [H/H] is no parameter (abundances are relative '
+                                     'to hydrogen)')
+            if isinstance(model, RatioEquil):
+                self.net.ratio_elements(model.pnames[0])
+        pnames = [n for m in models for n in m.pnames]
+        if len(set(pnames)) != len(pnames):
+            raise ValueError(f'VMR models: a parameter is named twice ({pnames})')
+        limit = _chemistry().MAX_ELEMENTS
+        for cls in (ScaleEquil, RatioEquil):
+            if sum(isinstance(m, cls) for m in models) > limit:
+                raise ValueError(f'at most {limit} {cls.__name__} models')
+        taken = set()
+        for model in models:
+            if isinstance(model, IsoVMR):
+                _check_free_model(self.atm, model, taken)
+
+    @functools.cached_property
+    def columns(self):
+        """The parameter columns as ChemNetwork.model_struct takes them (filed on first use, from
+        the atmosphere's vmr_par and iscale): par_metal, scales, ratios, hybrids."""
+        a, net = self.atm, self.net
+        eq = dict(par_metal=-1, scales=[], ratios=[], hybrids=[])
+        for model, col, isp in zip(a.vmr_models, a.vmr_par, a.iscale):
+            if isinstance(model, MetalEquil):
+                eq['par_metal'] = col
+            elif isinstance(model, ScaleEquil):
+                eq['scales'].append((net.element_index(model.element), col))
+            elif isinstance(model, RatioEquil):
+                eq['ratios'].append(net.ratio_elements(model.pnames[0]) + (col,))
+            else:
+                eq['hybrids'].append((isp, col))
+        return eq
+
+    def equilibrium_host(self, params, temp):
+        net, eq = self.net, self.columns
+        metallicity = None if eq['par_metal'] < 0 else params[eq['par_metal']]
+        e_scale = {net.elements[j]: params[col] for j, col in eq['scales']}
+        e_ratio = {f'{net.elements[x]}/{net.elements[y]}': params[col]
+                   for x, y, col in eq['ratios']}
+        b = net.element_abundances_host(metallicity, e_scale, e_ratio)
+        equil, _, status = net.equilibrium_host(temp, self.atm.pressure, b)
+        vmr = equil.copy()
+        for isp, col in eq['hybrids']:
+            column = net.hybrid_host(equil, self.atm.species[isp], params[col])
+            vmr[:, isp] = np.where(status > 0, column, 0.0)
+        return vmr, status
+
+    def host_vmr(self, params, temp):
+        """-> vmr[L, S], its reject bits, whether a layer is without VMRs."""
+        vmr, status = self.equilibrium_host(params, temp)
+        reject = REJECT_CHEMISTRY \
+            if np.any((status < 0) & (status != _chemistry().STATUS_REJECTED)) else 0
+        # a cell without VMRs has no mean mass: the walker is rejected already (this bit, or
+        # the temperature's), and its radius is not judged
+        return vmr, reject, bool(np.any(status < 0))
+
+    def scalars(self, st):
+        """Nothing: every VMR comes from the equilibrium launch (nvmr = nbulk = has_qcap = 0)."""
+
+    def device(self, st, d):
+        """The network's own struct; st.base_vmr_d is set per call (buffers)."""
+        self.chem_struct = self.net.bound_struct(d['pressure'], self.atm.npar, **self.columns)
+        self._buffers = {}
+
+    def buffers(self, nw, device):
+        """The buffers between the three launches of a call, kept per nw so that a call with
+        `out` allocates nothing: the temperatures as formed, the equilibrium VMRs and cell
+        statuses, and the atmosphere's struct pointing at those VMRs."""
+        key = (nw, str(device))
+        if key not in self._buffers:
+            L, S = self.atm.nlayers, self.atm.nspecies
+            temps = torch.empty((nw, L), dtype=torch.float64, device=device)
+            vmr = torch.empty((nw, L, S), dtype=torch.float64, device=device)
+            status = torch.empty((nw, L), dtype=torch.int32, device=device)
+            st = AtmModelStruct.from_buffer_copy(self.atm._struct)
+            st.base_vmr_d, st.base_vmr_stride = vmr.data_ptr(), L * S
+            self._buffers[key] = (temps, vmr, status, st)
+        return self._buffers[key]
+
+    def launch(self, st, params, nw, outputs):
+        temps, vmr, status, cst = self.buffers(nw, params.device)
+        stream = outputs[-1]
+        call('pb_walker_temperature', C.byref(st), params.data_ptr(), nw, temps.data_ptr(),
+             stream)
+        call('pb_equilibrium_vmr', C.byref(self.chem_struct), temps.data_ptr(),
+             params.data_ptr(), nw, vmr.data_ptr(), status.data_ptr(), stream)
+        call('pb_walker_atmosphere_chem', C.byref(cst), params.data_ptr(), nw,
+             status.data_ptr(), *outputs)
 
 
 class WalkerAtmosphere:
-    """params[nw, npar] -> the atmospheres of nw walkers, on the device in one launch.
+    """params[nw, npar] -> the atmospheres of nw walkers, on the device: one launch with free
+    VMRs, three with chemistry.
 
     pressure[L] (bar, ascending, 2 <= L <= 1024), species (names), mol_mass[nspec] (g mol-1),
     base_vmr[L, nspec], bulk (names of 1-4 bulk species), tmodel (an Isothermal, a Guillot with
@@ -549,30 +372,9 @@ class WalkerAtmosphere:
         self.mol_mass = np.ascontiguousarray(mol_mass, float)
         if self.mol_mass.shape != (S,):
             raise ValueError(f'mol_mass must have shape {(S,)}, got {self.mol_mass.shape}')
-        if chemistry is None:
-            self.base_vmr = np.ascontiguousarray(base_vmr, float)
-            if self.base_vmr.shape != (L, S):
-                raise ValueError(f'base_vmr must have shape {(L, S)}, got {self.base_vmr.shape}')
-            self.bulk = [str(b) for b in bulk]
-            if not 1 <= len(self.bulk) <= MAX_BULK or len(set(self.bulk)) != len(self.bulk):
-                raise ValueError(f'bulk: 1 ... {MAX_BULK} distinct species, got {self.bulk}')
-            for b in self.bulk:
-                if b not in self.species:
-                    raise ValueError(f'bulk species {b} is not in the atmosphere ({self.species})')
-            self.ibulk = [self.species.index(b) for b in self.bulk]
-            self.bratio, self.invsrat = ratio(self.base_vmr, self.ibulk)
-        else:
-            if self.species != list(chemistry.species):
-                raise ValueError(f'chemistry: species must be the network\'s {chemistry.species}, '
-                                 f'got {self.species}')
-            if base_vmr is not None or (bulk is not None and len(bulk)):
-                raise ValueError('chemistry: base_vmr and bulk are not taken (pass None): the '
-                                 'equilibrium gives every VMR, and the reference balances no bulk '
-                                 'in equilibrium')
-            if qcap is not None:
-                raise ValueError('chemistry: qcap is not taken (there are no bulk species)')
-            self.base_vmr, self.bulk, self.ibulk = None, [], []
-            self.bratio = self.invsrat = None
+        # where the VMRs come from: the one place that asks (it sets base_vmr ... qcap)
+        self._composition = (_FreeVmr if chemistry is None else _EquilibriumVmr)(
+            self, base_vmr, bulk, qcap)
 
         if type(tmodel) not in _TMODELS:
             raise ValueError('tmodel: an Isothermal, Guillot or Madhu of pyratbay_amd.atmosphere, '
@@ -588,47 +390,7 @@ class WalkerAtmosphere:
         self.vmr_models = list(vmr_models)
         if len(self.vmr_models) > MAX_VMR:
             raise ValueError(f'at most {MAX_VMR} VMR models, got {len(self.vmr_models)}')
-        taken = set(self.bulk)
-        self._equil = dict(par_metal=-1, scales=[], ratios=[], hybrids=[])
-        for model in self.vmr_models if chemistry is not None else []:
-            if not isinstance(model, (MetalEquil, ScaleEquil, RatioEquil, IsoVMR)):
-                raise ValueError(
-                    f'VMR model {getattr(model, "name", type(model).__name__)}: with chemistry, '
-                    'only MetalEquil, ScaleEquil, RatioEquil and (hybrid) IsoVMR models are '
-                    'taken; the reference\'s hybrid is hard-wired to IsoVMR')
-            if isinstance(model, ScaleEquil):
-                chemistry.element_index(model.element)
-                if model.element == 'H':
-                    raise ValueError('ScaleEquil: [H/H] is no parameter (abundances are relative '
-                                     'to hydrogen)')
-            if isinstance(model, RatioEquil):
-                chemistry.ratio_elements(model.pnames[0])
-        if chemistry is not None:
-            pnames = [n for m in self.vmr_models for n in m.pnames]
-            if len(set(pnames)) != len(pnames):
-                raise ValueError(f'VMR models: a parameter is named twice ({pnames})')
-            limit = _chemistry().MAX_ELEMENTS
-            for cls in (ScaleEquil, RatioEquil):
-                if sum(isinstance(m, cls) for m in self.vmr_models) > limit:
-                    raise ValueError(f'at most {limit} {cls.__name__} models')
-        for model in self.vmr_models:
-            if chemistry is not None and not isinstance(model, IsoVMR):
-                continue
-            if getattr(model, 'type', 'free') != 'free' or \
-                    not isinstance(model, (IsoVMR, ScaleVMR, SlantVMR)):
-                raise ValueError(
-                    f'VMR model {getattr(model, "name", type(model).__name__)}: '
-                    'equilibrium-chemistry and hybrid models are not supported without '
-                    'chemistry=ChemNetwork(...), only IsoVMR, ScaleVMR and SlantVMR')
-            if model.species not in self.species:
-                raise ValueError(f'VMR model {model.name}: species {model.species} is not in the '
-                                 f'atmosphere ({self.species})')
-            if model.species in taken:
-                raise ValueError(f'VMR model {model.name}: species {model.species} is a bulk '
-                                 'species or has a model already')
-            taken.add(model.species)
-            if not np.array_equal(np.asarray(model.pressure, float), self.pressure):
-                raise ValueError(f'VMR model {model.name} is defined on another pressure grid')
+        self._composition.check_models()
         self.iscale = [self.species.index(m.species) if hasattr(m, 'species') else -1
                        for m in self.vmr_models]
 
@@ -638,16 +400,6 @@ class WalkerAtmosphere:
         for model in self.vmr_models:
             self.vmr_par.append(len(names))
             names += list(model.pnames)
-        for model, col, isp in zip(self.vmr_models if chemistry is not None else [],
-                                   self.vmr_par, self.iscale):
-            if isinstance(model, MetalEquil):
-                self._equil['par_metal'] = col
-            elif isinstance(model, ScaleEquil):
-                self._equil['scales'].append((chemistry.element_index(model.element), col))
-            elif isinstance(model, RatioEquil):
-                self._equil['ratios'].append(chemistry.ratio_elements(model.pnames[0]) + (col,))
-            else:
-                self._equil['hybrids'].append((isp, col))
         nmodel = len(names)
         free = names if free is None else [str(f) for f in free]
         if free[:nmodel] != names:
@@ -678,14 +430,12 @@ class WalkerAtmosphere:
             raise ValueError('rplanet (cm) is needed, as a constant or a free parameter')
         if refpressure is None and self.par_scalar['log_refpressure'] < 0:
             raise ValueError('refpressure (bar) is needed, as a constant or a free parameter')
-        self.qcap = None if qcap is None else float(qcap)
 
         self._table_species = None
         self._cont_species, self._alk_species = [], []
         self._maps = None
         self._dev = None
         self._struct = None
-        self._chem_buffers = {}
         # (kept for the retrieval front end: the value of a column no retrieval parameter names)
         self.base_params = None if base_params is None else \
             np.array(base_params, dtype=np.float64)
@@ -716,21 +466,8 @@ class WalkerAtmosphere:
             reject |= REJECT_MADHU
         if np.any(~(temp > 0)) or not np.all(np.isfinite(temp)):
             reject |= REJECT_TEMP
-        no_vmr = False
-        if self.chemistry is not None:
-            vmr, status = self.equilibrium_host(params, temp)
-            if np.any((status < 0) & (status != _chemistry().STATUS_REJECTED)):
-                reject |= REJECT_CHEMISTRY
-            # a cell without VMRs has no mean mass: the walker is rejected already (this bit, or
-            # the temperature's), and its radius is not judged
-            no_vmr = bool(np.any(status < 0))
-        else:
-            pars = [params[o:o + m.npars] for o, m in zip(self.vmr_par, self.vmr_models)]
-            vmr = vmr_scale(self.base_vmr, self.species, self.vmr_models, pars, self.bulk,
-                            iscale=self.iscale, ibulk=self.ibulk, bratio=self.bratio,
-                            invsrat=self.invsrat)
-            if qcapcheck(vmr, self.qcap, self.ibulk):
-                reject |= REJECT_QCAP
+        vmr, bits, no_vmr = self._composition.host_vmr(params, temp)
+        reject |= bits
         with np.errstate(all='ignore'):
             dens = ideal_gas_density(vmr, self.pressure, temp)
             mm = mean_weight(vmr, mass=self.mol_mass)
@@ -762,18 +499,7 @@ class WalkerAtmosphere:
         """The VMRs of one walker with chemistry: the elemental abundances from its [M/H], [X/H]
         and X/Y, the equilibrium of every layer, then the hybrid columns, each capped from the
         equilibrium VMRs -> vmr[L, S], status[L] (chemistry.equilibrium_host's)."""
-        net, eq = self.chemistry, self._equil
-        metallicity = None if eq['par_metal'] < 0 else params[eq['par_metal']]
-        e_scale = {net.elements[j]: params[col] for j, col in eq['scales']}
-        e_ratio = {f'{net.elements[x]}/{net.elements[y]}': params[col]
-                   for x, y, col in eq['ratios']}
-        b = net.element_abundances_host(metallicity, e_scale, e_ratio)
-        equil, _, status = net.equilibrium_host(temp, self.pressure, b)
-        vmr = equil.copy()
-        for isp, col in eq['hybrids']:
-            column = net.hybrid_host(equil, self.species[isp], params[col])
-            vmr[:, isp] = np.where(status > 0, column, 0.0)
-        return vmr, status
+        return self._composition.equilibrium_host(params, temp)
 
     def evaluate_host(self, params):
         """One walker through the host forms: the same result tuple as evaluate() (NumPy arrays,
@@ -819,39 +545,23 @@ class WalkerAtmosphere:
         return self
 
     def _build_struct(self):
-        import torch
         require_gpu()
         if self._dev is None:
             d = {}
             d['pressure'] = dev(self.pressure)
             d['log10p'] = dev(np.log10(self.pressure))
             d['lnp'] = dev(np.log(self.pressure))
-            if self.chemistry is None:
-                d['base_vmr'] = dev(self.base_vmr)
-                d['bratio'] = dev(self.bratio)
-                d['invsrat'] = dev(self.invsrat)
             d['mass'] = dev(self.mol_mass)
             d['base_radius'] = dev(self.base_radius)
             if isinstance(self.tmodel, Madhu):
                 d['weights'] = dev(self.tmodel.weights)
-            vmr0 = np.zeros((max(len(self.vmr_models), 1), self.nlayers))
-            for i, model in enumerate(self.vmr_models):
-                if isinstance(model, ScaleVMR):
-                    vmr0[i] = model.vmr0
-            d['vmr0'] = dev(vmr0)
             self._dev = d
         d = self._dev
         for key, idx in zip(('tab_map', 'cont_map', 'alk_map'), self._index_maps()):
             d[key] = torch.tensor(idx if idx else [0], dtype=torch.int32, device='cuda')
         st = self.model_struct()
         st.madhu_weights_d = d['weights'].data_ptr() if 'weights' in d else None
-        st.vmr0_d = d['vmr0'].data_ptr()
-        if self.chemistry is None:
-            st.bulk_ratio_d, st.invsrat_d = d['bratio'].data_ptr(), d['invsrat'].data_ptr()
-            st.base_vmr_d = d['base_vmr'].data_ptr()
-        else:                   # base_vmr_d: the equilibrium VMRs of a call (_chemistry_buffers)
-            self._chem_struct = self.chemistry.bound_struct(d['pressure'], self.npar,
-                                                            **self._equil)
+        self._composition.device(st, d)
         st.pressure_d = d['pressure'].data_ptr()
         st.log10p_d, st.lnp_d = d['log10p'].data_ptr(), d['lnp'].data_ptr()
         st.mass_d, st.base_radius_d = d['mass'].data_ptr(), d['base_radius'].data_ptr()
@@ -859,23 +569,22 @@ class WalkerAtmosphere:
         st.cont_map_d = d['cont_map'].data_ptr() if self._cont_species else None
         st.alk_map_d = d['alk_map'].data_ptr() if self._alk_species else None
         self._struct = st
-        self._chem_buffers = {}
 
     def _chemistry_buffers(self, nw, device):
-        """The buffers between the three launches of a call with chemistry, kept per nw so that a
-        call with `out` allocates nothing: the temperatures as formed, the equilibrium VMRs and
-        cell statuses, and this model's struct pointing at those VMRs."""
-        import torch
-        key = (nw, str(device))
-        if key not in self._chem_buffers:
-            L, S = self.nlayers, self.nspecies
-            temps = torch.empty((nw, L), dtype=torch.float64, device=device)
-            vmr = torch.empty((nw, L, S), dtype=torch.float64, device=device)
-            status = torch.empty((nw, L), dtype=torch.int32, device=device)
-            st = AtmModelStruct.from_buffer_copy(self._struct)
-            st.base_vmr_d, st.base_vmr_stride = vmr.data_ptr(), L * S
-            self._chem_buffers[key] = (temps, vmr, status, st)
-        return self._chem_buffers[key]
+        """With chemistry: (temps, vmr, status, struct) of _EquilibriumVmr.buffers."""
+        return self._composition.buffers(nw, device)
+
+    def equilibrium_launch(self, nw, device):
+        """With chemistry, for tools that time or inspect the equilibrium launch alone: what
+        pb_equilibrium_vmr reads and writes in an evaluate() of nw walkers on `device`, as
+        chemistry.equilibrium_vmr names it -- dict(temps[nw, L], pressure[L], vmr[nw, L, S],
+        status[nw, L]: device tensors, the three per-nw ones those evaluate() reuses; columns:
+        par_metal, scales, ratios, hybrids).  Needs bind() first."""
+        if self._struct is None:
+            self._build_struct()
+        temps, vmr, status, _ = self._composition.buffers(nw, device)
+        return dict(temps=temps, pressure=self._dev['pressure'], vmr=vmr, status=status,
+                    columns=self._composition.columns)
 
     def model_struct(self):
         """The pb_atm_model of this model with its scalar fields set (device pointers: null)."""
@@ -889,14 +598,7 @@ class WalkerAtmosphere:
         if isinstance(self.tmodel, Madhu):
             st.madhu_radius = (len(self.tmodel.weights) - 1) // 2
             st.madhu_logp0, st.madhu_loge = float(self.tmodel.logp0), float(self.tmodel.loge)
-        # (with chemistry every VMR comes from the equilibrium launch: no model, no bulk here)
-        st.nvmr = len(self.vmr_models) if self.chemistry is None else 0
-        for i, model in enumerate(self.vmr_models if self.chemistry is None else []):
-            st.vmr_kind[i], st.vmr_species[i] = model.kind, self.iscale[i]
-            st.vmr_par[i] = self.vmr_par[i]
-        st.nbulk = len(self.ibulk)
-        for j, i in enumerate(self.ibulk):
-            st.bulk_species[j] = i
+        self._composition.scalars(st)
         st.rmodel = 0 if self.rmodel == 'hydro_m' else 1
         st.mplanet = float(self.mplanet or 0.0)
         st.gplanet = float(self.gplanet or 0.0)
@@ -905,8 +607,6 @@ class WalkerAtmosphere:
         st.par_rplanet = self.par_scalar['rplanet']
         st.par_log_refpressure = self.par_scalar['log_refpressure']
         st.par_mplanet = self.par_scalar['mplanet']
-        st.has_qcap = int(self.qcap is not None)
-        st.qcap = self.qcap if self.qcap is not None else 0.0
         st.ntab = len(self._table_species or [])
         st.ncont, st.nalk = len(self._cont_species), len(self._alk_species)
         return st
@@ -916,11 +616,10 @@ class WalkerAtmosphere:
         """params[nw, npar] (float64 device tensor, columns in `free` order) -> Profiles of
         device tensors: temps[nw, L], dens[nw, L, ntab], radius[nw, L], mm[nw, L],
         continuum_density[nw, L, ncont] / alkali_density[nw, L, nalk] (None without such
-        species), reject[nw] (int32 bit mask).  One launch, nothing read back, no allocation
-        when `out` (a Profiles of an earlier call with the same nw) is given: capturable into a
-        graph.  Shape and dtype are checked before any HIP call."""
-        import torch
-        from ._capi import call
+        species), reject[nw] (int32 bit mask).  One launch with free VMRs, three with chemistry
+        (the class docstring names them); nothing read back, no allocation when `out` (a Profiles
+        of an earlier call with the same nw) is given: capturable into a graph.  Shape and dtype
+        are checked before any HIP call."""
         if self._table_species is None:
             raise ValueError('evaluate: bind(table_species) first')
         if not isinstance(params, torch.Tensor) or params.dtype != torch.float64 or \
@@ -936,19 +635,17 @@ class WalkerAtmosphere:
             self._build_struct()
         st = self._struct
         nw, L = params.shape[0], self.nlayers
+        # the fields of Profiles in order: shape (None: no such output) and element type
+        want = [((nw, L), torch.float64), ((nw, L, st.ntab), torch.float64),
+                ((nw, L), torch.float64), ((nw, L), torch.float64),
+                ((nw, L, st.ncont) if st.ncont else None, torch.float64),
+                ((nw, L, st.nalk) if st.nalk else None, torch.float64), ((nw,), torch.int32)]
         if out is None:
-            def new(*shape, dtype=torch.float64):
-                return torch.empty(shape, dtype=dtype, device=params.device)
-            out = Profiles(new(nw, L), new(nw, L, st.ntab), new(nw, L), new(nw, L),
-                           new(nw, L, st.ncont) if st.ncont else None,
-                           new(nw, L, st.nalk) if st.nalk else None,
-                           new(nw, dtype=torch.int32))
+            out = Profiles(*[None if shape is None else
+                             torch.empty(shape, dtype=dtype, device=params.device)
+                             for shape, dtype in want])
         else:
-            want = ((nw, L), (nw, L, st.ntab), (nw, L), (nw, L),
-                    (nw, L, st.ncont) if st.ncont else None,
-                    (nw, L, st.nalk) if st.nalk else None, (nw,))
-            for name, t, shape in zip(Profiles._fields, out, want):
-                dtype = torch.int32 if name == 'reject' else torch.float64
+            for name, t, (shape, dtype) in zip(Profiles._fields, out, want):
                 if (t is None) != (shape is None) or \
                         (t is not None and (not isinstance(t, torch.Tensor) or
                                             tuple(t.shape) != shape or not t.is_contiguous() or
@@ -960,20 +657,5 @@ class WalkerAtmosphere:
                    None if out.continuum_density is None else out.continuum_density.data_ptr(),
                    None if out.alkali_density is None else out.alkali_density.data_ptr(),
                    out.reject.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        if self.chemistry is not None:
-            temps, vmr, status, cst = self._chemistry_buffers(nw, params.device)
-            stream = outputs[-1]
-            call('pb_walker_temperature', C.byref(st), params.data_ptr(), nw, temps.data_ptr(),
-                 stream)
-            call('pb_equilibrium_vmr', C.byref(self._chem_struct), temps.data_ptr(),
-                 params.data_ptr(), nw, vmr.data_ptr(), status.data_ptr(), stream)
-            call('pb_walker_atmosphere_chem', C.byref(cst), params.data_ptr(), nw,
-                 status.data_ptr(), *outputs)
-            return out
-        call('pb_walker_atmosphere', C.byref(st), params.data_ptr(), nw,
-             out.temps.data_ptr(), out.dens.data_ptr(), out.radius.data_ptr(),
-             out.mm.data_ptr(),
-             None if out.continuum_density is None else out.continuum_density.data_ptr(),
-             None if out.alkali_density is None else out.alkali_density.data_ptr(),
-             out.reject.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        self._composition.launch(st, params, nw, outputs)
         return out

@@ -259,10 +259,9 @@ __global__ __launch_bounds__(kWave) void k_walker_atmosphere(AtmArgs a)
         if (!(t > 0.0) || !(fabs(t) <= 1.79769313486231570815e308))
             flags |= PB_ATM_REJECT_TEMP;
     }
-    // the cells of the equilibrium chemistry that gave no VMRs (PB_CHEM_REJECTED is the
-    // temperature's own reject, flagged above)
-    // A walker with any cell without VMRs has no mean mass there, so its radius is not judged (it
-    // is rejected already).
+    // Equilibrium chemistry: a cell that gave no VMRs rejects the walker (but PB_CHEM_REJECTED,
+    // the temperature's own reject, flagged above).  Such a walker has no mean mass there, so its
+    // radius is not judged (it is rejected already).
     bool no_vmr = false;
     if (a.chem_status) {
         bool missing = false;
@@ -364,27 +363,38 @@ __global__ __launch_bounds__(kWave) void k_walker_temperature(pb_atm_model m, co
         temps[w * L + l] = s_temp[l];
 }
 
+inline int tmodel_npar(const pb_atm_model *m) { return m->tmodel == 0 ? 1 : 6; }
+
+// What walker_temperature() needs of the struct, reported under the entry point's name `who`:
+// the layers, the T(p) model, its parameter count, guillot's gravity, madhu's weights and the
+// two arrays it reads.
+int tmodel_check(const pb_atm_model *m, const char *who)
+{
+    PB_REQUIRE(m, "%s: null model struct", who);
+    PB_REQUIRE(m->nlayers >= 2 && m->nlayers <= PB_ATM_MAX_LAYERS, "%s: 2-%d layers, not %d", who,
+               PB_ATM_MAX_LAYERS, m->nlayers);
+    PB_REQUIRE(m->tmodel >= 0 && m->tmodel <= 2,
+               "%s: temperature model %d (0 isothermal, 1 guillot, 2 madhu)", who, m->tmodel);
+    PB_REQUIRE(m->npar >= tmodel_npar(m), "%s: %d parameters, the temperature model takes %d", who,
+               m->npar, tmodel_npar(m));
+    if (m->tmodel == 1)
+        PB_REQUIRE(m->guillot_gravity > 0.0, "%s: guillot gravity %g", who, m->guillot_gravity);
+    if (m->tmodel == 2)
+        PB_REQUIRE(m->madhu_radius >= 0 && m->madhu_weights_d && m->madhu_loge > 0.0,
+                   "%s: madhu needs its smoothing weights (radius %d)", who, m->madhu_radius);
+    PB_REQUIRE(m->pressure_d && m->log10p_d, "%s: null model array", who);
+    return PB_OK;
+}
+
 // chem: the call of pb_walker_atmosphere_chem, which may come without bulk species
 int atm_check(const pb_atm_model *m, bool chem)
 {
-    PB_REQUIRE(m, "pb_walker_atmosphere: null model struct");
-    PB_REQUIRE(m->nlayers >= 2 && m->nlayers <= PB_ATM_MAX_LAYERS,
-               "pb_walker_atmosphere: 2-%d layers, not %d", PB_ATM_MAX_LAYERS, m->nlayers);
+    const int rc = tmodel_check(m, "pb_walker_atmosphere");
+    if (rc != PB_OK)
+        return rc;
+    const int ntpar = tmodel_npar(m);
     PB_REQUIRE(m->nspecies >= 1 && m->nspecies <= PB_ATM_MAX_SPECIES,
                "pb_walker_atmosphere: 1-%d species, not %d", PB_ATM_MAX_SPECIES, m->nspecies);
-    PB_REQUIRE(m->tmodel >= 0 && m->tmodel <= 2,
-               "pb_walker_atmosphere: temperature model %d (0 isothermal, 1 guillot, 2 madhu)",
-               m->tmodel);
-    const int ntpar = m->tmodel == 0 ? 1 : 6;
-    PB_REQUIRE(m->npar >= ntpar, "pb_walker_atmosphere: %d parameters, the temperature model takes %d",
-               m->npar, ntpar);
-    if (m->tmodel == 1)
-        PB_REQUIRE(m->guillot_gravity > 0.0, "pb_walker_atmosphere: guillot gravity %g",
-                   m->guillot_gravity);
-    if (m->tmodel == 2)
-        PB_REQUIRE(m->madhu_radius >= 0 && m->madhu_weights_d && m->madhu_loge > 0.0,
-                   "pb_walker_atmosphere: madhu needs its smoothing weights (radius %d)",
-                   m->madhu_radius);
     PB_REQUIRE(m->nvmr >= 0 && m->nvmr <= PB_ATM_MAX_VMR,
                "pb_walker_atmosphere: at most %d VMR models, not %d", PB_ATM_MAX_VMR, m->nvmr);
     PB_REQUIRE(m->nbulk >= (chem ? 0 : 1) && m->nbulk <= PB_ATM_MAX_BULK,
@@ -419,7 +429,6 @@ int atm_check(const pb_atm_model *m, bool chem)
     }
     PB_REQUIRE(!scale || m->vmr0_d, "pb_walker_atmosphere: null vmr0 (ScaleVMR)");
     PB_REQUIRE((m->nbulk == 0 || (m->bulk_ratio_d && m->invsrat_d)) && m->base_vmr_d &&
-                   m->pressure_d && m->log10p_d &&
                    m->lnp_d && m->mass_d && m->base_radius_d,
                "pb_walker_atmosphere: null model array");
     PB_REQUIRE(m->rmodel == 0 || m->rmodel == 1,
@@ -445,10 +454,6 @@ int atm_check(const pb_atm_model *m, bool chem)
                "pb_walker_atmosphere: bad continuum / alkali maps");
     return PB_OK;
 }
-
-}  // namespace
-
-namespace {
 
 int walker_atmosphere(const pb_atm_model *model, const double *params_d, int nwalkers,
                       const int32_t *chem_status_d, bool chem, double *temps_d, double *dens_d,
@@ -495,23 +500,9 @@ int pb_walker_atmosphere_chem(const pb_atm_model *model, const double *params_d,
 int pb_walker_temperature(const pb_atm_model *model, const double *params_d, int nwalkers,
                           double *temps_d, void *stream)
 {
-    PB_REQUIRE(model, "pb_walker_temperature: null model struct");
-    PB_REQUIRE(model->nlayers >= 2 && model->nlayers <= PB_ATM_MAX_LAYERS,
-               "pb_walker_temperature: 2-%d layers, not %d", PB_ATM_MAX_LAYERS, model->nlayers);
-    PB_REQUIRE(model->tmodel >= 0 && model->tmodel <= 2,
-               "pb_walker_temperature: temperature model %d (0 isothermal, 1 guillot, 2 madhu)",
-               model->tmodel);
-    PB_REQUIRE(model->npar >= (model->tmodel == 0 ? 1 : 6),
-               "pb_walker_temperature: %d parameters, the temperature model takes %d", model->npar,
-               model->tmodel == 0 ? 1 : 6);
-    if (model->tmodel == 1)
-        PB_REQUIRE(model->guillot_gravity > 0.0, "pb_walker_temperature: guillot gravity %g",
-                   model->guillot_gravity);
-    if (model->tmodel == 2)
-        PB_REQUIRE(model->madhu_radius >= 0 && model->madhu_weights_d && model->madhu_loge > 0.0,
-                   "pb_walker_temperature: madhu needs its smoothing weights (radius %d)",
-                   model->madhu_radius);
-    PB_REQUIRE(model->pressure_d && model->log10p_d, "pb_walker_temperature: null model array");
+    const int rc = tmodel_check(model, "pb_walker_temperature");
+    if (rc != PB_OK)
+        return rc;
     PB_REQUIRE(nwalkers >= 0, "pb_walker_temperature: %d walkers", nwalkers);
     if (nwalkers == 0)
         return PB_OK;

@@ -295,3 +295,64 @@ def test_guillot_gravity_must_be_positive(pa):
             pa.WalkerAtmosphere(atm.pressure, atm.species, atm.mol_mass, atm.base_vmr, ['H2'],
                                 pa.Guillot(atm.pressure, gravity), [], mplanet=1e30, rplanet=7e9,
                                 refpressure=0.1, base_radius=atm.base_radius)
+
+
+def test_refusal_messages_are_stable(pa):
+    """One bad constructor argument per row and the whole message its caller gets, compared with
+    == : the checks sit in WalkerAtmosphere and in the object that forms its VMRs, and which of
+    two checks a bad argument meets first decides the message (a shorter pressure grid meets
+    base_vmr's shape before the T model's grid).  The messages are those of the commit before
+    atmosphere.py was split."""
+    atm, _ = ac.walker_atmosphere(G['case_list'][17])
+    p = atm.pressure
+    species = "['H2', 'He', 'H2O', 'CH4', 'CO', 'CO2']"
+    good = dict(pressure=p, species=atm.species, mol_mass=atm.mol_mass, base_vmr=atm.base_vmr,
+                bulk=['H2'], tmodel=pa.Isothermal(p), vmr_models=[pa.IsoVMR('CO', p)],
+                mplanet=1e30, rplanet=7e9, refpressure=0.1, base_radius=atm.base_radius)
+    pa.WalkerAtmosphere(**good)
+    rows = [
+        (dict(pressure=p[:-1]), 'base_vmr must have shape (10, 6), got (11, 6)'),
+        (dict(pressure=2 * p), 'tmodel is defined on another pressure grid'),
+        (dict(species=atm.species[:-1]), 'mol_mass must have shape (5,), got (6,)'),
+        (dict(base_vmr=atm.base_vmr[:-1]), 'base_vmr must have shape (11, 6), got (10, 6)'),
+        (dict(bulk=['H2', 'Ar']), f'bulk species Ar is not in the atmosphere ({species})'),
+        (dict(bulk=[]), 'bulk: 1 ... 4 distinct species, got []'),
+        (dict(tmodel=pa.Isothermal(2 * p)), 'tmodel is defined on another pressure grid'),
+        (dict(vmr_models=[pa.IsoVMR('H2', p)]),
+         'VMR model log_H2: species H2 is a bulk species or has a model already'),
+        (dict(vmr_models=[pa.IsoVMR('CO', p), pa.SlantVMR('CO', p)]),
+         'VMR model slant_CO: species CO is a bulk species or has a model already'),
+        (dict(vmr_models=[pa.IsoVMR('TiO', p)]),
+         f'VMR model log_TiO: species TiO is not in the atmosphere ({species})'),
+        (dict(vmr_models=[pa.IsoVMR('CO', 2 * p)]),
+         'VMR model log_CO is defined on another pressure grid'),
+        (dict(vmr_models=[pa.MetalEquil()]),
+         'VMR model metal_equil: equilibrium-chemistry and hybrid models are not supported '
+         'without chemistry=ChemNetwork(...), only IsoVMR, ScaleVMR and SlantVMR'),
+        (dict(vmr_models=[pa.IsoVMR('CO', p)] * 17), 'at most 16 VMR models, got 17'),
+        (dict(free=['T_iso', 'log_CO', 'rplanet', 'log_refpressure']),
+         "free: 'rplanet' and 'log_refpressure' cannot both be free (the reference maps one or "
+         'the other, pyrat_obj.py:269-272)'),
+        (dict(free=['T_iso', 'log_CO', 'tstar']),
+         "free: 'tstar' is not one of ('rplanet', 'log_refpressure', 'mplanet')"),
+        (dict(free=['log_CO', 'T_iso']),
+         "free must begin with the models' parameters ['T_iso', 'log_CO'], got "
+         "['log_CO', 'T_iso']"),
+        (dict(rmodel='hydro_g'), 'hydro_g needs gplanet (cm s-2)'),
+        (dict(mplanet=None), 'hydro_m needs mplanet (g), as a constant or a free parameter'),
+        (dict(rplanet=None), 'rplanet (cm) is needed, as a constant or a free parameter'),
+        (dict(refpressure=None),
+         'refpressure (bar) is needed, as a constant or a free parameter'),
+        (dict(base_radius=None),
+         'give base_radius[L], or base_params (the parameter vector of the base model, whose '
+         'radius it then is)'),
+        (dict(base_radius=None, base_params=[-5.0, -3.0]),
+         'base_params give a rejected model: temperature <= 0 or not finite, divergent hydro_m '
+         'profile, or a radius <= 0 or not finite'),
+        (dict(base_radius=atm.base_radius[::-1]),
+         'base_radius must be 11 finite, strictly decreasing radii'),
+    ]
+    for change, message in rows:
+        with pytest.raises(ValueError) as err:
+            pa.WalkerAtmosphere(**dict(good, **change))
+        assert str(err.value) == message, list(change)

@@ -341,3 +341,61 @@ def test_struct_mirror_and_check_before_hip(pa, ch, net):
     st = filled()
     st.pressure_d = None
     check(st, 'null model array')
+
+
+def test_refusal_messages_are_stable(pa, ch, net):
+    """The chemistry twin of test_atmosphere_cpu's table: one bad constructor argument per row
+    and the whole message, compared with == (a parameter named twice is met before a species
+    taken twice; the model count before either).  The messages are those of the commit before
+    atmosphere.py was split."""
+    L = 5
+    p = np.logspace(-6, 1, L)
+    only = ('with chemistry, only MetalEquil, ScaleEquil, RatioEquil and (hybrid) IsoVMR models '
+            "are taken; the reference's hybrid is hard-wired to IsoVMR")
+    not_taken = ('chemistry: base_vmr and bulk are not taken (pass None): the equilibrium gives '
+                 'every VMR, and the reference balances no bulk in equilibrium')
+    good = dict(pressure=p, species=cc.SPECIES, mol_mass=cc.MASS, base_vmr=None, bulk=None,
+                tmodel=pa.Isothermal(p), vmr_models=[pa.MetalEquil(), pa.IsoVMR('H2O', p)],
+                mplanet=1.5e30, rplanet=7.0e9, refpressure=0.1,
+                base_radius=np.linspace(8e9, 7e9, L), chemistry=net)
+    pa.WalkerAtmosphere(**good)
+    rows = [
+        (dict(species=cc.SPECIES[::-1]),
+         f"chemistry: species must be the network's {cc.SPECIES}, got {cc.SPECIES[::-1]}"),
+        (dict(base_vmr=np.full((L, 16), 1 / 16)), not_taken),
+        (dict(bulk=['H2']), not_taken),
+        (dict(qcap=0.9), 'chemistry: qcap is not taken (there are no bulk species)'),
+        (dict(vmr_models=[pa.ScaleVMR('H2O', p, np.full(L, 1e-4))]),
+         'VMR model scale_H2O: ' + only),
+        (dict(vmr_models=[pa.SlantVMR('H2O', p)]), 'VMR model slant_H2O: ' + only),
+        (dict(vmr_models=[pa.ScaleEquil('[H/H]')]),
+         'ScaleEquil: [H/H] is no parameter (abundances are relative to hydrogen)'),
+        (dict(vmr_models=[pa.ScaleEquil('[Na/H]')]),
+         "element 'Na' is not in the network (['H', 'He', 'C', 'N', 'O'])"),
+        (dict(vmr_models=[pa.RatioEquil('C/Na')]),
+         "element 'Na' is not in the network (['H', 'He', 'C', 'N', 'O'])"),
+        (dict(vmr_models=[pa.MetalEquil(), pa.MetalEquil()]),
+         "VMR models: a parameter is named twice (['[M/H]', '[M/H]'])"),
+        (dict(vmr_models=[pa.IsoVMR('H2O', p), pa.MetalEquil(), pa.IsoVMR('H2O', p)]),
+         "VMR models: a parameter is named twice (['log_H2O', '[M/H]', 'log_H2O'])"),
+        (dict(vmr_models=[pa.MetalEquil(), pa.IsoVMR('H2O', 2 * p)]),
+         'VMR model log_H2O is defined on another pressure grid'),
+        (dict(vmr_models=[pa.MetalEquil(), pa.IsoVMR('TiO', p)]),
+         f'VMR model log_TiO: species TiO is not in the atmosphere ({cc.SPECIES})'),
+        (dict(vmr_models=[pa.MetalEquil()] * 17), 'at most 16 VMR models, got 17'),
+        (dict(free=['T_iso', '[M/H]', 'log_H2O', 'rplanet', 'log_refpressure']),
+         "free: 'rplanet' and 'log_refpressure' cannot both be free (the reference maps one or "
+         'the other, pyrat_obj.py:269-272)'),
+        (dict(base_radius=None),
+         'give base_radius[L], or base_params (the parameter vector of the base model, whose '
+         'radius it then is)'),
+        (dict(base_radius=None, base_params=[7000.0, 0.0, -3.5]),
+         'base_params give a rejected model: equilibrium chemistry: not converged, a '
+         'temperature outside the Gibbs table, or an element ratio <= 0'),
+        # without the network the arguments are those of free VMRs, whose first check this misses
+        (dict(chemistry=None), 'base_vmr must have shape (5, 16), got (1,)'),
+    ]
+    for change, message in rows:
+        with pytest.raises(ValueError) as err:
+            pa.WalkerAtmosphere(**dict(good, **change))
+        assert str(err.value) == message, list(change)

@@ -201,6 +201,52 @@ def test_evaluate_vs_host(eng, pa, ch, net):
         assert a is None or np.array_equal(a.cpu().numpy(), b)
 
 
+def test_out_is_reused_with_chemistry(eng, pa, net):
+    """The buffers between the three launches are kept per nw.  nw = 3, L = 5 (walker 2 rejected
+    for C/O < 0): a second evaluate(params, out=first) returns the same tensors with the same
+    bits, through the same intermediate storage; a call at nw = 5 then gets buffers of its own
+    and leaves the nw = 3 result and buffers as they were."""
+    import torch
+    atm, base = cc.chem_atmosphere(pa, net, L=5, free_scalars=('rplanet',))
+    atm.bind(['H2O', 'CO', 'CH4'])
+    params = np.stack([base, base + [300.0, 0.7, 0.6, 3.0, 2e8], base + [0, 0, -1.0, 0, 0]])
+    params_d = eng.dev(params)
+    between = ('temps', 'vmr', 'status')
+
+    def snapshot(nw):
+        torch.cuda.synchronize()
+        launch = atm.equilibrium_launch(nw, params_d.device)
+        return ({k: launch[k].data_ptr() for k in between},
+                {k: launch[k].cpu().numpy() for k in between})
+    first = atm.evaluate(params_d)
+    tensors = tuple(first)
+    ptrs, held = snapshot(3)
+    want = [None if t is None else t.cpu().numpy() for t in first]
+    assert want[-1].tolist() == [0, 0, pa.REJECT_CHEMISTRY]
+    assert held['vmr'].shape == (3, 5, net.nspecies) and np.all(held['status'][:2] > 0)
+
+    again = atm.evaluate(params_d, out=first)
+    assert again is first and all(a is b for a, b in zip(again, tensors))
+    ptrs_again, held_again = snapshot(3)
+    assert ptrs_again == ptrs
+    for a, b in zip(again, want):
+        assert a is None or np.array_equal(a.cpu().numpy(), b)
+    for k in between:
+        assert np.array_equal(held_again[k], held[k], equal_nan=True)
+
+    more = np.concatenate([params[::-1], params[:2] + [50.0, 0.1, 0.05, 0.2, 1e7]])
+    other = atm.evaluate(eng.dev(more))
+    ptrs_other, held_other = snapshot(5)
+    assert held_other['vmr'].shape == (5, 5, net.nspecies)
+    assert not set(ptrs_other.values()) & set(ptrs.values())
+    assert other.reject.cpu().numpy()[0] == pa.REJECT_CHEMISTRY
+    assert snapshot(3)[0] == ptrs
+    for a, b in zip(first, want):
+        assert a is None or np.array_equal(a.cpu().numpy(), b)
+    for k in between:
+        assert np.array_equal(snapshot(3)[1][k], held[k], equal_nan=True)
+
+
 # ------------------------------------------------------------------------------ through Retrieval
 BLOCK = """
     T_iso       1400.0   500.0  3000.0   50.0

@@ -77,14 +77,14 @@ def main():
     profs = [chem_atm.evaluate(p) for p in chem_params]
     rejected = int(sum(int((p.reject != 0).sum().item()) for p in profs))
     L = chem_atm.nlayers
-    temps_d, vmr_d, status_d, _ = chem_atm._chemistry_buffers(BATCH, chem_params[0].device)
+    launch = chem_atm.equilibrium_launch(BATCH, chem_params[0].device)
+    temps_d, vmr_d, status_d = launch['temps'], launch['vmr'], launch['status']
+    pressure_d, columns = launch['pressure'], launch['columns']
     chem_atm.evaluate(chem_params[0])
     torch.cuda.synchronize()
     status = status_d.cpu().numpy()
     temps_h = temps_d.cpu().numpy()
     vmr_dev = vmr_d.cpu().numpy()
-    pressure_d = chem_atm._dev['pressure']
-    columns = chem_atm._equil
 
     def sync():
         torch.cuda.synchronize()
