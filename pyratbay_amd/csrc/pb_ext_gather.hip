@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "pb_ext_plan.h"
@@ -453,16 +454,86 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
     // compiler when the lambda below is instantiated for several call sites)
     const unsigned row_lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)(
         reinterpret_cast<char *>(s_row + kStagePad));
+    //
+    // The request of a whole row.  For a MUBUF load with the `lds` bit the 12-bit `offset:` field
+    // of the instruction is added on BOTH sides: memory address = base + voffset + offset (range
+    // checked against the descriptor as before), LDS address = LDS base + M0[15:0] + offset +
+    // lane * 16.  Consecutive 1-KiB pieces of a row differ by +1024 on both sides, so pieces 0..3
+    // are four loads with offset:0/1024/2048/3072 behind ONE write of M0, and pieces 4..7 the same
+    // behind a second one (M0 and voffset + 4096): no address arithmetic, compare or branch per
+    // piece.  M0 is written in the statement that reads it (the compiler does not keep it).
+    // `s_nop 4` opens the first statement of a request: the descriptor's SGPRs come from
+    // v_readfirstlane, and a VALU write of an SGPR needs five wait states before a VMEM
+    // instruction reads it; the hazard does apply here (the s_mov of M0 is an SALU read and
+    // would need none, the load does), and hipcc pads nothing inside a statement.  The second
+    // statement of a request follows the first in program order (both volatile) with the same
+    // descriptor registers, at least eight instructions later, and needs none.
+    // The number of pieces is EXACT, ceil(rowlim / 128): a piece writes all of its 128 samples
+    // (zeros beyond the descriptor's range), which the pad after a slot absorbs for the last
+    // piece of a row (tests/test_rows_per_step_cpu.py) but not for a surplus one -- with two rows
+    // per step (pitch = rowlim + 256) that would reach the data of the next slot.  It is formed
+    // where rowlim is (`npiece`), wave-uniform, and selects the statement by a scalar switch.
+    int npiece = (rowlim + 127) >> 7;              // 0 ... 8
+    typedef int dma_v4i __attribute__((ext_vector_type(4)));
+#define PB_DMA_OPEN "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+#define PB_DMA_LD(off) "buffer_load_dwordx4 %2, %3, 0 offen offset:" #off " lds\n\t"
+#define PB_DMA_LD1 PB_DMA_LD(0)
+#define PB_DMA_LD2 PB_DMA_LD1 PB_DMA_LD(1024)
+#define PB_DMA_LD3 PB_DMA_LD2 PB_DMA_LD(2048)
+#define PB_DMA_LD4 PB_DMA_LD3 PB_DMA_LD(3072)
+#define PB_DMA_GROUP(pad, loads, dst_, voff_)                                                    \
+    do {                                                                                         \
+        unsigned keep;                                                                           \
+        asm volatile(pad PB_DMA_OPEN loads "s_mov_b32 m0, %0"                                    \
+                     : "=&s"(keep)                                                               \
+                     : "s"(dst_), "v"(voff_), "s"(rsrc)                                          \
+                     : "memory");                                                                \
+    } while (0)
+    auto dma_pieces = [&](unsigned dst, int voff, dma_v4i rsrc) {
+        const unsigned dst4 = dst + 4096;
+        const int voff4 = voff + 4096;
+        switch (npiece) {                          // wave-uniform
+        case 1: PB_DMA_GROUP("s_nop 4\n\t", PB_DMA_LD1, dst, voff); break;
+        case 2: PB_DMA_GROUP("s_nop 4\n\t", PB_DMA_LD2, dst, voff); break;
+        case 3: PB_DMA_GROUP("s_nop 4\n\t", PB_DMA_LD3, dst, voff); break;
+        case 4: PB_DMA_GROUP("s_nop 4\n\t", PB_DMA_LD4, dst, voff); break;
+        case 5:
+            PB_DMA_GROUP("s_nop 4\n\t", PB_DMA_LD4, dst, voff);
+            PB_DMA_GROUP("", PB_DMA_LD1, dst4, voff4);
+            break;
+        case 6:
+            PB_DMA_GROUP("s_nop 4\n\t", PB_DMA_LD4, dst, voff);
+            PB_DMA_GROUP("", PB_DMA_LD2, dst4, voff4);
+            break;
+        case 7:
+            PB_DMA_GROUP("s_nop 4\n\t", PB_DMA_LD4, dst, voff);
+            PB_DMA_GROUP("", PB_DMA_LD3, dst4, voff4);
+            break;
+        case 8:
+            PB_DMA_GROUP("s_nop 4\n\t", PB_DMA_LD4, dst, voff);
+            PB_DMA_GROUP("", PB_DMA_LD4, dst4, voff4);
+            break;
+        default: break;                            // no row data in this (layer, isotope)
+        }
+    };
+#undef PB_DMA_GROUP
+#undef PB_DMA_LD4
+#undef PB_DMA_LD3
+#undef PB_DMA_LD2
+#undef PB_DMA_LD1
+#undef PB_DMA_LD
+#undef PB_DMA_OPEN
     // (tref, probe 4: the stamp that opened the step -- the descriptor chain is timed against it)
-    auto dma_desc = [&](unsigned long long d, int buf, int c_lo, int c_hi,
+    // `part`: true_type = the pieces [c_lo, c_hi) of the row only, one statement per piece (the
+    // kIssue == 2 experiment); false_type = the whole row through dma_pieces()
+    auto dma_desc = [&](unsigned long long d, int buf, auto part, int c_lo, int c_hi,
                         unsigned long long tref = 0) {
         const unsigned dlo = (unsigned)__builtin_amdgcn_readfirstlane((int)d);
         const unsigned dhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(d >> 32));
         const long long first = ((long long)(dhi & 0xffu) << 32) | dlo;
         const int len = (int)((dhi >> 8) & 0xfffu), mlo = (int)(dhi >> 20);
         const unsigned long long base = (unsigned long long)(a.pm + first);
-        typedef int v4i __attribute__((ext_vector_type(4)));
-        v4i rsrc;
+        dma_v4i rsrc;
         rsrc.x = __builtin_amdgcn_readfirstlane((int)base);
         rsrc.y = __builtin_amdgcn_readfirstlane((int)((base >> 32) & 0xffffu));
         rsrc.z = __builtin_amdgcn_readfirstlane(len * 8);
@@ -473,25 +544,29 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
             if (tref)
                 pc[20] += tick() - tref;
         }
-        voff += 1024 * c_lo;
-        dst += 1024 * (unsigned)c_lo;
-        for (int c = c_lo; c < c_hi && c * 128 < rowlim; c++) {
-            unsigned keep;
-            asm volatile("s_nop 4\n\t"
-                         "s_mov_b32 %0, m0\n\t"
-                         "s_mov_b32 m0, %1\n\t"
-                         "s_nop 0\n\t"
-                         "buffer_load_dwordx4 %2, %3, 0 offen lds\n\t"
-                         "s_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "s"(dst), "v"(voff), "s"(rsrc)
-                         : "memory");
-            voff += 1024;
-            dst += 1024;
+        if constexpr (!decltype(part)::value) {
+            dma_pieces(dst, voff, rsrc);
+        } else {
+            voff += 1024 * c_lo;
+            dst += 1024 * (unsigned)c_lo;
+            for (int c = c_lo; c < c_hi && c * 128 < rowlim; c++) {
+                unsigned keep;
+                asm volatile("s_nop 4\n\t"
+                             "s_mov_b32 %0, m0\n\t"
+                             "s_mov_b32 m0, %1\n\t"
+                             "s_nop 0\n\t"
+                             "buffer_load_dwordx4 %2, %3, 0 offen lds\n\t"
+                             "s_mov_b32 m0, %0"
+                             : "=&s"(keep)
+                             : "s"(dst), "v"(voff), "s"(rsrc)
+                             : "memory");
+                voff += 1024;
+                dst += 1024;
+            }
         }
     };
     auto dma_row = [&](int sg, int buf, unsigned long long tref = 0) {
-        dma_desc(s_desc[sg], buf, 0, 1 << 20, tref);
+        dma_desc(s_desc[sg], buf, std::false_type(), 0, 0, tref);
     };
     // out-of-window lanes fall outside the buffer descriptor and read 0 (no predicate)
     auto load_row = [&](int sg, auto Rc, double *reg) {
@@ -562,6 +637,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                 for (int i = tid; i < kNB * rowspan + kStagePad; i += kThreads)
                     s_row[i] = 0.0;
                 rowlim = lim;
+                npiece = (lim + 127) >> 7;
                 if constexpr (kMulti) {
                     const StageSlots sl = stage_slots(a.rowlds, lim, min(kRows, a.rows_cap));
                     pitch = sl.pitch;
@@ -945,7 +1021,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                     __syncthreads();
                     for (int sg = 0; sg < nseg; sg++) {
                         if (sg + 1 < nseg && wave == ((sg + 1) & (NW - 1))) {
-                            dma_desc(dn, (sg + 1) & 1, 0, 1 << 20);
+                            dma_desc(dn, (sg + 1) & 1, std::false_type(), 0, 0);
                             dn = s_desc[min(nseg - 1, sg + 1 + NW)];
                         }
                         walk(sg, sg & 1);
@@ -959,14 +1035,14 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                     // over NW wavefronts) from a descriptor it fetched one step ahead
                     constexpr int kPer = (8 + NW - 1) / NW;
                     unsigned long long dn = s_desc[min(nseg - 1, 1)];
-                    dma_desc(s_desc[0], 0, wave * kPer, wave * kPer + kPer);
+                    dma_desc(s_desc[0], 0, std::true_type(), wave * kPer, wave * kPer + kPer);
                     __builtin_amdgcn_s_waitcnt(0x0f70);
                     __syncthreads();
                     for (int sg = 0; sg < nseg; sg++) {
                         const unsigned long long dcur = dn;
                         dn = s_desc[min(nseg - 1, sg + 2)];
                         if (sg + 1 < nseg)
-                            dma_desc(dcur, (sg + 1) & 1, wave * kPer, wave * kPer + kPer);
+                            dma_desc(dcur, (sg + 1) & 1, std::true_type(), wave * kPer, wave * kPer + kPer);
                         walk(sg, sg & 1);
                         __builtin_amdgcn_s_waitcnt(0x0f70);
                         __syncthreads();
