@@ -17,6 +17,24 @@
  *   - Return value: PB_OK (0) or a negative PB_ERR_* code; pb_last_error() returns a
  *     thread-local message.  The library never calls exit() and has no CPU fallback:
  *     without a usable GPU every compute entry fails with PB_ERR_HIP.
+ *
+ * The Python binding reads THIS FILE (pyratbay_amd/_capi.py): constants, struct layouts and
+ * prototypes exist nowhere else, so a new entry point is declared here and nowhere in Python.  The
+ * reader takes a subset of C and refuses everything else:
+ *   - comments in this style only; #include <stdint.h>; #ifdef / #ifndef / #endif of PBHIP_H,
+ *     __cplusplus (around the extern "C" braces only) and PB_EXPERIMENTS (entries bound only when
+ *     the loaded library exports them); no #if, #else, line continuations or function-like macros;
+ *   - #define NAME <integer>: decimal or hex, negative, with or without parentheses;
+ *   - typedef struct pb_x pb_x; (a handle) and typedef struct pb_x { ... } pb_x; with fields of
+ *     int, int32_t, int64_t, uint64_t, uint8_t, double or a pointer to one of those, to void or
+ *     to a struct declared above; several declarators per statement; arrays of one or two
+ *     dimensions, of pointers too, whose bounds are integers or constants defined in this file;
+ *   - functions that return int, int64_t, void or const char *, with named parameters of the
+ *     scalar types above, `const char *` / `char *` (strings), or any other pointer, pointer to
+ *     pointer or array parameter (`int64_t stats[3]`) of the types above.
+ * No float, no unions, no nested or anonymous structs, no bit fields, no function pointers, no
+ * struct passed or returned by value.  An entry that returns int returns a status unless
+ * _capi.INT_QUERIES names it.
  */
 #ifndef PBHIP_H
 #define PBHIP_H

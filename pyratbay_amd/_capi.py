@@ -3,8 +3,10 @@
 There is no CPU fallback: if the shared library is missing or a call fails, an
 exception is raised.  torch is used only as plumbing for device memory and streams.
 """
+import collections
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -13,208 +15,199 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # product + the measured dead ends) or one of the debug builds of tools/debug/
 LIBPATH = os.environ.get('PB_LIBPBHIP') or os.path.join(_HERE, 'libpbhip.so')
 
-PB_OK = 0
-
 
 class PbError(RuntimeError):
     pass
 
 
+# ---------------------------------------------------------------------------------------------
+# include/pbhip.h is the one statement of the boundary: constants, structs and prototypes are read
+# from it (its opening comment names the subset of C this reader takes).  Whatever the reader
+# does not recognise raises -- nothing is skipped, or the reader would be a copy that can drift.
+# ---------------------------------------------------------------------------------------------
+HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'pbhip.h')
+
+_SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64,
+            'uint8_t': C.c_uint8, 'double': C.c_double}
+_RETURNS = {'int': C.c_int, 'int64_t': C.c_int64, 'void': None, 'const char *': C.c_char_p}
+# The entries whose int is a value.  Every other entry that returns int returns a status, which
+# call() checks against PB_OK.
+INT_QUERIES = frozenset((
+    'pb_version', 'pb_roctx_available', 'pb_two_stream_net_parts',
+    'pb_weighted_quantiles_resident_rows', 'pb_lbl_rows_per_step', 'pb_table_transit_supported'))
+
+_STATEMENT = re.compile(r"""\s*(?:
+      typedef\s+struct\s+(?P<tag>\w+)\s*(?:\{(?P<body>[^{}]*)\})?\s*(?P<alias>\w+)\s*;
+    | (?P<ret>[\w\s*]+?)\s*\b(?P<fn>\w+)\s*\((?P<args>[^(){};]*)\)\s*;
+    )""", re.X)
+_FIELD = re.compile(r'(?:const\s+)?(\w+)\b\s*(.+)', re.S)
+_DECLARATOR = re.compile(r'\s*(\**)\s*(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)')
+_PARAM = re.compile(
+    r'(?:const\s+)?(\w+)\b\s*((?:\*\s*(?:const\b\s*)?)*)\b\w+\s*((?:\[\s*\w*\s*\])*)')
+
+Header = collections.namedtuple('Header', 'constants structs protos experiments')
+
+
+def _quote(text):
+    return ' '.join(text.split())
+
+
+def _integer(text, what):
+    inner = text[1:-1] if text.startswith('(') and text.endswith(')') else text
+    try:
+        return int(inner.strip(), 0)
+    except ValueError:
+        raise PbError(f'pbhip.h: {what} is not an integer') from None
+
+
+def _fields(tag, body, constants, pointees):
+    """The _fields_ of one struct body."""
+    fields = []
+    for statement in filter(None, map(str.strip, body.split(';'))):
+        m = _FIELD.fullmatch(statement)
+        decls = [_DECLARATOR.fullmatch(d) for d in m.group(2).split(',')] if m else [None]
+        if None in decls:
+            raise PbError(f'pbhip.h: struct {tag}: cannot read `{_quote(statement)};`')
+        base = m.group(1)
+        for stars, name, dims in (d.groups() for d in decls):
+            if base not in (pointees if stars else _SCALARS):
+                raise PbError(f'pbhip.h: struct {tag}: unknown type `{base}` in '
+                              f'`{_quote(statement)};`')
+            ctype = C.c_void_p if stars else _SCALARS[base]
+            for bound in reversed(re.findall(r'\w+', dims)):
+                n = int(bound) if bound.isdigit() else constants.get(bound)
+                if n is None or n <= 0:
+                    raise PbError(f'pbhip.h: struct {tag}: array bound `{bound}` of '
+                                  f'`{_quote(statement)};` is not a positive integer or a '
+                                  'constant defined in the header')
+                ctype = ctype * n
+            fields.append((name, ctype))
+    return fields
+
+
+def _argtype(fn, param, pointees):
+    m = _PARAM.fullmatch(param.strip())
+    if not m:
+        raise PbError(f'pbhip.h: {fn}: cannot read the parameter `{_quote(param)}`')
+    base, stars, dims = m.groups()
+    pointer = bool(stars or dims)
+    if base not in (pointees if pointer else _SCALARS):
+        raise PbError(f'pbhip.h: {fn}: unknown type in the parameter `{_quote(param)}`')
+    if not pointer:
+        return _SCALARS[base]
+    return C.c_char_p if base == 'char' and stars.count('*') == 1 and not dims else C.c_void_p
+
+
+def parse_header(text):
+    """Header(constants {name: int}, structs {name: Structure subclass}, protos {name: (restype,
+    argtypes)}, experiments: the names declared under #ifdef PB_EXPERIMENTS) of the text of
+    pbhip.h.  PbError, quoting the text, for anything outside the subset the header states."""
+    constants, structs, protos, experiments = {}, {}, {}, set()
+    code = {None: [], 'PB_EXPERIMENTS': [], '__cplusplus': []}
+    conditions = []
+    for line in re.sub(r'/\*.*?\*/', ' ', text, flags=re.S).split('\n'):
+        m = re.match(r'\s*#\s*(\w+)\s*(.*?)\s*$', line)
+        if not m:
+            code[next((c for c in ('__cplusplus', 'PB_EXPERIMENTS') if c in conditions),
+                      None)].append(line)
+            continue
+        directive, rest = m.groups()
+        define = re.fullmatch(r'(\w+)(?:\s+(.+))?', rest) if directive == 'define' else None
+        if directive in ('ifdef', 'ifndef') and \
+                rest in ('PBHIP_H', '__cplusplus', 'PB_EXPERIMENTS'):
+            conditions.append(rest)
+        elif directive == 'endif' and conditions:
+            conditions.pop()
+        elif define:
+            if define.group(2) is not None:     # (without a value: the include guard)
+                constants[define.group(1)] = _integer(define.group(2), f'`{_quote(line)}`')
+        elif (directive, rest) != ('include', '<stdint.h>'):
+            raise PbError(f'pbhip.h: cannot read the preprocessor line `{_quote(line)}`')
+    if conditions:
+        raise PbError(f'pbhip.h: `#ifdef {conditions[-1]}` is not closed')
+    for piece in filter(None, map(_quote, code['__cplusplus'])):
+        if piece not in ('extern "C" {', '}'):
+            raise PbError(f'pbhip.h: cannot read `{piece}` under #ifdef __cplusplus')
+    pointees = set(_SCALARS) | {'void', 'char'}     # what a pointer may point to
+    for section in (None, 'PB_EXPERIMENTS'):
+        source, pos = '\n'.join(code[section]), 0
+        while source[pos:].strip():
+            m = _STATEMENT.match(source, pos)
+            if not m:
+                raise PbError('pbhip.h: cannot read the declaration '
+                              f'`{_quote(source[pos:].split(";")[0])};`')
+            pos = m.end()
+            tag, fn = m.group('tag'), m.group('fn')
+            if tag:
+                if tag != m.group('alias') or tag in pointees:
+                    raise PbError(f'pbhip.h: cannot read the declaration `{_quote(m.group())}`')
+                pointees.add(tag)
+                if m.group('body') is not None:
+                    structs[tag] = type(tag, (C.Structure,), {
+                        '__doc__': f'{tag} of include/pbhip.h.',
+                        '_fields_': _fields(tag, m.group('body'), constants, pointees)})
+                continue
+            ret = ' '.join(m.group('ret').replace('*', ' * ').split())
+            if ret not in _RETURNS or fn in protos:
+                raise PbError(f'pbhip.h: cannot read the declaration `{_quote(m.group())}`')
+            args = m.group('args').strip()
+            protos[fn] = (_RETURNS[ret], [] if args == 'void' else
+                          [_argtype(fn, p, pointees) for p in args.split(',')])
+            if section:
+                experiments.add(fn)
+    return Header(constants, structs, protos, experiments)
+
+
+_header = None
+
+
+def header():
+    """include/pbhip.h, read once per process."""
+    global _header
+    if _header is None:
+        if not os.path.exists(HEADER):
+            raise PbError(f'{HEADER} is missing: the binding reads its constants, structs and '
+                          'prototypes from it')
+        with open(HEADER) as f:
+            parsed = parse_header(f.read())
+        stray = sorted(n for n in INT_QUERIES if parsed.protos.get(n, (None,))[0] is not C.c_int)
+        if stray:
+            raise PbError(f'pbhip.h: {stray} of _capi.INT_QUERIES are not declared as int')
+        _header = parsed
+    return _header
+
+
+def constant(name):
+    """The value of `#define <name>` of include/pbhip.h."""
+    try:
+        return header().constants[name]
+    except KeyError:
+        raise PbError(f'pbhip.h defines no constant {name}') from None
+
+
+def struct(name):
+    """The ctypes.Structure of `typedef struct <name> { ... } <name>;` of include/pbhip.h."""
+    try:
+        return header().structs[name]
+    except KeyError:
+        raise PbError(f'pbhip.h defines no struct {name}') from None
+
+
+PB_OK = constant('PB_OK')
+# what call() does not compare with PB_OK: every entry that does not return int, and INT_QUERIES
+_UNCHECKED = INT_QUERIES | {n for n, (restype, _) in header().protos.items()
+                            if restype is not C.c_int}
 _lib = None
-
-vp = C.c_void_p
-i32, i64, u64, f64 = C.c_int, C.c_int64, C.c_uint64, C.c_double
-
-# name: argtypes (all functions return int unless listed in _RESTYPES)
-_PROTOS = {
-    'pb_version': [],
-    'pb_device_count': [C.POINTER(C.c_int)],
-    'pb_set_device': [i32],
-    'pb_timer_create': [C.POINTER(vp), i32],
-    'pb_timer_start': [vp, C.c_char_p, vp],
-    'pb_timer_mark': [vp, C.c_char_p, C.c_char_p, vp],
-    'pb_timer_count': [vp, C.POINTER(i32)],
-    'pb_timer_read': [vp, i32, C.c_char_p, i32, C.POINTER(f64)],
-    'pb_timer_destroy': [vp],
-    'pb_range_push': [C.c_char_p],
-    'pb_range_pop': [],
-    'pb_roctx_available': [],
-    'pb_voigt_create': [C.POINTER(vp), vp, i32, vp, i32, vp, f64, i32, i32, vp],
-    'pb_voigt_from_flat': [C.POINTER(vp), vp, i64, vp, i32, vp, i32, vp, vp, i32, i32, vp],
-    'pb_voigt_meta': [vp, vp, vp, C.POINTER(i64)],
-    'pb_voigt_flat_to_host': [vp, vp, i64],
-    'pb_voigt_device_bytes': [vp],
-    'pb_voigt_destroy': [vp],
-    'pb_lines_create': [C.POINTER(vp), vp, vp, vp, vp, i64, i32, vp, i64, f64, f64],
-    'pb_lines_stats': [vp, C.POINTER(i64 * 3)],
-    'pb_lines_grouped_on_device': [vp, C.POINTER(i32)],
-    'pb_lines_groups': [vp, vp, vp, vp, vp],
-    'pb_lines_destroy': [vp],
-    'pb_lbl_create': [C.POINTER(vp), vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp,
-                      i32, f64, f64, i32, i32],
-    'pb_lbl_set_isoiext': [vp, vp],
-    'pb_lbl_set_ethresh': [vp, f64],
-    'pb_lbl_set_gather_mode': [vp, i32],
-    'pb_lbl_set_concurrency': [vp, i32],
-    'pb_lbl_set_record_budget': [vp, i64],
-    'pb_lbl_last_chunks': [vp, C.POINTER(i32)],
-    'pb_lbl_last_gather_mode': [vp, C.POINTER(i32)],
-    'pb_lbl_extinction': [vp, vp, i64, i64, vp, vp, vp, i64, i64, i32, i32, vp],
-    'pb_lbl_extinction_begin': [vp, vp, i64, i64, vp, vp, vp, i64, i64, i32, i32, vp],
-    'pb_lbl_kmax_buffer': [vp, C.POINTER(vp), C.POINTER(i64)],
-    'pb_lbl_extinction_end': [vp, vp],
-    'pb_lbl_last_state': [vp, vp, vp, i32, i32, vp],
-    'pb_lbl_last_layer_kinds': [vp, vp, vp, i32, vp],
-    'pb_lbl_rows_per_step': [i32, i32, C.POINTER(i32)],
-    'pb_lbl_last_rows_per_step': [vp, vp, i32, i32, vp],
-    'pb_lbl_last_work': [vp, C.POINTER(i64 * 3), vp],
-    'pb_lbl_last_table_samples': [vp, C.POINTER(i64), vp],
-    'pb_lbl_timing_begin': [vp, i32],
-    'pb_lbl_timing_end': [vp, C.POINTER(f64), C.POINTER(i32)],
-    'pb_lbl_destroy': [vp],
-    'pb_interp_ec': [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-    'pb_interp_ec_set': [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-    'pb_transit_path': [vp, vp, i32, i32, i32, vp],
-    'pb_iso_partition': [vp, i64, i64, vp, i64, vp, i32, vp, i32, vp, vp],
-    'pb_resample_cross_section': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
-                                  i32, vp],
-    'pb_interp_ec_batch_work_doubles': [i32, i32],
-    'pb_interp_ec_batch_plan': [vp, i32, i32, i32, i32, i32, i32, i32],
-    'pb_interp_ec_batch': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
-    'pb_transit_work_doubles': [i32, i32, i32, i32, i32],
-    'pb_transit_spectrum_batch': [vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, i32, vp, vp],
-    'pb_transit_spectrum_ordered': [vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, i32, vp, vp],
-    'pb_interp_ec_batch_limited': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp],
-    'pb_transit_spectrum_limited': [vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, i32, vp, vp,
-                                    vp, vp, vp],
-    'pb_emission_flux_limited': [vp, vp, vp, vp, vp, vp, vp, vp, i32, f64, i32, i32, i32, i32, i32,
-                                 vp, vp, vp, vp],
-    'pb_emission_flux_batch': [vp, vp, vp, vp, vp, vp, vp, i32, f64, i32, i32, i32, i32, i32, vp],
-    'pb_emission_flux_ordered': [vp, vp, vp, vp, vp, vp, vp, vp, i32, f64, i32, i32, i32, i32, i32, vp],
-    'pb_band_integrate_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-    'pb_emission_observables': [vp, vp, vp, vp, vp, i64, i32, i32, f64, f64, vp],
-    'pb_band_scale': [vp, vp, vp, i32, i32, vp],
-    'pb_reject_walkers': [vp, vp, f64, f64, i32, i32, i32, vp],
-    'pb_inst_convolve_batch': [vp, vp, vp, vp, i32, i32, i32, vp],
-    'pb_hires_observe_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, i32, i32, i32, vp],
-    'pb_interp_ec_batch_cont_work_doubles': [vp, i32, i32, i32],
-    'pb_interp_ec_batch_cont': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
-    'pb_interp_ec_batch_cont_limited': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp,
-                                        i32, vp, vp],
-    'pb_deck_state_batch': [vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, vp],
-    'pb_cloud_plan': [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp],
-    'pb_cloudy_transit_batch': [vp, vp, vp, vp, vp, i64, vp, i64, vp, f64, i32, f64, i32, i32, i32,
-                                vp, vp, vp, vp, vp],
-    'pb_cloudy_emission_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f64, i32, i32, i32,
-                                 i32, vp, vp, vp, vp, vp],
-    'pb_walker_atmosphere': [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
-    'pb_walker_temperature': [vp, vp, i32, vp, vp],
-    'pb_equilibrium_vmr': [vp, vp, vp, i32, vp, vp, vp],
-    'pb_walker_atmosphere_chem': [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    'pb_iso_density': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
-    'pb_optdepth': [vp, vp, i64, vp, i32, f64, vp, i32, i32, vp],
-    'pb_optical_depth_transit': [vp, vp, vp, vp, i32, i32, f64, i32, i32, vp],
-    'pb_transit_spectrum': [vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, vp],
-    'pb_plane_parallel_optical_depth': [vp, vp, vp, vp, f64, i32, i32, i32, i32, vp],
-    'pb_trapezoid2D': [vp, vp, vp, vp, i32, i32, vp],
-    'pb_transmission': [vp, vp, vp, vp, i32, f64, i32, i32, vp],
-    'pb_blackbody_wn_2D': [vp, vp, i32, vp, i32, vp, vp],
-    'pb_blackbody_wn': [vp, vp, i32, f64, vp],
-    'pb_intensity': [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-    'pb_emission_flux': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-    'pb_transmission_deck': [vp, vp, vp, vp, i32, f64, i32, f64, i32, i32, vp],
-    'pb_transit_spectrum_deck': [vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, f64, i32, i32, vp],
-    'pb_emission_flux_deck': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
-    'pb_continuum': [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    'pb_alkali_cross_section': [vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, vp, vp, i32, vp, i32, i32, vp],
-    'pb_alkali_voigt_det_batch': [vp, vp, vp, f64, f64, f64, vp, i32, i32, i32, vp],
-    'pb_loglike': [vp, vp, vp, vp, i32, i32, vp],
-    'pb_star_band_scale_batch': [vp, vp, vp, vp, f64, vp, f64, vp, vp, vp, vp, vp, vp, vp, i32, i32,
-                                 i32, i32, vp],
-    'pb_loglike_obs': [vp, vp, vp, vp, vp, vp, f64, i32, vp, vp, vp, f64, i32, i32, i32, vp],
-    'pb_two_stream': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-    'pb_two_stream_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-    'pb_two_stream_batch_work_doubles': [i32, i32, i32],
-    'pb_two_stream_batch_star': [vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, vp, i32, i32, i32, vp],
-    'pb_retrieval_map': [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32,
-                         i32, i32, vp],
-    'pb_prior_transform': [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
-    'pb_log_posterior': [vp, vp, vp, vp, f64, i32, i32, vp],
-    'pb_demc_propose': [vp, vp, vp, vp, vp, vp, i64, u64, i64, f64, f64, f64, i32, i32, vp],
-    'pb_demc_accept': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, u64,
-                       i64, i64, i32, i32, i32, i32, vp],
-    'pb_gelman_rubin': [vp, vp, vp, i64, i32, i32, vp],
-    'pb_philox_uniform': [vp, u64, i64, i32, vp],
-    'pb_nested_select': [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp],
-    'pb_nested_propose': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, u64, f64, f64,
-                          i32, i32, i32, i32, vp],
-    'pb_nested_accept': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32,
-                         vp],
-    'pb_nested_finish': [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp],
-    'pb_nested_resample': [vp, vp, i64, i64, u64, vp],
-    'pb_modes_sqdist': [vp, vp, vp, i64, i32, i32, vp],
-    'pb_modes_link': [vp, vp, vp, vp, vp, vp, i32, i32, i32, f64, i32, i32, vp],
-    'pb_modes_assign': [vp, vp, vp, vp, i64, i32, i32, vp],
-    'pb_modes_rows': [vp, vp, vp, i64, i64, vp],
-    'pb_modes_evidence': [vp, vp, vp, vp, vp, vp, vp, i64, i32, vp],
-    'pb_lm_residuals': [vp, vp, vp, vp, vp, vp, f64, i32, vp, vp, vp, f64, i32, vp, vp, vp, vp, vp,
-                        vp, i32, i32, i32, i32, vp],
-    'pb_lm_probe': [vp, vp, vp, vp, vp, f64, i32, i64, vp],
-    'pb_lm_normal': [vp, vp, vp, vp, vp, i32, i32, i64, vp],
-    'pb_lm_work_doubles': [i32, i32, i64],
-    'pb_lm_step': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, i32, i64, vp],
-    'pb_lm_update': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, f64,
-                     i32, i32, i32, i32, i64, vp],
-    'pb_lm_covariance': [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, vp],
-    'pb_internal_flux': [vp, vp, f64, i32, vp],
-    'pb_two_stream_net_parts': [i32],
-    'pb_two_stream_net_work_doubles': [i32, i32, i32],
-    'pb_two_stream_net_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp],
-    'pb_radeq_update': [vp, i32, vp],
-    'pb_radeq_update_convective': [vp, vp, vp],
-    'pb_weighted_quantiles': [vp, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp],
-    'pb_weighted_quantiles_work_doubles': [i32, i32, i32],
-    'pb_weighted_quantiles_resident_rows': [],
-    'pb_band_contribution_emission_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f64, i32,
-                                            i32, i32, i32, i32, i32, vp, vp],
-    'pb_band_transmittance_batch': [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
-                                    vp, vp],
-    'pb_band_contribution_work_doubles': [i32, i32, i32, i32],
-    'pb_band_contribution_emission_cloudy_batch': [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f64,
-                                                   i32, i32, i32, i32, i32, i32, vp, vp, vp, vp,
-                                                   vp],
-    'pb_band_transmittance_cloudy_batch': [vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, f64, i32,
-                                           i32, i32, i32, vp, vp, vp, vp, vp],
-    'pb_simps2D': [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp],
-    'pb_ediff': [vp, vp, i32, vp],
-    'pb_band_integrate': [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, vp],
-}
-# entries of libpbhip_exp.so only (include/pbhip.h, "Experiments"): bound when the loaded library has them
-_EXP_PROTOS = {
-    'pb_lbl_last_wave_layers': [vp, vp, i32, vp],
-    'pb_lbl_dyn_stats': [vp, vp],
-    'pb_lbl_set_dyn_predict': [vp, i32],
-    'pb_table_transit_supported': [i32, i32, i32, i32, i32, i32],
-    'pb_table_transit_work_doubles': [i32, i32, i32, i32, i32],
-    'pb_table_transit_batch': [vp, vp, vp, vp, vp, vp, vp, f64, i32, i32, f64, i32, i32, i32, i32,
-                               i32, vp, vp],
-}
-_RESTYPES = {'pb_transit_work_doubles': C.c_int64, 'pb_two_stream_batch_work_doubles': C.c_int64,
-             'pb_two_stream_net_work_doubles': C.c_int64, 'pb_two_stream_net_parts': C.c_int,
-             'pb_weighted_quantiles_work_doubles': C.c_int64,
-             'pb_lm_work_doubles': C.c_int64,
-             'pb_weighted_quantiles_resident_rows': C.c_int,
-             'pb_band_contribution_work_doubles': C.c_int64,
-             'pb_interp_ec_batch_work_doubles': C.c_int64,
-             'pb_interp_ec_batch_cont_work_doubles': C.c_int64, 'pb_table_transit_work_doubles': C.c_int64,
-             'pb_table_transit_supported': C.c_int, 'pb_voigt_destroy': None, 'pb_lines_destroy': None, 'pb_lbl_destroy': None,
-             'pb_voigt_device_bytes': i64, 'pb_timer_destroy': None,
-             'pb_lbl_rows_per_step': C.c_int}
-_NO_CHECK = set(_RESTYPES) | {'pb_version', 'pb_roctx_available'}
 
 
 def exported_names():
-    return sorted(list(_PROTOS) + ['pb_last_error'])
+    return sorted(set(header().protos) - header().experiments)
+
+
+def experiment_names():
+    """The entries of libpbhip_exp.so only (include/pbhip.h, "Experiments"): bound when the loaded
+    library has them."""
+    return sorted(header().experiments)
 
 
 def experiments():
@@ -244,17 +237,11 @@ def lib():
                 '(or __graft_entry__.build()); there is no CPU fallback')
         _preload_torch_hip_runtime()
         handle = C.CDLL(LIBPATH)
-        handle.pb_last_error.restype = C.c_char_p
-        handle.pb_last_error.argtypes = []
-        for name, args in _PROTOS.items():
-            fn = getattr(handle, name)
-            fn.argtypes = args
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        for name, args in _EXP_PROTOS.items():
-            fn = getattr(handle, name, None)
+        for name, (restype, argtypes) in header().protos.items():
+            fn = getattr(handle, name, None) if name in header().experiments else \
+                getattr(handle, name)
             if fn is not None:
-                fn.argtypes = args
-                fn.restype = _RESTYPES.get(name, C.c_int)
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = handle
         global _owner_pid
         _owner_pid = os.getpid()
@@ -278,7 +265,7 @@ def call(name, *args):
                       '`make -C pyratbay_amd/csrc EXPERIMENTS=1` and set '
                       'PB_LIBPBHIP=pyratbay_amd/libpbhip_exp.so')
     rc = fn(*args)
-    if name not in _NO_CHECK and rc != PB_OK:
+    if name not in _UNCHECKED and rc != PB_OK:
         raise PbError(f'{name} failed ({rc}): {lib().pb_last_error().decode()}')
     return rc
 
@@ -288,7 +275,7 @@ def hptr(a):
     if a is None:
         return None
     assert a.flags.c_contiguous
-    return a.ctypes.data_as(vp)
+    return a.ctypes.data_as(C.c_void_p)
 
 
 def f64h(a):

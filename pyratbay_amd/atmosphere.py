@@ -21,7 +21,7 @@ import functools
 import numpy as np
 import torch
 
-from ._capi import call
+from ._capi import call, constant, struct
 from ._device import dev, require_gpu
 from .atm_models import (  # noqa: F401 -- imported back: every earlier spelling keeps working
     BAR, E2_CUTOFF, EULER, G_GRAV, K_BOLTZ, N_AVOGADRO, TCEA, Guillot, IsoVMR, Isothermal, Madhu,
@@ -29,13 +29,18 @@ from .atm_models import (  # noqa: F401 -- imported back: every earlier spelling
     gaussian_weights, hydro_g, hydro_m, ideal_gas_density, mean_weight, qcapcheck, ratio,
     vmr_scale)
 
-MAX_SPECIES, MAX_VMR, MAX_BULK, MAX_LAYERS = 32, 16, 4, 1024
+MAX_SPECIES, MAX_VMR = constant('PB_ATM_MAX_SPECIES'), constant('PB_ATM_MAX_VMR')
+MAX_BULK, MAX_LAYERS = constant('PB_ATM_MAX_BULK'), constant('PB_ATM_MAX_LAYERS')
 # isotope ratios of the table's slots (isotopes.py): labelled slots, fillers of one fill slot
-MAX_ISO_SLOTS, MAX_ISO_FILLERS = 32, 7
-REJECT_TEMP, REJECT_MADHU, REJECT_QCAP, REJECT_REFPRESSURE, REJECT_DIVERGENT = 1, 2, 4, 8, 16
-REJECT_ISOTOPE = 32                    # a non-finite or negative isotope ratio (isotopes.py)
-# (32 is taken by the isotope ratios, which share the mask: the chemistry's bit is the next one)
-REJECT_CHEMISTRY = 64                  # an equilibrium cell without VMRs (chemistry.py)
+MAX_ISO_SLOTS, MAX_ISO_FILLERS = constant('PB_ISO_MAX_SLOTS'), constant('PB_ISO_MAX_FILLERS')
+REJECT_TEMP, REJECT_MADHU = constant('PB_ATM_REJECT_TEMP'), constant('PB_ATM_REJECT_MADHU')
+REJECT_QCAP, REJECT_REFPRESSURE = (constant('PB_ATM_REJECT_QCAP'),
+                                   constant('PB_ATM_REJECT_REFPRESSURE'))
+REJECT_DIVERGENT = constant('PB_ATM_REJECT_DIVERGENT')
+REJECT_ISOTOPE = constant('PB_ISO_REJECT')  # a non-finite or negative isotope ratio (isotopes.py)
+# an equilibrium cell without VMRs (chemistry.py); the isotope ratios share the mask: its bit is
+# the next one
+REJECT_CHEMISTRY = constant('PB_ATM_REJECT_CHEMISTRY')
 REJECT_NAMES = {REJECT_TEMP: 'temperature <= 0 or not finite', REJECT_MADHU: 'madhu log_p1 > log_p3',
                 REJECT_QCAP: 'trace abundances above qcap',
                 REJECT_REFPRESSURE: 'reference pressure outside the grid',
@@ -48,38 +53,7 @@ REJECT_NAMES = {REJECT_TEMP: 'temperature <= 0 or not finite', REJECT_MADHU: 'ma
 # ---------------------------------------------------------------------------------------------
 # The batched form
 # ---------------------------------------------------------------------------------------------
-class AtmModelStruct(C.Structure):
-    """pb_atm_model of include/pbhip.h."""
-    _fields_ = [
-        ('nlayers', C.c_int), ('nspecies', C.c_int), ('npar', C.c_int),
-        ('tmodel', C.c_int),
-        ('guillot_gravity', C.c_double),
-        ('madhu_radius', C.c_int),
-        ('madhu_logp0', C.c_double), ('madhu_loge', C.c_double),
-        ('madhu_weights_d', C.c_void_p),
-        ('nvmr', C.c_int),
-        ('vmr_kind', C.c_int * MAX_VMR),
-        ('vmr_species', C.c_int * MAX_VMR),
-        ('vmr_par', C.c_int * MAX_VMR),
-        ('vmr0_d', C.c_void_p),
-        ('nbulk', C.c_int),
-        ('bulk_species', C.c_int * MAX_BULK),
-        ('bulk_ratio_d', C.c_void_p), ('invsrat_d', C.c_void_p),
-        ('base_vmr_d', C.c_void_p),
-        ('pressure_d', C.c_void_p),
-        ('log10p_d', C.c_void_p), ('lnp_d', C.c_void_p),
-        ('mass_d', C.c_void_p),
-        ('rmodel', C.c_int),
-        ('base_vmr_stride', C.c_int),
-        ('mplanet', C.c_double), ('gplanet', C.c_double), ('rplanet', C.c_double),
-        ('refpressure', C.c_double),
-        ('par_rplanet', C.c_int), ('par_log_refpressure', C.c_int), ('par_mplanet', C.c_int),
-        ('has_qcap', C.c_int),
-        ('qcap', C.c_double),
-        ('base_radius_d', C.c_void_p),
-        ('ntab', C.c_int), ('ncont', C.c_int), ('nalk', C.c_int),
-        ('tab_map_d', C.c_void_p), ('cont_map_d', C.c_void_p), ('alk_map_d', C.c_void_p),
-    ]
+AtmModelStruct = struct('pb_atm_model')
 
 
 Profiles = collections.namedtuple(

@@ -31,7 +31,11 @@ import ctypes as C
 
 import numpy as np
 
-MAX_NET_SPECIES, MAX_ELEMENTS, MAX_HYBRID = 64, 8, 16
+from ._capi import constant, struct
+
+MAX_NET_SPECIES, MAX_ELEMENTS, MAX_HYBRID = (constant('PB_CHEM_MAX_SPECIES'),
+                                             constant('PB_CHEM_MAX_ELEMENTS'),
+                                             constant('PB_CHEM_MAX_HYBRID'))
 MAX_ITERATIONS = 200
 # The largest full Newton step (on the major species and on ln n) at which a cell counts as
 # converged.  Newton converges quadratically, so the error left after such a step is its square;
@@ -39,10 +43,13 @@ MAX_ITERATIONS = 200
 # units of 1e-16 times the condition of the system.  1e-12 keeps two orders above that floor for
 # exp and log that differ in their last bits (profiles/chemistry.md has the iteration counts).
 TOLERANCE = 1.0e-12
-STATUS_REJECTED = -1          # temperature <= 0 or NaN: a walker rejected before the chemistry
-STATUS_TEMPERATURE = -2       # temperature outside gibbs_temps
-STATUS_RATIO = -3             # an X/Y <= 0, or an elemental abundance that is not finite and > 0
-STATUS_NOT_CONVERGED = -4     # MAX_ITERATIONS without a converged full step
+# temperature <= 0 or NaN: a walker rejected before the chemistry
+STATUS_REJECTED = constant('PB_CHEM_REJECTED')
+STATUS_TEMPERATURE = constant('PB_CHEM_TEMPERATURE')        # temperature outside gibbs_temps
+# an X/Y <= 0, or an elemental abundance that is not finite and > 0
+STATUS_RATIO = constant('PB_CHEM_RATIO')
+# MAX_ITERATIONS without a converged full step
+STATUS_NOT_CONVERGED = constant('PB_CHEM_NOT_CONVERGED')
 STATUS_NAMES = {STATUS_REJECTED: 'temperature <= 0',
                 STATUS_TEMPERATURE: 'temperature outside the Gibbs table',
                 STATUS_RATIO: 'an element ratio <= 0 or a non-finite abundance',
@@ -84,30 +91,7 @@ def gauss_solve(A, r):
     return x
 
 
-class ChemModelStruct(C.Structure):
-    """pb_chem_model of include/pbhip.h."""
-    _fields_ = [
-        ('nspecies', C.c_int), ('nelements', C.c_int), ('ntemps', C.c_int),
-        ('nlayers', C.c_int), ('npar', C.c_int),
-        ('ihydrogen', C.c_int),
-        ('base_dex', C.c_double * MAX_ELEMENTS),
-        ('is_metal', C.c_int * MAX_ELEMENTS),
-        ('par_metal', C.c_int),
-        ('nscale', C.c_int),
-        ('scale_element', C.c_int * MAX_ELEMENTS),
-        ('scale_par', C.c_int * MAX_ELEMENTS),
-        ('nratio', C.c_int),
-        ('ratio_num', C.c_int * MAX_ELEMENTS),
-        ('ratio_den', C.c_int * MAX_ELEMENTS),
-        ('ratio_par', C.c_int * MAX_ELEMENTS),
-        ('nhybrid', C.c_int),
-        ('hybrid_species', C.c_int * MAX_HYBRID),
-        ('hybrid_par', C.c_int * MAX_HYBRID),
-        ('max_iterations', C.c_int),
-        ('tolerance', C.c_double),
-        ('gibbs_temps_d', C.c_void_p), ('gibbs_d', C.c_void_p),
-        ('stoich_d', C.c_void_p), ('pressure_d', C.c_void_p),
-    ]
+ChemModelStruct = struct('pb_chem_model')
 
 
 class ChemNetwork:

@@ -20,7 +20,7 @@ import functools
 import numpy as np
 import torch
 
-from ._capi import call, hptr
+from ._capi import call, constant, hptr, struct
 from ._device import dev, _ptr, _stream
 
 # pyratbay/constants/astrophysical_constants.py:67-131 (scipy.constants, CODATA 2018)
@@ -570,50 +570,10 @@ class Continuum:
 # free continuum parameters; the terms are added by the batched interpolation before it stores ec
 # (pb_interp_ec_batch_cont), in the order of Continuum.add.
 # ---------------------------------------------------------------------------------------------
-_MAX_RANK1, _MAX_CIA = 8, 4
-_MAX_ALKALI, _MAX_ALKALI_LINES = 2, 4
-
-
-class ContBatchStruct(C.Structure):
-    """pb_cont_batch of include/pbhip.h."""
-    _fields_ = [
-        ('nrank1', C.c_int),
-        ('rank1_kind', C.c_int * _MAX_RANK1),
-        ('rank1_species', C.c_int * _MAX_RANK1),
-        ('rank1_par', C.c_int * _MAX_RANK1),
-        ('rank1_s0', C.c_double * _MAX_RANK1),
-        ('rank1_l0', C.c_double * _MAX_RANK1),
-        ('rank1_cs_d', C.c_void_p * _MAX_RANK1),
-        ('rank1_pressure_d', C.c_void_p * _MAX_RANK1),
-        ('ncia', C.c_int),
-        ('cia_ntemp', C.c_int * _MAX_CIA),
-        ('cia_nspec', C.c_int * _MAX_CIA),
-        ('cia_species', (C.c_int * _MAX_CIA) * _MAX_CIA),
-        ('cia_tab_d', C.c_void_p * _MAX_CIA),
-        ('cia_temps_d', C.c_void_p * _MAX_CIA),
-        ('cia_mask_d', C.c_void_p),
-        ('hminus', C.c_int),
-        ('hm_species', C.c_int * 2),
-        ('hm_sigma_bf_d', C.c_void_p),
-        ('hm_ff_d', C.c_void_p),
-        ('wn_d', C.c_void_p),
-        ('density_d', C.c_void_p),
-        ('ncs', C.c_int),
-        ('pars_d', C.c_void_p),
-        ('npars', C.c_int),
-        ('pars_stride', C.c_int),
-        ('nalkali', C.c_int),
-        ('alkali_nlines', C.c_int * _MAX_ALKALI),
-        ('alkali_wn0', (C.c_double * _MAX_ALKALI_LINES) * _MAX_ALKALI),
-        ('alkali_gf', (C.c_double * _MAX_ALKALI_LINES) * _MAX_ALKALI),
-        ('alkali_detuning', C.c_double * _MAX_ALKALI),
-        ('alkali_mass', C.c_double * _MAX_ALKALI),
-        ('alkali_lpar', C.c_double * _MAX_ALKALI),
-        ('alkali_part_func', C.c_double * _MAX_ALKALI),
-        ('alkali_cutoff', C.c_double * _MAX_ALKALI),
-        ('alkali_pressure_d', C.c_void_p),
-        ('alkali_density_d', C.c_void_p),
-    ]
+_MAX_RANK1, _MAX_CIA = constant('PB_CONT_MAX_RANK1'), constant('PB_CONT_MAX_CIA')
+_MAX_ALKALI, _MAX_ALKALI_LINES = (constant('PB_CONT_MAX_ALKALI'),
+                                  constant('PB_CONT_MAX_ALKALI_LINES'))
+ContBatchStruct = struct('pb_cont_batch')
 
 
 class BatchOperands:
@@ -722,29 +682,9 @@ class BatchOperands:
                                                               nwave, nwalkers))
 
 
-_MAX_CLOUD = 8
-
-
-class CloudTermsStruct(C.Structure):
-    """pb_cloud_terms of include/pbhip.h."""
-    _fields_ = [
-        ('nr', C.c_int),
-        ('cs_d', C.c_void_p * _MAX_CLOUD),
-        ('cs_stride', C.c_int64 * _MAX_CLOUD),
-        ('f_d', C.c_void_p),
-    ]
-
-
-class CloudModelsStruct(C.Structure):
-    """pb_cloud_models of include/pbhip.h."""
-    _fields_ = [
-        ('nr', C.c_int),
-        ('kind', C.c_int * _MAX_CLOUD),
-        ('par', C.c_int * _MAX_CLOUD),
-        ('s0', C.c_double * _MAX_CLOUD),
-        ('l0', C.c_double * _MAX_CLOUD),
-        ('pressure_d', C.c_void_p * _MAX_CLOUD),
-    ]
+_MAX_CLOUD = constant('PB_CLOUD_MAX')
+CloudTermsStruct = struct('pb_cloud_terms')
+CloudModelsStruct = struct('pb_cloud_models')
 
 
 def cloud_terms(cloud_cs, cloud_f):

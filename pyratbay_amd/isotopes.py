@@ -25,22 +25,12 @@ import ctypes as C
 
 import numpy as np
 
+from ._capi import constant, struct
 from .atmosphere import MAX_ISO_FILLERS, MAX_ISO_SLOTS, REJECT_ISOTOPE
 
-KIND_CONST, KIND_FREE, KIND_FILL = 0, 1, 2
-
-
-class IsoModelStruct(C.Structure):
-    """pb_iso_model of include/pbhip.h."""
-    _fields_ = [
-        ('nspec', C.c_int), ('npars', C.c_int), ('nlabelled', C.c_int),
-        ('slot', C.c_int * MAX_ISO_SLOTS),
-        ('kind', C.c_int * MAX_ISO_SLOTS),
-        ('par', C.c_int * MAX_ISO_SLOTS),
-        ('nfill', C.c_int * MAX_ISO_SLOTS),
-        ('fill', (C.c_int * MAX_ISO_FILLERS) * MAX_ISO_SLOTS),
-        ('constant', C.c_double * MAX_ISO_SLOTS),
-    ]
+KIND_CONST, KIND_FREE, KIND_FILL = (constant('PB_ISO_CONST'), constant('PB_ISO_FREE'),
+                                    constant('PB_ISO_FILL'))
+IsoModelStruct = struct('pb_iso_model')
 
 
 def parse(block):

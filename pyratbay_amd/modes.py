@@ -28,9 +28,10 @@ import types
 import numpy as np
 
 from . import nested
+from ._capi import constant
 from .nested import FINISH_CHUNKS, MAX_LIVE, MAX_PARAMS
 
-MAX_KNN = 32                        # PB_MODES_MAX_KNN: a row's running list of nearest rows
+MAX_KNN = constant('PB_MODES_MAX_KNN')      # a row's running list of nearest rows
 
 
 def default_min_mode(nfree):

@@ -42,12 +42,13 @@ import types
 
 import numpy as np
 
+from ._capi import constant
 from .sampler import (MAX_GENERATIONS, block_uniforms_host, gamma_host, index_host,
                       uniforms_host)
 
 TAG_NESTED_START, TAG_NESTED_STEP, TAG_NESTED_RESAMPLE = 3, 4, 5
-MAX_LIVE = 4096
-MAX_PARAMS = 128                    # PB_RETRIEVAL_MAX_PARAMS
+MAX_LIVE = constant('PB_NESTED_MAX_LIVE')
+MAX_PARAMS = constant('PB_RETRIEVAL_MAX_PARAMS')
 FINISH_CHUNKS = 256                 # the chunks finish sums in: one per thread of its block
 MAX_RESAMPLE = 2**32
 

@@ -47,9 +47,11 @@ import types
 
 import numpy as np
 
-MAX_PARAMS = 128                    # PB_RETRIEVAL_MAX_PARAMS
-MAX_TRIALS = 16                     # PB_LM_MAX_TRIALS
-CHUNK = 64                          # PB_LM_CHUNK: the lanes of cost_host, the staged points
+from ._capi import constant
+
+MAX_PARAMS = constant('PB_RETRIEVAL_MAX_PARAMS')
+MAX_TRIALS = constant('PB_LM_MAX_TRIALS')
+CHUNK = constant('PB_LM_CHUNK')     # the lanes of cost_host, the staged points
 RUNNING, GTOL, FTOL, XTOL, STALL, MAXIT = range(6)
 STATUS_NAMES = ('RUNNING', 'GTOL', 'FTOL', 'XTOL', 'STALL', 'MAXIT')
 DEFAULTS = dict(fd_step=1e-4, ntrial=4, nu=10.0, lam0=1e-3, gtol=1e-8, ftol=1e-10, xtol=1e-10,

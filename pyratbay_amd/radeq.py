@@ -187,36 +187,8 @@ def atmosphere_host(temp, pressure, vmr, mol_mass, radius_model=None, gravity=No
 # ---------------------------------------------------------------------------------------------
 # The device forms
 # ---------------------------------------------------------------------------------------------
-class RadeqStruct(C.Structure):
-    """pb_radeq of include/pbhip.h."""
-    _fields_ = [
-        ('nlayers', C.c_int), ('nwalkers', C.c_int), ('nparts', C.c_int), ('nrows', C.c_int),
-        ('tmin', C.c_double), ('tmax', C.c_double),
-        ('parts_d', C.c_void_p), ('dpress_d', C.c_void_p),
-        ('temps_d', C.c_void_p), ('temp_d', C.c_void_p),
-        ('dt_scale_d', C.c_void_p), ('signs_d', C.c_void_p), ('iter_d', C.c_void_p),
-        ('q_up_d', C.c_void_p), ('q_down_d', C.c_void_p),
-        ('wobble_d', C.c_void_p), ('sigma_d', C.c_void_p),
-        ('pressure_d', C.c_void_p), ('lnp_d', C.c_void_p),
-        ('vmr_d', C.c_void_p), ('vmr_stride', C.c_int64), ('nspecies', C.c_int),
-        ('mm_d', C.c_void_p), ('mm_stride', C.c_int),
-        ('ntab', C.c_int), ('ncont', C.c_int),
-        ('tab_map_d', C.c_void_p), ('cont_map_d', C.c_void_p),
-        ('dens_d', C.c_void_p), ('cdens_d', C.c_void_p),
-        ('rmodel', C.c_int), ('has_ref', C.c_int),
-        ('mplanet', C.c_double), ('gplanet', C.c_double), ('p0', C.c_double), ('r0', C.c_double),
-        ('radius_d', C.c_void_p), ('intervals_d', C.c_void_p),
-    ]
-
-
-class ConvectionStruct(C.Structure):
-    """pb_radeq_convection of include/pbhip.h."""
-    _fields_ = [
-        ('cp_temps_d', C.c_void_p), ('cp_table_d', C.c_void_p), ('cp_table_stride', C.c_int64),
-        ('ntemps', C.c_int), ('mol_mass_d', C.c_void_p), ('conv_dpress_d', C.c_void_p),
-        ('mplanet', C.c_double), ('coeff', C.c_double),
-        ('conv_flux_d', C.c_void_p), ('convective_d', C.c_void_p),
-    ]
+RadeqStruct = _capi.struct('pb_radeq')
+ConvectionStruct = _capi.struct('pb_radeq_convection')
 
 
 def net_parts(nwave):

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import table as _table
-from ._capi import call
+from ._capi import call, constant
 from ._device import _ptr, _stream, dev
 from .bands import HiresData
 from .continuum import CCSgray, Lecavelier
@@ -40,7 +40,7 @@ from .continuum import CCSgray, Lecavelier
 RUNITS = {'rjup': 7.1492e9, 'rearth': 6.3781e8, 'km': 1.0e5, 'm': 1.0e2, 'cm': 1.0}
 MASS_UNITS = {'mjup': 1.8982e30, 'mearth': 5.9724e27, 'kg': 1.0e3, 'gram': 1.0}
 
-MAX_PARAMS, MAX_DESTS = 128, 16
+MAX_PARAMS, MAX_DESTS = constant('PB_RETRIEVAL_MAX_PARAMS'), constant('PB_RETRIEVAL_MAX_DESTS')
 SOLO_PARAMS = ['log_p_ref', 'R_planet', 'M_planet', 'rv_shift', 'f_patchy', 'T_eff',
                'f_dilution']
 _CONT_PNAMES = {Lecavelier: ['log_k_ray', 'alpha_ray'],

@@ -41,7 +41,7 @@ def test_header_symbols_exported():
         # the measured dead ends are not in the product library
         for name in declared_symbols(experiments=True):
             assert not hasattr(lib, name), f'{name}: an experiment exported by libpbhip.so'
-    assert sorted(_capi._EXP_PROTOS) == declared_symbols(experiments=True)
+    assert _capi.experiment_names() == declared_symbols(experiments=True)
 
 
 def test_version_and_error_channel():
