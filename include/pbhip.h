@@ -449,7 +449,10 @@ int pb_internal_flux(double *f_int_d, const double *wn_d, double tint, int nwave
 /* ---- Radiative equilibrium (Pyrat.radiative_equilibrium, pyrat/pyrat_obj.py:559-646 ->
  * spectrum/radiative_transfer.py:141-272) for a batch of profiles, at fixed volume mixing ratios:
  * pb_radeq.hip.  One iteration is pb_interp_ec_batch[_cont], pb_two_stream_net_batch and
- * pb_radeq_update, or with convection pb_radeq_update_convective; nothing is read back.
+ * pb_radeq_update, or with convection pb_radeq_update_convective; nothing is read back.  With the
+ * equilibrium chemistry of every iteration (pb_radeq_equilibrium, further down) an iteration is
+ * five launches: the same two, the update with temps_only, pb_radeq_equilibrium at the new
+ * temperatures, and pb_radeq_update(init_only = 1) for the atmosphere of the new VMRs.
  *
  * pb_two_stream_net_batch = pb_two_stream_batch (same arguments, same bits in flux_d, ec_d
  * DESTROYED) that also integrates flux_up and flux_down of EVERY layer over wavenumber with the
@@ -508,6 +511,11 @@ typedef struct pb_radeq {
     double p0, r0;                 /* bar within the pressure grid (the caller's check), cm */
     double *radius_d;              /* [nwalkers, nlayers] */
     double *intervals_d;           /* [nwalkers, nlayers - 1] radius[i] - radius[i + 1] */
+    int temps_only;                /* != 0 (and init_only == 0): the update ends behind the new
+                                      temperatures (and the convective half); dens_d, cdens_d,
+                                      radius_d and intervals_d are not touched -- the caller forms
+                                      them with init_only = 1 once vmr_d and mm_d are those of the
+                                      new temperatures (pb_radeq_equilibrium) */
 } pb_radeq;
 
 /* One update of every profile (radiative_transfer.py:207-237, convection=False), one workgroup per
@@ -1408,6 +1416,38 @@ typedef struct pb_chem_model {
 } pb_chem_model;
 int pb_equilibrium_vmr(const pb_chem_model *model, const double *temps_d, const double *params_d,
                        int nwalkers, double *vmr_d, int32_t *status_d, void *stream);
+/* The equilibrium inside the radiative-equilibrium loop (RadiativeEquilibrium(chemistry=...), the
+ * reference's chem_model.thermochemical_equilibrium(temp) at the top of every iteration,
+ * spectrum/radiative_transfer.py:202-203): pb_equilibrium_vmr's solver on temps_d[nw][L] with the
+ * iterate of every cell carried from launch to launch, and the mean molecular mass.  Every pointer
+ * is device memory. */
+typedef struct pb_radeq_chem {
+    double *ln_ni_d;                    /* [nw][L][S] the iterate ln n_i, carried */
+    double *ln_n_d;                     /* [nw][L] its ln n, carried */
+    double *vmr_d;                      /* [nw][L][S] out */
+    double *mm_d;                       /* [nw][L] out: sum_i vmr_i mol_mass_i (xor butterfly over
+                                           the 64 lanes, lanes past S adding 0) */
+    const double *mol_mass_d;           /* [S] g mol-1 */
+    int32_t *status_d;                  /* [nw][L] out: iteration count or PB_CHEM_* */
+    int32_t *failures_d;                /* [nw][L] + 1 for every launch that left the cell with a
+                                           negative status (the caller zeroes it) */
+    double tol_all;                     /* > 0: a warm solve has converged once max_i |dln n_i|
+                                           is below it (and the cold test holds) */
+} pb_radeq_chem;
+/* warm == 0: every cell from the cold start with the test of pb_equilibrium_vmr; vmr_d and
+ * status_d are bit for bit its output; the converged iterate is stored.  warm != 0: a cell starts
+ * from its stored iterate and has converged when that test holds AND |dln n_i| < tol_all for every
+ * species (the test alone weighs a step by n_i and passes trace species that are still a factor
+ * off after one step from a neighbouring solution); a stored iterate that is not finite, or
+ * max_iterations without convergence, and the cell is solved from the cold start in the same
+ * launch, its output then bit for bit the cold one.  status: the iteration count of the solve that
+ * converged.  A cell that converges neither way, or whose temperature or abundances are refused
+ * (PB_CHEM_*), keeps vmr_d, mm_d and its iterate AS THEY WERE (unlike pb_equilibrium_vmr, which
+ * writes zeros: zeros would empty a layer of the next evaluation), gets the negative status and
+ * + 1 in failures_d.  model->nhybrid must be 0.  No LDS, no barrier, no atomic. */
+int pb_radeq_equilibrium(const pb_chem_model *model, const double *temps_d,
+                         const double *params_d, int nwalkers, int warm,
+                         const pb_radeq_chem *state, void *stream);
 int pb_walker_temperature(const pb_atm_model *model, const double *params_d, int nwalkers,
                           double *temps_d, void *stream);
 int pb_walker_atmosphere_chem(const pb_atm_model *model, const double *params_d, int nwalkers,

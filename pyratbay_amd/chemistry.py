@@ -24,8 +24,12 @@ gas phase only) on ln n_i and ln n, from the same cold start in every cell:
 The iterate is carried as ln n_i (n_i = exp(ln n_i) may underflow to 0 and then adds 0 to every
 sum); the ratio in l2 is therefore read from the logarithms, -(ln n_i - ln n).
 
-Out of scope: condensates, ions, networks above 64 species, re-equilibrating inside
-radiative_equilibrium (profiles/chemistry.md).
+Inside the radiative-equilibrium loop (radeq.RadiativeEquilibrium(chemistry=...)) a cell's
+temperature moves by little between two solves, so CarriedEquilibrium (pb_radeq_equilibrium) starts
+from the iterate of the previous one; equilibrium_host(start=...) is its host form and TOL_ALL the
+extra convergence test a carried start needs.
+
+Out of scope: condensates, ions, networks above 64 species (profiles/chemistry.md).
 """
 import ctypes as C
 
@@ -54,6 +58,12 @@ STATUS_NAMES = {STATUS_REJECTED: 'temperature <= 0',
                 STATUS_TEMPERATURE: 'temperature outside the Gibbs table',
                 STATUS_RATIO: 'an element ratio <= 0 or a non-finite abundance',
                 STATUS_NOT_CONVERGED: 'not converged'}
+# max_i |dln n_i| below which a solve from a carried iterate has converged.  The test above weighs
+# a step by n_i, so from a neighbouring solution it can pass after ONE step, with the trace species
+# still off by the first-order error of the major ones (a factor 2.3 measured); bounding every
+# species' own step removes that.  1e-6 and 1e-11 give the same result
+# (profiles/radeq_chemistry.md).
+TOL_ALL = 1.0e-9
 _MINOR = 1.0e-8               # n_i / n at and below which a species is a minor one
 _LN_MINOR = 9.2103404         # RP-1311 eq. 3.2: -ln(1e-4)
 
@@ -205,12 +215,21 @@ class ChemNetwork:
         return np.stack([np.interp(temp, self.gibbs_temps, self.gibbs_over_RT[:, i])
                          for i in range(self.nspecies)], axis=1)
 
-    def equilibrium_host(self, temp, pressure, b, tolerance=TOLERANCE):
+    def equilibrium_host(self, temp, pressure, b, tolerance=TOLERANCE, start=None,
+                         tol_all=TOL_ALL):
         """temp[L] (K), pressure[L] (bar), b[E] (element_abundances_host; None: a rejected walker)
         -> vmr[L, S], iterations[L], status[L].  status is the iteration count of a converged cell
         or a negative STATUS_*; a cell with a negative status has zeros in vmr and iterated
         nothing (STATUS_NOT_CONVERGED: MAX_ITERATIONS).  Every cell is solved from the same cold
-        start n_i = 0.1 / S, n = 0.1, so it depends on nothing but its own inputs."""
+        start n_i = 0.1 / S, n = 0.1, so it depends on nothing but its own inputs.
+
+        start: the host form of pb_radeq_equilibrium, which also returns the iterate, a fourth
+        element (ln_ni[L, S], ln_n[L]).  'cold': as above.  (ln_ni[L, S], ln_n[L]), the iterate an
+        earlier call returned: a cell starts from it and has converged when the test above holds
+        AND max_i |dln n_i| < tol_all (module docstring); a cell whose start is not finite, or that
+        does not converge from it, is solved from the cold start, with the cold result's bits;
+        iterations and status then count the cold solve.  A cell with a negative status returns
+        its start unchanged (the cold start under 'cold')."""
         temp = np.atleast_1d(np.asarray(temp, float))
         pressure = np.atleast_1d(np.asarray(pressure, float))
         L, S, E = len(temp), self.nspecies, self.nelements
@@ -232,21 +251,59 @@ class ChemNetwork:
         outside = ~((temp >= self.gibbs_temps[0]) & (temp <= self.gibbs_temps[-1]))
         status[(status == 0) & outside] = STATUS_TEMPERATURE
         live = np.where(status == 0)[0]
+        if start is None:
+            if live.size:
+                v, it, ok = self._newton(self.gibbs_at(temp[live]), np.log(pressure[live]), b,
+                                         tolerance)
+                vmr[live] = np.where(ok[:, None], v, 0.0)
+                iterations[live] = it
+                status[live] = np.where(ok, it, STATUS_NOT_CONVERGED)
+            return vmr, iterations, status
+        if isinstance(start, str):
+            if start != 'cold':
+                raise ValueError(f"start {start!r}: 'cold' or (ln_ni[L, S], ln_n[L])")
+            ln_ni, ln_n = self._cold_start(L)
+            warm = np.zeros(L, bool)
+        else:
+            ln_ni, ln_n = (np.array(v, float) for v in start)
+            if ln_ni.shape != (L, S) or ln_n.shape != (L,):
+                raise ValueError(f'start must have shapes {(L, S)} and {(L,)}, got {ln_ni.shape} '
+                                 f'and {ln_n.shape}')
+            warm = np.all(np.isfinite(ln_ni), axis=1) & np.isfinite(ln_n)
         if live.size:
-            v, it, ok = self._newton(self.gibbs_at(temp[live]), np.log(pressure[live]), b,
-                                     tolerance)
-            vmr[live] = np.where(ok[:, None], v, 0.0)
+            g, lnp = self.gibbs_at(temp[live]), np.log(pressure[live])
+            ok = np.zeros(len(live), bool)
+            it = np.zeros(len(live), np.int32)
+            v = np.zeros((len(live), S))
+            li, ln = ln_ni[live].copy(), ln_n[live].copy()
+            first = np.where(warm[live])[0]
+            if first.size:
+                v[first], it[first], ok[first], li[first], ln[first] = self._newton(
+                    g[first], lnp[first], b, tolerance, (li[first], ln[first]), tol_all)
+            again = np.where(~ok)[0]
+            if again.size:
+                v[again], it[again], ok[again], li[again], ln[again] = self._newton(
+                    g[again], lnp[again], b, tolerance, self._cold_start(again.size), None)
+            good = live[ok]
+            vmr[good], ln_ni[good], ln_n[good] = v[ok], li[ok], ln[ok]
             iterations[live] = it
             status[live] = np.where(ok, it, STATUS_NOT_CONVERGED)
-        return vmr, iterations, status
+        return vmr, iterations, status, (ln_ni, ln_n)
 
-    def _newton(self, g, lnp, b, tolerance):
+    def _cold_start(self, c):
+        """(ln_ni[c, S], ln_n[c]) every cell starts from: n_i = 0.1 / S, n = 0.1."""
+        return np.full((c, self.nspecies), np.log(0.1 / self.nspecies)), np.full(c, np.log(0.1))
+
+    def _newton(self, g, lnp, b, tolerance, start=None, tol_all=None):
         """The iteration of the module docstring on c cells at once (each on its own; a converged
-        cell is left alone): g[c, S], lnp[c] -> vmr[c, S], iterations[c], converged[c]."""
+        cell is left alone): g[c, S], lnp[c] -> vmr[c, S], iterations[c], converged[c].  start
+        (ln_ni[c, S], ln_n[c]): from that iterate instead of the cold start, and the iterate is
+        returned too (ln_ni, ln_n behind the three); tol_all: converged only when also
+        max_i |dln n_i| < tol_all."""
         a = self.stoich.astype(float)
         c, S, E = len(lnp), self.nspecies, self.nelements
-        ln_ni = np.full((c, S), np.log(0.1 / S))
-        ln_n = np.full(c, np.log(0.1))
+        ln_ni, ln_n = self._cold_start(c) if start is None else \
+            (np.array(start[0], float), np.array(start[1], float))
         iterations = np.zeros(c, np.int32)
         converged = np.zeros(c, bool)
         with np.errstate(all='ignore'):
@@ -284,10 +341,14 @@ class ChemNetwork:
                 iterations[idx] = it
                 small = np.all((ni * np.abs(dln_ni)) / sn[:, None] < tolerance, axis=1)
                 done = (lam == 1.0) & small & (np.abs(dln_n) < tolerance)
+                if tol_all is not None:
+                    done &= np.all(np.abs(dln_ni) < tol_all, axis=1)
                 converged[idx] = done
             ni = np.exp(ln_ni)
             vmr = ni / ni.sum(axis=1)[:, None]
-        return vmr, iterations, converged
+        if start is None:
+            return vmr, iterations, converged
+        return vmr, iterations, converged, ln_ni, ln_n
 
     def hybrid_host(self, vmr, species, value):
         """The column of a free log10(VMR) on top of the equilibrium vmr[L, S] (the reference's
@@ -382,3 +443,64 @@ def equilibrium_vmr(net, temps, pressure, params=None, par_metal=-1, scales=(), 
          None if params is None else params.data_ptr(), nw, vmr.data_ptr(), status.data_ptr(),
          torch.cuda.current_stream().cuda_stream)
     return vmr, status
+
+
+RadeqChemStruct = struct('pb_radeq_chem')
+
+
+class CarriedEquilibrium:
+    """The buffers of pb_radeq_equilibrium for nw profiles of L layers on pressure_d[L] (bar): the
+    carried iterate (ln_ni, ln_n), the outputs vmr[nw, L, S], mm[nw, L], status[nw, L] and the
+    failure counts failures[nw, L] (zeroed here), device tensors all.  params[nw, npar] (or None)
+    and the columns par_metal, scales, ratios as in equilibrium_vmr; hybrid models are refused
+    (the carried iterate is that of the equilibrium alone)."""
+
+    def __init__(self, net, nw, pressure_d, mol_mass, params=None, par_metal=-1, scales=(),
+                 ratios=(), hybrids=(), tol_all=TOL_ALL):
+        import torch
+        from ._device import dev
+        if len(hybrids):
+            raise ValueError(f'{len(hybrids)} hybrid models: pb_radeq_equilibrium carries the '
+                             'iterate of the equilibrium alone and takes none')
+        L, S = pressure_d.shape[0], net.nspecies
+        mol_mass = np.asarray(mol_mass, float)
+        if mol_mass.shape != (S,):
+            raise ValueError(f'mol_mass must have shape ({S},), got {mol_mass.shape}')
+        if not tol_all > 0.0:
+            raise ValueError(f'tol_all = {tol_all}: must be > 0')
+        npar = 0
+        if params is not None:
+            if not isinstance(params, torch.Tensor) or params.dtype != torch.float64 or \
+                    params.dim() != 2 or params.shape[0] != nw or not params.is_cuda or \
+                    not params.is_contiguous():
+                raise ValueError('params must be a contiguous float64 device tensor of shape '
+                                 f'({nw}, npar)')
+            npar = params.shape[1]
+        self.net, self.nw, self.params, self.pressure = net, nw, params, pressure_d
+        self.model = net.bound_struct(pressure_d, npar, par_metal=par_metal, scales=scales,
+                                      ratios=ratios)
+
+        def new(*shape, dtype=torch.float64, fill=float('nan')):
+            return torch.full(shape, fill, dtype=dtype, device=pressure_d.device)
+        self.ln_ni, self.ln_n = new(nw, L, S), new(nw, L)
+        self.vmr, self.mm = new(nw, L, S), new(nw, L)
+        self.status = new(nw, L, dtype=torch.int32, fill=0)
+        self.failures = new(nw, L, dtype=torch.int32, fill=0)
+        self.mol_mass = dev(mol_mass)
+        self.state = RadeqChemStruct()
+        for name in ('ln_ni', 'ln_n', 'vmr', 'mm', 'mol_mass', 'status', 'failures'):
+            setattr(self.state, name + '_d', getattr(self, name).data_ptr())
+        self.state.tol_all = float(tol_all)
+
+    def solve(self, temps, warm):
+        """One launch at temps[nw, L] (a contiguous float64 device tensor); nothing read back."""
+        import torch
+        from ._capi import call
+        if not isinstance(temps, torch.Tensor) or temps.dtype != torch.float64 or \
+                tuple(temps.shape) != (self.nw, self.pressure.shape[0]) or not temps.is_cuda or \
+                not temps.is_contiguous():
+            raise ValueError('temps must be a contiguous float64 device tensor of shape '
+                             f'{(self.nw, self.pressure.shape[0])}')
+        call('pb_radeq_equilibrium', C.byref(self.model), temps.data_ptr(),
+             None if self.params is None else self.params.data_ptr(), self.nw, int(bool(warm)),
+             C.byref(self.state), torch.cuda.current_stream().cuda_stream)

@@ -9,6 +9,10 @@
 // that the matrix lives in compile-time-indexed registers (a runtime-indexed register array would go
 // to scratch); the pivot row is found by compare-and-swap down the column for the same reason.
 // Everything in binary64; the build's -ffp-contract=off keeps products and sums apart.
+//
+// pb_radeq_equilibrium is the same solver inside the radiative-equilibrium loop (pb_radeq.hip),
+// where a cell's temperature moves by little between two launches: it starts from the iterate the
+// previous launch left and also writes the mean molecular mass (k_radeq_equilibrium below).
 #include "pb_common.h"
 
 namespace {
@@ -108,28 +112,19 @@ __device__ inline void gauss_solve(double (&A)[N][N], double (&r)[N])
     }
 }
 
-template <int E>
-__global__ __launch_bounds__(kWave * kCellsPerBlock) void k_equilibrium_vmr(ChemArgs a)
-{
-    constexpr int N = E + 1;
-    const pb_chem_model &m = a.m;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t cell = (int64_t)blockIdx.x * kCellsPerBlock + (threadIdx.x >> 6);
-    if (cell >= a.ncells)                      // a whole wavefront: the kernel has no barrier
-        return;
-    const int S = m.nspecies, L = m.nlayers;
-    const int64_t w = cell / L;
-    const int l = (int)(cell - w * L);
-    const bool live = lane < S;
-    const double *par = a.params + w * m.npar;   // dereferenced only at a column >= 0 (the check)
-    const double t = a.temps[cell];
+// The two kernels below are made of the same two statements, each written once: the status of a
+// cell before its iteration with its elemental abundances, and one Newton step.
 
+// 0, or the PB_CHEM_* status of a cell that is not iterated; b[E] (zeros on entry): the elemental
+// abundances of the walker whose parameters are par (ChemNetwork.element_abundances_host, the same
+// statements)
+template <int E>
+__device__ __forceinline__ int cell_inputs(const pb_chem_model &m, const double *par, double t,
+                                           double (&b)[E])
+{
     int status = 0;
     if (!(t > 0.0))
         status = PB_CHEM_REJECTED;
-
-    // ---- elemental abundances (ChemNetwork.element_abundances_host, the same statements)
-    double b[E] = {};
     if (status == 0) {
         double dex[E];
         const double metal = m.par_metal >= 0 ? par[m.par_metal] : 0.0;
@@ -175,6 +170,83 @@ __global__ __launch_bounds__(kWave * kCellsPerBlock) void k_equilibrium_vmr(Chem
     }
     if (status == 0 && !(t >= m.gibbs_temps_d[0] && t <= m.gibbs_temps_d[m.ntemps - 1]))
         status = PB_CHEM_TEMPERATURE;
+    return status;
+}
+
+// One iteration on this lane's ln_ni and the cell's ln_n, both updated; returns the convergence
+// test of pb_equilibrium_vmr (a full step, weighed by n_i).  dln_ni: this lane's undamped step
+// (0 in a lane without a species), which that test does not bound for a trace species.
+template <int E>
+__device__ __forceinline__ bool newton_step(const pb_chem_model &m, bool live,
+                                            const double (&stoich)[E], const double (&b)[E],
+                                            double g, double lnp, double &ln_ni, double &ln_n,
+                                            double &dln_ni)
+{
+    constexpr int N = E + 1;
+    const double ni = live ? exp(ln_ni) : 0.0;
+    const double n = exp(ln_n);
+    const double mu = live ? ((g + ln_ni) - ln_n) + lnp : 0.0;
+    double an[E];
+#pragma unroll
+    for (int k = 0; k < E; k++)
+        an[k] = stoich[k] * ni;
+    double A[N][N], r[N];
+#pragma unroll
+    for (int k = 0; k < E; k++) {
+#pragma unroll
+        for (int j = k; j < E; j++) {
+            const double s = wave_sum(stoich[k] * an[j]);
+            A[k][j] = s;
+            A[j][k] = s;
+        }
+        const double col = wave_sum(an[k]);
+        A[k][E] = col;
+        A[E][k] = col;
+        r[k] = (b[k] - col) + wave_sum(an[k] * mu);
+    }
+    const double sn = wave_sum(ni);
+    A[E][E] = sn - n;
+    r[E] = (n - sn) + wave_sum(ni * mu);
+    gauss_solve<N>(A, r);
+    const double dln_n = r[E];
+    double api = 0.0;
+#pragma unroll
+    for (int j = 0; j < E; j++)
+        api += stoich[j] * r[j];
+    dln_ni = live ? (-mu + dln_n) + api : 0.0;
+
+    // ---- damping (RP-1311 eqs. 3.1-3.3)
+    const bool major = live && ni / n > kMinor;
+    const double step = wave_max(major ? fabs(dln_ni) : 0.0);
+    const double l1 = 2.0 / fmax(5.0 * fabs(dln_n), step);
+    const bool minor = live && !major && dln_ni >= 0.0;
+    const double q = minor ? fabs((-(ln_ni - ln_n) - kLnMinor) / (dln_ni - dln_n)) : INFINITY;
+    const double l2 = wave_min(q);
+    const double lambda = fmin(1.0, fmin(l1, l2));
+    ln_ni += lambda * dln_ni;
+    ln_n += lambda * dln_n;
+    // n_i |dln n_i| / sum n < tolerance in every lane (false on NaN, like the host's)
+    const bool open = live && !((ni * fabs(dln_ni)) / sn < m.tolerance);
+    return lambda == 1.0 && !__any(open) && fabs(dln_n) < m.tolerance;
+}
+
+template <int E>
+__global__ __launch_bounds__(kWave * kCellsPerBlock) void k_equilibrium_vmr(ChemArgs a)
+{
+    const pb_chem_model &m = a.m;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t cell = (int64_t)blockIdx.x * kCellsPerBlock + (threadIdx.x >> 6);
+    if (cell >= a.ncells)                      // a whole wavefront: the kernel has no barrier
+        return;
+    const int S = m.nspecies, L = m.nlayers;
+    const int64_t w = cell / L;
+    const int l = (int)(cell - w * L);
+    const bool live = lane < S;
+    const double *par = a.params + w * m.npar;   // dereferenced only at a column >= 0 (the check)
+    const double t = a.temps[cell];
+
+    double b[E] = {};
+    int status = cell_inputs<E>(m, par, t, b);
 
     double x = 0.0;                            // this lane's VMR
     double stoich[E];
@@ -191,53 +263,9 @@ __global__ __launch_bounds__(kWave * kCellsPerBlock) void k_equilibrium_vmr(Chem
         int iterations = 0;
         bool converged = false;
         for (int it = 1; it <= m.max_iterations && !converged; it++) {
-            const double ni = live ? exp(ln_ni) : 0.0;
-            const double n = exp(ln_n);
-            const double mu = live ? ((g + ln_ni) - ln_n) + lnp : 0.0;
-            double an[E];
-#pragma unroll
-            for (int k = 0; k < E; k++)
-                an[k] = stoich[k] * ni;
-            double A[N][N], r[N];
-#pragma unroll
-            for (int k = 0; k < E; k++) {
-#pragma unroll
-                for (int j = k; j < E; j++) {
-                    const double s = wave_sum(stoich[k] * an[j]);
-                    A[k][j] = s;
-                    A[j][k] = s;
-                }
-                const double col = wave_sum(an[k]);
-                A[k][E] = col;
-                A[E][k] = col;
-                r[k] = (b[k] - col) + wave_sum(an[k] * mu);
-            }
-            const double sn = wave_sum(ni);
-            A[E][E] = sn - n;
-            r[E] = (n - sn) + wave_sum(ni * mu);
-            gauss_solve<N>(A, r);
-            const double dln_n = r[E];
-            double api = 0.0;
-#pragma unroll
-            for (int j = 0; j < E; j++)
-                api += stoich[j] * r[j];
-            const double dln_ni = live ? (-mu + dln_n) + api : 0.0;
-
-            // ---- damping (RP-1311 eqs. 3.1-3.3)
-            const bool major = live && ni / n > kMinor;
-            const double step = wave_max(major ? fabs(dln_ni) : 0.0);
-            const double l1 = 2.0 / fmax(5.0 * fabs(dln_n), step);
-            const bool minor = live && !major && dln_ni >= 0.0;
-            const double q = minor ? fabs((-(ln_ni - ln_n) - kLnMinor) / (dln_ni - dln_n))
-                                   : INFINITY;
-            const double l2 = wave_min(q);
-            const double lambda = fmin(1.0, fmin(l1, l2));
-            ln_ni += lambda * dln_ni;
-            ln_n += lambda * dln_n;
+            double dln_ni;
+            converged = newton_step<E>(m, live, stoich, b, g, lnp, ln_ni, ln_n, dln_ni);
             iterations = it;
-            // n_i |dln n_i| / sum n < tolerance in every lane (false on NaN, like the host's)
-            const bool open = live && !((ni * fabs(dln_ni)) / sn < m.tolerance);
-            converged = lambda == 1.0 && !__any(open) && fabs(dln_n) < m.tolerance;
         }
         if (converged) {
             const double ni = live ? exp(ln_ni) : 0.0;
@@ -284,48 +312,149 @@ __global__ __launch_bounds__(kWave * kCellsPerBlock) void k_equilibrium_vmr(Chem
         a.status[cell] = status;
 }
 
-int chem_check(const pb_chem_model *m)
+// ------------------------------------------------------- pb_radeq_equilibrium: a carried iterate
+
+struct CarriedArgs {
+    pb_chem_model m;
+    pb_radeq_chem c;
+    const double *temps, *params;
+    int64_t ncells;
+    int warm;
+};
+
+// k_equilibrium_vmr (the same layout, no hybrid models) inside the radiative-equilibrium loop: the
+// iterate of every cell is kept in c.ln_ni_d, c.ln_n_d from launch to launch.  warm == 0: the cold
+// start and the test of k_equilibrium_vmr, hence its bits.  warm != 0: from the stored iterate,
+// converged when that test holds AND |dln n_i| < tol_all in every lane with a species (the test
+// alone passes a trace species after one step from a converged neighbour state; the step of a
+// trace species then still carries the first-order error of the major ones); a stored iterate
+// that is not finite, or max_iterations without convergence, and the cell is solved from the cold
+// start as with warm == 0.  Every branch on these is uniform over the wavefront: the values come
+// out of butterflies and ballots.  A cell that ends with a negative status leaves vmr_d, mm_d and
+// its iterate as they were and counts in failures_d, which only its own lane 0 writes.
+template <int E>
+__global__ __launch_bounds__(kWave * kCellsPerBlock) void k_radeq_equilibrium(CarriedArgs a)
 {
-    PB_REQUIRE(m, "pb_equilibrium_vmr: null model struct");
+    const pb_chem_model &m = a.m;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t cell = (int64_t)blockIdx.x * kCellsPerBlock + (threadIdx.x >> 6);
+    if (cell >= a.ncells)                      // a whole wavefront: the kernel has no barrier
+        return;
+    const int S = m.nspecies, L = m.nlayers;
+    const int64_t w = cell / L;
+    const int l = (int)(cell - w * L);
+    const bool live = lane < S;
+    const double *par = a.params + w * m.npar;   // dereferenced only at a column >= 0 (the check)
+    const double t = a.temps[cell];
+
+    double b[E] = {};
+    int status = cell_inputs<E>(m, par, t, b);
+
+    double x = 0.0;                            // this lane's VMR
+    double ln_ni = 0.0, ln_n = 0.0;
+    double stoich[E];
+#pragma unroll
+    for (int j = 0; j < E; j++)
+        stoich[j] = live ? (double)m.stoich_d[lane * E + j] : 0.0;
+
+    if (status == 0) {
+        const double g = live ? interp_inside(m.gibbs_temps_d, m.gibbs_d + lane, S, m.ntemps, t)
+                              : 0.0;
+        const double lnp = log(m.pressure_d[l]);
+        bool carried = false;
+        if (a.warm) {
+            ln_ni = live ? a.c.ln_ni_d[cell * S + lane] : 0.0;
+            ln_n = a.c.ln_n_d[cell];
+            carried = !__any(!(fabs(ln_ni) <= kDblMax)) && fabs(ln_n) <= kDblMax;
+        }
+        int iterations = 0;
+        bool converged = false;
+        for (;;) {
+            if (!carried) {
+                ln_ni = live ? log(0.1 / (double)S) : 0.0;
+                ln_n = log(0.1);
+            }
+            for (int it = 1; it <= m.max_iterations && !converged; it++) {
+                double dln_ni;
+                converged = newton_step<E>(m, live, stoich, b, g, lnp, ln_ni, ln_n, dln_ni);
+                if (carried && __any(!(fabs(dln_ni) < a.c.tol_all)))
+                    converged = false;
+                iterations = it;
+            }
+            if (converged || !carried)
+                break;
+            carried = false;
+        }
+        if (converged) {
+            const double ni = live ? exp(ln_ni) : 0.0;
+            x = ni / wave_sum(ni);
+            status = iterations;
+        } else {
+            status = PB_CHEM_NOT_CONVERGED;
+        }
+    }
+
+    // ---- outputs, each written once; nothing but the status of a cell without a solution
+    if (status > 0) {
+        const double mm = wave_sum(live ? x * a.c.mol_mass_d[lane] : 0.0);
+        if (live) {
+            a.c.vmr_d[cell * S + lane] = x;
+            a.c.ln_ni_d[cell * S + lane] = ln_ni;
+        }
+        if (lane == 0) {
+            a.c.mm_d[cell] = mm;
+            a.c.ln_n_d[cell] = ln_n;
+        }
+    }
+    if (lane == 0) {
+        a.c.status_d[cell] = status;
+        if (status < 0)
+            a.c.failures_d[cell] += 1;
+    }
+}
+
+int chem_check(const pb_chem_model *m, const char *name)
+{
+    PB_REQUIRE(m, "%s: null model struct", name);
     PB_REQUIRE(m->nspecies >= 1 && m->nspecies <= PB_CHEM_MAX_SPECIES,
-               "pb_equilibrium_vmr: 1-%d species, not %d", PB_CHEM_MAX_SPECIES, m->nspecies);
+               "%s: 1-%d species, not %d", name, PB_CHEM_MAX_SPECIES, m->nspecies);
     PB_REQUIRE(m->nelements >= 1 && m->nelements <= PB_CHEM_MAX_ELEMENTS,
-               "pb_equilibrium_vmr: 1-%d elements, not %d", PB_CHEM_MAX_ELEMENTS, m->nelements);
-    PB_REQUIRE(m->ntemps >= 1, "pb_equilibrium_vmr: %d Gibbs temperatures", m->ntemps);
-    PB_REQUIRE(m->nlayers >= 1, "pb_equilibrium_vmr: %d layers", m->nlayers);
-    PB_REQUIRE(m->npar >= 0, "pb_equilibrium_vmr: %d parameters", m->npar);
+               "%s: 1-%d elements, not %d", name, PB_CHEM_MAX_ELEMENTS, m->nelements);
+    PB_REQUIRE(m->ntemps >= 1, "%s: %d Gibbs temperatures", name, m->ntemps);
+    PB_REQUIRE(m->nlayers >= 1, "%s: %d layers", name, m->nlayers);
+    PB_REQUIRE(m->npar >= 0, "%s: %d parameters", name, m->npar);
     PB_REQUIRE(m->ihydrogen >= 0 && m->ihydrogen < m->nelements,
-               "pb_equilibrium_vmr: hydrogen is element %d of %d", m->ihydrogen, m->nelements);
+               "%s: hydrogen is element %d of %d", name, m->ihydrogen, m->nelements);
     PB_REQUIRE(m->par_metal >= -1 && m->par_metal < m->npar,
-               "pb_equilibrium_vmr: [M/H] in column %d of %d", m->par_metal, m->npar);
+               "%s: [M/H] in column %d of %d", name, m->par_metal, m->npar);
     PB_REQUIRE(m->nscale >= 0 && m->nscale <= PB_CHEM_MAX_ELEMENTS,
-               "pb_equilibrium_vmr: at most %d [X/H], not %d", PB_CHEM_MAX_ELEMENTS, m->nscale);
+               "%s: at most %d [X/H], not %d", name, PB_CHEM_MAX_ELEMENTS, m->nscale);
     for (int k = 0; k < m->nscale; k++)
         PB_REQUIRE(m->scale_element[k] >= 0 && m->scale_element[k] < m->nelements &&
                        m->scale_par[k] >= 0 && m->scale_par[k] < m->npar,
-                   "pb_equilibrium_vmr: [X/H] %d: element %d of %d, column %d of %d", k,
+                   "%s: [X/H] %d: element %d of %d, column %d of %d", name, k,
                    m->scale_element[k], m->nelements, m->scale_par[k], m->npar);
     PB_REQUIRE(m->nratio >= 0 && m->nratio <= PB_CHEM_MAX_ELEMENTS,
-               "pb_equilibrium_vmr: at most %d X/Y, not %d", PB_CHEM_MAX_ELEMENTS, m->nratio);
+               "%s: at most %d X/Y, not %d", name, PB_CHEM_MAX_ELEMENTS, m->nratio);
     for (int k = 0; k < m->nratio; k++)
         PB_REQUIRE(m->ratio_num[k] >= 0 && m->ratio_num[k] < m->nelements &&
                        m->ratio_den[k] >= 0 && m->ratio_den[k] < m->nelements &&
                        m->ratio_par[k] >= 0 && m->ratio_par[k] < m->npar,
-                   "pb_equilibrium_vmr: X/Y %d: elements %d and %d of %d, column %d of %d", k,
+                   "%s: X/Y %d: elements %d and %d of %d, column %d of %d", name, k,
                    m->ratio_num[k], m->ratio_den[k], m->nelements, m->ratio_par[k], m->npar);
     PB_REQUIRE(m->nhybrid >= 0 && m->nhybrid <= PB_CHEM_MAX_HYBRID,
-               "pb_equilibrium_vmr: at most %d hybrid models, not %d", PB_CHEM_MAX_HYBRID,
+               "%s: at most %d hybrid models, not %d", name, PB_CHEM_MAX_HYBRID,
                m->nhybrid);
     for (int k = 0; k < m->nhybrid; k++)
         PB_REQUIRE(m->hybrid_species[k] >= 0 && m->hybrid_species[k] < m->nspecies &&
                        m->hybrid_par[k] >= 0 && m->hybrid_par[k] < m->npar,
-                   "pb_equilibrium_vmr: hybrid model %d: species %d of %d, column %d of %d", k,
+                   "%s: hybrid model %d: species %d of %d, column %d of %d", name, k,
                    m->hybrid_species[k], m->nspecies, m->hybrid_par[k], m->npar);
     PB_REQUIRE(m->max_iterations >= 1 && m->max_iterations <= 10000,
-               "pb_equilibrium_vmr: max_iterations %d (1-10000)", m->max_iterations);
-    PB_REQUIRE(m->tolerance > 0.0, "pb_equilibrium_vmr: tolerance %g", m->tolerance);
+               "%s: max_iterations %d (1-10000)", name, m->max_iterations);
+    PB_REQUIRE(m->tolerance > 0.0, "%s: tolerance %g", name, m->tolerance);
     PB_REQUIRE(m->gibbs_temps_d && m->gibbs_d && m->stoich_d && m->pressure_d,
-               "pb_equilibrium_vmr: null model array");
+               "%s: null model array", name);
     return PB_OK;
 }
 
@@ -334,13 +463,58 @@ void launch(const ChemArgs &a, unsigned blocks, hipStream_t stream)
 {
     k_equilibrium_vmr<E><<<blocks, kWave * kCellsPerBlock, 0, stream>>>(a);
 }
+template <int E>
+void launch(const CarriedArgs &a, unsigned blocks, hipStream_t stream)
+{
+    k_radeq_equilibrium<E><<<blocks, kWave * kCellsPerBlock, 0, stream>>>(a);
+}
 
 }  // namespace
+
+int pb_radeq_equilibrium(const pb_chem_model *model, const double *temps_d,
+                         const double *params_d, int nwalkers, int warm,
+                         const pb_radeq_chem *state, void *stream)
+{
+    const int rc = chem_check(model, "pb_radeq_equilibrium");
+    if (rc != PB_OK)
+        return rc;
+    PB_REQUIRE(model->nhybrid == 0, "pb_radeq_equilibrium: %d hybrid models: the carried iterate "
+               "is that of the equilibrium alone", model->nhybrid);
+    PB_REQUIRE(nwalkers >= 0, "pb_radeq_equilibrium: %d walkers", nwalkers);
+    PB_REQUIRE(state, "pb_radeq_equilibrium: null state struct");
+    if (nwalkers == 0)
+        return PB_OK;
+    const pb_radeq_chem &c = *state;
+    PB_REQUIRE(temps_d && c.ln_ni_d && c.ln_n_d && c.vmr_d && c.mm_d && c.mol_mass_d &&
+                   c.status_d && c.failures_d,
+               "pb_radeq_equilibrium: null pointer");
+    PB_REQUIRE(params_d || model->npar == 0, "pb_radeq_equilibrium: null params with %d columns",
+               model->npar);
+    PB_REQUIRE(c.tol_all > 0.0, "pb_radeq_equilibrium: tol_all %g", c.tol_all);
+    const int64_t ncells = (int64_t)nwalkers * model->nlayers;
+    const int64_t blocks = (ncells + kCellsPerBlock - 1) / kCellsPerBlock;
+    PB_REQUIRE(blocks <= 0x7fffffffLL, "pb_radeq_equilibrium: %lld cells are too many for one "
+               "launch", (long long)ncells);
+    CarriedArgs a{*model, c, temps_d, params_d, ncells, warm};
+    hipStream_t s = pb::as_stream(stream);
+    switch (model->nelements) {
+    case 1: launch<1>(a, (unsigned)blocks, s); break;
+    case 2: launch<2>(a, (unsigned)blocks, s); break;
+    case 3: launch<3>(a, (unsigned)blocks, s); break;
+    case 4: launch<4>(a, (unsigned)blocks, s); break;
+    case 5: launch<5>(a, (unsigned)blocks, s); break;
+    case 6: launch<6>(a, (unsigned)blocks, s); break;
+    case 7: launch<7>(a, (unsigned)blocks, s); break;
+    default: launch<8>(a, (unsigned)blocks, s); break;
+    }
+    PB_LAUNCH_CHECK();
+    return PB_OK;
+}
 
 int pb_equilibrium_vmr(const pb_chem_model *model, const double *temps_d, const double *params_d,
                        int nwalkers, double *vmr_d, int32_t *status_d, void *stream)
 {
-    const int rc = chem_check(model);
+    const int rc = chem_check(model, "pb_equilibrium_vmr");
     if (rc != PB_OK)
         return rc;
     PB_REQUIRE(nwalkers >= 0, "pb_equilibrium_vmr: %d walkers", nwalkers);

@@ -28,6 +28,10 @@
 // convects, and where one does the update again from Q_net + conv_flux.  Both halves are ONE
 // function (update_from_flux); the first one of the convective kernel leaves the state it reads
 // -- dt_scale, the sign row of this iteration -- unwritten until the outcome is known.
+//
+// With pb_radeq.temps_only the kernel ends behind the new temperatures: the loop that
+// re-equilibrates the chemistry every iteration (pb_radeq_equilibrium, pb_chemistry.hip) forms the
+// atmosphere in a launch of its own, init_only, once the VMRs are those of the new temperatures.
 #include "pb_atm_profile.h"
 #include "pb_common.h"
 #include "pb_planck.h"
@@ -519,6 +523,10 @@ __global__ __launch_bounds__(kUpdate) void k_radeq_update(pb_radeq a, pb_radeq_c
         update_from_flux(a, w, k, s.q, s, !kConv);
         if (kConv)
             convective_half(a, c, w, k, s);
+        // (the caller re-equilibrates the VMRs at the new temperatures first, then asks for the
+        // atmosphere with init_only)
+        if (a.temps_only)
+            return;
         s_next = s.a;
     } else {
         __syncthreads();

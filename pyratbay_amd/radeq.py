@@ -13,9 +13,23 @@ mixing-length convective flux (spectrum/convection.py:13-67) at the temperatures
 for a profile with a superadiabatic layer, the update again with that flux added to the net flux
 (radiative_transfer.py:239-272).
 
+With RadiativeEquilibrium(chemistry=ChemNetwork) the loop is the reference's radiative-
+thermochemical equilibrium (chem_model.thermochemical_equilibrium(temp) at the top of every
+iteration, radiative_transfer.py:202-203): five launches per iteration, still nothing read back.
+The update runs with pb_radeq.temps_only and stops behind the new temperatures;
+pb_radeq_equilibrium (csrc/pb_chemistry.hip) solves the gas-phase equilibrium of every layer there,
+by default from the iterate the previous iteration left (chemistry_start='previous'), and writes the
+mean mass; pb_radeq_update(init_only=1) forms densities, radius and intervals from them.  The
+convective half reads the VMRs, mean mass and radius of the evaluated profile, as the reference
+does.
+
 Deviations from the reference:
-  * the volume mixing ratios are FIXED (the reference calls chemcat's thermochemical equilibrium
-    every iteration); the mean molecular mass is therefore constant;
+  * without chemistry= the volume mixing ratios are FIXED (the reference calls chemcat's
+    thermochemical equilibrium every iteration); the mean molecular mass is then constant;
+  * with chemistry= the equilibrium is this package's own solver on the caller's table of G°/RT
+    (chemistry.py), not chemcat; a layer whose solve fails (a temperature outside the Gibbs table,
+    no convergence) KEEPS the VMRs and mean mass of the iteration before and counts in
+    .chem_failures -- zeros would silently empty the layer of the next evaluation;
   * the heat capacities of the convective half are np.interp on the caller's table of cp / R per
     species (the reference asks chemcat's chem_model.heat_capacity);
   * in the reference the convective branch's in-place dt_scale[wobble] *= 0.5 followed by the
@@ -246,7 +260,8 @@ def _check(cond, text):
 
 
 class RadiativeEquilibrium:
-    """Radiative-equilibrium iteration of nw profiles at fixed volume mixing ratios.
+    """Radiative-equilibrium iteration of nw profiles at fixed volume mixing ratios, or
+    (chemistry=) at the gas-phase equilibrium of every iteration's temperatures.
 
     spectrum: a TableSpectrum in a two-stream rt_path (its table, grid and Continuum);
     pressure[L] (bar, ascending); vmr[L, S] or [nw, L, S]; mol_mass[S] (g mol-1).
@@ -262,6 +277,17 @@ class RadiativeEquilibrium:
     column of vmr, read by np.interp (the end values outside the table); mixing_length: (alpha,
     beta) of convection.convective_flux.  Both are read only by run(convection=True), which also
     needs mplanet (the gravity is G mplanet / radius**2 whatever the radius model).
+    chemistry: a chemistry.ChemNetwork -- the VMRs of every iteration are its gas-phase equilibrium
+    at that iteration's temperatures.  vmr must then be None, the species are the network's
+    (mol_mass[S] and heat_capacity cover them; table_species and the Continuum's species must be
+    among them), and the default tmin / tmax are also cut to the Gibbs table's range.  metallicity
+    ([M/H]), e_scale ({'C': [C/H]}) and e_ratio ({'C/O': value}) are the abundances by the rule of
+    ChemNetwork.element_abundances_host, each value a scalar or [nw], fixed over a run.
+    chemistry_start: 'previous' (a layer's solve starts from the iterate of the iteration before)
+    or 'cold' (every solve from the cold start; the same VMRs to the solver's convergence).
+    After run(): .vmr[nw, L, S] and .mean_mass[nw, L] of the last row temps[:, -1] (like .radius),
+    .chem_status[nw, L] of the last solve, and .chem_failures[nw, L], the number of solves of the
+    run that failed in that layer -- to be checked after a run: a failed layer keeps its VMRs.
 
     For tests and diagnosis, beyond what the reference's loop leaves behind: run(...,
     diagnostics=True) keeps every iteration's q_up, q_down, dt_scale, wobbling layers and filter
@@ -271,12 +297,33 @@ class RadiativeEquilibrium:
     a Deck or cloud-type models in its Continuum, fewer than 2 layers, shapes that do not match,
     a heat-capacity table that is not finite, not ascending or has cp / R <= 1, and (in run) a
     starting temperature outside [tmin, tmax], or convection=True without heat_capacity, without
-    mplanet > 0, or with a radius that is 0 at the bottom (hydro_g without p0, r0)."""
+    mplanet > 0, or with a radius that is 0 at the bottom (hydro_g without p0, r0).  With
+    chemistry=: a vmr, species other than the network's, a table or continuum species outside
+    the network, an element ratio <= 0 or a non-finite abundance (naming the profile), a
+    chemistry_start other than 'previous' / 'cold', and (in run) a starting temperature outside
+    the Gibbs table."""
 
     def __init__(self, spectrum, pressure, vmr, mol_mass, radius_model=None, gravity=None,
                  mplanet=None, p0=None, r0=None, tint=0.0, flux_top=None, tmin=None, tmax=None,
-                 species=None, table_species=None, heat_capacity=None, mixing_length=(1.5, 0.5)):
+                 species=None, table_species=None, heat_capacity=None, mixing_length=(1.5, 0.5),
+                 chemistry=None, metallicity=None, e_scale=None, e_ratio=None,
+                 chemistry_start='previous'):
         self.model = spectrum
+        self.chemistry = chemistry
+        _check(chemistry_start in ('previous', 'cold'),
+               f"chemistry_start {chemistry_start!r}: 'previous' or 'cold'")
+        self.chemistry_start = chemistry_start
+        if chemistry is None:
+            _check(metallicity is None and not e_scale and not e_ratio,
+                   'metallicity, e_scale and e_ratio are the abundances of chemistry=')
+        else:
+            _check(vmr is None, 'with chemistry= the volume mixing ratios are the equilibrium '
+                   "ones of every iteration: vmr must be None")
+            _check(species is None or [str(s) for s in species] == chemistry.species,
+                   f"with chemistry= the species are the network's ({chemistry.species})")
+            species = chemistry.species
+            _check(table_species is not None, 'with chemistry= table_species must name the '
+                   "table's species among the network's")
         _check(getattr(spectrum, 'rt_path', None) == 'two_stream',
                f"rt_path {getattr(spectrum, 'rt_path_name', getattr(spectrum, 'rt_path', None))!r}: "
                "the net fluxes come from the two-stream geometry ('two_stream', "
@@ -299,10 +346,14 @@ class RadiativeEquilibrium:
                f'{self.pressure.shape}')
         _check(np.all(np.diff(self.pressure) > 0) and self.pressure[0] > 0,
                'pressure must be positive and ascending')
-        self.vmr = np.asarray(vmr, float)
-        _check(self.vmr.ndim in (2, 3) and self.vmr.shape[-2] == L,
-               f'vmr must have shape ({L}, S) or (nw, {L}, S), got {self.vmr.shape}')
-        nsp = self.vmr.shape[-1]
+        if chemistry is None:
+            self.vmr = np.asarray(vmr, float)
+            _check(self.vmr.ndim in (2, 3) and self.vmr.shape[-2] == L,
+                   f'vmr must have shape ({L}, S) or (nw, {L}, S), got {self.vmr.shape}')
+            nsp = self.vmr.shape[-1]
+        else:
+            self.vmr, nsp = None, chemistry.nspecies
+        self.nspecies = nsp
         self.mol_mass = np.asarray(mol_mass, float)
         _check(self.mol_mass.shape == (nsp,), f'mol_mass must have shape ({nsp},), got '
                f'{self.mol_mass.shape}')
@@ -356,7 +407,23 @@ class RadiativeEquilibrium:
             _check(np.all(np.diff(cp_temps) > 0), 'heat_capacity: cp_temps must be ascending')
             _check(np.all(cp_table > 1.0), 'heat_capacity: cp_over_R <= 1 (cv = cp - R <= 0)')
             self.heat_capacity = (cp_temps, cp_table)
-        counts = {'vmr': self.vmr.shape[0] if self.vmr.ndim == 3 else None,
+        # the abundances of the chemistry: per name a scalar or [nw]
+        self.abundances = {}
+        if chemistry is not None:
+            given = [] if metallicity is None else [(('metal',), metallicity)]
+            given += [(('scale', str(k)), v) for k, v in (e_scale or {}).items()]
+            given += [(('ratio', str(k)), v) for k, v in (e_ratio or {}).items()]
+            for key, v in given:
+                v = np.asarray(v, float)
+                _check(v.ndim in (0, 1), f'{key[-1]}: a scalar or [nw], got shape {v.shape}')
+                if key[0] == 'scale':
+                    chemistry.element_index(key[1])
+                elif key[0] == 'ratio':
+                    chemistry.ratio_elements(key[1])
+                self.abundances[key] = v
+        counts = {'vmr': self.vmr.shape[0] if self.vmr is not None and self.vmr.ndim == 3
+                  else None,
+                  **{key[-1]: v.shape[0] for key, v in self.abundances.items() if v.ndim == 1},
                   'tint': self.tint.shape[0] if self.tint.ndim == 1 else None,
                   'flux_top': ftshape[0] if ftshape is not None and len(ftshape) == 2 else None,
                   'heat_capacity': self.heat_capacity[1].shape[0] if self.heat_capacity is not None
@@ -364,9 +431,16 @@ class RadiativeEquilibrium:
         given = {k: v for k, v in counts.items() if v is not None}
         _check(len(set(given.values())) <= 1, f'different numbers of profiles: {given}')
         self.nprofiles = next(iter(given.values())) if given else None     # None: temp0 decides
+        for w in range(self.nprofiles or 1):
+            _check(chemistry is None or self._abundances_host(w) is not None,
+                   f'profile {w}: an element ratio <= 0 or an abundance that is not finite and '
+                   f'positive ({self._abundance_text(w)})')
         lo, hi = float(spectrum.tmin), float(spectrum.tmax)
         for m in ([] if cont is None else cont.cia):
             lo, hi = max(lo, float(m.tmin)), min(hi, float(m.tmax))
+        if chemistry is not None:
+            lo = max(lo, float(chemistry.gibbs_temps[0]))
+            hi = min(hi, float(chemistry.gibbs_temps[-1]))
         self.tmin = lo if tmin is None else float(tmin)
         self.tmax = hi if tmax is None else float(tmax)
         _check(self.tmin < self.tmax, f'tmin = {self.tmin} >= tmax = {self.tmax}')
@@ -375,7 +449,51 @@ class RadiativeEquilibrium:
         self.mixing_length = (float(mixing_length[0]), float(mixing_length[1]))
         self.temps = self.dt_scale = self.q_up = self.q_down = self.spectrum = None
         self.conv_flux = self.convective = None
+        self.mean_mass = self.chem_status = self.chem_failures = None
         self._state = None
+
+    # --------------------------------------------------------------------------- chemistry
+    def _abundance_values(self, w):
+        """(metallicity or None, e_scale, e_ratio) of profile w."""
+        metal, scale, ratio = None, {}, {}
+        for key, v in self.abundances.items():
+            value = float(v[w]) if v.ndim else float(v)
+            if key[0] == 'metal':
+                metal = value
+            else:
+                (scale if key[0] == 'scale' else ratio)[key[1]] = value
+        return metal, scale, ratio
+
+    def _abundances_host(self, w):
+        """b[E] of profile w (ChemNetwork.element_abundances_host), None where it is refused."""
+        return self.chemistry.element_abundances_host(*self._abundance_values(w))
+
+    def _abundance_text(self, w):
+        metal, scale, ratio = self._abundance_values(w)
+        return ', '.join([f'[M/H] = {metal}'] * (metal is not None) +
+                         [f'[{k}/H] = {v}' for k, v in scale.items()] +
+                         [f'{k} = {v}' for k, v in ratio.items()])
+
+    def _carried_equilibrium(self, nw, pressure_d):
+        """The CarriedEquilibrium of nw profiles: one column of params per abundance."""
+        from . import chemistry as ch
+        net = self.chemistry
+        for w in range(nw):
+            _check(self._abundances_host(w) is not None,
+                   f'profile {w}: an element ratio <= 0 or an abundance that is not finite and '
+                   f'positive ({self._abundance_text(w)})')
+        columns = dict(par_metal=-1, scales=[], ratios=[])
+        params = np.empty((nw, len(self.abundances)))
+        for col, (key, v) in enumerate(self.abundances.items()):
+            params[:, col] = v
+            if key[0] == 'metal':
+                columns['par_metal'] = col
+            elif key[0] == 'scale':
+                columns['scales'].append((net.element_index(key[1]), col))
+            else:
+                columns['ratios'].append((*net.ratio_elements(key[1]), col))
+        return ch.CarriedEquilibrium(net, nw, pressure_d, self.mol_mass,
+                                     dev(params) if params.shape[1] else None, **columns)
 
     # ------------------------------------------------------------------------------ set-up
     def _allocate(self, nw):
@@ -391,8 +509,16 @@ class RadiativeEquilibrium:
             return t if fill is None else t.fill_(fill)
         d['pressure'], d['lnp'] = dev(self.pressure), dev(np.log(self.pressure))
         d['dpress'] = dev(log_pressure_steps(self.pressure))
-        d['vmr'] = dev(self.vmr)
-        d['mm'] = dev(np.sum(self.vmr * self.mol_mass, axis=-1))
+        if self.chemistry is None:
+            d['vmr'] = dev(self.vmr)
+            d['mm'] = dev(np.sum(self.vmr * self.mol_mass, axis=-1))
+            per_profile = self.vmr.ndim == 3
+        else:
+            # the VMRs and the mean mass are what pb_radeq_equilibrium writes, per profile
+            d['chem'] = self._carried_equilibrium(nw, d['pressure'])
+            d['vmr'], d['mm'] = d['chem'].vmr, d['chem'].mm
+            d['chem_iterations'] = d['chem'].status
+            per_profile = True
         d['tab_map'] = torch.tensor(self.tab_map, dtype=torch.int32, device='cuda')
         d['cont_map'] = torch.tensor(self.cont_map or [0], dtype=torch.int32, device='cuda')
         d['tw'] = dev(trapezoid_weights(m.wn.cpu().numpy()))
@@ -431,9 +557,10 @@ class RadiativeEquilibrium:
         st.signs_d, st.iter_d = d['signs'].data_ptr(), d['iter'].data_ptr()
         st.q_up_d, st.q_down_d = d['q_up'].data_ptr(), d['q_down'].data_ptr()
         st.pressure_d, st.lnp_d = d['pressure'].data_ptr(), d['lnp'].data_ptr()
-        st.vmr_d, st.nspecies = d['vmr'].data_ptr(), self.vmr.shape[-1]
-        st.vmr_stride = L * self.vmr.shape[-1] if self.vmr.ndim == 3 else 0
-        st.mm_d, st.mm_stride = d['mm'].data_ptr(), L if self.vmr.ndim == 3 else 0
+        st.vmr_d, st.nspecies = d['vmr'].data_ptr(), self.nspecies
+        st.vmr_stride = L * self.nspecies if per_profile else 0
+        st.mm_d, st.mm_stride = d['mm'].data_ptr(), L if per_profile else 0
+        st.temps_only = int(self.chemistry is not None)
         st.ntab, st.ncont = ntab, ncont
         st.tab_map_d = d['tab_map'].data_ptr()
         st.cont_map_d = d['cont_map'].data_ptr() if ncont else None
@@ -481,7 +608,11 @@ class RadiativeEquilibrium:
         flux to the net flux of a profile with a superadiabatic layer and redoes its update.
         Leaves .conv_flux [nw, L] and .convective [nw] (int32: whether the second half ran) of the
         last iteration; with diagnostics, history['conv_flux'] [nw, nsamples, L] and
-        history['convective'] [nw, nsamples]."""
+        history['convective'] [nw, nsamples].
+        With chemistry=: five launches per iteration (module docstring); a continued run keeps the
+        stored iterate, which belongs to the last row.  With diagnostics, history['vmr']
+        [nw, nsamples, L, S] and history['chem_iterations'] [nw, nsamples, L] (int32) hold the
+        VMRs and the status of every iteration's solve, i.e. at the temperatures of row 1 + i."""
         import torch
         L = self.nlayers
         nsamples = int(nsamples)
@@ -517,6 +648,10 @@ class RadiativeEquilibrium:
             _check(np.all(host0 >= self.tmin) and np.all(host0 <= self.tmax),
                    f'temp0 outside the {self.tmin:.1f}-{self.tmax:.1f} K range of the opacities '
                    '(the table and the CIA tables)')
+            if self.chemistry is not None:
+                glo, ghi = self.chemistry.gibbs_temps[[0, -1]]
+                _check(np.all(host0 >= glo) and np.all(host0 <= ghi),
+                       f'temp0 outside the {glo:.1f}-{ghi:.1f} K range of the Gibbs table')
             if self._state is None or self._state['struct'].nwalkers != nw:
                 self._allocate(nw)
             start = torch.as_tensor(np.broadcast_to(host0, (nw, L)).copy(), device='cuda')
@@ -547,6 +682,19 @@ class RadiativeEquilibrium:
             st.wobble_d, st.sigma_d = d['wobble'].data_ptr(), d['sigma'].data_ptr()
         else:
             st.wobble_d = st.sigma_d = None
+        chem = d.get('chem')
+        if chem is not None:
+            warm = self.chemistry_start == 'previous'
+            chem.failures.zero_()
+            if hist is not None:
+                hist['vmr'] = torch.empty((nw, nsamples, L, self.nspecies), dtype=torch.float64,
+                                          device='cuda')
+                hist['chem_iterations'] = torch.empty((nw, nsamples, L), dtype=torch.int32,
+                                                      device='cuda')
+            # the equilibrium of the starting profile, from the cold start; a continued run's
+            # VMRs, mean mass and iterate are those of the last row already, which is its start
+            if not continue_run:
+                chem.solve(d['temp'], warm=False)
         _capi.call('pb_radeq_update', C.byref(st), 1, stream)
         ckw = {}
         if 'ops' in d:
@@ -556,11 +704,15 @@ class RadiativeEquilibrium:
                             **ckw)
             two_stream_net_batch(d['ec'], d['intervals'], m.wn, d['tw'], d['temp'], d['f_int'],
                                  d['flux_top'], out=d['flux'], parts=d['parts'], work=d['work'])
+            # (with chemistry temps_only is set: the update stops behind the new temperatures)
             if convection:
                 _capi.call('pb_radeq_update_convective', C.byref(st), C.byref(d['convection']),
                            stream)
             else:
                 _capi.call('pb_radeq_update', C.byref(st), 0, stream)
+            if chem is not None:
+                chem.solve(d['temp'], warm=warm)
+                _capi.call('pb_radeq_update', C.byref(st), 1, stream)
             if hist is not None:
                 for k in hist:
                     hist[k][:, i].copy_(d[k])
@@ -569,6 +721,9 @@ class RadiativeEquilibrium:
         self.dt_scale, self.q_up, self.q_down = d['dt_scale'], d['q_up'], d['q_down']
         self.spectrum = d['flux']
         self.radius = d['radius']
+        if chem is not None:
+            self.vmr, self.mean_mass = chem.vmr, chem.mm
+            self.chem_status, self.chem_failures = chem.status, chem.failures
         if convection:
             self.conv_flux, self.convective = d['conv_flux'], d['convective']
         return temps

@@ -838,7 +838,8 @@ class TableSpectrum:
 
     def radiative_equilibrium(self, pressure, vmr, mol_mass, **kw):
         """The radiative-equilibrium iteration (runmode = radeq, pyrat_obj.py:559-646) of a batch
-        of profiles on this model's table, grid and Continuum, at fixed volume mixing ratios: a
+        of profiles on this model's table, grid and Continuum, at fixed volume mixing ratios or
+        (vmr=None, chemistry=ChemNetwork) with the equilibrium chemistry of every iteration: a
         pyratbay_amd.radeq.RadiativeEquilibrium (its docstring has the keywords); .run(temp0,
         nsamples) iterates on the device.  Two-stream geometry only; a model with isotope ratios
         is refused (ValueError)."""
