@@ -1380,7 +1380,28 @@ int pb_walker_atmosphere(const pb_atm_model *model, const double *params_d, int 
  * nothing is renormalised.
  * status: the iteration count of a converged cell, or PB_CHEM_*; a cell with a negative status has
  * zeros in vmr_d and (but for PB_CHEM_NOT_CONVERGED) iterated nothing.  params_d may be NULL when
- * npar == 0.  The model struct (a host struct) is checked before any HIP call. */
+ * npar == 0.  The model struct (a host struct) is checked before any HIP call.
+ *
+ * Ions and electrons: charge_d[nspecies] (NULL: a neutral network, the solver above unchanged)
+ * holds a species' charge; the electron is a species with an all-zero stoich row and charge -1.
+ * The charge never enters stoich_d.  The charge balance sum_i q_i n_i = 0 takes one more row of the
+ * system, so nelements + 1 <= PB_CHEM_MAX_ELEMENTS, and the cold solve has three steps:
+ *   1. the neutral species alone, from the cold start of their sub-network (n_i = 0.1 / their
+ *      count): the iteration above on the lanes with charge 0, the others adding 0 to every sum;
+ *   2. every charged species is seeded from the potentials pi of that solve:
+ *      ln n_i = t_i + q_i pi_q, t_i = ln n - g_i - ln p + sum_j a_ij pi_j, pi_q = (LSE- - LSE+) / 2
+ *      with LSE the log-sum-exp of t_i over the species of one sign -- the neutral gas exactly for
+ *      charges +-1 while the ions are trace, and in logarithms, so nothing underflows;
+ *   3. the system of order nelements + 2 from there: the balance matrix is [stoich | charge], the
+ *      right-hand side of the charge row 0, damping as above.
+ * (From the cold start alone an ion would move by about one unit of ln n per iteration.)
+ * Step 3 has converged when the test above holds AND |dln n_i| < 1e-9 for every charged species:
+ * the test above weighs a step by n_i, and ions are trace species, so alone it does not see the
+ * charge balance.  Where sum_i q_i^2 n_i == 0 (every ion has underflowed) the charge row and column
+ * of that iteration are replaced by an identity row with right-hand side 0 and the charged species
+ * keep their ln n_i.  Steps 1 and 3 are each capped at max_iterations; status is the sum of their
+ * iteration counts; a failure of either gives PB_CHEM_NOT_CONVERGED.  A hybrid on a charged
+ * species is for the caller to refuse (charge_d is device memory). */
 #define PB_ATM_REJECT_CHEMISTRY 64  /* an equilibrium cell that did not converge, a temperature
                                        outside the Gibbs table, a bad element ratio (32 is
                                        PB_ISO_REJECT) */
@@ -1413,6 +1434,7 @@ typedef struct pb_chem_model {
     const double *gibbs_d;              /* [ntemps][nspecies] */
     const int32_t *stoich_d;            /* [nspecies][nelements] */
     const double *pressure_d;           /* [nlayers] bar */
+    const int32_t *charge_d;            /* [nspecies], or NULL: a neutral network */
 } pb_chem_model;
 int pb_equilibrium_vmr(const pb_chem_model *model, const double *temps_d, const double *params_d,
                        int nwalkers, double *vmr_d, int32_t *status_d, void *stream);
@@ -1444,7 +1466,10 @@ typedef struct pb_radeq_chem {
  * converged.  A cell that converges neither way, or whose temperature or abundances are refused
  * (PB_CHEM_*), keeps vmr_d, mm_d and its iterate AS THEY WERE (unlike pb_equilibrium_vmr, which
  * writes zeros: zeros would empty a layer of the next evaluation), gets the negative status and
- * + 1 in failures_d.  model->nhybrid must be 0.  No LDS, no barrier, no atomic. */
+ * + 1 in failures_d.  model->nhybrid must be 0.  No LDS, no barrier, no atomic.
+ * With model->charge_d a warm cell goes straight to step 3 of the solve with charges (the full
+ * system from its stored iterate, both tests above and that of the charged species), the cold
+ * solve is the three steps, and mm_d includes the electrons through mol_mass_d. */
 int pb_radeq_equilibrium(const pb_chem_model *model, const double *temps_d,
                          const double *params_d, int nwalkers, int warm,
                          const pb_radeq_chem *state, void *stream);

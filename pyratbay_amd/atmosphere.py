@@ -200,6 +200,7 @@ class _EquilibriumVmr:
         for model in models:
             if isinstance(model, IsoVMR):
                 _check_free_model(self.atm, model, taken)
+                self.net.refuse_charged_hybrid(self.net.species.index(model.species))
 
     @functools.cached_property
     def columns(self):

@@ -29,7 +29,27 @@ temperature moves by little between two solves, so CarriedEquilibrium (pb_radeq_
 from the iterate of the previous one; equilibrium_host(start=...) is its host form and TOL_ALL the
 extra convergence test a carried start needs.
 
-Out of scope: condensates, ions, networks above 64 species (profiles/chemistry.md).
+Ions and electrons: ChemNetwork(..., charges=[S]) gives every species its charge; the electron is a
+species 'e-' with an all-zero stoich row and charge -1, and the charge never enters stoich.  The
+charge balance sum_i q_i n_i = 0 is one more row of the system (net.balance = [stoich | charges],
+its b is 0), which then has order E + 2.  Allowing that row is not enough (profiles/
+chemistry_ions.md): from the cold start an ion moves by about one unit of ln n per iteration, and
+the convergence test above, which weighs a step by n_i, does not see the charge balance of trace
+ions at all.  So the cold solve takes three steps:
+    1. the neutral species alone, from the cold start of their sub-network (its statements and
+       bits), which leaves the element potentials pi of its last solve;
+    2. every charged species is seeded in logarithms: ln n_i = t_i + q_i pi_q with
+       t_i = ln n - g_i - ln p + sum_j a_ij pi_j and pi_q = (LSE- - LSE+) / 2, LSE the log-sum-exp
+       of t over the species of one sign (exact for charges +-1 while the ions are trace);
+    3. the full system from there, converged when the test above holds AND |dln n_i| < TOL_ALL for
+       every charged species.  Where sum_i q_i^2 n_i == 0 (every ion has underflowed) the charge
+       row and column of that iteration are an identity row with right-hand side 0 and the
+       charged species keep their ln n_i.
+iterations and status are the sum of steps 1 and 3, each capped at MAX_ITERATIONS.  A carried start
+goes straight to step 3.  charges=None or all zeros is the neutral network: the statements above,
+every refusal and every bit unchanged.
+
+Out of scope: condensates, networks above 64 species (profiles/chemistry.md).
 """
 import ctypes as C
 
@@ -113,9 +133,17 @@ class ChemNetwork:
 
     ValueError for: rank(stoich) < E, an element no species holds, a species with no element, no H
     among the elements, ions or an electron 'element', a table that is not finite or whose
-    temperatures do not ascend, more than min(64, the atmosphere's species limit) species, E > 8."""
+    temperatures do not ascend, more than min(64, the atmosphere's species limit) species, E > 8.
 
-    def __init__(self, species, elements, stoich, gibbs_temps, gibbs_over_RT, base_dex):
+    charges[S] (integers; None or all zeros: a neutral network, everything above as it is): the
+    charge of every species.  Names ending in '+' or '-' and 'e-' are then taken, and a species
+    holds an element or a charge.  ValueError for: charged species of one sign only, an element
+    that no neutral species holds, rank(stoich of the neutral species) < E, rank([stoich |
+    charges]) < E + 1, E > 7 (the charge balance takes one of the eight rows).  net.charges is the
+    int32 array (or None), net.balance [S, E + 1] = [stoich | charges]; net.stoich stays [S, E]."""
+
+    def __init__(self, species, elements, stoich, gibbs_temps, gibbs_over_RT, base_dex,
+                 charges=None):
         self.species = [str(s) for s in species]
         self.elements = [str(e) for e in elements]
         S, E = self.nspecies, self.nelements = len(self.species), len(self.elements)
@@ -127,8 +155,18 @@ class ChemNetwork:
         for e in self.elements:
             if e.lower().rstrip('-') == 'e' or e[-1] in '+-':
                 raise ValueError(f"elements: '{e}': ions and electrons are not supported")
+        if charges is not None:
+            charges = np.asarray(charges)
+            if charges.shape != (S,) or not np.all(np.isfinite(charges)) or \
+                    np.any(charges != np.round(charges)):
+                raise ValueError(f'charges must hold {S} integers, one per species, got '
+                                 f'{charges}')
+            charges = np.ascontiguousarray(charges, np.int32)
+        self.charges = charges
+        # all zeros is the neutral network: today's statements, refusals and bits
+        self.charged = charges is not None and bool(np.any(charges))
         for s in self.species:
-            if s[-1] in '+-' or s.lower() in ('e', 'e-'):
+            if not self.charged and (s[-1] in '+-' or s.lower() in ('e', 'e-')):
                 raise ValueError(f"species '{s}': ions and electrons are not supported")
         if 'H' not in self.elements:
             raise ValueError(f"elements: no 'H' among {self.elements} (abundances are relative "
@@ -144,11 +182,16 @@ class ChemNetwork:
             if not np.any(self.stoich[:, j]):
                 raise ValueError(f"element '{e}' is in no species")
         for i, s in enumerate(self.species):
-            if not np.any(self.stoich[i]):
-                raise ValueError(f"species '{s}' holds no element")
-        if np.linalg.matrix_rank(self.stoich.astype(float)) < E:
+            if not np.any(self.stoich[i]) and not (self.charged and self.charges[i]):
+                raise ValueError(f"species '{s}' holds no element" +
+                                 ' and no charge' * self.charged)
+        if self.charged:
+            self._check_charges()
+        elif np.linalg.matrix_rank(self.stoich.astype(float)) < E:
             raise ValueError(f'stoich has rank {np.linalg.matrix_rank(self.stoich.astype(float))} '
                              f'< {E} elements: the element balances are not independent')
+        self.balance = np.ascontiguousarray(np.column_stack(
+            [self.stoich, np.zeros(S, np.int32) if charges is None else self.charges]), np.int32)
         self.gibbs_temps = np.ascontiguousarray(gibbs_temps, float)
         self.gibbs_over_RT = np.ascontiguousarray(gibbs_over_RT, float)
         nT = len(self.gibbs_temps)
@@ -165,6 +208,31 @@ class ChemNetwork:
         self.ihydrogen = self.elements.index('H')
         self.is_metal = np.array([e not in ('H', 'He') for e in self.elements])
         self._dev = None
+
+    def _check_charges(self):
+        """What a network with ions and electrons has to hold on top (the class docstring)."""
+        E, q = self.nelements, self.charges
+        if E + 1 > MAX_ELEMENTS:
+            raise ValueError(f'{E} elements with charges: the charge balance takes one of the '
+                             f'{MAX_ELEMENTS} rows, at most {MAX_ELEMENTS - 1} elements')
+        if not (np.any(q > 0) and np.any(q < 0)):
+            raise ValueError('charges: charged species of both signs must be present (got '
+                             f'{[s for s, c in zip(self.species, q) if c]}): no charge balance '
+                             'otherwise')
+        neutral = self.stoich[q == 0].astype(float)
+        for j, e in enumerate(self.elements):
+            if not np.any(neutral[:, j]):
+                raise ValueError(f"element '{e}' is in no neutral species (the neutral "
+                                 'sub-network is solved first)')
+        full = np.column_stack([self.stoich, q]).astype(float)
+        rank = np.linalg.matrix_rank(full)
+        if rank < E + 1:
+            raise ValueError(f'[stoich | charges] has rank {rank} < {E} elements + 1: the charge '
+                             'balance is not independent of the element balances')
+        rank = np.linalg.matrix_rank(neutral)
+        if rank < E:
+            raise ValueError(f'the stoich of the neutral species has rank {rank} < {E} elements: '
+                             'the element balances are not independent')
 
     # ------------------------------------------------------------------------ abundances
     def element_index(self, name):
@@ -221,7 +289,8 @@ class ChemNetwork:
         -> vmr[L, S], iterations[L], status[L].  status is the iteration count of a converged cell
         or a negative STATUS_*; a cell with a negative status has zeros in vmr and iterated
         nothing (STATUS_NOT_CONVERGED: MAX_ITERATIONS).  Every cell is solved from the same cold
-        start n_i = 0.1 / S, n = 0.1, so it depends on nothing but its own inputs.
+        start n_i = 0.1 / S, n = 0.1, so it depends on nothing but its own inputs.  (A network
+        with charges: the three steps of the module docstring, iterations their sum.)
 
         start: the host form of pb_radeq_equilibrium, which also returns the iterate, a fourth
         element (ln_ni[L, S], ln_n[L]).  'cold': as above.  (ln_ni[L, S], ln_n[L]), the iterate an
@@ -283,7 +352,7 @@ class ChemNetwork:
             again = np.where(~ok)[0]
             if again.size:
                 v[again], it[again], ok[again], li[again], ln[again] = self._newton(
-                    g[again], lnp[again], b, tolerance, self._cold_start(again.size), None)
+                    g[again], lnp[again], b, tolerance, iterate=True)
             good = live[ok]
             vmr[good], ln_ni[good], ln_n[good] = v[ok], li[ok], ln[ok]
             iterations[live] = it
@@ -294,61 +363,131 @@ class ChemNetwork:
         """(ln_ni[c, S], ln_n[c]) every cell starts from: n_i = 0.1 / S, n = 0.1."""
         return np.full((c, self.nspecies), np.log(0.1 / self.nspecies)), np.full(c, np.log(0.1))
 
-    def _newton(self, g, lnp, b, tolerance, start=None, tol_all=None):
+    def _newton(self, g, lnp, b, tolerance, start=None, tol_all=None, iterate=False):
         """The iteration of the module docstring on c cells at once (each on its own; a converged
         cell is left alone): g[c, S], lnp[c] -> vmr[c, S], iterations[c], converged[c].  start
         (ln_ni[c, S], ln_n[c]): from that iterate instead of the cold start, and the iterate is
-        returned too (ln_ni, ln_n behind the three); tol_all: converged only when also
-        max_i |dln n_i| < tol_all."""
+        returned too (ln_ni, ln_n behind the three; iterate=True: also from the cold start);
+        tol_all: converged only when also max_i |dln n_i| < tol_all.  With charges the cold start
+        is the three steps of the module docstring, a given start goes straight to the third."""
         a = self.stoich.astype(float)
-        c, S, E = len(lnp), self.nspecies, self.nelements
-        ln_ni, ln_n = self._cold_start(c) if start is None else \
-            (np.array(start[0], float), np.array(start[1], float))
-        iterations = np.zeros(c, np.int32)
-        converged = np.zeros(c, bool)
+        c = len(lnp)
         with np.errstate(all='ignore'):
-            for it in range(1, MAX_ITERATIONS + 1):
-                idx = np.where(~converged)[0]
-                if not idx.size:
-                    break
-                li, ln = ln_ni[idx], ln_n[idx]
-                ni, n = np.exp(li), np.exp(ln)
-                mu = ((g[idx] + li) - ln[:, None]) + lnp[idx][:, None]
-                an = a[None, :, :] * ni[:, :, None]                       # a_ik n_i
-                A = np.empty((len(idx), E + 1, E + 1))
-                A[:, :E, :E] = np.einsum('sk,csj->ckj', a, an)
-                col = an.sum(axis=1)
-                A[:, :E, E] = col
-                A[:, E, :E] = col
-                sn = ni.sum(axis=1)
-                A[:, E, E] = sn - n
-                r = np.empty((len(idx), E + 1))
-                r[:, :E] = (b - col) + np.einsum('csk,cs->ck', an, mu)
-                r[:, E] = (n - sn) + (ni * mu).sum(axis=1)
-                x = gauss_solve(A, r)
-                dln_n = x[:, E]
-                dln_ni = (-mu + dln_n[:, None]) + x[:, :E] @ a.T
-                rel = li - ln[:, None]                                    # ln(n_i / n)
-                major = ni / n[:, None] > _MINOR
-                step = np.where(major, np.abs(dln_ni), 0.0).max(axis=1)
-                l1 = 2.0 / np.fmax(5.0 * np.abs(dln_n), step)
-                minor = ~major & (dln_ni >= 0.0)
-                q = np.abs((-rel - _LN_MINOR) / (dln_ni - dln_n[:, None]))
-                l2 = np.fmin.reduce(np.where(minor, q, np.inf), axis=1)
-                lam = np.fmin(1.0, np.fmin(l1, l2))
-                ln_ni[idx] = li + lam[:, None] * dln_ni
-                ln_n[idx] = ln + lam * dln_n
-                iterations[idx] = it
-                small = np.all((ni * np.abs(dln_ni)) / sn[:, None] < tolerance, axis=1)
-                done = (lam == 1.0) & small & (np.abs(dln_n) < tolerance)
-                if tol_all is not None:
-                    done &= np.all(np.abs(dln_ni) < tol_all, axis=1)
-                converged[idx] = done
+            if not self.charged:
+                ln_ni, ln_n = self._cold_start(c) if start is None else \
+                    (np.array(start[0], float), np.array(start[1], float))
+                ln_ni, ln_n, iterations, converged, _ = self._iterate(
+                    a, b, g, lnp, tolerance, ln_ni, ln_n, tol_all)
+            else:
+                ions = self.charges != 0
+                full, b_full = self.balance.astype(float), np.append(np.asarray(b, float), 0.0)
+                if start is not None:
+                    ln_ni, ln_n, iterations, converged, _ = self._iterate(
+                        full, b_full, g, lnp, tolerance, np.array(start[0], float),
+                        np.array(start[1], float), tol_all, ions)
+                else:
+                    ln_ni, ln_n, iterations, converged = self._cold_ions(
+                        a, full, b, b_full, g, lnp, tolerance, ions)
             ni = np.exp(ln_ni)
             vmr = ni / ni.sum(axis=1)[:, None]
-        if start is None:
+        if start is None and not iterate:
             return vmr, iterations, converged
         return vmr, iterations, converged, ln_ni, ln_n
+
+    def _cold_ions(self, a, full, b, b_full, g, lnp, tolerance, ions):
+        """The cold solve of a network with charges (module docstring): the neutral sub-network,
+        the charged species seeded from its element potentials, then the full system."""
+        c, S = g.shape
+        neutral = ~ions
+        count = int(neutral.sum())
+        # 1: exactly the sub-network of the neutral species, from ITS cold start
+        sub_ni, ln_n, iterations, converged, pi = self._iterate(
+            a[neutral], b, g[:, neutral], lnp, tolerance,
+            np.full((c, count), np.log(0.1 / count)), np.full(c, np.log(0.1)))
+        ln_ni = np.zeros((c, S))
+        ln_ni[:, neutral] = sub_ni
+        # 2: ln n_i = ln n - g_i - ln p + sum_j a_ij pi_j + q_i pi_q, in logarithms throughout
+        q = self.charges[ions].astype(float)
+        t = ((ln_n[:, None] - g[:, ions]) - lnp[:, None]) + pi @ a[ions].T
+
+        def lse(mask):
+            top = np.max(np.where(mask, t, -np.inf), axis=1)
+            return top + np.log(np.sum(np.where(mask, np.exp(t - top[:, None]), 0.0), axis=1))
+        pi_q = 0.5 * (lse(q < 0.0) - lse(q > 0.0))
+        ln_ni[:, ions] = t + q * pi_q[:, None]
+        # 3: the full system of order E + 2 on the cells the first step solved
+        ok = np.where(converged)[0]
+        if ok.size:
+            ln_ni[ok], ln_n[ok], more, converged[ok], _ = self._iterate(
+                full, b_full, g[ok], lnp[ok], tolerance, ln_ni[ok], ln_n[ok], None, ions)
+            iterations[ok] += more
+        return ln_ni, ln_n, iterations, converged
+
+    def _iterate(self, a, b, g, lnp, tolerance, ln_ni, ln_n, tol_all=None, ions=None):
+        """The Newton loop proper on the balance matrix a[S, E] (stoich, or [stoich | charges]
+        with ions[S] marking the charged species and b's last entry 0) from the iterate
+        (ln_ni[c, S], ln_n[c]), both updated in place -> ln_ni, ln_n, iterations[c], converged[c],
+        pi[c, E] (the potentials of each cell's last solve)."""
+        c, S = g.shape
+        E = a.shape[1]
+        iterations = np.zeros(c, np.int32)
+        converged = np.zeros(c, bool)
+        pi = np.zeros((c, E))
+        for it in range(1, MAX_ITERATIONS + 1):
+            idx = np.where(~converged)[0]
+            if not idx.size:
+                break
+            li, ln = ln_ni[idx], ln_n[idx]
+            ni, n = np.exp(li), np.exp(ln)
+            mu = ((g[idx] + li) - ln[:, None]) + lnp[idx][:, None]
+            an = a[None, :, :] * ni[:, :, None]                       # a_ik n_i
+            A = np.empty((len(idx), E + 1, E + 1))
+            A[:, :E, :E] = np.einsum('sk,csj->ckj', a, an)
+            col = an.sum(axis=1)
+            A[:, :E, E] = col
+            A[:, E, :E] = col
+            sn = ni.sum(axis=1)
+            A[:, E, E] = sn - n
+            r = np.empty((len(idx), E + 1))
+            r[:, :E] = (b - col) + np.einsum('csk,cs->ck', an, mu)
+            r[:, E] = (n - sn) + (ni * mu).sum(axis=1)
+            if ions is not None:
+                # sum_i q_i^2 n_i == 0: every ion has underflowed, the charge row and column are
+                # zeros; an identity row in their place, and the ions keep their ln n_i
+                drop = A[:, E - 1, E - 1] == 0.0
+                A[drop, E - 1, :] = 0.0
+                A[drop, :, E - 1] = 0.0
+                A[drop, E - 1, E - 1] = 1.0
+                r[drop, E - 1] = 0.0
+                held = drop[:, None] & ions[None, :]
+            x = gauss_solve(A, r)
+            dln_n = x[:, E]
+            dln_ni = (-mu + dln_n[:, None]) + x[:, :E] @ a.T
+            if ions is not None:
+                dln_ni = np.where(held, 0.0, dln_ni)
+            rel = li - ln[:, None]                                    # ln(n_i / n)
+            major = ni / n[:, None] > _MINOR
+            step = np.where(major, np.abs(dln_ni), 0.0).max(axis=1)
+            l1 = 2.0 / np.fmax(5.0 * np.abs(dln_n), step)
+            minor = ~major & (dln_ni >= 0.0)
+            if ions is not None:
+                minor &= ~held
+            q = np.abs((-rel - _LN_MINOR) / (dln_ni - dln_n[:, None]))
+            l2 = np.fmin.reduce(np.where(minor, q, np.inf), axis=1)
+            lam = np.fmin(1.0, np.fmin(l1, l2))
+            ln_ni[idx] = li + lam[:, None] * dln_ni
+            ln_n[idx] = ln + lam * dln_n
+            iterations[idx] = it
+            pi[idx] = x[:, :E]
+            small = np.all((ni * np.abs(dln_ni)) / sn[:, None] < tolerance, axis=1)
+            done = (lam == 1.0) & small & (np.abs(dln_n) < tolerance)
+            if tol_all is not None:
+                done &= np.all(np.abs(dln_ni) < tol_all, axis=1)
+            if ions is not None:
+                # the weighted test does not see a trace species, hence not the charge balance
+                done &= np.all(np.abs(dln_ni[:, ions]) < TOL_ALL, axis=1)
+            converged[idx] = done
+        return ln_ni, ln_n, iterations, converged, pi
 
     def hybrid_host(self, vmr, species, value):
         """The column of a free log10(VMR) on top of the equilibrium vmr[L, S] (the reference's
@@ -356,11 +495,17 @@ class ChemNetwork:
         over the species' elements j, of (sum_i vmr_i a_ij) / a_species,j -- the species cannot
         hold more of an element than the mixture has.  Nothing is renormalised."""
         k = self.species.index(species)
+        self.refuse_charged_hybrid(k)
         vmr = np.asarray(vmr, float)
         caps = [(vmr * self.stoich[:, j]).sum(axis=1) / self.stoich[k, j]
                 for j in range(self.nelements) if self.stoich[k, j]]
         max_vmr = np.min(caps, axis=0)
         return np.clip(np.float64(10.0)**value, 0.0, max_vmr)
+
+    def refuse_charged_hybrid(self, k):
+        if self.charged and self.charges[k]:
+            raise ValueError(f"hybrid model on '{self.species[k]}': a charged species takes no "
+                             'free VMR (the charge balance would not hold)')
 
     # ----------------------------------------------------------------------------- device
     def device_arrays(self):
@@ -370,6 +515,9 @@ class ChemNetwork:
         if self._dev is None:
             self._dev = dict(temps=dev(self.gibbs_temps), gibbs=dev(self.gibbs_over_RT),
                              stoich=torch.tensor(self.stoich, dtype=torch.int32, device='cuda'))
+            if self.charged:
+                self._dev['charges'] = torch.tensor(self.charges, dtype=torch.int32,
+                                                    device='cuda')
         return self._dev
 
     def model_struct(self, nlayers, npar, par_metal=-1, scales=(), ratios=(), hybrids=()):
@@ -392,6 +540,8 @@ class ChemNetwork:
         for k, (x, y, col) in enumerate(ratios):
             st.ratio_num[k], st.ratio_den[k], st.ratio_par[k] = x, y, col
         for k, (i, col) in enumerate(hybrids):
+            if 0 <= i < self.nspecies:
+                self.refuse_charged_hybrid(i)
             st.hybrid_species[k], st.hybrid_par[k] = i, col
         st.max_iterations, st.tolerance = MAX_ITERATIONS, TOLERANCE
         return st
@@ -402,6 +552,7 @@ class ChemNetwork:
         st = self.model_struct(pressure_d.shape[0], npar, **columns)
         st.gibbs_temps_d, st.gibbs_d = d['temps'].data_ptr(), d['gibbs'].data_ptr()
         st.stoich_d, st.pressure_d = d['stoich'].data_ptr(), pressure_d.data_ptr()
+        st.charge_d = d['charges'].data_ptr() if self.charged else None
         return st
 
 

@@ -13,6 +13,11 @@
 // pb_radeq_equilibrium is the same solver inside the radiative-equilibrium loop (pb_radeq.hip),
 // where a cell's temperature moves by little between two launches: it starts from the iterate the
 // previous launch left and also writes the mean molecular mass (k_radeq_equilibrium below).
+//
+// A network with ions and electrons (pb_chem_model.charge_d) adds the charge balance as one more
+// row, the lane's charge as its balance column; both kernels are templates on (E, Charged), and the
+// instantiations without charges are the kernels of a neutral network unchanged.  With charges the
+// cold solve takes three steps (cold_solve_ions), all branches still uniform over the wavefront.
 #include "pb_common.h"
 
 namespace {
@@ -22,6 +27,7 @@ constexpr int kCellsPerBlock = 4;
 constexpr double kMinor = 1.0e-8;          // n_i / n at and below which a species is a minor one
 constexpr double kLnMinor = 9.2103404;     // RP-1311 eq. 3.2: -ln(1e-4)
 constexpr double kDblMax = 1.79769313486231570815e308;
+constexpr double kTolIons = 1.0e-9;        // |dln n_i| of a charged species at convergence (TOL_ALL)
 
 struct ChemArgs {
     pb_chem_model m;
@@ -175,12 +181,18 @@ __device__ __forceinline__ int cell_inputs(const pb_chem_model &m, const double 
 
 // One iteration on this lane's ln_ni and the cell's ln_n, both updated; returns the convergence
 // test of pb_equilibrium_vmr (a full step, weighed by n_i).  dln_ni: this lane's undamped step
-// (0 in a lane without a species), which that test does not bound for a trace species.
-template <int E>
+// (0 in a lane without a species), which that test does not bound for a trace species.  pi: the
+// potentials of this solve.
+// Charged: the last balance column is the lane's charge and b's last entry 0, so the system has
+// order E + 1 with E counting that row.  The weighted test does not see a trace species, hence not
+// the charge balance: a charged lane also needs |dln n_i| < kTolIons.  sum_i q_i^2 n_i == 0 (every
+// ion has underflowed; the same bits in all lanes): an identity row in place of the charge row and
+// column, and the charged lanes keep their ln n_i for this step.
+template <int E, bool Charged = false>
 __device__ __forceinline__ bool newton_step(const pb_chem_model &m, bool live,
                                             const double (&stoich)[E], const double (&b)[E],
                                             double g, double lnp, double &ln_ni, double &ln_n,
-                                            double &dln_ni)
+                                            double &dln_ni, double (&pi)[E])
 {
     constexpr int N = E + 1;
     const double ni = live ? exp(ln_ni) : 0.0;
@@ -207,12 +219,25 @@ __device__ __forceinline__ bool newton_step(const pb_chem_model &m, bool live,
     const double sn = wave_sum(ni);
     A[E][E] = sn - n;
     r[E] = (n - sn) + wave_sum(ni * mu);
+    if constexpr (Charged) {
+        const bool drop = A[E - 1][E - 1] == 0.0;
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            A[E - 1][j] = drop ? 0.0 : A[E - 1][j];
+            A[j][E - 1] = drop ? 0.0 : A[j][E - 1];
+        }
+        A[E - 1][E - 1] = drop ? 1.0 : A[E - 1][E - 1];
+        r[E - 1] = drop ? 0.0 : r[E - 1];
+        live = live && !(drop && stoich[E - 1] != 0.0);
+    }
     gauss_solve<N>(A, r);
     const double dln_n = r[E];
     double api = 0.0;
 #pragma unroll
-    for (int j = 0; j < E; j++)
+    for (int j = 0; j < E; j++) {
         api += stoich[j] * r[j];
+        pi[j] = r[j];
+    }
     dln_ni = live ? (-mu + dln_n) + api : 0.0;
 
     // ---- damping (RP-1311 eqs. 3.1-3.3)
@@ -227,10 +252,85 @@ __device__ __forceinline__ bool newton_step(const pb_chem_model &m, bool live,
     ln_n += lambda * dln_n;
     // n_i |dln n_i| / sum n < tolerance in every lane (false on NaN, like the host's)
     const bool open = live && !((ni * fabs(dln_ni)) / sn < m.tolerance);
+    if constexpr (Charged)
+        if (__any(live && stoich[E - 1] != 0.0 && !(fabs(dln_ni) < kTolIons)))
+            return false;
     return lambda == 1.0 && !__any(open) && fabs(dln_n) < m.tolerance;
 }
 
+// A lane's balance row [stoich | charge] and the right-hand side [b | 0] of the charged system
 template <int E>
+__device__ __forceinline__ void with_charge(const double (&stoich)[E], const double (&b)[E],
+                                            double charge, double (&bal)[E + 1],
+                                            double (&b0)[E + 1])
+{
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        bal[j] = stoich[j];
+        b0[j] = b[j];
+    }
+    bal[E] = charge;
+    b0[E] = 0.0;
+}
+
+// The cold solve of a cell whose network has charged species (ChemNetwork._cold_ions, the same
+// statements), in three steps.  From the cold start the ions would approach their values by one
+// unit of ln n per iteration (Newton on e^u - e^v = 0), dG_ion / (2 R T) iterations, so:
+//   1. the neutral lanes alone, from the cold start of their sub-network: its statements and bits;
+//   2. the charged lanes seeded from its potentials: ln n_i = t_i + q_i pi_q with
+//      t_i = ln n - g_i - ln p + sum_j a_ij pi_j and pi_q = (LSE- - LSE+) / 2, the log-sum-exp of t
+//      over the lanes of either sign (two wave maxima, two wave sums): exact for charges +-1 while
+//      the ions are trace, and never underflowing;
+//   3. the full system of order E + 2 from there.
+// Each loop is capped at max_iterations; iterations: their sum.  Returns whether both converged.
+template <int E>
+__device__ __forceinline__ bool cold_solve_ions(const pb_chem_model &m, bool live, double charge,
+                                                const double (&stoich)[E], const double (&b)[E],
+                                                double g, double lnp, double &ln_ni,
+                                                double &ln_n, int &iterations)
+{
+    const bool neutral = live && charge == 0.0;
+    const int count = __popcll(__ballot(neutral));
+    ln_ni = neutral ? log(0.1 / (double)count) : 0.0;
+    ln_n = log(0.1);
+    double dln_ni, pi[E];
+    bool converged = false;
+    iterations = 0;
+    for (int it = 1; it <= m.max_iterations && !converged; it++) {
+        converged = newton_step<E>(m, neutral, stoich, b, g, lnp, ln_ni, ln_n, dln_ni, pi);
+        iterations = it;
+    }
+    if (!converged)
+        return false;
+
+    double api = 0.0;
+#pragma unroll
+    for (int j = 0; j < E; j++)
+        api += stoich[j] * pi[j];
+    const double t = ((ln_n - g) - lnp) + api;
+    const bool minus = live && charge < 0.0, plus = live && charge > 0.0;
+    const double top_minus = wave_max(minus ? t : -INFINITY);
+    const double top_plus = wave_max(plus ? t : -INFINITY);
+    const double lse_minus = top_minus + log(wave_sum(minus ? exp(t - top_minus) : 0.0));
+    const double lse_plus = top_plus + log(wave_sum(plus ? exp(t - top_plus) : 0.0));
+    const double pi_q = 0.5 * (lse_minus - lse_plus);
+    if (minus || plus)
+        ln_ni = t + charge * pi_q;
+
+    double bal[E + 1], b0[E + 1], pi0[E + 1];
+    with_charge<E>(stoich, b, charge, bal, b0);
+    const int first = iterations;
+    converged = false;
+    for (int it = 1; it <= m.max_iterations && !converged; it++) {
+        converged = newton_step<E + 1, true>(m, live, bal, b0, g, lnp, ln_ni, ln_n, dln_ni, pi0);
+        iterations = first + it;
+    }
+    return converged;
+}
+
+// Charged: the network has ions and electrons (m.charge_d), E < PB_CHEM_MAX_ELEMENTS; without, the
+// kernel is that of a neutral network to the instruction.
+template <int E, bool Charged>
 __global__ __launch_bounds__(kWave * kCellsPerBlock) void k_equilibrium_vmr(ChemArgs a)
 {
     const pb_chem_model &m = a.m;
@@ -262,10 +362,16 @@ __global__ __launch_bounds__(kWave * kCellsPerBlock) void k_equilibrium_vmr(Chem
         double ln_n = log(0.1);
         int iterations = 0;
         bool converged = false;
-        for (int it = 1; it <= m.max_iterations && !converged; it++) {
-            double dln_ni;
-            converged = newton_step<E>(m, live, stoich, b, g, lnp, ln_ni, ln_n, dln_ni);
-            iterations = it;
+        if constexpr (Charged) {
+            const double charge = live ? (double)m.charge_d[lane] : 0.0;
+            converged = cold_solve_ions<E>(m, live, charge, stoich, b, g, lnp, ln_ni, ln_n,
+                                           iterations);
+        } else {
+            for (int it = 1; it <= m.max_iterations && !converged; it++) {
+                double dln_ni, pi[E];
+                converged = newton_step<E>(m, live, stoich, b, g, lnp, ln_ni, ln_n, dln_ni, pi);
+                iterations = it;
+            }
         }
         if (converged) {
             const double ni = live ? exp(ln_ni) : 0.0;
@@ -332,7 +438,10 @@ struct CarriedArgs {
 // start as with warm == 0.  Every branch on these is uniform over the wavefront: the values come
 // out of butterflies and ballots.  A cell that ends with a negative status leaves vmr_d, mm_d and
 // its iterate as they were and counts in failures_d, which only its own lane 0 writes.
-template <int E>
+// Charged: a carried iterate goes straight to the full system with the charge row (step 3 of
+// cold_solve_ions, with both tests and that of the charged lanes), the cold solve is the three
+// steps; the mean mass counts the electrons through the caller's mol_mass_d.
+template <int E, bool Charged>
 __global__ __launch_bounds__(kWave * kCellsPerBlock) void k_radeq_equilibrium(CarriedArgs a)
 {
     const pb_chem_model &m = a.m;
@@ -369,21 +478,43 @@ __global__ __launch_bounds__(kWave * kCellsPerBlock) void k_radeq_equilibrium(Ca
         }
         int iterations = 0;
         bool converged = false;
-        for (;;) {
-            if (!carried) {
-                ln_ni = live ? log(0.1 / (double)S) : 0.0;
-                ln_n = log(0.1);
+        if constexpr (Charged) {
+            // a carried iterate goes straight to the full system; the cold solve is the three
+            // steps of cold_solve_ions
+            const double charge = live ? (double)m.charge_d[lane] : 0.0;
+            if (carried) {
+                double bal[E + 1], b0[E + 1];
+                with_charge<E>(stoich, b, charge, bal, b0);
+                for (int it = 1; it <= m.max_iterations && !converged; it++) {
+                    double dln_ni, pi[E + 1];
+                    converged = newton_step<E + 1, true>(m, live, bal, b0, g, lnp, ln_ni, ln_n,
+                                                         dln_ni, pi);
+                    if (__any(!(fabs(dln_ni) < a.c.tol_all)))
+                        converged = false;
+                    iterations = it;
+                }
             }
-            for (int it = 1; it <= m.max_iterations && !converged; it++) {
-                double dln_ni;
-                converged = newton_step<E>(m, live, stoich, b, g, lnp, ln_ni, ln_n, dln_ni);
-                if (carried && __any(!(fabs(dln_ni) < a.c.tol_all)))
-                    converged = false;
-                iterations = it;
+            if (!converged)
+                converged = cold_solve_ions<E>(m, live, charge, stoich, b, g, lnp, ln_ni, ln_n,
+                                               iterations);
+        } else {
+            for (;;) {
+                if (!carried) {
+                    ln_ni = live ? log(0.1 / (double)S) : 0.0;
+                    ln_n = log(0.1);
+                }
+                for (int it = 1; it <= m.max_iterations && !converged; it++) {
+                    double dln_ni, pi[E];
+                    converged = newton_step<E>(m, live, stoich, b, g, lnp, ln_ni, ln_n, dln_ni,
+                                               pi);
+                    if (carried && __any(!(fabs(dln_ni) < a.c.tol_all)))
+                        converged = false;
+                    iterations = it;
+                }
+                if (converged || !carried)
+                    break;
+                carried = false;
             }
-            if (converged || !carried)
-                break;
-            carried = false;
         }
         if (converged) {
             const double ni = live ? exp(ln_ni) : 0.0;
@@ -420,6 +551,9 @@ int chem_check(const pb_chem_model *m, const char *name)
                "%s: 1-%d species, not %d", name, PB_CHEM_MAX_SPECIES, m->nspecies);
     PB_REQUIRE(m->nelements >= 1 && m->nelements <= PB_CHEM_MAX_ELEMENTS,
                "%s: 1-%d elements, not %d", name, PB_CHEM_MAX_ELEMENTS, m->nelements);
+    PB_REQUIRE(!m->charge_d || m->nelements + 1 <= PB_CHEM_MAX_ELEMENTS,
+               "%s: %d elements with charges: the charge balance takes one of the %d rows", name,
+               m->nelements, PB_CHEM_MAX_ELEMENTS);
     PB_REQUIRE(m->ntemps >= 1, "%s: %d Gibbs temperatures", name, m->ntemps);
     PB_REQUIRE(m->nlayers >= 1, "%s: %d layers", name, m->nlayers);
     PB_REQUIRE(m->npar >= 0, "%s: %d parameters", name, m->npar);
@@ -458,15 +592,44 @@ int chem_check(const pb_chem_model *m, const char *name)
     return PB_OK;
 }
 
-template <int E>
+template <int E, bool Charged>
 void launch(const ChemArgs &a, unsigned blocks, hipStream_t stream)
 {
-    k_equilibrium_vmr<E><<<blocks, kWave * kCellsPerBlock, 0, stream>>>(a);
+    k_equilibrium_vmr<E, Charged><<<blocks, kWave * kCellsPerBlock, 0, stream>>>(a);
 }
-template <int E>
+template <int E, bool Charged>
 void launch(const CarriedArgs &a, unsigned blocks, hipStream_t stream)
 {
-    k_radeq_equilibrium<E><<<blocks, kWave * kCellsPerBlock, 0, stream>>>(a);
+    k_radeq_equilibrium<E, Charged><<<blocks, kWave * kCellsPerBlock, 0, stream>>>(a);
+}
+
+// the instantiation of a model: its elements, and whether it has charges (chem_check: then at
+// most PB_CHEM_MAX_ELEMENTS - 1 elements)
+template <class Args>
+void launch_model(const Args &a, unsigned blocks, hipStream_t stream)
+{
+    if (a.m.charge_d) {
+        switch (a.m.nelements) {
+        case 1: launch<1, true>(a, blocks, stream); break;
+        case 2: launch<2, true>(a, blocks, stream); break;
+        case 3: launch<3, true>(a, blocks, stream); break;
+        case 4: launch<4, true>(a, blocks, stream); break;
+        case 5: launch<5, true>(a, blocks, stream); break;
+        case 6: launch<6, true>(a, blocks, stream); break;
+        default: launch<7, true>(a, blocks, stream); break;
+        }
+        return;
+    }
+    switch (a.m.nelements) {
+    case 1: launch<1, false>(a, blocks, stream); break;
+    case 2: launch<2, false>(a, blocks, stream); break;
+    case 3: launch<3, false>(a, blocks, stream); break;
+    case 4: launch<4, false>(a, blocks, stream); break;
+    case 5: launch<5, false>(a, blocks, stream); break;
+    case 6: launch<6, false>(a, blocks, stream); break;
+    case 7: launch<7, false>(a, blocks, stream); break;
+    default: launch<8, false>(a, blocks, stream); break;
+    }
 }
 
 }  // namespace
@@ -496,17 +659,7 @@ int pb_radeq_equilibrium(const pb_chem_model *model, const double *temps_d,
     PB_REQUIRE(blocks <= 0x7fffffffLL, "pb_radeq_equilibrium: %lld cells are too many for one "
                "launch", (long long)ncells);
     CarriedArgs a{*model, c, temps_d, params_d, ncells, warm};
-    hipStream_t s = pb::as_stream(stream);
-    switch (model->nelements) {
-    case 1: launch<1>(a, (unsigned)blocks, s); break;
-    case 2: launch<2>(a, (unsigned)blocks, s); break;
-    case 3: launch<3>(a, (unsigned)blocks, s); break;
-    case 4: launch<4>(a, (unsigned)blocks, s); break;
-    case 5: launch<5>(a, (unsigned)blocks, s); break;
-    case 6: launch<6>(a, (unsigned)blocks, s); break;
-    case 7: launch<7>(a, (unsigned)blocks, s); break;
-    default: launch<8>(a, (unsigned)blocks, s); break;
-    }
+    launch_model(a, (unsigned)blocks, pb::as_stream(stream));
     PB_LAUNCH_CHECK();
     return PB_OK;
 }
@@ -528,17 +681,7 @@ int pb_equilibrium_vmr(const pb_chem_model *model, const double *temps_d, const 
     PB_REQUIRE(blocks <= 0x7fffffffLL, "pb_equilibrium_vmr: %lld cells are too many for one launch",
                (long long)ncells);
     ChemArgs a{*model, temps_d, params_d, vmr_d, status_d, ncells};
-    hipStream_t s = pb::as_stream(stream);
-    switch (model->nelements) {
-    case 1: launch<1>(a, (unsigned)blocks, s); break;
-    case 2: launch<2>(a, (unsigned)blocks, s); break;
-    case 3: launch<3>(a, (unsigned)blocks, s); break;
-    case 4: launch<4>(a, (unsigned)blocks, s); break;
-    case 5: launch<5>(a, (unsigned)blocks, s); break;
-    case 6: launch<6>(a, (unsigned)blocks, s); break;
-    case 7: launch<7>(a, (unsigned)blocks, s); break;
-    default: launch<8>(a, (unsigned)blocks, s); break;
-    }
+    launch_model(a, (unsigned)blocks, pb::as_stream(stream));
     PB_LAUNCH_CHECK();
     return PB_OK;
 }
