@@ -326,6 +326,15 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
     const int rowspan = a.rowlds + kStagePad;                            // buffer pitch
     constexpr int kNB = 2;                        // row buffers
     Rec *s_rec = reinterpret_cast<Rec *>(s_row + kNB * rowspan + kStagePad);   // [kThreads]
+    // LDS byte address of the records (taken once, as row_lds0): with a record's own offset it fits
+    // the 16 bits a hit word has for it (find_hits), whatever the launch's rowlds <= kStageRowMax
+    static_assert((kNB * (kStageRowMax + kStagePad) + kStagePad) * 8 + kThreads * 16 <= 65536,
+                  "a hit word holds the LDS offset of a record in 16 bits");
+    typedef double rec_v2 __attribute__((ext_vector_type(2)));
+    typedef const rec_v2 rec_cv2;
+    typedef __attribute__((address_space(3))) rec_cv2 *rec_lds_p;
+    const unsigned rec_off0 =
+        (unsigned)(size_t)(__attribute__((address_space(3))) char *)(reinterpret_cast<char *>(s_rec));
     long long *s_src = reinterpret_cast<long long *>(s_rec + kThreads);  // row start, -1 empty
     unsigned long long *s_desc = reinterpret_cast<unsigned long long *>(s_src);   // per segment
     unsigned long long *s_segmask =
@@ -398,8 +407,14 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
     const int tlen = (int)(tend - t0);
     const int rlo = wave * kStageSpan;            // first sample of sub-tile 0 (tile coords)
 
-    const double kthresh =
-        a.ethresh * __longlong_as_double((long long)a.kmax_bits[(int64_t)layer * a.nrows + row]);
+    // (wave-uniform numbers that a vector load brought: kept in scalar registers, or they are
+    // spilled to scratch around the step loop)
+    auto uniform = [](double x) {
+        return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)),
+                                __builtin_amdgcn_readfirstlane(__double2loint(x)));
+    };
+    const double kthresh = uniform(
+        a.ethresh * __longlong_as_double((long long)a.kmax_bits[(int64_t)layer * a.nrows + row]));
     // packed records of this layer, indexed by the position in the phase-sorted group list
     const int64_t recbase = a.rec16 ? (int64_t)layer * a.rec_pitch - a.grp_lo
                                     : (int64_t)layer * a.ngroups;
@@ -524,9 +539,10 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
 #undef PB_DMA_LD
 #undef PB_DMA_OPEN
     // (tref, probe 4: the stamp that opened the step -- the descriptor chain is timed against it)
+    // `boff`: byte offset of the row's buffer (or slot) from buffer 0.
     // `part`: true_type = the pieces [c_lo, c_hi) of the row only, one statement per piece (the
     // kIssue == 2 experiment); false_type = the whole row through dma_pieces()
-    auto dma_desc = [&](unsigned long long d, int buf, auto part, int c_lo, int c_hi,
+    auto dma_desc = [&](unsigned long long d, unsigned boff, auto part, int c_lo, int c_hi,
                         unsigned long long tref = 0) {
         const unsigned dlo = (unsigned)__builtin_amdgcn_readfirstlane((int)d);
         const unsigned dhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(d >> 32));
@@ -539,7 +555,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
         rsrc.z = __builtin_amdgcn_readfirstlane(len * 8);
         rsrc.w = 0x00020000;
         int voff = (2 * lane - (mlo & ~1)) * 8;
-        unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(row_lds0 + buf * (kMulti ? pitch : rowspan) * 8));
+        unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(row_lds0 + boff));
         if constexpr (kProbe == 4) {
             if (tref)
                 pc[20] += tick() - tref;
@@ -565,8 +581,9 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
             }
         }
     };
-    auto dma_row = [&](int sg, int buf, unsigned long long tref = 0) {
-        dma_desc(s_desc[sg], buf, std::false_type(), 0, 0, tref);
+    auto bufoff = [&](int buf) { return (unsigned)(buf * rowspan * 8); };   // one row per step
+    auto dma_row = [&](int sg, unsigned boff, unsigned long long tref = 0) {
+        dma_desc(s_desc[sg], boff, std::false_type(), 0, 0, tref);
     };
     // out-of-window lanes fall outside the buffer descriptor and read 0 (no predicate)
     auto load_row = [&](int sg, auto Rc, double *reg) {
@@ -615,7 +632,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
             continue;                              // no key of this isotope in the chunk
         const unsigned long long t_iso = tick();
         const int64_t li = (int64_t)layer * a.niso + iso;
-        const double dens = a.li_dens[li];
+        const double dens = uniform(a.li_dens[li]);
         int64_t reach = a.li_hmax[li];
         if (a.cutoff > 0.0)
             reach = min(reach, (int64_t)(a.cutoff / a.ownstep) + 2 * (int64_t)a.ls_ofactor[layer] + 2);
@@ -625,7 +642,8 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
         // candidates of every phase key: [s_phs[p], s_phs[p] + count) in the phase list,
         // then an exclusive scan of the counts (thread t owns a run of `per` phases)
         __syncthreads();
-        const int cell0 = a.li_ilor[li] * a.ndop;      // first cell of the isotope's Lorentz row
+        // first cell of the isotope's Lorentz row (wave-uniform: kept in a scalar register)
+        const int cell0 = __builtin_amdgcn_readfirstlane(a.li_ilor[li] * a.ndop);
         for (int d = tid; d < a.ndop; d += kThreads) {
             s_cbase[d] = a.pm_base[cell0 + d];
             s_csize[d] = a.psize[cell0 + d];
@@ -640,8 +658,10 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                 npiece = (lim + 127) >> 7;
                 if constexpr (kMulti) {
                     const StageSlots sl = stage_slots(a.rowlds, lim, min(kRows, a.rows_cap));
-                    pitch = sl.pitch;
-                    nrow = sl.rows;
+                    // (wave-uniform, but formed from a vector load: said so, or the step loop's
+                    // arithmetic on them is done by the vector unit and read back)
+                    pitch = __builtin_amdgcn_readfirstlane(sl.pitch);
+                    nrow = __builtin_amdgcn_readfirstlane(sl.rows);
                 }
             }
         }
@@ -884,35 +904,39 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         else
                             lo = mid + 1;
                     }
-                    hits[u] = slo < tlen ? (unsigned)first | ((unsigned)(lo - first) << 16) : 0u;
+                    // what the walk uses, ready made: the LDS byte address of the first record
+                    // << 16 | the bytes of the pair's four-record trips (a multiple of 64) | the
+                    // 0-3 records left after them; 0 = no record
+                    const unsigned n = (unsigned)(lo - first);
+                    hits[u] = slo < tlen && n
+                                  ? (rec_off0 + (unsigned)first * 16u) << 16 | (n & ~3u) << 4 | (n & 3u)
+                                  : 0u;
                 }
             };
-            auto walk = [&](int sg, int buf) {
-                if ((sg & 63) == 0) {
-                    const unsigned long long tf = tick();
-                    find_hits(sg);
-                    pc[3] += tick() - tf;
-                }
+            // the hit words of the 64 segments from sg on (sg: a multiple of 64)
+            auto block_hits = [&](int sg) {
+                const unsigned long long tf = tick();
+                find_hits(sg);
+                pc[3] += tick() - tf;
+            };
+            // `rowp`: byte address of this lane's first sample in the staged row of the segment
+            auto walk_row = [&](int sg, const char *rowp) {
                 bool any = false;
-                // byte address of this lane's first sample in the staged row
-                const char *rowp = reinterpret_cast<const char *>(
-                    s_row + kStagePad + buf * (kMulti ? pitch : rowspan) + rlo + lane);
 #pragma unroll
                 for (int u = 0; u < S; u++) {
                     const unsigned h = (unsigned)__builtin_amdgcn_readlane((int)hits[u], sg & 63);
-                    if (h < 0x10000u)
+                    if (h == 0u)
                         continue;
                     if constexpr (kProbe == 4) {
-                        pc[12] += h >> 16;
+                        pc[12] += ((h & 0xffc0u) >> 4) + (h & 3u);
                         any = true;
                     }
-                    const int first = (int)(h & 0xffff);
-                    const int last = first + (int)(h >> 16);
                     // per record: ONE 16-byte broadcast read of {k, offset, window}, four
                     // 64-sample row reads, four fma; four records per trip
                     const char *rs = rowp + (size_t)u * kSub * 8;
-                    const double2 *recs = reinterpret_cast<const double2 *>(s_rec);
-                    auto visit = [&](const double2 raw) {
+                    rec_lds_p recs = (rec_lds_p)(size_t)(h >> 16);
+                    const rec_lds_p trips_end = (rec_lds_p)(size_t)((h >> 16) + (h & 0xffc0u));
+                    auto visit = [&](const rec_v2 raw) {
                         const double k = raw.x;
                         const int qoff = __double2loint(raw.y);
                         if constexpr (kProbe == 1 || kProbe == 2) {
@@ -939,35 +963,55 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         acc[u][2] = fma(k, a2, acc[u][2]);
                         acc[u][3] = fma(k, a3, acc[u][3]);
                     };
-                    int r = first;
-                    for (; r + 3 < last; r += 4) {
-                        const double2 w0 = recs[r], w1 = recs[r + 1], w2 = recs[r + 2],
-                                      w3 = recs[r + 3];
+                    // the trips loop on the record address alone
+                    for (; recs != trips_end; recs += 4) {
+                        const rec_v2 w0 = recs[0], w1 = recs[1], w2 = recs[2], w3 = recs[3];
                         visit(w0);
                         visit(w1);
                         visit(w2);
                         visit(w3);
                     }
+                    const int left = (int)(h & 3u);
                     if constexpr (kProbe == 3) {
                         // remainder records software-pipelined: the next record's {k, offset} is
                         // requested before the current record's row reads are consumed
-                        if (r < last) {
-                            double2 cur = recs[r];
-                            for (; r + 1 < last; r++) {
-                                const double2 nxt = recs[r + 1];
+                        if (left) {
+                            rec_v2 cur = recs[0];
+                            for (int r = 1; r < left; r++) {
+                                const rec_v2 nxt = recs[r];
                                 visit(cur);
                                 cur = nxt;
                             }
                             visit(cur);
                         }
                     } else {
-                        for (; r < last; r++)
-                            visit(recs[r]);
+                        // the 0-3 records left, in record order: one if the count is odd, then
+                        // two (read together, immediate offsets 0 / 16) if its bit 1 is set.  No
+                        // loop and no padding record; two branches that skip forward and no
+                        // if / else, which the structuriser would rebuild with copies of the
+                        // accumulators at every join.
+                        if (left & 1) {
+                            visit(recs[0]);
+                            recs += 1;
+                        }
+                        if (left & 2) {
+                            const rec_v2 w0 = recs[0], w1 = recs[1];
+                            visit(w0);
+                            visit(w1);
+                        }
                     }
                 }
                 if constexpr (kProbe == 4)
                     pc[13] += any ? 1 : 0;
             };
+            // one row per step (register path, kIssue experiments, !kMulti): the row of `sg` lies
+            // in buffer `buf`; the hit words are renewed where a block of 64 segments starts
+            auto walk = [&](int sg, int buf) {
+                if ((sg & 63) == 0)
+                    block_hits(sg);
+                walk_row(sg, reinterpret_cast<const char *>(s_row + kStagePad + buf * rowspan + rlo + lane));
+            };
+            (void)walk;
             // Software pipeline over the segments.  Segment j lives in register set j % D;
             // its loads are issued D steps before its row is written to LDS buffer j % 2
             // (one step before it is walked).  Every step issues exactly R loads (the
@@ -1021,7 +1065,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                     __syncthreads();
                     for (int sg = 0; sg < nseg; sg++) {
                         if (sg + 1 < nseg && wave == ((sg + 1) & (NW - 1))) {
-                            dma_desc(dn, (sg + 1) & 1, std::false_type(), 0, 0);
+                            dma_desc(dn, bufoff((sg + 1) & 1), std::false_type(), 0, 0);
                             dn = s_desc[min(nseg - 1, sg + 1 + NW)];
                         }
                         walk(sg, sg & 1);
@@ -1042,7 +1086,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         const unsigned long long dcur = dn;
                         dn = s_desc[min(nseg - 1, sg + 2)];
                         if (sg + 1 < nseg)
-                            dma_desc(dcur, (sg + 1) & 1, std::true_type(), wave * kPer, wave * kPer + kPer);
+                            dma_desc(dcur, bufoff((sg + 1) & 1), std::true_type(), wave * kPer, wave * kPer + kPer);
                         walk(sg, sg & 1);
                         __builtin_amdgcn_s_waitcnt(0x0f70);
                         __syncthreads();
@@ -1050,6 +1094,13 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                     continue;
                 }
                 if constexpr (!kMulti) {
+                    // (the two buffers take turns: `cur8` is the byte offset of the one being
+                    // walked, cur8 ^ flip8 the other's, carried instead of formed per segment)
+                    const unsigned flip8 = (unsigned)rowspan * 8u;
+                    const char *const lane_row = reinterpret_cast<const char *>(s_row + kStagePad + rlo + lane);
+                    unsigned cur8 = 0;
+                    // the next segment this wavefront requests (segment g: wavefront g mod NW)
+                    int mine = wave == 0 ? NW : wave;
                     unsigned long long ta = tick();
                     if (wave == 0)
                         dma_row(0, 0);
@@ -1060,9 +1111,12 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         pc[8] += tb - ta;
                         ta = tb;
                     }
-                    for (int sg = 0; sg < nseg; sg++) {
-                        if (sg + 1 < nseg && wave == ((sg + 1) & (NW - 1)))
-                            dma_row(sg + 1, (sg + 1) & 1, ta);
+                    for (int sg = 0; sg < nseg; sg++, cur8 ^= flip8) {
+                        if (mine == sg + 1) {
+                            if (mine < nseg)
+                                dma_row(mine, cur8 ^ flip8, ta);
+                            mine += NW;
+                        }
                         if constexpr (kProbe == 4) {
                             const unsigned long long tb = tick();
                             // (4: the wavefront whose turn it was to request the row; 18: the
@@ -1075,7 +1129,9 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                             }
                             ta = tb;
                             const unsigned long long f0 = pc[3];
-                            walk(sg, sg & 1);
+                            if ((sg & 63) == 0)
+                                block_hits(sg);
+                            walk_row(sg, lane_row + cur8);
                             // (every LDS value of the walk has been consumed by its FMA: lgkmcnt(0))
                             const unsigned long long tc = tick();
                             pc[5] += (tc - ta) - (pc[3] - f0);
@@ -1089,7 +1145,9 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                             pc[21] += 1;
                             continue;
                         }
-                        walk(sg, sg & 1);
+                        if ((sg & 63) == 0)
+                            block_hits(sg);
+                        walk_row(sg, lane_row + cur8);
                         __builtin_amdgcn_s_waitcnt(0x0f70);       // the row of sg+1 has landed
                         __syncthreads();
                     }
@@ -1097,20 +1155,51 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                 }
                 // A step stages and walks the segments [sg, se): at most nrow of them, fewer at
                 // the end of the batch and before a multiple of 64 (find_hits serves 64 segments
-                // at a time).  Its rows lie in the slots half * nrow + (segment - sg), the two
-                // halves of the slots taking turns; the rows of the next step [se, sn) are
+                // at a time, so a step never straddles one and the hit words are renewed at the
+                // start of a step).  Its rows lie in the slots half * nrow + (segment - sg), the
+                // two halves of the slots taking turns; the rows of the next step [se, sn) are
                 // requested into the other half while this one is walked, segment g by wavefront
                 // g mod NW, so no wavefront requests two rows in a row.  One wait and one barrier
                 // end a step; with nrow == 1 this is one row per step in two buffers.
-                auto step_end = [&](int s0) { return min(min(s0 + nrow, nseg), (s0 | 63) + 1); };
-                auto request = [&](int s0, int s1, int slot0, unsigned long long tref) {
-                    const int g = s0 + ((wave - s0) & (NW - 1));   // my segment of the step, if any
-                    if (g < s1)
-                        dma_row(g, slot0 + (g - s0), tref);
-                    return g < s1;
+                // Carried from step to step instead of formed anew: `cur8`, the byte offset of the
+                // half being walked (cur8 ^ flip8 is the other; a segment's slot lies pitch8 bytes
+                // after the one before it), `hits_from`, the first segment the hit words do not
+                // serve yet, and, where steps can straddle at all, `bend`, the end of the block of
+                // 64 segments that holds `se`.  They cannot with nrow = 1 or 2 (kRows <= 2): the
+                // steps of a batch start at multiples of nrow, and 64 is one, so a step's end is
+                // one add and one min.
+                constexpr bool kAligned = kRows <= 2;
+                const unsigned pitch8 = (unsigned)pitch * 8u, flip8 = (unsigned)nrow * pitch8;
+                const char *const lane_row = reinterpret_cast<const char *>(s_row + kStagePad + rlo + lane);
+                // `mine`: the next segment this wavefront requests.  The steps are requested in
+                // order and hold at most NW segments, so on entry it is the one segment at or
+                // after s0 that is this wavefront's, and the test is one compare.
+                int mine = wave;
+                auto request = [&](int s0, int s1, unsigned boff0, unsigned long long tref) {
+                    const bool ask = mine < s1;
+                    if (ask) {
+                        dma_row(mine, boff0 + (unsigned)(mine - s0) * pitch8, tref);
+                        mine += NW;
+                    }
+                    return ask;
                 };
                 unsigned long long ta = tick();
-                int sg = 0, se = step_end(0), half = 0;
+                int bend = kAligned ? nseg : min(64, nseg);
+                int sg = 0, se = min(nrow, bend), hits_from = 0;
+                unsigned cur8 = 0;
+                // (a step holds at least one segment: no test before the first)
+                auto walk_step = [&]() {
+                    if (sg == hits_from) {
+                        block_hits(sg);
+                        hits_from += 64;
+                    }
+                    const char *rp = lane_row + cur8;
+                    int g = sg;
+                    do {
+                        walk_row(g, rp);
+                        rp += pitch8;
+                    } while (++g < se);
+                };
                 request(0, se, 0, 0);
                 __builtin_amdgcn_s_waitcnt(0x0f70);           // vmcnt(0)
                 __syncthreads();
@@ -1119,9 +1208,13 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                     pc[8] += tb - ta;
                     ta = tb;
                 }
-                while (sg < nseg) {
-                    const int sn = step_end(se);
-                    const bool asked = request(se, sn, (half ^ 1) * nrow, ta);
+                do {                                      // nseg > 0
+                    if constexpr (!kAligned) {
+                        if (se == bend)
+                            bend = min(bend + 64, nseg);
+                    }
+                    const int sn = min(se + nrow, bend);
+                    const bool asked = request(se, sn, cur8 ^ flip8, ta);
                     if constexpr (kProbe == 4) {
                         const unsigned long long tb = tick();
                         // (4: the wavefronts whose turn it was to request a row; 18: the others,
@@ -1134,8 +1227,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         }
                         ta = tb;
                         const unsigned long long f0 = pc[3];
-                        for (int g = sg; g < se; g++)
-                            walk(g, half * nrow + (g - sg));
+                        walk_step();
                         // (every LDS value of the walk has been consumed by its FMA: lgkmcnt(0))
                         const unsigned long long tc = tick();
                         pc[5] += (tc - ta) - (pc[3] - f0);
@@ -1149,15 +1241,14 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         pc[21] += (unsigned long long)(se - sg);
                     } else {
                         (void)asked;
-                        for (int g = sg; g < se; g++)
-                            walk(g, half * nrow + (g - sg));
+                        walk_step();
                         __builtin_amdgcn_s_waitcnt(0x0f70);   // the rows of [se, sn) have landed
                         __syncthreads();
                     }
                     sg = se;
                     se = sn;
-                    half ^= 1;
-                }
+                    cur8 ^= flip8;
+                } while (sg < nseg);
             } else if (nseg > 0) {
                 run(std::integral_constant<int, 2>(), std::integral_constant<int, kRowRegs>());
             }
