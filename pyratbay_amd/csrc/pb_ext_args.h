@@ -77,6 +77,19 @@ __host__ __device__ inline StageSlots stage_slots(int rowlds, int rowlim, int ca
     return {pitch, rows};
 }
 
+// The slot rule: live segment g of a batch (numbered from 0 in every batch) is walked in step
+// g / rows and lies in slot (g / rows & 1) * rows + g % rows -- this many BYTES after slot 0,
+// with pitch8 = 8 * pitch.  rows = 1, pitch = rowlds + kStagePad: the two buffers of the one-row
+// loop.  The requests of k_ext_staged place a row there (by offsets they carry from step to
+// step), and on the LDS-DMA path the batch set-up adds it to the row offset of every record of the
+// segment, so the walk of every segment reads from slot 0's address.
+static_assert(kStageRowsMax == 2, "stage_slot_off8(): rows is a power of two");
+__host__ __device__ inline unsigned stage_slot_off8(int g, int rows, unsigned pitch8)
+{
+    // for a power of two, (g / rows & 1) * rows + g % rows = g mod 2 rows
+    return (unsigned)(g & (2 * rows - 1)) * pitch8;
+}
+
 // staged gather (k_ext_staged): wavefronts and threads of a workgroup
 constexpr int kStagedWaves = 8;
 constexpr int kStagedThreads = kStagedWaves * 64;

@@ -452,6 +452,11 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
     // pb_ext_args.h), set with rowlim; every other instance keeps one row per step, two buffers
     constexpr bool kMulti = kDma && kIssue == 0 && kRows > 1;
     int pitch = rowspan, nrow = 1;
+    // The product instances fold a segment's slot into the row offsets of its records
+    // (stage_slot_off8(), pb_ext_args.h), so their walk reads every segment from the lane's address
+    // in slot 0.  The register path and the kIssue / kProbe forms add the buffer's offset to the
+    // lane's address per segment instead: the independent statement of the same addresses.
+    constexpr bool kFold = kDma && kIssue == 0 && kProbe == 0;
     static_assert(kRows <= kStageRowsMax && kStageRowsMax <= NW,
                   "a wavefront requests at most one row of a step");
     // kDma: the row of a segment goes global -> LDS directly (`buffer_load_dwordx4 ... lds`,
@@ -746,10 +751,12 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
             // ---- one record per lane, in (phase, iown) order, from k_records ----
             long long src = -1;                        // phase row of my record (table element)
             unsigned mwin = 0;                         // its window in row coordinates
+            // {k, qoff, win} of my record: stored behind the segment detection, which says in
+            // which slot the record's row will lie
+            double k = 0.0;
+            unsigned win = 0;
+            int qoff = 0;
             {
-                double k = 0.0;
-                unsigned win = 0;
-                int qoff = 0;
                 const int x = x0 + tid;
                 if (x < total) {
                     int plo = 0, pup = nvirt;           // largest pv with s_cum[pv] <= x
@@ -812,9 +819,6 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         k = 0.0;
                     }
                 }
-                s_rec[tid].k = k;
-                s_rec[tid].qoff = qoff;
-                s_rec[tid].win = win;
                 s_src[tid] = src;
                 s_m[tid] = mwin;
             }
@@ -844,6 +848,20 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         before += c;
                     nseg += c;
                 }
+                // live segment starts in the lanes below mine
+                const int below = (int)__builtin_amdgcn_mbcnt_hi(
+                    (unsigned)(livemask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)livemask, 0u));
+                // My record goes to LDS, with the slot of its segment folded into its row offset
+                // (kFold).  A live record's segment is the last live start at or before it --
+                // before + below, less one where the start is not mine; a record behind a dead
+                // start is dead itself (k = 0, an empty window: no pair holds it) and its offset
+                // is never used.
+                if constexpr (kFold)
+                    qoff += (int)stage_slot_off8(before + below - (live ? 0 : 1), nrow,
+                                                 (unsigned)pitch * 8u);
+                s_rec[tid].k = k;
+                s_rec[tid].qoff = qoff;
+                s_rec[tid].win = win;
                 if (live) {
                     // end of my segment = next start after me
                     int w = tid >> 6;
@@ -858,7 +876,7 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                             break;
                         m = s_segmask[w];
                     }
-                    const int pos = before + __builtin_popcountll(livemask & ((1ull << lane) - 1ull));
+                    const int pos = before + below;
                     s_seg[pos] = (unsigned)tid | ((unsigned)end << 16);
                     // the row descriptor of the segment, packed: first element of the window
                     // (40 bits) | window length << 40 (12 bits) | window start << 52 (12 bits).
@@ -1147,7 +1165,8 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         }
                         if ((sg & 63) == 0)
                             block_hits(sg);
-                        walk_row(sg, lane_row + cur8);
+                        // (kFold: the buffer's offset is in the records; cur8 serves the request)
+                        walk_row(sg, kFold ? lane_row : lane_row + cur8);
                         __builtin_amdgcn_s_waitcnt(0x0f70);       // the row of sg+1 has landed
                         __syncthreads();
                     }
@@ -1193,12 +1212,19 @@ __global__ __launch_bounds__(NW * 64, 8) void k_ext_staged(LblArgs a)
                         block_hits(sg);
                         hits_from += 64;
                     }
-                    const char *rp = lane_row + cur8;
                     int g = sg;
-                    do {
-                        walk_row(g, rp);
-                        rp += pitch8;
-                    } while (++g < se);
+                    if constexpr (kFold) {
+                        // (the slot's offset is in the records of the segment)
+                        do {
+                            walk_row(g, lane_row);
+                        } while (++g < se);
+                    } else {
+                        const char *rp = lane_row + cur8;
+                        do {
+                            walk_row(g, rp);
+                            rp += pitch8;
+                        } while (++g < se);
+                    }
                 };
                 request(0, se, 0, 0);
                 __builtin_amdgcn_s_waitcnt(0x0f70);           // vmcnt(0)
