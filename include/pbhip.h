@@ -26,7 +26,7 @@
  *     the loaded library exports them); no #if, #else, line continuations or function-like macros;
  *   - #define NAME <integer>: decimal or hex, negative, with or without parentheses;
  *   - typedef struct pb_x pb_x; (a handle) and typedef struct pb_x { ... } pb_x; with fields of
- *     int, int32_t, int64_t, uint64_t, uint8_t, double or a pointer to one of those, to void or
+ *     int, int16_t, int32_t, int64_t, uint64_t, uint8_t, double or a pointer to one of those, to void or
  *     to a struct declared above; several declarators per statement; arrays of one or two
  *     dimensions, of pointers too, whose bounds are integers or constants defined in this file;
  *   - functions that return int, int64_t, void or const char *, with named parameters of the
@@ -1641,6 +1641,43 @@ int pb_band_transmittance_cloudy_batch(double *out_d, const double *ec_d, const 
                                        int nbands, int nwalkers, const int32_t *deck_itop_d,
                                        const pb_cloud_terms *cloud, const double *f_patchy_d,
                                        double *work_d, void *stream);
+
+/* =========================================================================
+ * Line lists to TLI columns  (the reference's `runmode = tli`: Hitran.dbread,
+ * pyratbay/opacity/linelist/hitran.py:173-203; Exomol.dbread, exomol.py:177-204)
+ * ========================================================================= */
+/* flag bits of a record (flags_d): a field whose text is not on the fast path of the conversion
+ * (pb_linelist.hip: an integer of at most 2^53 times or over a power of ten up to 1e22) or not in
+ * its grammar, which the host reads with float() / int() instead; an isotope character that the
+ * map does not have; a record with fewer than three tokens; a state id outside [0, nstates) */
+#define PB_LL_HITRAN_ISO 1
+#define PB_LL_HITRAN_WN 2
+#define PB_LL_HITRAN_A21 4
+#define PB_LL_HITRAN_ELOW 8
+#define PB_LL_HITRAN_G2 16
+#define PB_LL_EXOMOL_UP 1
+#define PB_LL_EXOMOL_LOW 2
+#define PB_LL_EXOMOL_A21 4
+#define PB_LL_EXOMOL_TOKEN 8
+#define PB_LL_EXOMOL_STATE 16
+/* text_d[nrec * recsize]: nrec whole records of recsize bytes (153 ... 255 for HITRAN, 5 ... 255
+ * for ExoMol), at any byte alignment -> wn_d, elow_d, a21_d, g2_d [nrec] doubles, iso_d [nrec]
+ * int16 (HITRAN: the index of the record's isotope character, '1'..'9' -> 0..8, '0' -> 9,
+ * 'A' -> 10, 'B' -> 11; ExoMol: `iso`), flags_d [nrec].  A flagged field is written as NaN (the
+ * isotope as -1) and *nflagged_d, which the caller zeroes, grows by one per flagged record.
+ * ExoMol: energy_d, degeneracy_d [nstates] doubles, dense in the state id; wn = E[up] - E[low],
+ * elow = E[low], g2 = g[up]. */
+int pb_parse_hitran(const uint8_t *text_d, int64_t nrec, int recsize, double *wn_d, double *elow_d,
+                    double *a21_d, double *g2_d, int16_t *iso_d, uint8_t *flags_d,
+                    int32_t *nflagged_d, void *stream);
+int pb_parse_exomol(const uint8_t *text_d, int64_t nrec, int recsize, const double *energy_d,
+                    const double *degeneracy_d, int64_t nstates, int iso, double *wn_d,
+                    double *elow_d, double *a21_d, double *g2_d, int16_t *iso_d, uint8_t *flags_d,
+                    int32_t *nflagged_d, void *stream);
+/* gf_d[n] = g2 * a21 * c1 / divisor / (wn * wn), every operation rounded on its own, in this
+ * order (NumPy's of hitran.py:199) */
+int pb_linelist_gf(const double *wn_d, const double *a21_d, const double *g2_d, int64_t n,
+                   double c1, double divisor, double *gf_d, void *stream);
 
 /* =========================================================================
  * Experiments -- NOT in libpbhip.so.  `make -C pyratbay_amd/csrc EXPERIMENTS=1` builds

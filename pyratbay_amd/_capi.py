@@ -27,8 +27,8 @@ class PbError(RuntimeError):
 # ---------------------------------------------------------------------------------------------
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'pbhip.h')
 
-_SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64,
-            'uint8_t': C.c_uint8, 'double': C.c_double}
+_SCALARS = {'int': C.c_int, 'int16_t': C.c_int16, 'int32_t': C.c_int32, 'int64_t': C.c_int64,
+            'uint64_t': C.c_uint64, 'uint8_t': C.c_uint8, 'double': C.c_double}
 _RETURNS = {'int': C.c_int, 'int64_t': C.c_int64, 'void': None, 'const char *': C.c_char_p}
 # The entries whose int is a value.  Every other entry that returns int returns a status, which
 # call() checks against PB_OK.
