@@ -1680,6 +1680,48 @@ int pb_linelist_gf(const double *wn_d, const double *a21_d, const double *g2_d, 
                    double c1, double divisor, double *gf_d, void *stream);
 
 /* =========================================================================
+ * Partition functions from ExoMol states  (the reference's `pf` step: exomol_states,
+ * pyratbay/opacity/partitions/partitions.py:329-427)
+ * ========================================================================= */
+/* flag bits of a `.states` record (flags_d): the id, the energy or the degeneracy token is off
+ * the fast path or outside its grammar (id: an optional '+' and 1 ... 18 digits; degeneracy: an
+ * optional '+' and 1 ... 15 digits; energy: the decimal rule of the line-list kernels); fewer than
+ * three blank-separated tokens end within bytes 0 ... 32, or a white-space byte other than the
+ * blank lies there; the record's layout: byte recsize - 1 is no line feed, a line feed lies
+ * earlier, or the energy and degeneracy tokens do not lie wholly inside bytes 12 ... 31 */
+#define PB_LL_STATES_ID 1
+#define PB_LL_STATES_ENERGY 2
+#define PB_LL_STATES_G 4
+#define PB_LL_STATES_TOKEN 8
+#define PB_LL_STATES_LAYOUT 16
+/* records of one workgroup of pb_parse_states; temperatures of one tile and the smallest number
+ * of states of one chunk of pb_pf_states */
+#define PB_STATES_RECORDS_PER_BLOCK 128
+#define PB_PF_TEMPS_PER_TILE 1024
+#define PB_PF_MIN_CHUNK 1024
+#define PB_PF_MAX_CHUNKS 4096
+/* text_d[nrec * recsize]: nrec whole records of recsize bytes (33 ... 255, the line feed
+ * included), at any byte alignment -> id_d [nrec] int64, energy_d, degeneracy_d [nrec] doubles,
+ * flags_d [nrec]: the first three blank-separated tokens as integer, decimal, integer.  A flagged
+ * token is written as -1 (id) or NaN, all three of a record with a token or layout flag, and
+ * *nflagged_d, which the caller zeroes, grows by one per flagged record. */
+int pb_parse_states(const uint8_t *text_d, int64_t nrec, int recsize, int64_t *id_d,
+                    double *energy_d, double *degeneracy_d, uint8_t *flags_d, int32_t *nflagged_d,
+                    void *stream);
+/* q_d[ntemp] = sum_j degeneracy_d[j] * exp((-c2 * energy_d[j]) * (1 / temp_d[t])) over the nstates
+ * states (0 ... 2^31-1; ntemp 0 ... 65536).  The states are cut into chunks of a size that is
+ * a function of (nstates, ntemp) alone; one partial per (chunk, temperature)
+ * goes to work_d [pb_pf_states_work(nstates, ntemp) doubles] and the partials of a temperature
+ * are added in ascending chunk order: no atomics, the same bits on every call and stream.  q_d and
+ * work_d may hold anything on entry.  nstates = 0 gives zeros; ntemp = 0 launches nothing.
+ * pb_pf_states_work writes the two sizes to host memory: sizes_h[0] the doubles of work_d (0 when
+ * there is nothing to launch: work_d may then be null), sizes_h[1] the states per chunk. */
+int pb_pf_states_work(int64_t nstates, int ntemp, int64_t sizes_h[2]);
+int pb_pf_states(const double *energy_d, const double *degeneracy_d, int64_t nstates,
+                 const double *temp_d, int ntemp, double c2, double *q_d, double *work_d,
+                 void *stream);
+
+/* =========================================================================
  * Experiments -- NOT in libpbhip.so.  `make -C pyratbay_amd/csrc EXPERIMENTS=1` builds
  * libpbhip_exp.so (compiled with -DPB_EXPERIMENTS) = the product library + the variants that were
  * built, verified and measured SLOWER than the default path (profiles/notes_r0*.md): gather modes

@@ -17,123 +17,19 @@
 // which is odd, so the even lanes of a 32-lane group sit on different banks and so do the odd
 // ones: a read is 2-way conflicted at worst.  (161: 40.25 dwords, four lanes 161 dwords apart.)
 //
-// Text to double.  A field is blanks, a sign, digits with at most one point, an exponent, blanks.
-// It gives an integer w of its digits and a decimal exponent q.  If w <= 2^53 and |q| <= 22 the
-// value is double(w) * 1e q or double(w) / 1e -q: both operands are exact, so the one IEEE
-// operation rounds correctly and returns the bits of Python's float() (Clinger's fast path).
-// Every other field -- more digits, a larger exponent, nan, inf, an underscore, an empty field,
-// any byte outside this grammar -- sets the record's flag bit of that field; the host parses those
-// fields itself with float() from the bytes it still holds (pyratbay_amd/linelist.py).  The device
-// does not guess.
+// Text to double: the rule of pb_text.h (Decimal).  A field it refuses sets the record's flag bit
+// of that field; the host parses those fields itself with float() from the bytes it still holds
+// (pyratbay_amd/linelist.py).  The device does not guess.
 #include "pb_common.h"
+#include "pb_text.h"
 
 namespace {
 
+using namespace pb_text;
+
 constexpr int kBlock = 256;
-constexpr int kMaxRecsize = 255;              // shift + 256 * 255 + slack stays within 64 KiB
-constexpr int kSlack = 16;                    // dword reads of a field's last bytes end inside it
 constexpr int kHitranEnd = 153;               // end of the last field read (g2, [146:153])
 constexpr int kExomolMin = 5;                 // "1 2 3"
-
-// 1e0 ... 1e22: the powers of ten a double holds exactly
-__host__ __device__ __forceinline__ double pow10_exact(int q)
-{
-    constexpr double table[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,
-                                  1e8,  1e9,  1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
-                                  1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-    return table[q];
-}
-
-// The field grammar as a machine fed one byte at a time (decimal_fast_path_host of linelist.py is
-// the same machine in Python; __host__ too, so that a host program can run it against strtod).
-struct Decimal {
-    enum { LEAD, SIGN, INT, FRAC, EXP, EXPSIGN, EXPDIG, TRAIL, BAD };
-    uint64_t w = 0;          // the digits, leading zeros dropped, at most 19 of them
-    int nsig = 0;            // digits from the first non-zero one on
-    int ndig = 0;            // digits of the mantissa
-    int nfrac = 0;           // of them behind the point
-    int ex = 0;              // exponent digits (clamped: anything above 22 is flagged anyway)
-    int state = LEAD;
-    bool neg = false, eneg = false;
-
-    __host__ __device__ __forceinline__ void step(uint32_t c)
-    {
-        const uint32_t d = c - '0';
-        if (d < 10u) {
-            if (state <= FRAC) {
-                if (state < INT)
-                    state = INT;
-                ndig++;
-                nfrac += state == FRAC;
-                nsig += (w != 0 || d != 0);
-                if (nsig <= 19)
-                    w = w * 10 + d;
-            } else if (state <= EXPDIG) {
-                state = EXPDIG;
-                ex = ex * 10 + (int)d;
-                ex = ex > 100000 ? 100000 : ex;
-            } else {
-                state = BAD;
-            }
-        } else if (c == ' ') {
-            if (state == INT || state == FRAC || state == EXPDIG)
-                state = TRAIL;
-            else if (state != LEAD && state != TRAIL)
-                state = BAD;
-        } else if (c == '.') {
-            state = state <= INT ? FRAC : BAD;
-        } else if (c == 'e' || c == 'E') {
-            state = ((state == INT || state == FRAC) && ndig > 0) ? EXP : BAD;
-        } else if (c == '+' || c == '-') {
-            if (state == LEAD) {
-                state = SIGN;
-                neg = c == '-';
-            } else if (state == EXP) {
-                state = EXPSIGN;
-                eneg = c == '-';
-            } else {
-                state = BAD;
-            }
-        } else {
-            state = BAD;
-        }
-    }
-
-    // the value when the field is on the fast path; false: the host parses it
-    __host__ __device__ __forceinline__ bool finish(double &value) const
-    {
-        const bool grammar = ndig > 0 &&
-                             (state == INT || state == FRAC || state == EXPDIG || state == TRAIL);
-        const int q = (eneg ? -ex : ex) - nfrac;
-        if (!(grammar && nsig <= 19 && w <= (1ull << 53) && q >= -22 && q <= 22)) {
-            value = __builtin_nan("");
-            return false;
-        }
-        const double m = (double)w;                          // exact: w <= 2^53
-        const double v = q < 0 ? m / pow10_exact(-q) : m * pow10_exact(q);
-        value = neg ? -v : v;
-        return true;
-    }
-};
-
-// kLen bytes of LDS from byte position `pos` on, as aligned dword reads shifted into place: out[j]
-// holds bytes 4j .. 4j+3 of the field (ds_read_b32 of an unaligned address is not an option, and
-// one ds_read_u8 per character is 2.5 times as many LDS instructions)
-template <int kLen>
-__device__ __forceinline__ void field_dwords(const uint32_t *s_text, int pos,
-                                             uint32_t (&out)[(kLen + 3) / 4])
-{
-    constexpr int n = (kLen + 3) / 4;
-    const uint32_t *p = s_text + (pos >> 2);
-    const uint32_t sh = pos & 3;
-    uint32_t d[n + 1];
-#pragma unroll
-    for (int j = 0; j <= n; j++)
-        d[j] = p[j];
-#pragma unroll
-    for (int j = 0; j < n; j++)
-        out[j] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], sh);
-}
 
 template <int kLen>
 __device__ __forceinline__ bool fixed_field(const uint32_t *s_text, int pos, double &value)
@@ -147,30 +43,6 @@ __device__ __forceinline__ bool fixed_field(const uint32_t *s_text, int pos, dou
     return dec.finish(value);
 }
 
-// The workgroup's records into LDS: aligned 16-byte loads of every 16-byte block that holds at
-// least one of their bytes (such a block lies in the same page as that byte, so the bytes of it
-// before the first record or after the last one are readable; they are not used).  Returns the
-// position of the first record's first byte in s_text.
-__device__ __forceinline__ int stage_records(uint4 *s_text, const uint8_t *text, int64_t first,
-                                             int nrec, int recsize)
-{
-    const uintptr_t start = (uintptr_t)text + (uint64_t)first * (uint64_t)recsize;
-    const uintptr_t base = start & ~(uintptr_t)15;
-    const int shift = (int)(start - base);
-    const int nvec = (shift + nrec * recsize + 15) >> 4;
-    const uint4 *src = (const uint4 *)base;
-    for (int i = threadIdx.x; i < nvec; i += kBlock)
-        s_text[i] = src[i];
-    __syncthreads();
-    return shift;
-}
-
-__device__ __forceinline__ void count_flagged(uint32_t flags, int32_t *nflagged)
-{
-    if (flags)
-        atomicAdd(nflagged, 1);           // the compiler makes one add per wavefront of it
-}
-
 // HITRAN / HITEMP .par records (hitran.py:33-43): isotope character [2], wavenumber [3:15],
 // A21 [25:35], Elow [45:55], g2 [146:153]
 __global__ __launch_bounds__(kBlock) void k_parse_hitran(
@@ -181,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void k_parse_hitran(
     extern __shared__ __attribute__((aligned(16))) uint4 s_text[];
     const int64_t first = (int64_t)blockIdx.x * kBlock;
     const int n = (int)min((int64_t)kBlock, nrec - first);
-    const int shift = stage_records(s_text, text, first, n, recsize);
+    const int shift = stage_records<kBlock>(s_text, text, first, n, recsize);
     const int t = threadIdx.x;
     if (t >= n)
         return;
@@ -223,11 +95,6 @@ __global__ __launch_bounds__(kBlock) void k_parse_hitran(
     count_flagged(fl, nflagged);
 }
 
-__device__ __forceinline__ bool is_space(uint32_t c)
-{
-    return c == ' ' || (c >= 9 && c <= 13);           // what bytes.split() splits at
-}
-
 // ExoMol .trans records (exomol.py:177-204): the first three tokens are the upper state's id, the
 // lower state's id and A21; then wn = E[up] - E[low], elow = E[low], g2 = g[up].
 __global__ __launch_bounds__(kBlock) void k_parse_exomol(
@@ -240,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void k_parse_exomol(
     extern __shared__ __attribute__((aligned(16))) uint4 s_text[];
     const int64_t first = (int64_t)blockIdx.x * kBlock;
     const int n = (int)min((int64_t)kBlock, nrec - first);
-    const int shift = stage_records(s_text, text, first, n, recsize);
+    const int shift = stage_records<kBlock>(s_text, text, first, n, recsize);
     const int t = threadIdx.x;
     if (t >= n)
         return;
@@ -322,11 +189,6 @@ __global__ __launch_bounds__(kBlock) void k_linelist_gf(
     }
 }
 
-int lds_bytes(int recsize)
-{
-    return (15 + kBlock * recsize + kSlack + 15) & ~15;
-}
-
 }  // namespace
 
 extern "C" {
@@ -344,7 +206,7 @@ int pb_parse_hitran(const uint8_t *text_d, int64_t nrec, int recsize, double *wn
                "pb_parse_hitran: null pointer");
     if (nrec == 0)
         return PB_OK;
-    k_parse_hitran<<<pb::div_up(nrec, kBlock), kBlock, lds_bytes(recsize),
+    k_parse_hitran<<<pb::div_up(nrec, kBlock), kBlock, lds_bytes(kBlock, recsize),
                      pb::as_stream(stream)>>>(text_d, nrec, recsize, wn_d, elow_d, a21_d, g2_d,
                                               iso_d, flags_d, nflagged_d);
     PB_LAUNCH_CHECK();
@@ -369,7 +231,7 @@ int pb_parse_exomol(const uint8_t *text_d, int64_t nrec, int recsize, const doub
                "pb_parse_exomol: null pointer");
     if (nrec == 0)
         return PB_OK;
-    k_parse_exomol<<<pb::div_up(nrec, kBlock), kBlock, lds_bytes(recsize),
+    k_parse_exomol<<<pb::div_up(nrec, kBlock), kBlock, lds_bytes(kBlock, recsize),
                      pb::as_stream(stream)>>>(text_d, nrec, recsize, energy_d, degeneracy_d,
                                               nstates, iso, wn_d, elow_d, a21_d, g2_d, iso_d,
                                               flags_d, nflagged_d);

@@ -26,9 +26,10 @@ layout of the reference's isotopes.dat, read_pf() its tabulated partition functi
 reference's data files are not shipped.
 
 Out of scope: the reference's other readers (pands, tioschwenke, vald, voplez, repack); TIPS and
-polynomial partition functions (partition='tips' / 'poly' are refused); computing partition
-functions from ExoMol or Kurucz data; a correctly rounded device conversion beyond the fast path
-(the flagged route covers it); compressed `.trans.bz2` transitions (`.states.bz2` is read).
+polynomial partition functions (partition='tips' / 'poly' are refused; partitions.py makes a
+tabulated partition from ExoMol states, ExoMol `.pf` files or Kurucz files instead); a correctly
+rounded device conversion beyond the fast path (the flagged route covers it); compressed
+`.trans.bz2` transitions (`.states.bz2` is read).
 """
 import bz2
 import itertools
@@ -306,9 +307,20 @@ def exomol_states_file(trans):
     return os.path.join(folder, sfile)
 
 
-def read_states(sfile):
+def read_states(sfile, device=False):
     """(energy, degeneracy) dense in the state id up to the largest one (ids may have gaps, which
-    stay 0): the first three tokens of every line.  `<sfile>.bz2` is read when sfile is absent."""
+    stay 0): the first three tokens of every line.  `<sfile>.bz2` is read when sfile is absent.
+    device=True: the text is parsed and scattered on the device (partitions.read_states_device,
+    pb_parse_states), with the same arrays bit for bit; a file whose lines differ in length is
+    read here."""
+    if device:
+        from . import partitions
+        path = sfile if os.path.isfile(sfile) else sfile + '.bz2'
+        if not os.path.isfile(path):
+            raise ValueError(f"Exomol file '{sfile}' does not exist")
+        got = partitions.read_states_device(path)
+        if got is not None:
+            return got
     if os.path.isfile(sfile):
         with open(sfile, 'rb') as f:
             lines = f.readlines()
@@ -424,10 +436,11 @@ class Exomol(_Database):
     """ExoMol `.trans` files of one molecule, each with the `.states` file its name points to.
     The file's isotope is read from its name and looked up in `isotopes`; files of several
     isotopologues of one molecule are separate Exomol objects or one (make_tli merges objects of
-    equal name either way)."""
+    equal name either way).  device=True reads the `.states` files on the device (read_states);
+    partition=(temps, pf, isotopes) may come straight from partitions.exomol_states."""
     kind = 'Exomol'
 
-    def __init__(self, files, isotopes, iso_mass, iso_ratio, partition):
+    def __init__(self, files, isotopes, iso_mass, iso_ratio, partition, device=False):
         files = [files] if isinstance(files, (str, os.PathLike)) else list(files)
         named = [get_exomol_mol(os.fspath(f)) for f in files]
         if len({m for m, _ in named}) > 1:
@@ -446,7 +459,7 @@ class Exomol(_Database):
             file.iso = self.isotopes.index(iso)
             sfile = exomol_states_file(file.path)
             if sfile not in states:
-                states[sfile] = read_states(sfile)
+                states[sfile] = read_states(sfile, device=device)
             file.energy, file.degeneracy = states[sfile]
 
     def _wave(self, file, f, irec):
@@ -529,20 +542,21 @@ class _Chunker:
         self.streams = _device.side_streams(2)
         self.used = [0, 0]                       # chunks that went through each buffer
 
-    def parse(self, db, file, istart, istop, columns):
-        """Records istart..istop of `file` into `columns` (device tensors of the window's
-        length); returns the number of flagged records."""
+    def run(self, source, nrec, recsize, launch, patch, short):
+        """nrec records of recsize bytes read from `source` (readinto) through the two buffers;
+        returns the number of flagged records.  launch(b, first, n, stream): enqueue the parse
+        of the n records in self.text[b], records first .. first + n - 1 of the read, counting
+        the flagged ones into self.count[b].  patch(b, first, n): called on the host, under the
+        buffer's stream, when that count came back non-zero and while self.pinned[b] still holds
+        the chunk's bytes; returns how many records it patched.  short(first, n): the exception
+        for a source that ends inside the chunk."""
         torch = self.torch
-        from ._device import _ptr
-        from ._capi import call
-        recsize = file.recsize
         per_chunk = self.nbytes // recsize
         if per_chunk < 1:
             raise ValueError(f'chunk_bytes = {self.nbytes} holds no record of {recsize} bytes')
-        nread = istop - istart + 1
         flagged = 0
         pending = [None, None]                   # (event, first, n) of the chunk in each buffer
-        launch = torch.cuda.current_stream()
+        main = torch.cuda.current_stream()
 
         def settle(b):
             nonlocal flagged
@@ -552,54 +566,71 @@ class _Chunker:
             pending[b] = None
             event.synchronize()
             if int(self.count_h[b][0]):
-                flags = columns['flags'][first:first + n].cpu().numpy()
                 with torch.cuda.stream(self.streams[b]):
-                    flagged += _patch_flagged(db, file, istart, first,
-                                              self.pinned[b].numpy()[:n * recsize], flags,
-                                              columns)
+                    flagged += patch(b, first, n)
                 self.streams[b].synchronize()
 
-        if db.kind == 'Exomol':
-            energy = torch.from_numpy(file.energy).cuda()
-            degeneracy = torch.from_numpy(file.degeneracy.astype(np.float64)).cuda()
         ready = torch.cuda.Event()
-        ready.record(launch)                     # the columns exist before a side stream writes
-        with open(file.path, 'rb') as f:
-            f.seek(istart * recsize)
-            for k, first in enumerate(range(0, nread, per_chunk)):
-                b = k & 1
-                settle(b)                        # the buffer's previous chunk is done with it
-                n = min(per_chunk, nread - first)
-                view = memoryview(self.pinned[b].numpy())[:n * recsize]
-                if f.readinto(view) != n * recsize:
-                    raise ValueError(f'{file.path}: the file ended inside record '
-                                     f'{istart + first} ... {istart + first + n - 1}')
-                stream = self.streams[b]
-                with torch.cuda.stream(stream):
-                    stream.wait_event(ready)
-                    self.text[b][:n * recsize].copy_(self.pinned[b][:n * recsize],
-                                                     non_blocking=True)
-                    self.count[b].zero_()
-                    out = [_ptr(columns[c][first:first + n])
-                           for c in ('wn', 'elow', 'a21', 'g2', 'iso', 'flags')]
-                    sp = torch.cuda.current_stream().cuda_stream
-                    if db.kind == 'HITRAN':
-                        call('pb_parse_hitran', _ptr(self.text[b]), n, recsize, *out,
-                             _ptr(self.count[b]), sp)
-                    else:
-                        call('pb_parse_exomol', _ptr(self.text[b]), n, recsize, _ptr(energy),
-                             _ptr(degeneracy), len(file.energy), file.iso, *out,
-                             _ptr(self.count[b]), sp)
-                    self.count_h[b].copy_(self.count[b], non_blocking=True)
-                    event = torch.cuda.Event()
-                    event.record(stream)
-                pending[b] = (event, first, n)
-                self.used[b] += 1
+        ready.record(main)                       # the columns exist before a side stream writes
+        for k, first in enumerate(range(0, nrec, per_chunk)):
+            b = k & 1
+            settle(b)                            # the buffer's previous chunk is done with it
+            n = min(per_chunk, nrec - first)
+            view = memoryview(self.pinned[b].numpy())[:n * recsize]
+            if source.readinto(view) != n * recsize:
+                raise short(first, n)
+            stream = self.streams[b]
+            with torch.cuda.stream(stream):
+                stream.wait_event(ready)
+                self.text[b][:n * recsize].copy_(self.pinned[b][:n * recsize],
+                                                 non_blocking=True)
+                self.count[b].zero_()
+                launch(b, first, n, torch.cuda.current_stream().cuda_stream)
+                self.count_h[b].copy_(self.count[b], non_blocking=True)
+                event = torch.cuda.Event()
+                event.record(stream)
+            pending[b] = (event, first, n)
+            self.used[b] += 1
         settle(0)
         settle(1)
         for s in self.streams:
-            launch.wait_stream(s)
+            main.wait_stream(s)
         return flagged
+
+    def parse(self, db, file, istart, istop, columns):
+        """Records istart..istop of `file` into `columns` (device tensors of the window's
+        length); returns the number of flagged records."""
+        torch = self.torch
+        from ._device import _ptr
+        from ._capi import call
+        recsize = file.recsize
+        if db.kind == 'Exomol':
+            energy = torch.from_numpy(file.energy).cuda()
+            degeneracy = torch.from_numpy(file.degeneracy.astype(np.float64)).cuda()
+
+        def launch(b, first, n, stream):
+            out = [_ptr(columns[c][first:first + n])
+                   for c in ('wn', 'elow', 'a21', 'g2', 'iso', 'flags')]
+            if db.kind == 'HITRAN':
+                call('pb_parse_hitran', _ptr(self.text[b]), n, recsize, *out,
+                     _ptr(self.count[b]), stream)
+            else:
+                call('pb_parse_exomol', _ptr(self.text[b]), n, recsize, _ptr(energy),
+                     _ptr(degeneracy), len(file.energy), file.iso, *out,
+                     _ptr(self.count[b]), stream)
+
+        def patch(b, first, n):
+            flags = columns['flags'][first:first + n].cpu().numpy()
+            return _patch_flagged(db, file, istart, first,
+                                  self.pinned[b].numpy()[:n * recsize], flags, columns)
+
+        def short(first, n):
+            return ValueError(f'{file.path}: the file ended inside record '
+                              f'{istart + first} ... {istart + first + n - 1}')
+
+        with open(file.path, 'rb') as f:
+            f.seek(istart * recsize)
+            return self.run(f, istop - istart + 1, recsize, launch, patch, short)
 
 
 def _read_device(db, file, istart, istop, chunker):
